@@ -2,8 +2,14 @@
 """bench.py -- BEV Mpix/s of the batched homography warp (BASELINE.json metric) on N GPUs of one node.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype f32|u8] [--interp linear|nearest] [--config 1|3]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W [--config 3]
+
+A plain run sets up, warms up, times the K steps of the headline and prints its line (value, ms_per_step, the roofline of the
+headline's own launches).  `--full` adds every side measurement below: the streaming-ceiling probe and the in-kernel clock,
+the CPU baseline with its oracle check, the variants, the other configs and the `summary`.  `--dump-outputs DIR` writes what
+the last timed step returned (see dump_outputs) so that two builds can be compared output for output.
 
 A "step" is one launch of the hot path over one batch of synthetic frames already resident in HBM.  The headline is
 BASELINE.json configs[1] = 32 x (1920x1080x3 -> 1024x1024x3) bilinear warp per GPU, "keystone" homography with a per-frame
@@ -13,7 +19,7 @@ rank with no data-path collective (weak scaling); torch.distributed carries the 
 Several distinct buffer sets (> 1 GB in total) are rotated so that a step never finds its frames in the 256 MB Infinity
 Cache left by the previous one.
 
-ONE JSON line (rank 0).  At N = 1 it also carries, measured in the same run:
+ONE JSON line (rank 0).  With --full at N = 1 it also carries, measured in the same run:
   variants   the other pixel types of configs[1] -- uint8 bilinear (the reference's own pixel type, vis_homo.py:86-89) and
              nearest, uint8 -> float32 planes -- and the rotated "brno" footprint for uint8 and float32
   configs    configs[0] (one 720p -> 512^2 uint8 frame: GPU resident / PCIe-inclusive, CPU oracle 1 thread and all cores,
@@ -80,7 +86,13 @@ def parse():
     p.add_argument("--no-configs", action="store_true", help="skip the configs block (N = 1)")
     p.add_argument("--cpu-seconds", type=float, default=3.0, help="wall budget of the cpu_baseline sample (the oracle needs < 1 s of 16 cores to time)")
     p.add_argument("--leg-steps", type=int, default=300, help="timed launches of every side measurement (variants, configs[3]); --steps governs the headline only")
+    p.add_argument("--full", action="store_true",
+                   help="also run every side measurement (probe and clock, CPU baseline, variants, configs, summary); a plain run times the headline only")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, rank 0)")
     a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
     shape = {1: ([1920, 1080], [1024, 1024]), 3: ([3840, 2160], [2048, 2048])}[a.config]
     a.src = a.src or shape[0]
     a.dst = a.dst or shape[1]
@@ -439,6 +451,29 @@ def oracle_check(w, frames=(0, -1)):
             exp = (exp.astype(np.float32) * np.float32(1.0 / 255.0) + np.float32(0.0)).transpose(2, 0, 1)
         ok = ok and bool(np.array_equal(got, exp))
     return ok
+
+
+DUMP_SAMPLE = 1 << 21          # values of the whole batch sampled at fixed, seeded positions
+DUMP_FRAME_VALUES = 1 << 22    # frame 0 is written whole up to this many values, strided in both axes beyond it
+
+
+def dump_outputs(w, last_step, out_dir):
+    """What the timed path returned in its last step -- the (B, dh, dw, 3) destination batch of `w.step(last_step)` -- as float32
+    .npy files under out_dir (< 64 MB in all):
+      output_frame0.npy         frame 0 of the batch (strided by the smallest s with (dh/s)(dw/s)3 <= DUMP_FRAME_VALUES; 1 at configs[1])
+      output_sample.npy         DUMP_SAMPLE values of the whole batch at seeded flat positions (numpy default_rng(0), sorted, unique)
+      output_sample_index.npy   those flat positions into the (B, dh, dw, 3) batch, float64 (exact)"""
+    torch.cuda.synchronize()
+    out = w.dsts[last_step % w.nsets]
+    os.makedirs(out_dir, exist_ok=True)
+    s = 1
+    while (w.dh // s) * (w.dw // s) * w.C > DUMP_FRAME_VALUES:
+        s += 1
+    np.save(os.path.join(out_dir, "output_frame0.npy"), out[0, ::s, ::s].float().cpu().numpy())
+    idx = np.unique(np.random.default_rng(0).integers(0, out.numel(), DUMP_SAMPLE, dtype=np.int64))
+    vals = out.reshape(-1)[torch.from_numpy(idx).to(out.device)].float().cpu().numpy()
+    np.save(os.path.join(out_dir, "output_sample.npy"), vals)
+    np.save(os.path.join(out_dir, "output_sample_index.npy"), idx.astype(np.float64))
 
 
 def variant_line(w, steps, warmup, barrier, label=None, probe=False, check=True):
@@ -801,14 +836,17 @@ def main():
     shard.init(backend=backend, device=dev)  # no-op for one process; no RCCL communicator is created (north_star: no collectives)
 
     big = args.config == 3
+    probe = args.full and not args.no_probe
     main_wl = Workload(args, args.dtype, args.interp, rank, dev, device_frames=big and args.no_cpu_baseline)
-    ceiling = measured_ceiling(main_wl) if (rank == 0 and not args.no_probe) else None  # same process, same buffers, before the headline
+    ceiling = measured_ceiling(main_wl) if (rank == 0 and probe) else None  # same process, same buffers, before the headline
     elapsed_local, launch_ms = main_wl.run(args.steps, args.warmup, shard.barrier)
+    if rank == 0 and args.dump_outputs:  # before anything else writes the destination buffers (the clock build, --full)
+        dump_outputs(main_wl, args.steps - 1, args.dump_outputs)
     elapsed = shard.max_over_ranks(elapsed_local)
     kernel_ms_max = shard.max_over_ranks(float(launch_ms.mean()))  # slowest rank's mean launch duration (HIP events)
     kernel_ms_min = -shard.max_over_ranks(-float(launch_ms.mean()))
     sclk = None
-    if rank == 0 and not args.no_probe:
+    if rank == 0 and probe:
         try:
             sclk = kernel_clock(main_wl)
         except Exception as e:  # a diagnostic must not lose the headline
@@ -835,13 +873,13 @@ def main():
             "kernel_ms_mean": round(float(launch_ms.mean()), 4), "kernel_ms_max_over_ranks": round(kernel_ms_max, 4),
             "kernel_ms_min_over_ranks": round(kernel_ms_min, 4), "wall_ms_per_step_rank0": round(elapsed_local / args.steps * 1e3, 4),
         }
-        if world == 1 and not args.no_cpu_baseline and main_wl.frames_np:
+        if world == 1 and args.full and not args.no_cpu_baseline and main_wl.frames_np:
             gpu_out = main_wl.dsts[0][:len(main_wl.frames_np)].cpu().numpy()  # set 0 holds the seeded frames
             result["cpu_baseline"] = cpu_baseline(main_wl.frames_np, main_wl.Ms, (dw, dh), main_wl.interp, gpu_out, args.cpu_seconds)
     del main_wl
     torch.cuda.empty_cache()
 
-    if world == 1 and not args.no_variants:
+    if world == 1 and args.full and not args.no_variants:
         variants = []
         n = max(args.leg_steps, args.steps)
         for dt, ip, planar, hom, tbl in (("u8", "linear", False, "keystone", False), ("u8", "nearest", False, "keystone", False), ("f32", "linear", False, "keystone", False),
@@ -851,7 +889,7 @@ def main():
                 continue
             w = Workload(args, dt, ip, rank, dev, planar=planar, homography=hom, device_frames=True, verdicts=tbl)
             variants.append(variant_line(w, n, max(5, args.warmup // 2), shard.barrier, label=dt if not planar else "u8 -> f32 planar",
-                                         probe=not args.no_probe and not planar and not tbl))
+                                         probe=probe and not planar and not tbl))
             if tbl:
                 variants[-1]["verdict_table"] = "per-tile verdicts of these matrices filled by one untimed launch, read by the timed ones (bevwarp_warp_classes)"
                 # entries of one run are minutes apart on a clock-managed chip: the table's own effect is read from launches INTERLEAVED on
@@ -872,7 +910,7 @@ def main():
             torch.cuda.empty_cache()
         result["variants"] = variants
 
-    if world == 1 and not args.no_configs:
+    if world == 1 and args.full and not args.no_configs:
         cfg = {}
         for name, fn in (("configs[0]", lambda: config0(dev)), ("configs[2]", lambda: config2(dev)), ("configs[3]", lambda: config3(args, dev, shard.barrier)),
                          ("configs[4]", lambda: config4(dev)), ("f3_composite", lambda: composite_config(dev)), ("f1_small_branch", lambda: small_branch_config(dev)),
@@ -885,7 +923,7 @@ def main():
         result["configs"] = cfg
 
     if rank == 0:
-        if world == 1:
+        if world == 1 and args.full:
             result["summary"] = summary_of(result)  # LAST key: the tail of the line alone carries every number
         print(json.dumps(result), flush=True)
     shard.barrier()

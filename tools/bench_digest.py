@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Print the numbers of a bench.py JSON line that DESIGN.md / README.md quote:  python tools/bench_digest.py profiles/r03_bench_default.json"""
+"""Print the numbers of a `bench.py --full` JSON line that DESIGN.md / README.md quote:  python tools/bench_digest.py profiles/r03_bench_default.json"""
 import json
 import sys
 
