@@ -39,6 +39,7 @@ _MINV_CACHE_MAX = 256
 _MINV_PINNED_MAX = 4096
 _minv_cache = collections.OrderedDict()  # (matrix bytes, device, inverse_given) -> device tensor, least recently used first
 _minv_pinned = {}                        # entries whose address a hipGraph capture has seen: never evicted
+_minv_retired = []                       # pinned entries written in place since: no longer looked up, still never freed
 
 
 def device_inverse(M, device, inverse_given=False):
@@ -49,7 +50,12 @@ def device_inverse(M, device, inverse_given=False):
     that is looked up while the current stream is being captured into a graph is pinned for the life of the process
     (the graph replays its address; 72 bytes per matrix, at most _MINV_PINNED_MAX entries -- re-capturing with ever new
     matrices beyond that raises: pass `M_inv_device`), and a cache MISS during capture raises -- upload the matrices before capturing
-    (or pass `M_inv_device`, which the caller owns)."""
+    (or pass `M_inv_device`, which the caller owns).
+
+    The returned tensor is the cache entry itself.  Writing into it with an in-place torch op (`copy_`, `mul_`, ...) bumps its
+    `_version`: the entry no longer holds the inverse of its key, so a later lookup drops it and uploads the key's matrices anew,
+    and the verdict tables of the written tensor are refilled (_tile_classes).  Writes through its raw address are not seen: as for
+    any matrix tensor whose verdicts are cached, keeping them away is the caller's job (include/bevwarp.h, bevwarp_warp_classes)."""
     if isinstance(M, torch.Tensor) and M.is_cuda and inverse_given:
         return M.to(torch.float64).reshape(-1, 3, 3).contiguous()
     device = torch.device(device)
@@ -61,22 +67,28 @@ def device_inverse(M, device, inverse_given=False):
             capturing = torch.cuda.is_current_stream_capturing()
     hit = _minv_pinned.get(key)
     if hit is not None:
-        return hit
+        if hit._version == hit._bevwarp_version:
+            return hit
+        _minv_retired.append(_minv_pinned.pop(key))  # (written in place: a captured graph may still replay its address)
     hit = _minv_cache.get(key)
+    if hit is not None and hit._version != hit._bevwarp_version:
+        del _minv_cache[key]  # written in place: no longer the inverse of its key (every use recorded its stream, see below)
+        hit = None
     if hit is None:
         if capturing:
             raise RuntimeError("device_inverse: homography not resident while a graph is being captured; call the step once "
                                "before capturing, or pass M_inv_device")
         inv = Mh if inverse_given else invert_homography(Mh)
         hit = torch.from_numpy(inv).to(device)
-        hit._bevwarp_owned = True  # (cached by value, never written again: its tile verdicts may be cached too, _tile_classes)
+        hit._bevwarp_owned = True  # (cached by value: its tile verdicts may be cached too, _tile_classes)
+        hit._bevwarp_version = hit._version
         _minv_cache[key] = hit
         while len(_minv_cache) > _MINV_CACHE_MAX:
             _minv_cache.popitem(last=False)  # (safe: every use recorded its stream, see below)
     else:
         _minv_cache.move_to_end(key)
     if capturing:
-        if len(_minv_pinned) >= _MINV_PINNED_MAX:
+        if len(_minv_pinned) + len(_minv_retired) >= _MINV_PINNED_MAX:
             raise RuntimeError("device_inverse: %d homography sets are already pinned by graph captures; pass M_inv_device (a tensor the "
                                "caller owns) when capturing graphs with ever new matrices" % _MINV_PINNED_MAX)
         _minv_pinned[key] = _minv_cache.pop(key)
@@ -90,6 +102,11 @@ try:  # the current stream's raw hipStream_t without building a torch.cuda.Strea
 except AttributeError:  # pragma: no cover - older / CPU-only builds
     def _raw_stream(dev_index):
         return torch.cuda.current_stream(dev_index).cuda_stream
+
+try:  # the current stream's capture state (torch.cuda.is_current_stream_capturing without its Python frame)
+    _capturing = torch._C._cuda_isCurrentStreamCapturing
+except AttributeError:  # pragma: no cover - older / CPU-only builds
+    _capturing = torch.cuda.is_current_stream_capturing
 
 _PLANS_MAX = 1024
 _plans = {}  # validated launches by (addresses, shapes, strides, dtypes, dsize, flags) -> (entry point, bound arguments, device index)
@@ -121,33 +138,44 @@ def _border(border_value, C):
 
 
 _CLASSES_MAX = 64
-_class_tables = collections.OrderedDict()  # (matrix tensor address, n matrices, batch, sizes, format) -> (verdict table, the matrix tensor)
+_class_tables = collections.OrderedDict()  # (matrix tensor address, n matrices, batch, sizes, format) -> (verdict table, the matrix tensor, its _version)
 
 
 def _tile_classes(M_inv_device, n_m, call_args, stream):
     """The per-tile verdict table (include/bevwarp.h, bevwarp_warp_classes) of a launch whose matrices are owned by device_inverse --
-    cached by value and never written again, so verdicts derived from them once hold for every later launch with the same geometry:
-    the camera loop of vis_homo.py:85-91 warps every frame of a video through one H_bev_img.  Filled on first use (one launch that
-    writes no pixel); None for matrices the caller owns (their contents may change under the same address), while a graph is being
-    captured (the fill would allocate), and for launches the library keeps no table for."""
+    cached by value, so verdicts derived from them once hold for every later launch with the same geometry: the camera loop of
+    vis_homo.py:85-91 warps every frame of a video through one H_bev_img.  None for matrices the caller owns (their contents may change
+    under the same address), while a graph is being captured (the fill would allocate, and a graph would replay the table's address:
+    captured launches classify for themselves -- a plan that carries a table launches plain bevwarp_warp under capture too; tables are
+    not pinned for graphs), and for launches the library keeps no table for.
+
+    Contents: a table is kept with the matrix tensor's `_version`.  An in-place torch op on the tensor changes it, and the next launch
+    refills the table (a plan that carries the table falls back to this path); writes through the raw address are not seen -- the
+    caller's to avoid, as include/bevwarp.h says.
+    Streams: filled on first use (one launch that writes no pixel), and the filling call then waits on the host until the fill has run
+    (a one-time wait per matrices and geometry, the camera loop pays it on its first frame): a launch on any other stream that finds the
+    table in the cache or in a plan reads finished verdicts."""
     if not getattr(M_inv_device, "_bevwarp_owned", False):
         return None
     (_, _, B, H, W, dh, dw, C, _, _, _, _, _, _, dtype, interp, _) = call_args
     key = (M_inv_device.data_ptr(), n_m, B, H, W, dh, dw, C, dtype, interp)
     with torch.cuda.device(M_inv_device.device):
-        if torch.cuda.is_current_stream_capturing():  # (a graph would replay the table's raw address: captured launches classify for themselves)
+        if torch.cuda.is_current_stream_capturing():
             return None
         hit = _class_tables.get(key)
         if hit is not None:
-            _class_tables.move_to_end(key)
-            return hit[0]
+            if hit[2] == M_inv_device._version:
+                _class_tables.move_to_end(key)
+                return hit[0]
+            del _class_tables[key]  # the matrices were written in place since the fill: these verdicts are not theirs
         lib = _lib.load()
         nbytes = lib.bevwarp_tile_classes_bytes(B, H, W, dh, dw, C, dtype, interp)
         if nbytes <= 0:
             return None
         table = torch.zeros(nbytes // 4, dtype=torch.int32, device=M_inv_device.device)
         _lib.check(lib.bevwarp_warp_classes(*call_args, table.data_ptr(), 1, ctypes.c_void_p(stream)))
-    _class_tables[key] = (table, M_inv_device)  # (holding the matrix tensor keeps its address from being handed out again)
+        torch.cuda.current_stream().synchronize()  # (the stream `stream` is: cached verdicts are finished verdicts)
+    _class_tables[key] = (table, M_inv_device, M_inv_device._version)  # (holding the matrix tensor keeps its address from being handed out again)
     while len(_class_tables) > _CLASSES_MAX:
         _class_tables.popitem(last=False)
     return table
@@ -175,12 +203,20 @@ def warp_perspective(src, M, dsize, flags=INTER_LINEAR, border_value=None, out=N
             plan = _plans.get(key)
         except (AttributeError, TypeError, IndexError):
             plan = None
+        if plan is not None and plan[3] is not None and M_inv_device._version != plan[5]:
+            plan = None  # verdicts of matrices since written in place: the slow path refills them
         if plan is not None:
-            fn, args, dev_index = plan[:3]
+            # (a plan with a verdict table launches the plain entry point while a graph is being captured: the graph would replay the
+            # table's address, and nothing keeps the table alive for the graph's life)
+            fn, args, dev_index, table = plan[:4]
             if torch.cuda.current_device() == dev_index:
+                if table is not None and _capturing():
+                    fn, args = plan[6], args[:-2]
                 st = fn(*args, _raw_stream(dev_index))
             else:
                 with torch.cuda.device(dev_index):
+                    if table is not None and _capturing():
+                        fn, args = plan[6], args[:-2]
                     st = fn(*args, _raw_stream(dev_index))
             if st:
                 _lib.check(st)
@@ -222,7 +258,7 @@ def warp_perspective(src, M, dsize, flags=INTER_LINEAR, border_value=None, out=N
     stream = torch.cuda.current_stream(s4.device).cuda_stream
     args = (s4.data_ptr(), d4.data_ptr(), B, H, W, dh, dw, C, s4.stride(0) * esz, s4.stride(1) * esz, d4.stride(0) * esz, d4.stride(1) * esz,
             M_inv_device.data_ptr(), n_m, _DTYPES[s4.dtype], interp, None if bv is None else bv.ctypes.data_as(ctypes.c_void_p))
-    fn = _lib.load().bevwarp_warp
+    fn = plain = _lib.load().bevwarp_warp
     table = _tile_classes(M_inv_device, n_m, args, stream)
     if table is not None:  # verdicts of these very matrices and this geometry: the kernel reads them instead of deriving them
         table.record_stream(torch.cuda.current_stream(s4.device))
@@ -233,9 +269,10 @@ def warp_perspective(src, M, dsize, flags=INTER_LINEAR, border_value=None, out=N
     if key is not None and not copied:  # validated and launched: the next call with these very buffers skips the checks
         if len(_plans) >= _PLANS_MAX:
             _plans.clear()
+        # (a plan with a verdict table keeps the table AND the matrices it belongs to alive -- their address must not be handed out again
+        # while the plan can be hit -- and holds the matrices' _version it was filled for, and the plain entry point for graph captures)
         _plans[key] = (fn, args, s4.device.index if s4.device.index is not None else torch.cuda.current_device(), table,
-                       M_inv_device if table is not None else None)  # (a plan with a verdict table keeps the table AND the matrices it belongs to alive:
-        #                                                          their address must not be handed out again while the plan can be hit)
+                       M_inv_device if table is not None else None, M_inv_device._version if table is not None else None, plain)
     if out is not None:
         return out
     if len(shape) == 2:

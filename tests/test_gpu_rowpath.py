@@ -7,6 +7,8 @@ import pytest
 import torch
 
 from oracle import cpu_oracle as co
+from tests import parity as P
+from tests.parity import report_comparisons  # noqa: F401  (oracle comparisons per launch mode, written at the module's end)
 from tests import workloads as wl
 
 pytestmark = pytest.mark.gpu
@@ -20,17 +22,19 @@ def W():
 
 
 def run_gpu(W, src_np, M, dsize, interp, **kw):
-    t = torch.from_numpy(np.ascontiguousarray(src_np)).cuda()
-    poison = torch.full((dsize[1], dsize[0]) + tuple(t.shape[2:]), 77, dtype=t.dtype, device="cuda")  # unwritten pixels must not pass as zeros
-    if "out" not in kw and t.dim() <= 3:
-        kw = dict(kw, out=poison)
-    out = W.warp_perspective(t, M, dsize, flags=interp, **kw)
-    torch.cuda.synchronize()
-    return out.reshape(poison.shape).cpu().numpy() if out is poison else out.cpu().numpy()
+    """The warp in both launch modes (tests/parity.py): {mode: host result}."""
+    t = src_np if isinstance(src_np, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(src_np)).cuda()
+    if "out" not in kw:
+        kw = dict(kw, out=P.poisoned_out(t, dsize))  # unwritten pixels must not pass as zeros
+    return P.warp_modes(t, M, dsize, interp, **kw)
+
+
+def frames_of(res, i):
+    return {m: r[i] for m, r in res.items()}
 
 
 def both(W, src, M, dsize, interp, **kw):
-    np.testing.assert_array_equal(run_gpu(W, src, M, dsize, interp, **kw), co.warp_perspective(src, M, dsize, interp, **kw))
+    P.check_modes(run_gpu(W, src, M, dsize, interp, **kw), co.warp_perspective(src, M, dsize, interp, **kw))
 
 
 @pytest.mark.parametrize("c", [1, 2, 3, 4])
@@ -63,9 +67,7 @@ def test_float_border_far_outside_is_exact(W):
     src = rng.random((90, 110, 3), dtype=np.float32)
     bv = [0.3, 0.7, 1.0 / 3.0]
     M = np.array([[1, 0, -400.0 - 13 / 32], [0, 1, -250.0 - 7 / 32], [0, 0, 1.0]])
-    out = run_gpu(W, src, M, (300, 70), 1, border_value=bv)
-    for k in range(3):
-        assert (out[..., k] == np.float32(bv[k])).all()
+    P.check_modes(run_gpu(W, src, M, (300, 70), 1, border_value=bv), np.broadcast_to(np.float32(bv), (70, 300, 3)))
     for shift in ((-60.0 - 13 / 32, -20.0 - 7 / 32), (95.0 + 5 / 32, 70.0 + 9 / 32), (-100.0 - 1 / 32, 0.25)):
         M = np.array([[1, 0, shift[0]], [0, 1, shift[1]], [0, 0, 1.0]])
         both(W, src, M, (300, 70), 1, border_value=bv)
@@ -95,7 +97,7 @@ def test_w_sign_change_and_far_coordinates(W, interp):
     M2 = np.array([[1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [1.0 / 300.0, 0.0, -1.0]])  # W = 0 along a column
     both(W, src, M2, (512, 32), interp)
     T = np.array([[1, 0, 1e7], [0, 1, 0], [0, 0, 1.0]])
-    assert not run_gpu(W, src, T, (512, 32), interp).any()
+    P.check_modes(run_gpu(W, src, T, (512, 32), interp), np.zeros((32, 512, 3), np.uint8))
     both(W, src.astype(np.float32) / 255, M, (256, 64), interp)
 
 
@@ -116,9 +118,9 @@ def test_padded_rows_batch_and_per_frame_matrices(W):
     Ms = np.stack([wl.jitter_H(base, i, px=7.0) for i in range(B)])
     big = torch.from_numpy(np.stack([wl.frame(10 + i, sh, sw + 24, np.uint8) for i in range(B)])).cuda()
     view = big[:, :, 12:12 + sw]
-    got = W.warp_perspective(view, Ms, (dw, dh)).cpu().numpy()
+    got = run_gpu(W, view, Ms, (dw, dh), 1)
     for i in range(B):
-        np.testing.assert_array_equal(got[i], co.warp_perspective(np.ascontiguousarray(view[i].cpu().numpy()), Ms[i], (dw, dh)))
+        P.check_modes(frames_of(got, i), co.warp_perspective(np.ascontiguousarray(view[i].cpu().numpy()), Ms[i], (dw, dh)))
 
 
 def test_fused_resize_warp_small_branch(W):
@@ -136,7 +138,9 @@ def test_fused_resize_warp_small_branch(W):
     t = torch.from_numpy(img).cuda()
     got = W.warp_perspective_resized(t, M_small, (512, 256), (852, 480)).cpu().numpy()
     S = W.resize_matrix((1920, 1080), (852, 480))
-    np.testing.assert_array_equal(got, co.warp_perspective(img, M_small @ S, (512, 256), 1))
+    exp = co.warp_perspective(img, M_small @ S, (512, 256), 1)
+    np.testing.assert_array_equal(got, exp)
+    P.check_modes(run_gpu(W, t, M_small @ S, (512, 256), 1), exp)  # (what warp_perspective_resized calls, in both launch modes)
     # two-step path: bilinear resize with half-pixel centres (what cv2.resize computes, up to its fixed-point rounding)
     sm = torch.nn.functional.interpolate(t.permute(2, 0, 1)[None].float(), size=(480, 852), mode="bilinear", align_corners=False)
     sm = sm[0].permute(1, 2, 0).round().clamp(0, 255).to(torch.uint8).contiguous()
@@ -202,13 +206,13 @@ def test_row_strides_of_every_alignment(W, sw):
     rows of a pixel share their alignment only when the stride is a multiple of 4), and an odd frame base."""
     M = wl.synth_brno_H(1920, 1080, 512, 48) @ np.diag([1920 / sw, 1080 / 359, 1.0])
     src = wl.frame(30, 359, sw, np.uint8)
-    both(W, src, M, (512, 48), 1)
+    exp = co.warp_perspective(src, M, (512, 48), 1)
+    P.check_modes(run_gpu(W, src, M, (512, 48), 1), exp)
     buf = torch.zeros(359 * sw * 3 + 8, dtype=torch.uint8, device="cuda")
     for shift in (1, 2, 3):
         view = buf[shift:shift + 359 * sw * 3].view(359, sw, 3)
         view.copy_(torch.from_numpy(src))
-        got = W.warp_perspective(view, M, (512, 48)).cpu().numpy()
-        np.testing.assert_array_equal(got, co.warp_perspective(src, M, (512, 48), 1))
+        P.check_modes(run_gpu(W, view, M, (512, 48), 1), exp)
 
 
 # ---- launches of hundreds of tiles (per-frame matrices, taller tiles from 2 x the resident workgroups up): batches of small
@@ -223,10 +227,10 @@ def _batch_case(W, dtype_c, sw, sh, dw, dh, B, kind, interp, pad_to=None, border
         big = torch.zeros((B, sh, pad_to, c), dtype=torch.uint8, device="cuda")
         big[:, :, :sw] = t
         t = big[:, :, :sw]
-    got = W.warp_perspective(t, Ms, (dw, dh), flags=interp, border_value=border).cpu().numpy()
+    got = run_gpu(W, t, Ms, (dw, dh), interp, border_value=border)
     for i in range(B):
         exp = co.warp_perspective(frames[i], Ms[i], (dw, dh), interp, border_value=0 if border is None else border)
-        np.testing.assert_array_equal(got[i], exp, err_msg="frame %d" % i)
+        P.check_modes(frames_of(got, i), exp, lambda g, e: np.testing.assert_array_equal(g, e, err_msg="frame %d" % i))
 
 
 @pytest.mark.parametrize("c", [1, 2, 3, 4])
@@ -302,11 +306,10 @@ def test_turned_footprints_through_unaligned_views(W, c, dtype):
     src_big[:, 1:1 + sw] = torch.from_numpy(src).cuda()
     for interp in (0, 1):
         out_big = torch.full((dh, dw + 5, c), 77, dtype=src_big.dtype, device="cuda")
-        W.warp_perspective(src_big[:, 1:1 + sw], M, (dw, dh), flags=interp, out=out_big[:, 3:3 + dw])
-        torch.cuda.synchronize()
+        res = run_gpu(W, src_big[:, 1:1 + sw], M, (dw, dh), interp, out=out_big[:, 3:3 + dw])
+        P.check_modes({m: r.reshape(dh, dw, c) for m, r in res.items()}, co.warp_perspective(src, M, (dw, dh), interp).reshape(dh, dw, c))
         got = out_big.cpu().numpy()
-        np.testing.assert_array_equal(got[:, 3:3 + dw], co.warp_perspective(src, M, (dw, dh), interp).reshape(dh, dw, c))
-        assert (got[:, :3] == 77).all() and (got[:, 3 + dw:] == 77).all()  # nothing written outside the view
+        assert (got[:, :3] == 77).all() and (got[:, 3 + dw:] == 77).all()  # nothing written outside the view, in either mode
 
 
 def _random_homography(rng, sw, sh, dw, dh):
@@ -340,11 +343,11 @@ def test_random_homographies_all_formats(W, seed):
         Ms = np.stack([_random_homography(rng, sw, sh, dw, dh) for _ in range(B)])
         frames = np.stack([wl.frame(100 * seed + case + i, sh, sw, dtype, c) for i in range(B)])
         border = None if rng.random() < 0.5 else [float(rng.integers(0, 200))] * c
-        got = W.warp_perspective(torch.from_numpy(frames).cuda(), Ms, (dw, dh), flags=interp, border_value=border).cpu().numpy()
+        got = run_gpu(W, torch.from_numpy(frames).cuda(), Ms, (dw, dh), interp, border_value=border)
         for i in range(B):
             exp = co.warp_perspective(frames[i], Ms[i], (dw, dh), interp, border_value=0 if border is None else border)
-            np.testing.assert_array_equal(got[i].reshape(exp.shape), exp, err_msg="seed %d case %d frame %d: %dx%d -> %dx%d c=%d %s interp=%d" % (
-                seed, case, i, sw, sh, dw, dh, c, np.dtype(dtype).name, interp))
+            msg = "seed %d case %d frame %d: %dx%d -> %dx%d c=%d %s interp=%d" % (seed, case, i, sw, sh, dw, dh, c, np.dtype(dtype).name, interp)
+            P.check_modes({m: r[i].reshape(exp.shape) for m, r in got.items()}, exp, lambda g, e: np.testing.assert_array_equal(g, e, err_msg=msg))
 
 
 @pytest.mark.parametrize("dtype", [np.uint8, np.float32])
@@ -358,7 +361,7 @@ def test_row_affine_tiles_and_their_tolerance(W, dtype, interp):
     src = wl.frame(31, sh, sw, dtype)
 
     def both_inv(M):  # cv2.WARP_INVERSE_MAP: M is the dst -> src map itself, so its entries are exactly what the kernel sees
-        np.testing.assert_array_equal(run_gpu(W, src, M, (dw, dh), interp | 16), co.warp_perspective(src, M, (dw, dh), interp, m_is_inverse=True))
+        P.check_modes(run_gpu(W, src, M, (dw, dh), interp | 16), co.warp_perspective(src, M, (dw, dh), interp, m_is_inverse=True))
 
     base = np.array([[1.25, 0.0, 20.0], [0.0, 1.5, 30.0], [0.0, 0.004, 1.0]])  # keystone form: Y / W and W depend on y only
     both_inv(base)
@@ -375,9 +378,9 @@ def test_row_affine_tiles_and_their_tolerance(W, dtype, interp):
     # a least-squares keystone (the benchmark's matrix) and its jittered frames, batched
     Ms = np.stack([wl.jitter_H(wl.keystone_H(sw, sh, dw, dh), g) for g in range(4)])
     frames = np.stack([wl.frame(32 + g, sh, sw, dtype) for g in range(4)])
-    got = W.warp_perspective(torch.from_numpy(frames).cuda(), Ms, (dw, dh), flags=interp).cpu().numpy()
+    got = run_gpu(W, torch.from_numpy(frames).cuda(), Ms, (dw, dh), interp)
     for g in range(4):
-        np.testing.assert_array_equal(got[g], co.warp_perspective(frames[g], Ms[g], (dw, dh), interp))
+        P.check_modes(frames_of(got, g), co.warp_perspective(frames[g], Ms[g], (dw, dh), interp))
 
 
 @pytest.mark.parametrize("misalign", [0, 1, 2, 3])
@@ -397,9 +400,7 @@ def test_pair_tiles_scales_mirrors_and_alignments(W, misalign):
 
     def check(M):
         out = torch.full((dh, dw, 3), 77, dtype=torch.uint8, device="cuda")
-        W.warp_perspective(view, M, (dw, dh), flags=1 | 16, out=out)
-        torch.cuda.synchronize()
-        np.testing.assert_array_equal(out.cpu().numpy(), co.warp_perspective(src, M, (dw, dh), 1, m_is_inverse=True))
+        P.check_modes(run_gpu(W, view, M, (dw, dh), 1 | 16, out=out), co.warp_perspective(src, M, (dw, dh), 1, m_is_inverse=True))
 
     for s in (0.3, 0.75, 1.0, 1.5, 1.875, 1.93, 1.9375, 1.94, 1.97):
         check(np.array([[s, 0.0, 4.25], [0.0, 1.5, 30.0], [0.0, 0.0, 1.0]]))                       # pure scale: the same step on every row
@@ -421,6 +422,6 @@ def test_pair_tiles_full_height_batched(W):
         s = rng.uniform(0.6, 1.93)
         Ms.append(np.array([[s, 0.0, rng.uniform(2, 6)], [0.0, 0.44, rng.uniform(3, 9)], [0.0, rng.uniform(-1e-4, 1e-4), 1.0]]))
     Ms = np.stack(Ms)
-    got = W.warp_perspective(torch.from_numpy(frames).cuda(), Ms, (dw, dh), flags=1 | 16).cpu().numpy()
+    got = run_gpu(W, torch.from_numpy(frames).cuda(), Ms, (dw, dh), 1 | 16)
     for g in range(B):
-        np.testing.assert_array_equal(got[g], co.warp_perspective(frames[g], Ms[g], (dw, dh), 1, m_is_inverse=True))
+        P.check_modes(frames_of(got, g), co.warp_perspective(frames[g], Ms[g], (dw, dh), 1, m_is_inverse=True))

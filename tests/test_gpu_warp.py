@@ -7,6 +7,8 @@ import pytest
 import torch
 
 from oracle import cpu_oracle as co
+from tests import parity as P
+from tests.parity import report_comparisons  # noqa: F401  (oracle comparisons per launch mode, written at the module's end)
 from tests import workloads as wl
 
 pytestmark = pytest.mark.gpu
@@ -22,19 +24,22 @@ def W():
 
 
 def run_gpu(W, src_np, M, dsize, interp, **kw):
-    t = torch.from_numpy(np.ascontiguousarray(src_np)).cuda()
-    poison = torch.full((dsize[1], dsize[0]) + tuple(t.shape[2:]), 77, dtype=t.dtype, device="cuda")  # unwritten pixels must not pass as zeros
-    if "out" not in kw and t.dim() <= 3:
-        kw = dict(kw, out=poison)
-    out = W.warp_perspective(t, M, dsize, flags=interp, **kw)
-    torch.cuda.synchronize()
-    return out.reshape(poison.shape).cpu().numpy() if out is poison else out.cpu().numpy()
+    """The warp in both launch modes (tests/parity.py): {mode: host result}."""
+    t = src_np if isinstance(src_np, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(src_np)).cuda()
+    if "out" not in kw:
+        kw = dict(kw, out=P.poisoned_out(t, dsize))  # unwritten pixels must not pass as zeros
+    return P.warp_modes(t, M, dsize, interp, **kw)
 
 
-def check(got, exp):
+def check_one(got, exp):
     if exp.dtype == np.float32:
         assert np.abs(got - exp).max() <= F32_TOL
     np.testing.assert_array_equal(got, exp)
+
+
+def check(res, exp):
+    """Each launch mode's result against the oracle's `exp`."""
+    P.check_modes(res, exp, check_one)
 
 
 SHAPES = [
@@ -70,7 +75,7 @@ def test_channel_counts(W, c, dtype, interp):
     check(run_gpu(W, src, M, (160, 200), interp), co.warp_perspective(src, M, (160, 200), interp))
     g = src[:, :, 0]
     got = run_gpu(W, g, M, (160, 200), interp)
-    assert got.shape == (200, 160)
+    assert all(r.shape == (200, 160) for r in got.values())
     check(got, co.warp_perspective(g, M, (160, 200), interp))
 
 
@@ -81,19 +86,18 @@ def test_batch_per_frame_and_shared_matrix(W, dtype):
     Ms = np.stack([wl.jitter_H(base, i) for i in range(B)])
     frames = np.stack([wl.frame(i, sh, sw, dtype) for i in range(B)])
     t = torch.from_numpy(frames).cuda()
-    got = W.warp_perspective(t, Ms, (dw, dh)).cpu().numpy()
+    got = run_gpu(W, t, Ms, (dw, dh), W.INTER_LINEAR)
     for i in range(B):
-        check(got[i], co.warp_perspective(frames[i], Ms[i], (dw, dh)))
-    got = W.warp_perspective(t, base, (dw, dh)).cpu().numpy()
+        check({m: r[i] for m, r in got.items()}, co.warp_perspective(frames[i], Ms[i], (dw, dh)))
+    got = run_gpu(W, t, base, (dw, dh), W.INTER_LINEAR)
     for i in range(B):
-        check(got[i], co.warp_perspective(frames[i], base, (dw, dh)))
+        check({m: r[i] for m, r in got.items()}, co.warp_perspective(frames[i], base, (dw, dh)))
     with pytest.raises(ValueError):
         W.warp_perspective(t, Ms[:3], (dw, dh))
-    # WARP_INVERSE_MAP and preallocated output
-    out = torch.empty((B, dh, dw, 3), dtype=t.dtype, device="cuda")
-    r = W.warp_perspective(t, co.invert3x3(base), (dw, dh), flags=W.INTER_LINEAR | W.WARP_INVERSE_MAP, out=out)
-    assert r is out
-    check(out.cpu().numpy()[2], co.warp_perspective(frames[2], base, (dw, dh)))
+    # WARP_INVERSE_MAP and preallocated output (poisoned: unwritten pixels must not pass)
+    out = torch.full((B, dh, dw, 3), 77, dtype=t.dtype, device="cuda")
+    got = run_gpu(W, t, co.invert3x3(base), (dw, dh), W.INTER_LINEAR | W.WARP_INVERSE_MAP, out=out)  # (asserts the call returns `out`)
+    check({m: r[2] for m, r in got.items()}, co.warp_perspective(frames[2], base, (dw, dh)))
 
 
 def test_row_padding_and_frame_views(W):
@@ -103,18 +107,16 @@ def test_row_padding_and_frame_views(W):
     big = torch.from_numpy(wl.frame(7, sh, sw + 40, np.uint8)).cuda()
     view = big[:, 8:8 + sw]  # rows keep the pitch of the parent: not 16-byte aligned
     assert not view.is_contiguous()
-    got = W.warp_perspective(view, M, (dw, dh)).cpu().numpy()
-    check(got, co.warp_perspective(np.ascontiguousarray(view.cpu().numpy()), M, (dw, dh)))
+    check(run_gpu(W, view, M, (dw, dh), 1), co.warp_perspective(np.ascontiguousarray(view.cpu().numpy()), M, (dw, dh)))
     view4 = big[:, 16:16 + 576]
-    got = W.warp_perspective(view4, M, (dw, dh)).cpu().numpy()
-    check(got, co.warp_perspective(np.ascontiguousarray(view4.cpu().numpy()), M, (dw, dh)))
+    check(run_gpu(W, view4, M, (dw, dh), 1), co.warp_perspective(np.ascontiguousarray(view4.cpu().numpy()), M, (dw, dh)))
 
 
 @pytest.mark.parametrize("dtype", [np.uint8, np.float32])
 def test_border_value_identity_translation(W, dtype):
     src = wl.frame(1, 90, 150, dtype)
     eye = np.eye(3)
-    np.testing.assert_array_equal(run_gpu(W, src, eye, (100, 60), 1), src[:60, :100])
+    check(run_gpu(W, src, eye, (100, 60), 1), src[:60, :100])
     M = np.array([[1, 0, 5.0], [0, 1, -3.0], [0, 0, 1]])
     for interp in (0, 1):
         check(run_gpu(W, src, M, (170, 100), interp, border_value=[7, 200.4, 300][:3]),
@@ -124,9 +126,9 @@ def test_border_value_identity_translation(W, dtype):
     # rotation by 90 degrees and a flip: exact permutations
     h, w = src.shape[:2]
     R = np.array([[0, -1, h - 1.0], [1, 0, 0], [0, 0, 1]])
-    np.testing.assert_array_equal(run_gpu(W, src, R, (h, w), 1), np.rot90(src, -1))
+    check(run_gpu(W, src, R, (h, w), 1), np.rot90(src, -1))
     Fm = np.array([[-1, 0, w - 1.0], [0, 1, 0], [0, 0, 1]])
-    np.testing.assert_array_equal(run_gpu(W, src, Fm, (w, h), 0), src[:, ::-1])
+    check(run_gpu(W, src, Fm, (w, h), 0), src[:, ::-1])
 
 
 def test_degenerate_homographies(W):
@@ -139,7 +141,7 @@ def test_degenerate_homographies(W):
         check(run_gpu(W, src, M, (128, 96), interp), co.warp_perspective(src, M, (128, 96), interp))
     # far outside: nothing in bounds
     T = np.array([[1, 0, 1e6], [0, 1, 0], [0, 0, 1.0]])
-    assert not run_gpu(W, src, T, (64, 64), 1).any()
+    check(run_gpu(W, src, T, (64, 64), 1), np.zeros((64, 64, 3), np.uint8))
     with pytest.raises(ValueError):
         W.warp_perspective(torch.zeros((8, 8, 3), dtype=torch.uint8, device="cuda"), np.full((3, 3), np.nan), (8, 8))
     with pytest.raises(ValueError):
@@ -166,9 +168,9 @@ def test_numpy_cv2_call_shape(W):
     M = wl.synth_brno_H(1280, 720, 512, 512)
     out = bw.warpPerspective(img, M, (512, 512))
     assert out.dtype == np.uint8 and out.shape == (512, 512, 3)
-    check(out, co.warp_perspective(img, M, (512, 512)))
+    check_one(out, co.warp_perspective(img, M, (512, 512)))
     out = bw.warpPerspective(img, M, (512, 512), flags=bw.INTER_NEAREST, borderValue=(1, 2, 3))
-    check(out, co.warp_perspective(img, M, (512, 512), 0, border_value=[1, 2, 3]))
+    check_one(out, co.warp_perspective(img, M, (512, 512), 0, border_value=[1, 2, 3]))
 
 
 def test_footprint_matches_oracle(W):
@@ -196,9 +198,12 @@ def test_config2_batch32_1080p_to_1024(W, dtype):
         if i in (0, 13, 31):
             host[i] = f
         frames[i] = torch.from_numpy(f).cuda()
-    out = W.warp_perspective(frames, Ms, (dw, dh))
+    res = run_gpu(W, frames, Ms, (dw, dh), 1)
     for i, f in host.items():
-        check(out[i].cpu().numpy(), co.warp_perspective(f, Ms[i], (dw, dh), nthreads=8))
+        check({m: r[i] for m, r in res.items()}, co.warp_perspective(f, Ms[i], (dw, dh), nthreads=8))
+    np.testing.assert_array_equal(res["table"], res["plain"])  # (the frames without an oracle run: both modes agree)
+    out = torch.from_numpy(res["plain"]).cuda()
+    del res
     # property: same frames, same matrix -> identical outputs, regardless of batch position
     frames[5] = frames[0]
     Ms2 = Ms.copy()
@@ -230,9 +235,12 @@ def test_config2_size_other_paths(W, dtype, interp, kind):
     f0 = torch.from_numpy(host[0]).cuda()
     for i in range(B):
         frames[i] = torch.from_numpy(host[i]).cuda() if i in host else f0.flip(i % 2)
-    out = W.warp_perspective(frames, Ms, (dw, dh), flags=interp)
+    res = run_gpu(W, frames, Ms, (dw, dh), interp)
     for i, f in host.items():
-        check(out[i].cpu().numpy(), co.warp_perspective(f, Ms[i], (dw, dh), interp, nthreads=8))
+        check({m: r[i] for m, r in res.items()}, co.warp_perspective(f, Ms[i], (dw, dh), interp, nthreads=8))
+    np.testing.assert_array_equal(res["table"], res["plain"])
+    out = torch.from_numpy(res["plain"]).cuda()
+    del res
     # a frame's result does not depend on its place in the batch (frames 1.. are flips of frame 0: redo one of them alone)
     j = 6
     alone = W.warp_perspective(frames[j:j + 1], Ms[j:j + 1], (dw, dh), flags=interp)
@@ -270,14 +278,12 @@ def test_every_tile_shape_matches_oracle(W, dtype, interp):
     big = torch.from_numpy(wl.frame(7, 300, 640, dtype)).cuda()
     view = big[:, 16:16 + 576]
     Mv = wl.keystone_H(576, 300, 128, 96)
-    got = W.warp_perspective(view, Mv, (128, 96), flags=interp).cpu().numpy()
-    check(got, co.warp_perspective(np.ascontiguousarray(view.cpu().numpy()), Mv, (128, 96), interp))
+    check(run_gpu(W, view, Mv, (128, 96), interp), co.warp_perspective(np.ascontiguousarray(view.cpu().numpy()), Mv, (128, 96), interp))
     # odd destination widths: rows start at byte offsets that rule out the wide stores
     for c in (1, 2, 3):
         src = wl.frame(5, 200, 320, dtype, c)
         Mo = wl.synth_brno_H(320, 200, 301, 41)
-        got = W.warp_perspective(torch.from_numpy(src).cuda(), Mo, (301, 41), flags=interp).cpu().numpy()
-        check(got, co.warp_perspective(src, Mo, (301, 41), interp))
+        check(run_gpu(W, src, Mo, (301, 41), interp), co.warp_perspective(src, Mo, (301, 41), interp))
 
 
 def test_config4_full_per_gpu_shard_properties(W):
@@ -291,10 +297,13 @@ def test_config4_full_per_gpu_shard_properties(W):
     frames = torch.empty((B, sh, sw, 3), dtype=torch.uint8, device="cuda")
     for i in range(B):
         frames[i] = uniq[i % 4] if i < 4 else uniq[i % 4].flip(i % 2)
-    out = W.warp_perspective(frames, Ms, (dw, dh))
+    res = run_gpu(W, frames, Ms, (dw, dh), 1)
     for i in (0, 3, 31):
         exp = co.warp_perspective(frames[i].cpu().numpy(), Ms[i], (dw, dh), nthreads=8)
-        assert np.array_equal(out[i].cpu().numpy(), exp), "frame %d" % i
+        P.check_modes({m: r[i] for m, r in res.items()}, exp, lambda got, exp: np.testing.assert_array_equal(got, exp, err_msg="frame %d" % i))
+    np.testing.assert_array_equal(res["table"], res["plain"])
+    out = torch.from_numpy(res["plain"]).cuda()
+    del res
     # batch-position invariance: frame 5 and its homography moved to slot 29 (and the reverse) give the same pixels
     perm = list(range(B))
     perm[5], perm[29] = 29, 5
@@ -322,10 +331,8 @@ def test_side_by_side_rois_of_one_image(W):
         left, right = big[:, :w // 2], big[:, w // 2:]
         M = wl.keystone_H(w // 2, h, w // 2, h)
         exp = co.warp_perspective(np.ascontiguousarray(img[:, :w // 2]), M, (w // 2, h))
-        out = W.warp_perspective(left, M, (w // 2, h), out=right)
-        torch.cuda.synchronize()
-        assert out is right
-        check(big[:, w // 2:].cpu().numpy(), exp)
+        check(run_gpu(W, left, M, (w // 2, h), 1, out=right), exp)  # (asserts the call returns `right`)
+        check_one(big[:, w // 2:].cpu().numpy(), exp)
         np.testing.assert_array_equal(big[:, :w // 2].cpu().numpy(), img[:, :w // 2])  # the source half is untouched
         with pytest.raises(ValueError, match="overlap"):
             W.warp_perspective(left, M, (w // 2, h), out=big[:, w // 2 - 1:w - 1])
@@ -349,7 +356,7 @@ def test_validated_launch_cache_hits_and_misses(W):
     W.warp_perspective(src, None, (dw, dh), out=out, M_inv_device=minv)  # the hit: same buffers, new pixels
     torch.cuda.synchronize()
     assert len(W._plans) == 1
-    check(out.cpu().numpy(), co.warp_perspective(f1, M, (dw, dh)))
+    check_one(out.cpu().numpy(), co.warp_perspective(f1, M, (dw, dh)))
     # same shape and strides, other dtype: 36-byte matrices must not be read as 72-byte ones
     with pytest.raises(ValueError):
         W.warp_perspective(src, None, (dw, dh), out=out, M_inv_device=minv.to(torch.float32))
@@ -416,9 +423,9 @@ def test_two_step_small_branch_pixel_for_pixel():
     img = wl.frame(0, 1080, 1920, np.uint8)
     M_small = wl.synth_brno_H(852, 480, 320, 640)
     t = torch.from_numpy(img).cuda()
-    got = warp.warp_perspective(resize(t, (852, 480)), M_small, (320, 640)).cpu().numpy()
+    got = run_gpu(warp, resize(t, (852, 480)), M_small, (320, 640), 1)
     exp = co.warp_perspective(co.resize_linear_u8(img, (852, 480)), M_small, (320, 640), 1)
-    np.testing.assert_array_equal(got, exp)
+    check(got, exp)
 
 
 def test_resize_random_shapes():
@@ -527,3 +534,156 @@ def test_tile_verdict_tables_reproduce_the_plain_call():
     mine = warp.device_inverse(Ms, dev).clone()  # a tensor the caller owns: no table is kept for it
     warp.warp_perspective(t, None, (dw, dh), M_inv_device=mine)
     assert len(warp._class_tables) == 1
+
+
+# ---- the verdict-table cache of the Python entry (bev_amd/warp.py::_tile_classes, _plans): a table is trusted by the kernel, so it
+# ---- must never outlive the matrix contents, the memory or the fill it belongs to.
+def _class_entry(W, minv):
+    hits = [v for k, v in W._class_tables.items() if k[0] == minv.data_ptr() and v[1] is minv]
+    assert len(hits) == 1
+    return hits[0]
+
+
+def test_verdict_tables_follow_in_place_writes_of_the_matrices(W):
+    """A device_inverse tensor rewritten in place (minv.copy_) after its table was filled: the next launch -- through the slow path, and
+    through a plan that carries the old table -- refills it and equals the oracle of the new matrices; the value cache stops handing the
+    rewritten tensor out for the old key.  The matrices are chosen so that stale verdicts could only err on the safe side: the new map
+    (a translation) keeps the whole destination deep inside the frame, the old one is the same map shifted right so that the right half
+    of the destination leaves the frame -- a stale table says outside / edge-cut where the truth is interior (border pixels: a clean
+    mismatch), never the reverse."""
+    sw, sh, dw, dh = 640, 360, 512, 64
+    dev = torch.device("cuda", 0)
+    f = wl.frame(50, sh, sw, np.uint8)
+    src = torch.from_numpy(f).to(dev)
+    M2 = np.array([[1, 0, -40.0], [0, 1, -100.0], [0, 0, 1]])  # destination (x, y) samples source (x + 40, y + 100)
+    exp = co.warp_perspective(f, M2, (dw, dh), 1)
+    inv2 = torch.from_numpy(W.invert_homography(M2).reshape(1, 3, 3)).to(dev)
+    for ty, path in ((100.0, "slow path"), (101.0, "plan")):
+        M = np.array([[1, 0, -400.0], [0, 1, -ty], [0, 0, 1]])  # source x 400 .. 911: tiles right of x = 240 sample outside the frame
+        minv = W.device_inverse(M, dev)
+        out = torch.full((dh, dw, 3), 77, dtype=torch.uint8, device=dev)
+        if path == "plan":
+            W.warp_perspective(src, None, (dw, dh), out=out, M_inv_device=minv)  # fills the table, stores a plan that carries it
+            assert any(p[3] is not None and p[4] is minv for p in W._plans.values())
+        else:
+            W.warp_perspective(src, None, (dw, dh), M_inv_device=minv)
+        torch.cuda.synchronize()
+        old = _class_entry(W, minv)
+        minv.copy_(inv2)
+        if path == "plan":
+            got = W.warp_perspective(src, None, (dw, dh), out=out, M_inv_device=minv)
+            assert got is out
+        else:
+            got = W.warp_perspective(src, None, (dw, dh), M_inv_device=minv)
+        torch.cuda.synchronize()
+        np.testing.assert_array_equal(got.cpu().numpy(), exp, err_msg=path)
+        new = _class_entry(W, minv)
+        assert new[0] is not old[0] and new[2] == minv._version  # refilled for the written contents
+        again = W.device_inverse(M, dev)
+        assert again is not minv
+        np.testing.assert_array_equal(again.cpu().numpy(), W.invert_homography(M).reshape(1, 3, 3))
+
+
+def _recording_lib(monkeypatch, on_call):
+    """Installs a proxy of the loaded library as bev_amd._lib.load(): on_call(name, args) runs after every warp entry point's call.
+    Installed before the calls under test, so their plans store the wrapped callables too."""
+    from bev_amd import _lib
+    real = _lib.load()
+
+    class Recording:
+        def __getattr__(self, name):
+            fn = getattr(real, name)
+            if not name.startswith("bevwarp_warp"):
+                return fn
+
+            def call(*args):
+                st = fn(*args)
+                on_call(name, args)
+                return st
+            return call
+    proxy = Recording()
+    monkeypatch.setattr(_lib, "load", lambda: proxy)
+    return real
+
+
+def test_graph_capture_through_a_plan_with_a_table(W, monkeypatch):
+    """tools.graphed_step.GraphedStep after eager warm-up calls that stored a plan carrying a verdict table: the capture must launch the
+    plain entry point (a graph would replay the table's address, which nothing keeps alive).  Asserted on the host before the graph is
+    ever replayed; then the table is dropped from every cache, the allocator hands its memory out again filled with bogus verdicts, and
+    three replays on new frames equal the oracle."""
+    from tools.graphed_step import GraphedStep
+    launched = []
+    real = _recording_lib(monkeypatch, lambda name, args: launched.append((name, torch.cuda.is_current_stream_capturing())))
+    W._plans.clear()
+    sw, sh, dw, dh = 640, 360, 512, 64
+    M = wl.keystone_H(sw, sh, dw, dh)
+    src = torch.zeros((sh, sw, 3), dtype=torch.uint8, device="cuda")
+    out = torch.empty((dh, dw, 3), dtype=torch.uint8, device="cuda")
+    minv = W.device_inverse(M, src.device)
+    g = GraphedStep(lambda: W.warp_perspective(src, None, (dw, dh), out=out, M_inv_device=minv))
+    eager = [n for n, capturing in launched if not capturing]
+    captured = [n for n, capturing in launched if capturing]
+    assert eager.count("bevwarp_warp_classes") >= 2  # warm-up: the fill, then launches reading the table (the last ones through the plan)
+    assert any(p[3] is not None for p in W._plans.values())
+    assert captured == ["bevwarp_warp"], captured
+    nbytes = real.bevwarp_tile_classes_bytes(1, sh, sw, dh, dw, 3, 0, 1)
+    W._plans.clear()
+    W._class_tables.clear()
+    churn = [torch.full((nbytes // 4,), -0x7ffffffe, dtype=torch.int32, device="cuda") for _ in range(16)]  # 0x80000002: "outside"
+    torch.cuda.synchronize()
+    for i in range(3):
+        f = wl.frame(90 + i, sh, sw, np.uint8)
+        src.copy_(torch.from_numpy(f).cuda())
+        g.replay()
+        torch.cuda.synchronize()
+        np.testing.assert_array_equal(out.cpu().numpy(), co.warp_perspective(f, M, (dw, dh), 1))
+    del churn
+    W._plans.clear()  # (they hold the recording proxy's callables)
+
+
+def test_verdict_table_filled_on_one_stream_is_used_on_another(W, monkeypatch):
+    """The first call, on stream A held back by a spin of some tens of ms, fills the table; a call on stream B then finds it in the cache.
+    The fill must have run before the table is cached -- asserted on the host before anything is launched on B -- and B's launch,
+    which reads the table, equals the oracle."""
+    dev = torch.device("cuda", 0)
+    fills, uses = [], []
+
+    def on_call(name, args):
+        if name == "bevwarp_warp_classes":
+            if args[-2] == 1:  # BEVWARP_CLASSES_FILL: mark the point right behind the fill on its stream
+                ev = torch.cuda.Event()
+                ev.record(torch.cuda.ExternalStream(args[-1].value, device=dev))
+                fills.append(ev)
+            else:
+                uses.append(args[-1].value)
+    _recording_lib(monkeypatch, on_call)
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    torch.cuda._sleep(1000000)
+    t1.record()
+    t1.synchronize()
+    cycles = int(min(max(1e6 * 40.0 / max(t0.elapsed_time(t1), 1e-3), 1e6), 5e8))  # ~40 ms, bounded
+    sw, sh, dw, dh = 640, 360, 448, 72
+    M = wl.jitter_H(wl.keystone_H(sw, sh, dw, dh), 3)
+    f = wl.frame(95, sh, sw, np.uint8)
+    src = torch.from_numpy(f).to(dev)
+    W.device_inverse(M, dev)  # (uploaded now: the upload on a miss is a blocking copy, which would wait for the spin below by itself)
+    a, b = torch.cuda.Stream(dev), torch.cuda.Stream(dev)
+    a.wait_stream(torch.cuda.current_stream(dev))
+    b.wait_stream(torch.cuda.current_stream(dev))
+    spun = torch.cuda.Event()
+    with torch.cuda.stream(a):
+        torch.cuda._sleep(cycles)
+        spun.record(a)
+        assert not spun.query()  # (A is still held back when the fill is queued behind the spin)
+        out_a = W.warp_perspective(src, M, (dw, dh))
+    assert len(fills) == 1
+    assert fills[0].query(), "the verdict table was cached before its fill had run"
+    with torch.cuda.stream(b):
+        out_b = W.warp_perspective(src, M, (dw, dh))
+    assert len(fills) == 1 and uses[-1] == b.cuda_stream  # B read the cached table
+    torch.cuda.synchronize()
+    exp = co.warp_perspective(f, M, (dw, dh), 1)
+    np.testing.assert_array_equal(out_b.cpu().numpy(), exp)
+    np.testing.assert_array_equal(out_a.cpu().numpy(), exp)
+    W._plans.clear()
