@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "bevwarp.h"
+#include "warp_border.h"
 #include "warp_kernels.h"
 
 #pragma clang fp contract(off)
@@ -68,7 +69,7 @@ const char* bevwarp_strerror(int status) {
     switch (status) {
         case BEVWARP_OK: return "ok";
         case BEVWARP_ERR_BAD_ARG: return "bad argument (null pointer, non-positive size or misaligned stride)";
-        case BEVWARP_ERR_UNSUPPORTED: return "unsupported dtype / channel count / interpolation";
+        case BEVWARP_ERR_UNSUPPORTED: return "unsupported dtype / channel count / interpolation / border mode";
         case BEVWARP_ERR_TOO_LARGE: return "source image side exceeds 32767 px, a row 16 MiB or a frame 2 GiB";
         case BEVWARP_ERR_NOT_FINITE: return "homography contains NaN or Inf";
         case BEVWARP_ERR_HIP: return "HIP runtime error (see bevwarp_last_hip_error)";
@@ -113,12 +114,12 @@ struct PlanarOut {  // bevwarp_warp_planar: float32 channel planes instead of in
     const double *scale, *bias;
 };
 
-int warp_impl(const void* src, void* dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int channels,
-              int64_t src_frame_stride, int64_t src_row_stride, int64_t dst_frame_stride, int64_t dst_row_stride, const double* M_inv,
-              int m_count, int dtype, int interp, const double* border_value, void* stream, const PlanarOut* po, void* classes = nullptr,
-              int classes_mode = 0, int64_t* classes_bytes = nullptr) {
-    using namespace bevwarp;
-    if (!classes_bytes && (!src || !dst || !M_inv)) return BEVWARP_ERR_BAD_ARG;
+// The argument checks of a warp (bevwarp_warp and its variants, bevwarp_warp_border): BEVWARP_OK or the status to return.
+// sizes_only: the pointers are placeholders (bevwarp_tile_classes_bytes) and may be NULL.
+int check_warp_args(const void* src, const void* dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int channels,
+                    int64_t src_frame_stride, int64_t src_row_stride, int64_t dst_frame_stride, int64_t dst_row_stride, const double* M_inv,
+                    int m_count, int dtype, int interp, const PlanarOut* po, bool sizes_only) {
+    if (!sizes_only && (!src || !dst || !M_inv)) return BEVWARP_ERR_BAD_ARG;
     if (batch < 0 || src_h <= 0 || src_w <= 0 || dst_h <= 0 || dst_w <= 0) return BEVWARP_ERR_BAD_ARG;
     if (dtype != BEVWARP_U8 && dtype != BEVWARP_F32) return BEVWARP_ERR_UNSUPPORTED;
     if (interp != BEVWARP_NEAREST && interp != BEVWARP_LINEAR) return BEVWARP_ERR_UNSUPPORTED;
@@ -150,6 +151,17 @@ int warp_impl(const void* src, void* dst, int batch, int src_h, int src_w, int d
                                dst_row_stride, dst_frame_stride, batch)) {
         return BEVWARP_ERR_OVERLAP;
     }
+    return BEVWARP_OK;
+}
+
+int warp_impl(const void* src, void* dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int channels,
+              int64_t src_frame_stride, int64_t src_row_stride, int64_t dst_frame_stride, int64_t dst_row_stride, const double* M_inv,
+              int m_count, int dtype, int interp, const double* border_value, void* stream, const PlanarOut* po, void* classes = nullptr,
+              int classes_mode = 0, int64_t* classes_bytes = nullptr) {
+    using namespace bevwarp;
+    const int st = check_warp_args(src, dst, batch, src_h, src_w, dst_h, dst_w, channels, src_frame_stride, src_row_stride, dst_frame_stride,
+                                   dst_row_stride, M_inv, m_count, dtype, interp, po, classes_bytes != nullptr);
+    if (st != BEVWARP_OK || batch == 0) return st;
 
     WarpArgs a;
     memset(&a, 0, sizeof(a));
@@ -243,6 +255,54 @@ int bevwarp_warp(const void* src, void* dst, int batch, int src_h, int src_w, in
                  int m_count, int dtype, int interp, const double* border_value, void* stream) {
     return warp_impl(src, dst, batch, src_h, src_w, dst_h, dst_w, channels, src_frame_stride, src_row_stride, dst_frame_stride, dst_row_stride,
                      M_inv, m_count, dtype, interp, border_value, stream, nullptr);
+}
+
+int bevwarp_warp_border(const void* src, void* dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int channels,
+                        int64_t src_frame_stride, int64_t src_row_stride, int64_t dst_frame_stride, int64_t dst_row_stride, const double* M_inv,
+                        int m_count, int dtype, int interp, int border_mode, const double* border_value, void* stream) {
+    using namespace bevwarp;
+    if (border_mode == BEVWARP_BORDER_CONSTANT)  // the constant border is bevwarp_warp itself
+        return bevwarp_warp(src, dst, batch, src_h, src_w, dst_h, dst_w, channels, src_frame_stride, src_row_stride, dst_frame_stride, dst_row_stride,
+                            M_inv, m_count, dtype, interp, border_value, stream);
+    if (border_mode < BEVWARP_BORDER_REPLICATE || border_mode > BEVWARP_BORDER_TRANSPARENT) return BEVWARP_ERR_UNSUPPORTED;  // (BORDER_ISOLATED too)
+    const int st = check_warp_args(src, dst, batch, src_h, src_w, dst_h, dst_w, channels, src_frame_stride, src_row_stride, dst_frame_stride,
+                                   dst_row_stride, M_inv, m_count, dtype, interp, nullptr, false);
+    if (st != BEVWARP_OK || batch == 0) return st;
+    (void)border_value;  // (read by no mode but the constant one, as in OpenCV)
+    if (dst_w > (1 << 20) || dst_h > (1 << 20)) return BEVWARP_ERR_TOO_LARGE;
+    BorderArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src = (const uint8_t*)src;
+    a.dst = (uint8_t*)dst;
+    a.minv = M_inv;
+    a.src_fs = src_frame_stride, a.src_rs = src_row_stride;
+    a.dst_fs = dst_frame_stride, a.dst_rs = dst_row_stride;
+    a.src_h = src_h, a.src_w = src_w, a.dst_h = dst_h, a.dst_w = dst_w;
+    a.m_stride = m_count == 1 ? 0 : 9;
+    a.bw0 = block_width(dst_w, dst_h);
+    a.tiles_x = (dst_w + kBorderTileW - 1) / kBorderTileW;
+    a.tiles_per_frame = a.tiles_x * ((dst_h + kBorderTileH - 1) / kBorderTileH);
+    const int64_t items = (int64_t)batch * a.tiles_per_frame;
+    if (items > 0x7fffffffLL) return BEVWARP_ERR_TOO_LARGE;
+    a.bw0_magic = div_magic((uint64_t)dst_w + kBorderTileW, (uint32_t)a.bw0);
+    a.tx_magic = div_magic((uint64_t)a.tiles_per_frame, (uint32_t)a.tiles_x);
+    a.tpf_magic = div_magic((uint64_t)items, (uint32_t)a.tiles_per_frame);
+    // the remainder periods of the mode (unused by REPLICATE and TRANSPARENT) and offsets that make every saturated index
+    // (>= -32768) non-negative
+    auto period = [&](int n, uint32_t& per, uint32_t& off, uint32_t& mag) {
+        per = border_mode == BEVWARP_BORDER_WRAP ? (uint32_t)n : border_mode == BEVWARP_BORDER_REFLECT ? 2u * n : (n > 1 ? 2u * n - 2u : 1u);
+        off = (32768u + per - 1u) / per * per;
+        mag = div_magic((uint64_t)off + 32769u, per);
+    };
+    period(src_w, a.per_x, a.off_x, a.mag_x);
+    period(src_h, a.per_y, a.off_y, a.mag_y);
+    const int esz = dtype == BEVWARP_U8 ? 1 : 4;
+    const int dst_align = dtype == BEVWARP_U8 ? (channels == 4 ? 16 : (channels == 2 ? 8 : 4)) : 16;
+    a.dst_vec_ok = ((uintptr_t)dst % dst_align == 0) && (dst_row_stride % dst_align == 0) && (dst_frame_stride % dst_align == 0);
+    const int src_align = (dtype == BEVWARP_U8 && (channels == 2 || channels == 4)) ? channels : esz;
+    a.src_vec_ok = ((uintptr_t)src % src_align == 0) && (src_row_stride % src_align == 0) && (batch == 1 || src_frame_stride % src_align == 0);
+    const hipError_t e = launch_warp_border(a, dtype, channels, interp, border_mode, items, (hipStream_t)stream);
+    return e == hipSuccess ? BEVWARP_OK : hip_fail(e);
 }
 
 int bevwarp_warp_classes(const void* src, void* dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int channels, int64_t src_frame_stride,

@@ -20,7 +20,16 @@ from . import _lib
 INTER_NEAREST = _lib.INTER_NEAREST
 INTER_LINEAR = _lib.INTER_LINEAR
 WARP_INVERSE_MAP = 16  # cv2 flag value
+# cv2 border modes (cv::BorderTypes values); BORDER_CONSTANT is the warp kernel's own, the others are bevwarp_warp_border
 BORDER_CONSTANT = 0
+BORDER_REPLICATE = 1
+BORDER_REFLECT = 2
+BORDER_WRAP = 3
+BORDER_REFLECT_101 = 4
+BORDER_REFLECT101 = BORDER_REFLECT_101
+BORDER_DEFAULT = BORDER_REFLECT_101
+BORDER_TRANSPARENT = 5
+_BORDER_MODES = (BORDER_CONSTANT, BORDER_REPLICATE, BORDER_REFLECT, BORDER_WRAP, BORDER_REFLECT_101, BORDER_TRANSPARENT)
 
 _DTYPES = {torch.uint8: _lib.U8, torch.float32: _lib.F32}
 
@@ -181,7 +190,7 @@ def _tile_classes(M_inv_device, n_m, call_args, stream):
     return table
 
 
-def warp_perspective(src, M, dsize, flags=INTER_LINEAR, border_value=None, out=None, M_inv_device=None):
+def warp_perspective(src, M, dsize, flags=INTER_LINEAR, border_value=None, out=None, M_inv_device=None, border_mode=BORDER_CONSTANT):
     """Batched perspective warp on the GPU.
 
     src      (B, H, W, C) or (H, W, C) or (H, W) uint8 / float32 CUDA tensor, channels-last, rows contiguous.
@@ -190,6 +199,11 @@ def warp_perspective(src, M, dsize, flags=INTER_LINEAR, border_value=None, out=N
     dsize    (width, height) = (u_size, v_size), as OpenCV.
     flags    INTER_LINEAR (default) or INTER_NEAREST, optionally | WARP_INVERSE_MAP.
     out      optional preallocated result; M_inv_device optional (n, 3, 3) f64 CUDA tensor to skip the cache.
+    border_mode  BORDER_CONSTANT (default; `border_value`), BORDER_REPLICATE, BORDER_REFLECT, BORDER_WRAP, BORDER_REFLECT_101
+             (every tap reads a source pixel, border_value is ignored) or BORDER_TRANSPARENT: only pixels whose taps are all
+             inside the source are written, every other pixel of `out` keeps its contents (warp several cameras into one
+             canvas, one call each).  TRANSPARENT without `out` returns a zeroed result where it writes nothing (OpenCV would
+             leave those pixels uninitialised).  Semantics: include/bevwarp.h, bevwarp_warp_border.
     Returns a tensor shaped like src with (height, width) replaced.  Asynchronous on the current stream."""
     if out is not None and M_inv_device is not None and border_value is None:
         # Steady-state call of a camera loop: same buffers, same geometry as a call that has already been validated.  The
@@ -199,7 +213,8 @@ def warp_perspective(src, M, dsize, flags=INTER_LINEAR, border_value=None, out=N
             # (addresses can be recycled by the allocator: everything the slow path validates is part of the key -- dtypes and
             # devices of all three tensors included, or a float32 / CPU matrix tensor at a recycled address would skip _check_minv)
             key = (src.data_ptr(), out.data_ptr(), M_inv_device.data_ptr(), src.shape, src.stride(), out.shape, out.stride(), M_inv_device.shape,
-                   M_inv_device.stride(), src.dtype, out.dtype, M_inv_device.dtype, src.device, out.device, M_inv_device.device, dsize[0], dsize[1], flags)
+                   M_inv_device.stride(), src.dtype, out.dtype, M_inv_device.dtype, src.device, out.device, M_inv_device.device, dsize[0], dsize[1], flags,
+                   border_mode)  # (a plan serves the border mode it was made for only)
             plan = _plans.get(key)
         except (AttributeError, TypeError, IndexError):
             plan = None
@@ -223,6 +238,9 @@ def warp_perspective(src, M, dsize, flags=INTER_LINEAR, border_value=None, out=N
             return out
     else:
         key = None
+    if border_mode not in _BORDER_MODES:
+        raise ValueError("unsupported border mode %r (BORDER_CONSTANT, _REPLICATE, _REFLECT, _WRAP, _REFLECT_101, _TRANSPARENT)" % (border_mode,))
+    border_mode = int(border_mode)
     if not isinstance(src, torch.Tensor) or not src.is_cuda:
         raise ValueError("warp_perspective needs a CUDA (HIP) tensor; use warpPerspective for numpy images")
     if src.dtype not in _DTYPES:
@@ -248,21 +266,25 @@ def warp_perspective(src, M, dsize, flags=INTER_LINEAR, border_value=None, out=N
         M_inv_device = device_inverse(M, s4.device, inverse_given=bool(int(flags) & WARP_INVERSE_MAP))
     n_m = _check_minv(M_inv_device, s4.device, B)
     if out is None:
-        d4 = torch.empty((B, dh, dw, C), dtype=s4.dtype, device=s4.device)
+        d4 = (torch.zeros if border_mode == BORDER_TRANSPARENT else torch.empty)((B, dh, dw, C), dtype=s4.dtype, device=s4.device)
     else:
         _check_out(out, s4.dtype, s4.device, B * dh * dw * C)
         d4 = out.reshape(B, dh, dw, C)
         if d4.data_ptr() != out.data_ptr() or d4.stride(3) != 1 or d4.stride(2) != C:
             raise ValueError("out must be a contiguous-row channels-last tensor")
-    bv = _border(border_value, C)
+    bv = _border(border_value, C) if border_mode == BORDER_CONSTANT else None  # (only the constant border reads it)
     stream = torch.cuda.current_stream(s4.device).cuda_stream
     args = (s4.data_ptr(), d4.data_ptr(), B, H, W, dh, dw, C, s4.stride(0) * esz, s4.stride(1) * esz, d4.stride(0) * esz, d4.stride(1) * esz,
             M_inv_device.data_ptr(), n_m, _DTYPES[s4.dtype], interp, None if bv is None else bv.ctypes.data_as(ctypes.c_void_p))
-    fn = plain = _lib.load().bevwarp_warp
-    table = _tile_classes(M_inv_device, n_m, args, stream)
-    if table is not None:  # verdicts of these very matrices and this geometry: the kernel reads them instead of deriving them
-        table.record_stream(torch.cuda.current_stream(s4.device))
-        fn, args = _lib.load().bevwarp_warp_classes, args + (table.data_ptr(), 0)
+    if border_mode == BORDER_CONSTANT:
+        fn = plain = _lib.load().bevwarp_warp
+        table = _tile_classes(M_inv_device, n_m, args, stream)
+        if table is not None:  # verdicts of these very matrices and this geometry: the kernel reads them instead of deriving them
+            table.record_stream(torch.cuda.current_stream(s4.device))
+            fn, args = _lib.load().bevwarp_warp_classes, args + (table.data_ptr(), 0)
+    else:  # the other borders: a kernel of their own, which classifies no tiles (no verdict table)
+        fn = plain = _lib.load().bevwarp_warp_border
+        args, table = args[:-1] + (border_mode, None), None
     with torch.cuda.device(s4.device):
         st = fn(*args, ctypes.c_void_p(stream))
     _lib.check(st)
@@ -361,15 +383,25 @@ def scalar_border(borderValue, channels):
 
 def warpPerspective(src, M, dsize, dst=None, flags=INTER_LINEAR, borderMode=BORDER_CONSTANT, borderValue=0, device="cuda"):
     """cv2.warpPerspective call shape for numpy images: uploads, warps on the GPU, downloads.
-    (The per-frame PCIe round trip dominates here; batch frames with warp_perspective for throughput.)"""
-    if borderMode != BORDER_CONSTANT:
-        raise ValueError("only BORDER_CONSTANT is implemented (the reference never passes another mode)")
+    (The per-frame PCIe round trip dominates here; batch frames with warp_perspective for throughput.)
+    borderMode: any of the six BORDER_* modes above.  With BORDER_TRANSPARENT a given `dst` is the canvas: it is uploaded, the
+    pixels the source covers are written into it and it is returned (several cameras stitched into one image, one call each);
+    without one, uncovered pixels are 0."""
+    if borderMode not in _BORDER_MODES:
+        raise ValueError("unsupported borderMode %r (BORDER_CONSTANT, _REPLICATE, _REFLECT, _WRAP, _REFLECT_101, _TRANSPARENT)" % (borderMode,))
     img = np.asarray(src)
     if img.dtype not in (np.uint8, np.float32):
         raise ValueError("unsupported dtype %s (uint8 / float32)" % img.dtype)
+    dw, dh = int(dsize[0]), int(dsize[1])
+    shape = (dh, dw) + tuple(img.shape[2:])
+    canvas = None
+    if borderMode == BORDER_TRANSPARENT and dst is not None:
+        if not isinstance(dst, np.ndarray) or dst.shape != shape or dst.dtype != img.dtype:
+            raise ValueError("dst must be a %s array of shape %s (the canvas BORDER_TRANSPARENT writes into)" % (img.dtype, shape))
+        canvas = torch.from_numpy(np.ascontiguousarray(dst)).to(device)
     t = torch.from_numpy(np.ascontiguousarray(img)).to(device)
     bv = scalar_border(borderValue, 1 if img.ndim == 2 else img.shape[2])
-    res = warp_perspective(t, np.asarray(M, dtype=np.float64), dsize, flags=flags, border_value=bv).cpu().numpy()
+    res = warp_perspective(t, np.asarray(M, dtype=np.float64), dsize, flags=flags, border_value=bv, out=canvas, border_mode=borderMode).cpu().numpy()
     if dst is not None:
         dst[...] = res
         return dst

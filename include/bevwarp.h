@@ -7,6 +7,8 @@
  *
  *   bevwarp_warp            cv2.warpPerspective(img, H_bev_img, (u_size, v_size))
  *                             vis_homo.py:89, vis_homo.py:91, bev/tool/compo.py:38,46,47
+ *   bevwarp_warp_border     cv2.warpPerspective(img, H, dsize, dst, flags, borderMode): the drop-in surface's other borders
+ *                             (the reference passes none; stitching cameras with BORDER_TRANSPARENT needs one)
  *   bevwarp_warp_classes, bevwarp_tile_classes_bytes
  *                           the same call inside a camera loop (one H_bev_img, every frame of the video): vis_homo.py:85-91
  *   bevwarp_invert_homography  the cv::invert(M) step inside that call (M is the forward src->dst map)
@@ -101,6 +103,38 @@ int bevwarp_warp(const void *src, void *dst, int batch, int src_h, int src_w, in
                  int64_t src_frame_stride, int64_t src_row_stride, int64_t dst_frame_stride, int64_t dst_row_stride,
                  const double *M_inv, int m_count, int dtype, int interp, const double *border_value /*HOST*/,
                  void *stream);
+
+/* Same numeric values as OpenCV's cv::BorderTypes (cv2.BORDER_*). */
+typedef enum bevwarp_border {
+    BEVWARP_BORDER_CONSTANT = 0,
+    BEVWARP_BORDER_REPLICATE = 1,
+    BEVWARP_BORDER_REFLECT = 2,
+    BEVWARP_BORDER_WRAP = 3,
+    BEVWARP_BORDER_REFLECT_101 = 4,
+    BEVWARP_BORDER_TRANSPARENT = 5
+} bevwarp_border;
+
+/*
+ * bevwarp_warp with OpenCV's other border modes: cv2.warpPerspective(..., borderMode=border_mode).  Arguments up to `interp`
+ * and their checks are bevwarp_warp's; the coordinate maps (and their 1/32-px quantisation) are too.  Per destination pixel,
+ * with (sx, sy) the integer source position (bilinear: X >> 5, Y >> 5) SATURATED TO INT16 as OpenCV's maps are:
+ *   BEVWARP_BORDER_CONSTANT     exactly bevwarp_warp (the call is delegated to it; border_value as there).
+ *   BEVWARP_BORDER_REPLICATE    every tap index p (sx, sx + 1, sy, sy + 1; nearest: sx, sy) goes through OpenCV's
+ *   BEVWARP_BORDER_REFLECT      borderInterpolate(p, len, mode) -- clamp / reflect with the edge pixel repeated (fedcba|abcd) /
+ *   BEVWARP_BORDER_WRAP         p mod len / reflect about the edge pixel (dcb|abcd); len 1 maps every index to 0 -- and the
+ *   BEVWARP_BORDER_REFLECT_101  four taps are blended as bevwarp_warp blends them.  No pixel is the border value.
+ *   BEVWARP_BORDER_TRANSPARENT  only inliers are written: nearest 0 <= sx < src_w and 0 <= sy < src_h; bilinear
+ *                               0 <= sx <= src_w - 2 and 0 <= sy <= src_h - 2 (remapBilinear's test: an identity warp leaves
+ *                               the last source column and row unwritten).  Every other destination byte is neither read
+ *                               nor written -- dst keeps what it held: warping several cameras into one canvas, one call each.
+ *   border_value  HOST; read by BEVWARP_BORDER_CONSTANT only (ignored otherwise, as in OpenCV).
+ *   border_mode   any other value (OpenCV's BORDER_ISOLATED bit included) returns BEVWARP_ERR_UNSUPPORTED.
+ * Semantics restated from OpenCV 3.x-4.x imgwarp.cpp (remapNearest / remapBilinear); parity unpinned, like the rest of the warp.
+ */
+int bevwarp_warp_border(const void *src, void *dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int channels,
+                        int64_t src_frame_stride, int64_t src_row_stride, int64_t dst_frame_stride, int64_t dst_row_stride,
+                        const double *M_inv, int m_count, int dtype, int interp, int border_mode,
+                        const double *border_value /*HOST*/, void *stream);
 
 /*
  * bevwarp_warp with the per-tile verdicts of an earlier launch (ABI v7).  Which way a tile is processed -- inside the frame, outside,
