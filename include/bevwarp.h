@@ -252,7 +252,7 @@ int bevwarp_rbox_transform(const void *boxes, int n, int stride, const double *H
  *   dets_img[i]       = dehomogenise(H_img_world @ (dets_world[i].xy, 1))   when H_img_world    n x 2
  * dets_bev rows have det_stride >= 5 values, trks_world rows trk_stride >= 5 (a tracker's state row may carry more).
  * H_world_bev as in bevwarp_rbox_transform; H_img_world (HOST, 9 doubles) may be NULL (then dets_img is not touched).
- * m == 0 is allowed (only dets_world / dets_img are produced).  n <= 65535.
+ * m == 0 is allowed (only dets_world / dets_img are produced).  n <= 64000.
  */
 int bevwarp_tracker_step(const void *dets_bev, int n, int det_stride, const void *trks_world, int m, int trk_stride,
                          const double *H_world_bev /*HOST*/, const double *H_img_world /*HOST, may be NULL*/,

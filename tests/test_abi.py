@@ -161,7 +161,7 @@ def test_tracker_step_validates_before_touching_the_device(lib):
     assert call(a0=None) == -1                    # null detections
     assert call(a10=None) == -1                   # m > 0 without an IoU buffer
     assert call(a13=_lib.U8) == -2                # dtype
-    assert call(a1=70000) == -3                   # n > 65535
+    assert call(a1=70000) == -3                   # n > 64000
     shear = np.array([[1.0, 0, 0], [0, 2.0, 0], [0, 0, 1]])
     assert call(a6=shear.ctypes.data_as(ctypes.c_void_p)) == -1       # axes scale differently
     proj = np.array([[1.0, 0, 0], [0, 1.0, 0], [1e-3, 0, 1]])
