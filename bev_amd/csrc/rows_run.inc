@@ -261,12 +261,6 @@
     // kernel its layout otherwise costs unturned footprints 3 %)
     if (__builtin_expect(tile_in, 1)) {
         if (__builtin_expect(!tile_slanted, 1)) {
-            if constexpr (kStageable) {
-                if (tile_affine && tile_stage) {
-                    staged_tile();
-                    return;
-                }
-            }
             if (tile_affine) {
                 if constexpr (kPairable) {
                     if (tile_pair) {

@@ -11,11 +11,6 @@
     // -- the tile's four corner pixels decide how it is processed
     bool tile_in, tile_slanted, tile_out, tile_affine;
     bool tile_pair = false;  // row-affine tile whose taps advance by 0 .. 2 source pixels per destination pixel: pixel pairs share a 16-byte window
-    // staged tiles (rows_staged.inc): the source rows r_first .. r_first + n_rows - 1 and the bytes [span_start, span_start + span_len) of
-    // each hold every tap of the tile
-    bool tile_stage = false;
-    uint32_t stage_span_start = 0, stage_span_len = 0;
-    int stage_r_first = 0, stage_n_rows = 0;
     // A caller that warps many batches through the same matrices and geometry (a camera loop) may hand in the verdicts of an earlier
     // fill launch (bevwarp_warp_classes): the tile's set-up below -- a tenth of the 8-bit kernel's vector instructions -- is then one
     // scalar load.  The table is indexed by workgroup, so it is only valid for the launch geometry it was filled with (the host checks).
@@ -96,40 +91,6 @@
             // most 2 pixels apart whatever the rounding (a fast coordinate is a unit of 1/32 pixel off at worst).
             const double stp = m0 * cr;
             tile_pair = tile_affine && (((uint32_t)__ballot(stp >= 0.0 && stp <= 1.9375)) & 0xFu) == 0xFu;
-        }
-        if constexpr (kStageable) {
-            // The tile maps into the quadrilateral of its corners' images: source columns / rows min .. max of the four.  One pixel / row of
-            // slack on either side for the unit a fast coordinate may be off (and for the corner lanes evaluating the row terms in another
-            // order than the consumers do); the taps reach one pixel / row further, an aligned window 12 bytes from its start.
-            auto min4 = [](int v) {
-                v = min(v, __shfl_xor(v, 1));
-                return min(v, __shfl_xor(v, 2));
-            };
-            auto max4 = [](int v) {
-                v = max(v, __shfl_xor(v, 1));
-                return max(v, __shfl_xor(v, 2));
-            };
-            const int lo = min4(csx), hi = max4(csx), rlo = min4(csy), rhi = max4(csy);
-            const int row_bytes = src_w * PBs, rows_t = y_last - y0 + 1;
-            int b0 = max(0, (lo - 1) * PBs) & ~15;
-            const int b1 = (hi + 3) * PBs + (kAligned ? 12 : 0);
-            const int len = (b1 - b0 + 15) & ~15;
-            bool ok = len <= kSlot && len <= row_bytes;
-            if (b0 + len > row_bytes) {  // (the 16-byte rounding would read past the row's end: start earlier instead)
-                b0 = (row_bytes - len) & ~3;
-                ok = ok && b0 + len >= b1;
-            }
-            const int r0 = max(rlo - 1, 0), r1 = min(rhi + 2, src_h - 1);
-            // rows of the source increase with the destination row (the producer walks them upwards), and are not many more than the
-            // tile's own: a strongly minifying map would stage rows that no tap reads
-            const int sy_top = __builtin_amdgcn_readlane(csy, 0), sy_bot = __builtin_amdgcn_readlane(csy, 2);
-            ok = ok && sy_bot >= sy_top && r1 - r0 + 1 <= rows_t + (rows_t >> 2) + 4 && rows_t >= 8;
-            ok = ok && ((reinterpret_cast<uintptr_t>(frame) | (uintptr_t)rs32) & 3u) == 0;
-            tile_stage = __builtin_amdgcn_readfirstlane((int)ok) != 0;
-            stage_span_start = (uint32_t)__builtin_amdgcn_readfirstlane(b0);
-            stage_span_len = (uint32_t)__builtin_amdgcn_readfirstlane(len);
-            stage_r_first = __builtin_amdgcn_readfirstlane(r0);
-            stage_n_rows = __builtin_amdgcn_readfirstlane(r1 - r0 + 1);
         }
         if constexpr (NSRC == 1) {
             if (a.classify_out) {  // fill mode: the verdict, no pixels

@@ -16,8 +16,9 @@
 // pass.  No workgroup barrier.
 //
 // Layout of the sources: coords.h (coordinate arithmetic), sample.h (blending, guarded sampler), this file (the kernel: its
-// prologue here, its stages in the fragments rows_coords.inc / rows_sample.inc / rows_store.inc / rows_tiles.inc), and one
-// translation unit per pixel type and interpolation (warp_u8_linear.hip, ...) so that the formats compile side by side.
+// prologue here, its stages in the fragments rows_coords.inc / rows_sample.inc / rows_store.inc / rows_tiles.inc, how a tile
+// is run in rows_run.inc; included in that order), and one translation unit per pixel type and interpolation
+// (warp_u8_linear.hip, ...) so that the formats compile side by side.
 //
 // Coordinates are float64.  The reference rounds fX = (X0 + M0 x1) * (32 / W) half-to-even; the fast chain (one
 // v_rcp_f64 + Newton step shared by the lane's pixels, FMAs, row terms evaluated once per row) lands within 2^-40
@@ -50,10 +51,8 @@ namespace {
 #define warp_rows warp_rows_clockbuild
 // One record of kClkWords counters per workgroup (blockIdx mod kClkRecords), ACCUMULATED with plain read-modify-writes by one lane of the
 // workgroup -- no atomics: thousands of workgroups adding to a handful of shared words serialise in the L2's atomic unit and slow the
-// very kernel that is being timed several-fold.  Words: [0] shader ticks the workgroup lived, [1] 100-MHz ticks, [2] workgroups;
-// staged tiles (rows_staged.inc): [4] producer ticks, [5] rows it found no free slot for at once, [6] source rows, [7] tiles;
-// [8] consumer ticks (sum of three), [9] ticks waiting for source rows, [10] of those before the first row, [11] rows.
-constexpr int kClkWords = 32, kClkRecords = 8192;  // (a record: words 0 .. 7 as listed, then [8 + 4 c ..] = the four consumer words of consumer c)
+// very kernel that is being timed several-fold.  Words: [0] shader ticks the workgroup lived, [1] 100-MHz ticks, [2] workgroups.
+constexpr int kClkWords = 4, kClkRecords = 8192;  // (three words in use; four keep a record's address a shift)
 static __device__ unsigned long long g_clk[kClkRecords * kClkWords];
 __device__ __forceinline__ void clk_add(int word, unsigned long long v) { g_clk[(blockIdx.x & (kClkRecords - 1)) * kClkWords + word] += v; }
 #endif
@@ -93,26 +92,7 @@ __global__ __launch_bounds__(kWG * NSRC) __attribute__((amdgpu_waves_per_eu(NSRC
     // loses 13 us of 75 (ablations: profiles/r03_tables.txt).  Stored at the end of the tile, nothing waits behind them.
     // (composite: one row, its passes go to the LDS tiles at once.)
     constexpr int kRowsLds = NSRC > 1 ? 1 : (sizeof(T) == 1 ? 6 : 4);  // passes of a wave over the tallest tile (24 / 16 rows)
-    // STAGED tiles (rows_staged.inc): one producer wave copies the tile's source rows into a ring of LDS slots with coalesced LDS-DMA
-    // loads, three consumer waves read their taps from the ring.  The ring, two transposition rows per consumer and the four
-    // hand-off words share the LDS of the deferred-store rows (a tile is processed one way or the other).
-    // MEASURED AND NOT ENABLED (round 4, profiles/r04_staged_tiles.txt): bit-exact on the whole GPU suite, and within +-3 % of the gather
-    // pipelines on float pixels (equal at 1080p with non-temporal ring fills, -3.4 % on the 4K shard) but 5 % SLOWER on 8-bit pixels,
-    // whose consumers carry 15 % more vector instructions (LDS addresses) on SIMDs that are already the limiter.  The fragment stays
-    // in the tree as the record of the experiment; `python tools/ablate.py stage=stage` builds a library with it switched on.
-    constexpr bool kStageEnabled = false;
-    constexpr bool kStageable = kStageEnabled && NSRC == 1 && INTERP == kLinear && C == 3 && (sizeof(T) == 4 || RS4);
-    constexpr int kCons = kWaves - 1;                       // consumer waves of a staged tile
-    constexpr int kRing = sizeof(T) == 1 ? 16 : 10;         // source rows the ring holds
-    constexpr int kFlight = sizeof(T) == 1 ? 12 : 6;        // rows the producer keeps in flight (<= kRing - 2, rows_staged.inc)
-    constexpr int kSlot = sizeof(T) == 1 ? 1536 : 3072;     // bytes of one slot: the widest row span a staged tile may have
-    constexpr int kStageTr = 2 * TRW * 4;                   // bytes of a consumer's two transposition rows
-    constexpr int kStageFlagOff = kRing * kSlot + kCons * kStageTr;
-    constexpr int kStageAux = 0;                            // cache policy of the ring fills (0: default, 2: nt)
-    constexpr int kTrDwords = kWaves * NSRC * kRowsLds * TRW;
-    constexpr int kLdsDwords = kStageable && (kStageFlagOff + 16) / 4 > kTrDwords ? (kStageFlagOff + 16) / 4 : kTrDwords;
-    constexpr int kLdsWaves = (kLdsDwords + kRowsLds * TRW - 1) / (kRowsLds * TRW);  // (= kWaves * NSRC unless a staged build needs more: its layout is a byte view)
-    __shared__ __attribute__((aligned(16))) uint32_t s_tr[kLdsWaves][kRowsLds][TRW];
+    __shared__ __attribute__((aligned(16))) uint32_t s_tr[kWaves * NSRC][kRowsLds][TRW];
     // (composite only) the warped tiles, one packed pixel per dword: [source][row of the tile][pixel]
     __shared__ __attribute__((aligned(16))) uint32_t s_tile[NSRC > 1 ? NSRC * kCompositeRows * TW : 4];
     constexpr int NEED = LOADB / 4;  // dwords of a tap row the blend takes, starting AT the left tap
@@ -190,7 +170,6 @@ __global__ __launch_bounds__(kWG * NSRC) __attribute__((amdgpu_waves_per_eu(NSRC
 #include "rows_sample.inc"
 #include "rows_store.inc"
 #include "rows_tiles.inc"
-#include "rows_staged.inc"
 #include "rows_run.inc"
     if constexpr (NSRC > 1) {
         // -- composite_reg_img (bev/tool/compo.py:16-23) on the three LDS tiles.  The reference evaluates
@@ -271,14 +250,12 @@ void launch_channels(const WarpArgs& a, int channels, dim3 grid, hipStream_t str
 }
 
 #ifdef BEVWARP_CLOCK
-inline hipError_t read_clock_of_this_unit(unsigned long long* out16, int reset) {  // out16 += this translation unit's counters
-    static unsigned long long v[kClkRecords * kClkWords];  // (2 MB: not on the stack; the diagnostic build is single-threaded)
+inline hipError_t read_clock_of_this_unit(unsigned long long* out16, int reset) {  // out16[0..2] += this translation unit's counters
+    static unsigned long long v[kClkRecords * kClkWords];  // (256 KB: not on the stack; the diagnostic build is single-threaded)
     hipError_t e = hipMemcpyFromSymbol(v, HIP_SYMBOL(g_clk), sizeof(v));
     if (e != hipSuccess) return e;
-    for (int r = 0; r < kClkRecords; r++) {
-        for (int i = 0; i < 8; i++) out16[i] += v[r * kClkWords + i];
-        for (int i = 8; i < 20; i++) out16[8 + (i & 3)] += v[r * kClkWords + i];  // the three consumers' words, folded
-    }
+    for (int r = 0; r < kClkRecords; r++)
+        for (int i = 0; i < 3; i++) out16[i] += v[r * kClkWords + i];
     if (reset) {
         void* p = nullptr;
         e = hipGetSymbolAddress(&p, HIP_SYMBOL(g_clk));
