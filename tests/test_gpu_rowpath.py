@@ -208,7 +208,7 @@ def test_row_strides_of_every_alignment(W, sw):
     src = wl.frame(30, 359, sw, np.uint8)
     exp = co.warp_perspective(src, M, (512, 48), 1)
     P.check_modes(run_gpu(W, src, M, (512, 48), 1), exp)
-    buf = torch.zeros(359 * sw * 3 + 8, dtype=torch.uint8, device="cuda")
+    buf = torch.full((359 * sw * 3 + 8,), 0xA5, dtype=torch.uint8, device="cuda")  # (not the border value: a tap taken from beside the frame shows)
     for shift in (1, 2, 3):
         view = buf[shift:shift + 359 * sw * 3].view(359, sw, 3)
         view.copy_(torch.from_numpy(src))
@@ -224,7 +224,7 @@ def _batch_case(W, dtype_c, sw, sh, dw, dh, B, kind, interp, pad_to=None, border
     Ms = np.stack([wl.jitter_H(base, i, px=3.0) for i in range(B)])
     t = torch.from_numpy(frames).cuda()
     if pad_to:  # a row-padded view: row stride pad_to * c bytes
-        big = torch.zeros((B, sh, pad_to, c), dtype=torch.uint8, device="cuda")
+        big = torch.full((B, sh, pad_to, c), 0xA5, dtype=torch.uint8, device="cuda")  # (padding that is not the border value)
         big[:, :, :sw] = t
         t = big[:, :, :sw]
     got = run_gpu(W, t, Ms, (dw, dh), interp, border_value=border)
@@ -302,7 +302,7 @@ def test_turned_footprints_through_unaligned_views(W, c, dtype):
     sw, sh, dw, dh = 637, 355, 301, 45
     M = wl.rotated_H(sw, sh, dw, dh, 33.0, 1.7)  # reaches past the frame on two sides
     src = wl.frame(23, sh, sw, dtype, c)
-    src_big = torch.zeros((sh, sw + 3, c), dtype=torch.from_numpy(src).dtype, device="cuda")
+    src_big = torch.full((sh, sw + 3, c), 0xA5 if dtype == np.uint8 else float("nan"), dtype=torch.from_numpy(src).dtype, device="cuda")  # (not the border value)
     src_big[:, 1:1 + sw] = torch.from_numpy(src).cuda()
     for interp in (0, 1):
         out_big = torch.full((dh, dw + 5, c), 77, dtype=src_big.dtype, device="cuda")
@@ -392,7 +392,7 @@ def test_pair_tiles_scales_mirrors_and_alignments(W, misalign):
     multiple of 4: the RS4 kernel) -- all must equal the oracle."""
     sw, sh, dw, dh = 1020, 300, 512, 96
     src = wl.frame(41 + misalign, sh, sw, np.uint8)
-    big = torch.zeros((sh, sw + 4, 3), dtype=torch.uint8, device="cuda")  # row stride 3072: a multiple of 4
+    big = torch.full((sh, sw + 4, 3), 0xA5, dtype=torch.uint8, device="cuda")  # row stride 3072: a multiple of 4; padding that is not the border value
     lo = (misalign * 3) % 4  # the view starts `misalign` pixels in: 0 / 3 / 2 / 1 bytes off a 4-byte boundary
     big[:, misalign:misalign + sw] = torch.from_numpy(src).cuda()
     view = big[:, misalign:misalign + sw]
