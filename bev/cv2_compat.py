@@ -1,4 +1,4 @@
 from bev_amd.cv2_compat import *  # noqa: F401,F403
 from bev_amd.cv2_compat import (BORDER_CONSTANT, BORDER_DEFAULT, BORDER_REFLECT, BORDER_REFLECT101, BORDER_REFLECT_101,  # noqa: F401
-                                BORDER_REPLICATE, BORDER_TRANSPARENT, BORDER_WRAP, INTER_LINEAR, INTER_NEAREST, WARP_INVERSE_MAP,
+                                BORDER_REPLICATE, BORDER_TRANSPARENT, BORDER_WRAP, INTER_CUBIC, INTER_LINEAR, INTER_NEAREST, WARP_INVERSE_MAP,
                                 findHomography, invert, perspectiveTransform, resize, warpPerspective)

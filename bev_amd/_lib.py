@@ -11,7 +11,7 @@ _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.environ.get("BEVWARP_LIB") or os.path.join(_CSRC, "libbevwarp.so")  # override = A/B builds
 
 U8, F32, F64 = 0, 1, 2
-INTER_NEAREST, INTER_LINEAR = 0, 1
+INTER_NEAREST, INTER_LINEAR, INTER_CUBIC = 0, 1, 2
 ABI_VERSION = 7
 
 # every symbol include/bevwarp.h declares: (name, restype, argtypes)

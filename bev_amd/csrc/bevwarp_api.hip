@@ -8,7 +8,9 @@
 
 #include "bevwarp.h"
 #include "host_plan.h"
+#include "cubic_tab.h"
 #include "warp_border.h"
+#include "warp_cubic.h"
 #include "warp_kernels.h"
 
 #pragma clang fp contract(off)
@@ -44,6 +46,18 @@ void copy_grid(Args& a, const TilePlan& p) {
 void copy_plan(WarpArgs& a, const TilePlan& p) {
     copy_grid(a, p);
     a.tile_h = p.tile_h, a.total_tiles = p.total_tiles, a.chunk = p.chunk, a.stagger = p.stagger, a.tail_split = p.tail_split;
+}
+// border_value (HOST, `channels` doubles or NULL) as the kernels take it: float32, and saturate_cast<uchar> (round half to even, clamp)
+template <class U8>
+int border_values(const double* border_value, int channels, float* f, U8* u8) {
+    for (int k = 0; k < 4; k++) {
+        const double b = (border_value && k < channels) ? border_value[k] : 0.0;
+        if (!isfinite(b)) return BEVWARP_ERR_NOT_FINITE;
+        f[k] = (float)b;
+        const double r = nearbyint(b);
+        u8[k] = (U8)(r < 0 ? 0 : (r > 255 ? 255 : r));
+    }
+    return BEVWARP_OK;
 }
 }  // namespace
 
@@ -123,13 +137,7 @@ int warp_impl(const WarpCall& c) {
             a.pbias[k] = (float)bi;
         }
     }
-    for (int k = 0; k < 4; k++) {
-        const double b = (c.border_value && k < c.channels) ? c.border_value[k] : 0.0;
-        if (!isfinite(b)) return BEVWARP_ERR_NOT_FINITE;
-        a.bval_f[k] = (float)b;
-        const double r = nearbyint(b);  // saturate_cast<uchar>: round half to even, clamp
-        a.bval_u8[k] = (uint8_t)(r < 0 ? 0 : (r > 255 ? 255 : r));
-    }
+    if (border_values(c.border_value, c.channels, a.bval_f, a.bval_u8) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
     if (c.classes) {
         if ((uintptr_t)c.classes % 4) return BEVWARP_ERR_BAD_ARG;
         if (c.classes_mode == BEVWARP_CLASSES_FILL)
@@ -146,6 +154,9 @@ extern "C" {
 int bevwarp_warp(const void* src, void* dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int channels,
                  int64_t src_frame_stride, int64_t src_row_stride, int64_t dst_frame_stride, int64_t dst_row_stride, const double* M_inv,
                  int m_count, int dtype, int interp, const double* border_value, void* stream) {
+    if (interp == BEVWARP_CUBIC)  // the bicubic kernel has every border, the constant one included
+        return bevwarp_warp_border(src, dst, batch, src_h, src_w, dst_h, dst_w, channels, src_frame_stride, src_row_stride, dst_frame_stride, dst_row_stride,
+                                   M_inv, m_count, dtype, interp, BEVWARP_BORDER_CONSTANT, border_value, stream);
     return warp_impl({{src, src_h, src_w, src_frame_stride, src_row_stride}, {dst, dst_h, dst_w, dst_frame_stride, dst_row_stride}, batch, channels, dtype, interp,
                       M_inv, m_count, border_value, stream});
 }
@@ -153,26 +164,32 @@ int bevwarp_warp(const void* src, void* dst, int batch, int src_h, int src_w, in
 int bevwarp_warp_border(const void* src, void* dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int channels,
                         int64_t src_frame_stride, int64_t src_row_stride, int64_t dst_frame_stride, int64_t dst_row_stride, const double* M_inv,
                         int m_count, int dtype, int interp, int border_mode, const double* border_value, void* stream) {
-    if (border_mode == BEVWARP_BORDER_CONSTANT)  // the constant border is bevwarp_warp itself
+    const bool cubic = interp == BEVWARP_CUBIC;
+    if (border_mode == BEVWARP_BORDER_CONSTANT && !cubic)  // the constant border is bevwarp_warp itself
         return bevwarp_warp(src, dst, batch, src_h, src_w, dst_h, dst_w, channels, src_frame_stride, src_row_stride, dst_frame_stride, dst_row_stride,
                             M_inv, m_count, dtype, interp, border_value, stream);
-    if (border_mode < BEVWARP_BORDER_REPLICATE || border_mode > BEVWARP_BORDER_TRANSPARENT) return BEVWARP_ERR_UNSUPPORTED;  // (BORDER_ISOLATED too)
+    if (border_mode < BEVWARP_BORDER_CONSTANT || border_mode > BEVWARP_BORDER_TRANSPARENT) return BEVWARP_ERR_UNSUPPORTED;  // (BORDER_ISOLATED too)
     // (border_value is read by no mode but the constant one, as in OpenCV)
-    const WarpCall c = {{src, src_h, src_w, src_frame_stride, src_row_stride}, {dst, dst_h, dst_w, dst_frame_stride, dst_row_stride}, batch, channels, dtype, interp,
-                        M_inv, m_count, nullptr, stream};
+    WarpCall c = {{src, src_h, src_w, src_frame_stride, src_row_stride}, {dst, dst_h, dst_w, dst_frame_stride, dst_row_stride}, batch, channels, dtype, interp,
+                  M_inv, m_count, nullptr, stream};
+    c.cubic_ok = true;
     const int st = plan::check_warp(c);
     if (st != BEVWARP_OK || batch == 0) return st;
     const TilePlan p = plan::plan_border(batch, dst_h, dst_w, kBorderTileW, kBorderTileH);
     if (p.status != BEVWARP_OK) return p.status;
-    BorderArgs a;
+    CubicArgs a;  // (the border kernel takes its BorderArgs part)
     copy_call(a, c);
     copy_grid(a, p);
-    const plan::BorderPeriod px = plan::border_period(border_mode, src_w), py = plan::border_period(border_mode, src_h);
+    // the 4 taps of a bicubic window reach one index beyond a saturated one: a period plan of their own
+    const plan::BorderPeriod px = cubic ? cubic::window_period(border_mode, src_w) : plan::border_period(border_mode, src_w);
+    const plan::BorderPeriod py = cubic ? cubic::window_period(border_mode, src_h) : plan::border_period(border_mode, src_h);
     a.per_x = px.per, a.off_x = px.off, a.mag_x = px.mag;
     a.per_y = py.per, a.off_y = py.off, a.mag_y = py.mag;
     a.dst_vec_ok = plan::wide_stores_ok(c.dst_image(), plan::store_align(dtype, channels, false));
     a.src_vec_ok = plan::pixel_loads_ok(c.src_image(), plan::pixel_load_align(dtype, channels));
-    return launched(launch_warp_border(a, dtype, channels, interp, border_mode, p.total_tiles, (hipStream_t)stream));
+    if (!cubic) return launched(launch_warp_border(a, dtype, channels, interp, border_mode, p.total_tiles, (hipStream_t)stream));
+    if (border_values(border_mode == BEVWARP_BORDER_CONSTANT ? border_value : nullptr, channels, a.cv_f, a.cv_u8) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
+    return launched(launch_warp_cubic(a, dtype, channels, border_mode, p.total_tiles, (hipStream_t)stream));
 }
 
 int bevwarp_warp_classes(const void* src, void* dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int channels, int64_t src_frame_stride,

@@ -96,6 +96,7 @@ struct WarpCall {  // (an aggregate: every entry point fills it once, the option
     const double *scale, *bias;
     void* classes;  // bevwarp_warp_classes
     int classes_mode;
+    bool cubic_ok;  // bevwarp_warp, bevwarp_warp_border: the entry points behind which a bicubic kernel stands
 
     int elem() const { return dtype == BEVWARP_U8 ? 1 : 4; }
     Image src_image() const { return {(uintptr_t)src.base, src.h, (uint64_t)src.w * channels * elem(), src.rs, src.fs, batch}; }
@@ -106,8 +107,8 @@ struct WarpCall {  // (an aggregate: every entry point fills it once, the option
 // The checks that need no pointer, in the order their statuses are documented: sizes, format, matrix count.
 inline int format_status(const WarpCall& c) {
     if (c.batch < 0 || c.src.h <= 0 || c.src.w <= 0 || c.dst.h <= 0 || c.dst.w <= 0) return BEVWARP_ERR_BAD_ARG;
-    if ((c.dtype != BEVWARP_U8 && c.dtype != BEVWARP_F32) || (c.interp != BEVWARP_NEAREST && c.interp != BEVWARP_LINEAR) || c.channels < 1 || c.channels > 4)
-        return BEVWARP_ERR_UNSUPPORTED;
+    const bool interp_ok = c.interp == BEVWARP_NEAREST || c.interp == BEVWARP_LINEAR || (c.interp == BEVWARP_CUBIC && c.cubic_ok);
+    if ((c.dtype != BEVWARP_U8 && c.dtype != BEVWARP_F32) || !interp_ok || c.channels < 1 || c.channels > 4) return BEVWARP_ERR_UNSUPPORTED;
     if (c.m_count != 1 && c.m_count != c.batch) return BEVWARP_ERR_BAD_ARG;
     return BEVWARP_OK;
 }

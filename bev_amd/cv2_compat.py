@@ -6,7 +6,8 @@ OpenCV's argument order, defaults, flag values and return shapes, so that an int
 and leave /root/reference/vis_homo.py:89-91, bev/homo.py:36 and bev/tool/compo.py:38,46,47 untouched.
 
     cv2.warpPerspective(img, H, (w, h)[, dst, flags, borderMode, borderValue])   vis_homo.py:89,91; compo.py:38,46,47
-        (borderMode: BORDER_CONSTANT, _REPLICATE, _REFLECT, _WRAP, _REFLECT_101 / _REFLECT101 / _DEFAULT, _TRANSPARENT)
+        (flags: INTER_NEAREST, INTER_LINEAR, INTER_CUBIC; borderMode: BORDER_CONSTANT, _REPLICATE, _REFLECT, _WRAP, _REFLECT_101 /
+         _REFLECT101 / _DEFAULT, _TRANSPARENT)
     cv2.findHomography(pts_src, pts_tgt[, method]) -> (H, mask)                  bev/homo.py:36
     cv2.perspectiveTransform(pts (N,1,2), H) -> (N,1,2)                          (OpenCV's name for pts_world_bev, bev/rbox.py:136-151)
     cv2.invert(M) -> (retval, M_inv)                                             the 3x3 step inside warpPerspective
@@ -36,6 +37,7 @@ __version__ = "bev_amd.cv2_compat"
 # flag values of OpenCV 4.x
 INTER_NEAREST = 0
 INTER_LINEAR = 1
+INTER_CUBIC = 2
 WARP_INVERSE_MAP = 16
 BORDER_CONSTANT = 0
 BORDER_REPLICATE = 1
@@ -50,11 +52,11 @@ RANSAC, LMEDS, RHO = 8, 4, 16
 
 
 def warpPerspective(src, M, dsize, dst=None, flags=INTER_LINEAR, borderMode=BORDER_CONSTANT, borderValue=0):
-    """uint8 / float32 images of 1-4 channels; INTER_LINEAR or INTER_NEAREST, optionally | WARP_INVERSE_MAP;
+    """uint8 / float32 images of 1-4 channels; INTER_LINEAR, INTER_NEAREST or INTER_CUBIC, optionally | WARP_INVERSE_MAP;
     BORDER_CONSTANT with cv::Scalar border semantics, BORDER_REPLICATE / _REFLECT / _WRAP / _REFLECT_101, or BORDER_TRANSPARENT
     (a given `dst` is the canvas that keeps the pixels the source does not cover).  Bit-exact with the classic fixed-point
     algorithm (oracle/warp_oracle.c states which OpenCV code path that is; the other borders follow remapNearest /
-    remapBilinear -- restated from memory, parity unpinned)."""
+    remapBilinear and INTER_CUBIC follows remapBicubic -- restated from memory, parity unpinned)."""
     return _warp.warpPerspective(src, M, dsize, dst=dst, flags=flags, borderMode=borderMode, borderValue=borderValue)
 
 

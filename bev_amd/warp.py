@@ -19,6 +19,7 @@ from . import _lib
 
 INTER_NEAREST = _lib.INTER_NEAREST
 INTER_LINEAR = _lib.INTER_LINEAR
+INTER_CUBIC = _lib.INTER_CUBIC  # bevwarp_warp_border's bicubic kernel, every border mode (BORDER_CONSTANT included)
 WARP_INVERSE_MAP = 16  # cv2 flag value
 # cv2 border modes (cv::BorderTypes values); BORDER_CONSTANT is the warp kernel's own, the others are bevwarp_warp_border
 BORDER_CONSTANT = 0
@@ -197,13 +198,15 @@ def warp_perspective(src, M, dsize, flags=INTER_LINEAR, border_value=None, out=N
     M        (3, 3) shared or (B, 3, 3) per-frame forward homography (numpy or tensor); with
              flags | WARP_INVERSE_MAP it is taken as the dst -> src map instead.
     dsize    (width, height) = (u_size, v_size), as OpenCV.
-    flags    INTER_LINEAR (default) or INTER_NEAREST, optionally | WARP_INVERSE_MAP.
+    flags    INTER_LINEAR (default), INTER_NEAREST or INTER_CUBIC, optionally | WARP_INVERSE_MAP.  INTER_CUBIC is OpenCV's classic
+             remapBicubic (restated from memory, parity unpinned; include/bevwarp.h) for every border mode.
     out      optional preallocated result; M_inv_device optional (n, 3, 3) f64 CUDA tensor to skip the cache.
     border_mode  BORDER_CONSTANT (default; `border_value`), BORDER_REPLICATE, BORDER_REFLECT, BORDER_WRAP, BORDER_REFLECT_101
              (every tap reads a source pixel, border_value is ignored) or BORDER_TRANSPARENT: only pixels whose taps are all
              inside the source are written, every other pixel of `out` keeps its contents (warp several cameras into one
              canvas, one call each).  TRANSPARENT without `out` returns a zeroed result where it writes nothing (OpenCV would
-             leave those pixels uninitialised).  Semantics: include/bevwarp.h, bevwarp_warp_border.
+             leave those pixels uninitialised).  With INTER_CUBIC, TRANSPARENT writes the pixels whose integer position lies in
+             the source.  Semantics: include/bevwarp.h, bevwarp_warp_border.
     Returns a tensor shaped like src with (height, width) replaced.  Asynchronous on the current stream."""
     if out is not None and M_inv_device is not None and border_value is None:
         # Steady-state call of a camera loop: same buffers, same geometry as a call that has already been validated.  The
@@ -246,8 +249,8 @@ def warp_perspective(src, M, dsize, flags=INTER_LINEAR, border_value=None, out=N
     if src.dtype not in _DTYPES:
         raise ValueError("unsupported dtype %s (uint8 / float32)" % src.dtype)
     interp = int(flags) & 7
-    if interp not in (INTER_NEAREST, INTER_LINEAR):
-        raise ValueError("unsupported interpolation flag %d" % interp)
+    if interp not in (INTER_NEAREST, INTER_LINEAR, INTER_CUBIC):
+        raise ValueError("unsupported interpolation flag %d (INTER_NEAREST, INTER_LINEAR, INTER_CUBIC)" % interp)
     shape = tuple(src.shape)
     s4 = src
     if src.dim() == 2:
@@ -276,15 +279,15 @@ def warp_perspective(src, M, dsize, flags=INTER_LINEAR, border_value=None, out=N
     stream = torch.cuda.current_stream(s4.device).cuda_stream
     args = (s4.data_ptr(), d4.data_ptr(), B, H, W, dh, dw, C, s4.stride(0) * esz, s4.stride(1) * esz, d4.stride(0) * esz, d4.stride(1) * esz,
             M_inv_device.data_ptr(), n_m, _DTYPES[s4.dtype], interp, None if bv is None else bv.ctypes.data_as(ctypes.c_void_p))
-    if border_mode == BORDER_CONSTANT:
+    if border_mode == BORDER_CONSTANT and interp != INTER_CUBIC:
         fn = plain = _lib.load().bevwarp_warp
         table = _tile_classes(M_inv_device, n_m, args, stream)
         if table is not None:  # verdicts of these very matrices and this geometry: the kernel reads them instead of deriving them
             table.record_stream(torch.cuda.current_stream(s4.device))
             fn, args = _lib.load().bevwarp_warp_classes, args + (table.data_ptr(), 0)
-    else:  # the other borders: a kernel of their own, which classifies no tiles (no verdict table)
+    else:  # the other borders, and bicubic with any border: kernels of their own, which classify no tiles (no verdict table)
         fn = plain = _lib.load().bevwarp_warp_border
-        args, table = args[:-1] + (border_mode, None), None
+        args, table = args[:-1] + (border_mode, args[-1]), None  # (border_value: None unless BORDER_CONSTANT, i.e. bicubic)
     with torch.cuda.device(s4.device):
         st = fn(*args, ctypes.c_void_p(stream))
     _lib.check(st)
@@ -313,11 +316,11 @@ def warp_to_planar(src, M, dsize, scale=1.0 / 255.0, bias=0.0, flags=INTER_LINEA
     src (B, H, W, C) / (H, W, C) / (H, W) uint8 or float32 CUDA tensor; scale / bias scalars or per-channel sequences (e.g.
     1 / (255 * std) and -mean / std); other arguments as warp_perspective.  Returns (B, C, h, w), or (C, h, w) for a
     single frame.  Asynchronous on the current stream."""
+    interp = int(flags) & 7
+    if interp not in (INTER_NEAREST, INTER_LINEAR):  # (no bicubic kernel writes planes)
+        raise ValueError("unsupported interpolation flag %d (warp_to_planar: INTER_NEAREST, INTER_LINEAR)" % interp)
     if not isinstance(src, torch.Tensor) or not src.is_cuda or src.dtype not in _DTYPES:
         raise ValueError("warp_to_planar needs a uint8 or float32 CUDA (HIP) tensor")
-    interp = int(flags) & 7
-    if interp not in (INTER_NEAREST, INTER_LINEAR):
-        raise ValueError("unsupported interpolation flag %d" % interp)
     if src.dim() == 2:
         s4 = src[None, :, :, None]
     elif src.dim() == 3:
@@ -384,6 +387,7 @@ def scalar_border(borderValue, channels):
 def warpPerspective(src, M, dsize, dst=None, flags=INTER_LINEAR, borderMode=BORDER_CONSTANT, borderValue=0, device="cuda"):
     """cv2.warpPerspective call shape for numpy images: uploads, warps on the GPU, downloads.
     (The per-frame PCIe round trip dominates here; batch frames with warp_perspective for throughput.)
+    flags: INTER_LINEAR, INTER_NEAREST or INTER_CUBIC, optionally | WARP_INVERSE_MAP.
     borderMode: any of the six BORDER_* modes above.  With BORDER_TRANSPARENT a given `dst` is the canvas: it is uploaded, the
     pixels the source covers are written into it and it is returned (several cameras stitched into one image, one call each);
     without one, uncovered pixels are 0."""

@@ -65,8 +65,9 @@ typedef enum bevwarp_status {
 
 typedef enum bevwarp_dtype { BEVWARP_U8 = 0, BEVWARP_F32 = 1, BEVWARP_F64 = 2 } bevwarp_dtype;
 
-/* Same numeric values as cv2.INTER_NEAREST / cv2.INTER_LINEAR. */
-typedef enum bevwarp_interp { BEVWARP_NEAREST = 0, BEVWARP_LINEAR = 1 } bevwarp_interp;
+/* Same numeric values as cv2.INTER_NEAREST / cv2.INTER_LINEAR / cv2.INTER_CUBIC.  BEVWARP_CUBIC is taken by bevwarp_warp and
+ * bevwarp_warp_border only; every other entry point with an `interp` returns BEVWARP_ERR_UNSUPPORTED for it. */
+typedef enum bevwarp_interp { BEVWARP_NEAREST = 0, BEVWARP_LINEAR = 1, BEVWARP_CUBIC = 2 } bevwarp_interp;
 
 int bevwarp_version(void);
 const char *bevwarp_strerror(int status);
@@ -96,6 +97,7 @@ int bevwarp_invert_homography(const double *M_fwd /*HOST*/, double *M_inv /*HOST
  *   interp         BEVWARP_NEAREST: (X, Y) = round-half-even((x', y') / w'); copy or border.
  *                  BEVWARP_LINEAR : coordinates quantised to 1/32 px, 4 taps, each tap outside the
  *                  source replaced by the border value; u8 in 15-bit fixed point, f32 in float.
+ *                  BEVWARP_CUBIC  : 16 taps, bevwarp_warp_border's BEVWARP_BORDER_CONSTANT (defined there).
  *   border_value   HOST, `channels` doubles, or NULL for 0.
  *   channels       1..4.   src_w, src_h <= 32767.
  */
@@ -118,7 +120,7 @@ typedef enum bevwarp_border {
  * bevwarp_warp with OpenCV's other border modes: cv2.warpPerspective(..., borderMode=border_mode).  Arguments up to `interp`
  * and their checks are bevwarp_warp's; the coordinate maps (and their 1/32-px quantisation) are too.  Per destination pixel,
  * with (sx, sy) the integer source position (bilinear: X >> 5, Y >> 5) SATURATED TO INT16 as OpenCV's maps are:
- *   BEVWARP_BORDER_CONSTANT     exactly bevwarp_warp (the call is delegated to it; border_value as there).
+ *   BEVWARP_BORDER_CONSTANT     exactly bevwarp_warp (nearest, bilinear: the call is delegated to it; border_value as there).
  *   BEVWARP_BORDER_REPLICATE    every tap index p (sx, sx + 1, sy, sy + 1; nearest: sx, sy) goes through OpenCV's
  *   BEVWARP_BORDER_REFLECT      borderInterpolate(p, len, mode) -- clamp / reflect with the edge pixel repeated (fedcba|abcd) /
  *   BEVWARP_BORDER_WRAP         p mod len / reflect about the edge pixel (dcb|abcd); len 1 maps every index to 0 -- and the
@@ -130,6 +132,25 @@ typedef enum bevwarp_border {
  *   border_value  HOST; read by BEVWARP_BORDER_CONSTANT only (ignored otherwise, as in OpenCV).
  *   border_mode   any other value (OpenCV's BORDER_ISOLATED bit included) returns BEVWARP_ERR_UNSUPPORTED.
  * Semantics restated from OpenCV 3.x-4.x imgwarp.cpp (remapNearest / remapBilinear); parity unpinned, like the rest of the warp.
+ *
+ * interp == BEVWARP_CUBIC (cv2.INTER_CUBIC), all six modes -- remapBicubic, restated from memory, parity unpinned as above:
+ *   maps      the bilinear maps (X, Y in 1/32 px).  The 4 x 4 tap window starts at sx = sat16(X >> 5) - 1, sy = sat16(Y >> 5) - 1
+ *             (saturation first); (fy, fx) = (Y & 31, X & 31) selects the weights.
+ *   weights   float32, A = -0.75, x = f / 32:  c0 = ((A(x+1) - 5A)(x+1) + 8A)(x+1) - 4A,  c1 = ((A+2)x - (A+3))x x + 1,
+ *             c2 = the same of 1 - x,  c3 = 1 - c0 - c1 - c2;  W[4 i + j] = cy[i] * cx[j] (i the row).  8-bit pixels: each
+ *             rounded to int16 at scale 32768 (half to even, saturated), then the entry's sum is brought to 32768 at one of
+ *             the taps (i, j) in {2, 3} x {2, 3}: a deficit is added to the largest of them, a surplus taken off the smallest.
+ *   inlier    0 <= sx < max(src_w - 3, 0) and 0 <= sy < max(src_h - 3, 0), any mode: all 16 taps are source pixels;
+ *             sum = ((r0 + r1) + r2) + r3 with r_i = ((S[i][0] W[4i] + S[i][1] W[4i+1]) + S[i][2] W[4i+2]) + S[i][3] W[4i+3].
+ *   otherwise TRANSPARENT writes the pixel only if (sx + 1, sy + 1) lies in the source (so it writes exactly the pixels whose
+ *             integer position does -- an identity warp writes every pixel) and then continues with REFLECT_101's indices;
+ *             CONSTANT stores the border value itself when the whole window is outside (sx >= src_w, sx + 4 <= 0, sy >= src_h
+ *             or sy + 4 <= 0); else, with cv the border value (CONSTANT) or 0 and every tap index through borderInterpolate
+ *             (-1 = outside, CONSTANT only): sum = cv * ONE, then tap by tap, rows outermost, sum = sum + (S - cv) * W,
+ *             taps outside skipped.
+ *   result    8-bit: integers, ONE = 32768, clamp((sum + 16384) >> 15, 0, 255) -- bicubic overshoots, both clamps are live.
+ *             float32: ONE = 1, every multiply and add rounded to float32 in the order written, no FMA; the two orders
+ *             (row sums for inliers, tap by tap otherwise) are both part of the definition.
  */
 int bevwarp_warp_border(const void *src, void *dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int channels,
                         int64_t src_frame_stride, int64_t src_row_stride, int64_t dst_frame_stride, int64_t dst_row_stride,
