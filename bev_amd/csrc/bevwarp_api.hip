@@ -114,8 +114,8 @@ int bevwarp_invert_homography(const double* S, double* D, int n) {
 }  // extern "C"
 
 namespace {
-// bevwarp_warp and its planar and verdict-table variants
-int warp_impl(const WarpCall& c) {
+// bevwarp_warp and its planar and verdict-table variants (plane_format: WarpArgs::planar of a planar call)
+int warp_impl(const WarpCall& c, int plane_format = kPlaneF32) {
     const int st = plan::check_warp(c);
     if (st != BEVWARP_OK || c.batch == 0) return st;
     const TilePlan p = plan::plan_rows(c.batch, c.dst.h, c.dst.w, c.dtype, tile_width(c.dtype), rows_per_pass(), resident_workgroups(c.dtype, c.channels, c.interp));
@@ -125,11 +125,10 @@ int warp_impl(const WarpCall& c) {
     copy_call(a, c);
     a.batch = c.batch;
     copy_plan(a, p);
-    a.dst_vec_ok = plan::wide_stores_ok(c.dst_image(), plan::store_align(c.dtype, c.channels, c.planar));
+    a.dst_vec_ok = plan::call_wide_stores_ok(c);
     if (c.planar) {
-        a.planar = 1;
+        a.planar = plane_format;
         a.dst_ps = c.plane_stride;
-        a.dst_vec_ok = a.dst_vec_ok && (c.plane_stride % 16 == 0);
         for (int k = 0; k < 4; k++) {
             const double sc = (c.scale && k < c.channels) ? c.scale[k] : 1.0, bi = (c.bias && k < c.channels) ? c.bias[k] : 0.0;
             if (!isfinite(sc) || !isfinite(bi)) return BEVWARP_ERR_NOT_FINITE;
@@ -220,6 +219,20 @@ int bevwarp_warp_planar(const void* src, void* dst, int batch, int src_h, int sr
                         const double* scale, const double* bias, void* stream) {
     return warp_impl({{src, src_h, src_w, src_frame_stride, src_row_stride}, {dst, dst_h, dst_w, dst_frame_stride, dst_row_stride}, batch, channels, dtype, interp,
                       M_inv, m_count, border_value, stream, true, dst_plane_stride, scale, bias});
+}
+
+int bevwarp_warp_planes(const void* src, void* dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int channels,
+                        int64_t src_frame_stride, int64_t src_row_stride, int64_t dst_frame_stride, int64_t dst_plane_stride,
+                        int64_t dst_row_stride, const double* M_inv, int m_count, int dtype, int interp, const double* border_value,
+                        const double* scale, const double* bias, int plane_dtype, void* stream) {
+    if (plane_dtype == BEVWARP_F32)  // float32 planes are bevwarp_warp_planar itself
+        return bevwarp_warp_planar(src, dst, batch, src_h, src_w, dst_h, dst_w, channels, src_frame_stride, src_row_stride, dst_frame_stride, dst_plane_stride,
+                                   dst_row_stride, M_inv, m_count, dtype, interp, border_value, scale, bias, stream);
+    if (plane_dtype != BEVWARP_F16 && plane_dtype != BEVWARP_BF16) return BEVWARP_ERR_UNSUPPORTED;
+    WarpCall c = {{src, src_h, src_w, src_frame_stride, src_row_stride}, {dst, dst_h, dst_w, dst_frame_stride, dst_row_stride}, batch, channels, dtype, interp,
+                  M_inv, m_count, border_value, stream, true, dst_plane_stride, scale, bias};
+    c.plane_elem = 2;
+    return warp_impl(c, plane_dtype == BEVWARP_F16 ? kPlaneF16 : kPlaneBF16);
 }
 
 int bevwarp_composite(const void* bg, const void* fg, const void* mask, void* out, int64_t n, void* stream) {

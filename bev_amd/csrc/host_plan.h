@@ -71,9 +71,14 @@ inline bool regions_overlap(const Image& s, const Image& d) {
 }
 
 // Wide stores: one lane writes its 4 consecutive 8-bit pixels (4 C bytes; 12-byte stores need 4-byte alignment) or 16 bytes of
-// float data (float planes of 8-bit sources included).  The frame stride counts even for a single frame.
-inline int store_align(int dtype, int channels, bool planar) { return (dtype == BEVWARP_U8 && !planar) ? (channels == 4 ? 16 : (channels == 2 ? 8 : 4)) : 16; }
+// float data (float planes of 8-bit sources included), or 4 elements of a plane (8 bytes of the 16-bit planes).  The frame stride
+// counts even for a single frame.
+inline int store_align(int dtype, int channels, bool planar, int plane_elem = 4) {
+    if (planar) return 4 * plane_elem;
+    return dtype == BEVWARP_U8 ? (channels == 4 ? 16 : (channels == 2 ? 8 : 4)) : 16;
+}
 inline bool wide_stores_ok(const Image& d, int align) { return d.base % align == 0 && d.rs % align == 0 && d.fs % align == 0; }
+// (a planar call's wide stores: call_wide_stores_ok below -- the plane stride counts as well)
 // The border kernel's whole-pixel loads: 8-bit pixels of 2 / 4 channels that are all 2- / 4-byte aligned (one load per tap).
 inline int pixel_load_align(int dtype, int channels) { return (dtype == BEVWARP_U8 && (channels == 2 || channels == 4)) ? channels : (dtype == BEVWARP_U8 ? 1 : 4); }
 inline bool pixel_loads_ok(const Image& s, int align) { return s.base % align == 0 && s.rs % align == 0 && (s.batch == 1 || s.fs % align == 0); }
@@ -91,18 +96,25 @@ struct WarpCall {  // (an aggregate: every entry point fills it once, the option
     int m_count;
     const double* border_value;
     void* stream;
-    bool planar;  // bevwarp_warp_planar: float32 channel planes, plane_stride bytes apart, instead of interleaved pixels of the source type
+    bool planar;  // bevwarp_warp_planar, _planes: channel planes, plane_stride bytes apart, instead of interleaved pixels of the source type
     int64_t plane_stride;
     const double *scale, *bias;
     void* classes;  // bevwarp_warp_classes
     int classes_mode;
     bool cubic_ok;  // bevwarp_warp, bevwarp_warp_border: the entry points behind which a bicubic kernel stands
+    int plane_elem = 4;  // bytes of a plane's element: 4 (float32), 2 (bevwarp_warp_planes: float16, bfloat16)
 
     int elem() const { return dtype == BEVWARP_U8 ? 1 : 4; }
     Image src_image() const { return {(uintptr_t)src.base, src.h, (uint64_t)src.w * channels * elem(), src.rs, src.fs, batch}; }
     // (planar: one plane's rows; the planes of a frame are plane_stride apart)
-    Image dst_image() const { return {(uintptr_t)dst.base, dst.h, (uint64_t)dst.w * (planar ? 4 : channels * elem()), dst.rs, dst.fs, batch}; }
+    Image dst_image() const { return {(uintptr_t)dst.base, dst.h, (uint64_t)dst.w * (planar ? plane_elem : channels * elem()), dst.rs, dst.fs, batch}; }
 };
+
+// Does the call's destination admit the wide stores?  (planes: 4 elements per store, and the plane stride is a stride like the others)
+inline bool call_wide_stores_ok(const WarpCall& c) {
+    const int align = store_align(c.dtype, c.channels, c.planar, c.plane_elem);
+    return wide_stores_ok(c.dst_image(), align) && (!c.planar || c.plane_stride % align == 0);
+}
 
 // The checks that need no pointer, in the order their statuses are documented: sizes, format, matrix count.
 inline int format_status(const WarpCall& c) {
@@ -123,14 +135,14 @@ inline int check_warp(const WarpCall& c) {
     if (st != BEVWARP_OK) return st;
     const Image s = c.src_image(), d = c.dst_image();
     if ((st = layout_status(s, c.elem())) != BEVWARP_OK) return st;
-    if (c.planar) {  // destination: `channels` float32 planes per frame -- the rule twice: rows in a plane (asked of a lone plane too), planes in a frame
+    if (c.planar) {  // destination: `channels` planes per frame -- the rule twice: rows in a plane (asked of a lone plane too), planes in a frame
         const Image rows_in_plane = {d.base, d.rows, d.row_bytes, d.rs, c.plane_stride, 2}, planes_in_frame = {d.base, c.channels, 0, c.plane_stride, d.fs, d.batch};
-        if (layout_status(rows_in_plane, 4) != BEVWARP_OK || layout_status(planes_in_frame, 4) != BEVWARP_OK) return BEVWARP_ERR_BAD_ARG;
+        if (layout_status(rows_in_plane, c.plane_elem) != BEVWARP_OK || layout_status(planes_in_frame, c.plane_elem) != BEVWARP_OK) return BEVWARP_ERR_BAD_ARG;
     } else if ((st = layout_status(d, c.elem())) != BEVWARP_OK) {
         return st;
     }
     if ((st = source_size_status(s, c.src.w)) != BEVWARP_OK || c.batch == 0) return st;
-    if (c.planar) {  // (float planes: bounding ranges only -- a frame's planes need not share the rows' stride)
+    if (c.planar) {  // (planes: bounding ranges only -- a frame's planes need not share the rows' stride)
         const uintptr_t d1 = d.end() + (uint64_t)(c.channels - 1) * c.plane_stride;
         return (s.base < d1 && d.base < s.end()) ? BEVWARP_ERR_OVERLAP : BEVWARP_OK;
     }

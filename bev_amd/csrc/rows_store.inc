@@ -1,5 +1,5 @@
 // rows_store.inc -- FRAGMENT of the body of warp_rows (warp_rows.h includes it inside the kernel; its lambdas capture the kernel's state by
-// reference and are always inlined).  Not a header: the store stage: LDS row -> registers in store order -> memory (wide stores, element stores for ragged lanes, float planes, the composite's LDS tiles).
+// reference and are always inlined).  Not a header: the store stage: LDS row -> registers in store order -> memory (wide stores, element stores for ragged lanes, float32 and 16-bit planes, the composite's LDS tiles).
     // -- LDS row -> registers in store order (u8: pixels 4 l .. 4 l + 3 of the segment; float: 16-byte unit u * 64 + l)
     constexpr int kVec = sizeof(T) == 1 ? 64 : TRW / 4;  // 16-byte units in the wave's row segment
     constexpr int NQ = (kVec + 63) / 64;
@@ -54,6 +54,30 @@
         const bool lane_vec = a.dst_vec_ok && lane_px == PPL;
         if constexpr (sizeof(T) == 1) {  // the lane's 4 pixels = 4 C contiguous bytes, one instruction
             const uint32_t p[4] = {out[0].x, out[0].y, out[0].z, out[0].w};
+            if constexpr (PFMT == kPlanes16) {  // 16-bit planes: the float32 value of the float planes, converted; one 8-byte store per channel
+                if (kBlk && y + st_row > y_last) return;
+                uint8_t* dp = dframe + (int64_t)(y + st_row) * a.dst_rs + (int64_t)st_x * 2;
+                auto planes = [&](auto as) __attribute__((always_inline)) {
+#pragma unroll
+                    for (int k = 0; k < C; k++) {
+                        const float sc = a.pscale[k], bi = a.pbias[k];
+                        const uint32_t h[4] = {as((float)((p[0] >> (8 * k)) & 0xffu) * sc + bi), as((float)((p[1] >> (8 * k)) & 0xffu) * sc + bi),
+                                               as((float)((p[2] >> (8 * k)) & 0xffu) * sc + bi), as((float)((p[3] >> (8 * k)) & 0xffu) * sc + bi)};
+                        uint16_t* dk = reinterpret_cast<uint16_t*>(dp + k * a.dst_ps);
+                        if (__builtin_expect(lane_vec, 1)) {
+                            u32x2 o = {h[0] | (h[1] << 16), h[2] | (h[3] << 16)};
+                            wide_store(reinterpret_cast<u32x2*>(dk), o);
+                        } else {
+                            for (int i = 0; i < lane_px; i++) dk[i] = (uint16_t)h[i];
+                        }
+                    }
+                };
+                if (a.planar == kPlaneBF16)  // (wave-uniform)
+                    planes(BitsBF16{});
+                else
+                    planes(BitsF16{});
+                return;
+            }
             if constexpr (PLANAR) {  // float planes: one 16-byte store per channel
                 if (kBlk && y + st_row > y_last) return;
                 uint8_t* dp = dframe + (int64_t)(y + st_row) * a.dst_rs + (int64_t)st_x * 4;
@@ -104,6 +128,12 @@
                 if (px >= a.dst_w || py > y_last) continue;
 #pragma unroll
                 for (int k = 0; k < C; k++) {
+                    if constexpr (PFMT == kPlanes16) {  // (2-byte stores, 64 consecutive elements of a plane row per instruction)
+                        uint16_t* dk = reinterpret_cast<uint16_t*>(dframe + k * a.dst_ps + (int64_t)py * a.dst_rs) + px;
+                        const float v = o[j * C + k] * a.pscale[k] + a.pbias[k];
+                        *dk = (uint16_t)(a.planar == kPlaneBF16 ? BitsBF16{}(v) : BitsF16{}(v));
+                        continue;
+                    }
                     float* dk = reinterpret_cast<float*>(dframe + k * a.dst_ps + (int64_t)py * a.dst_rs) + px;
                     *dk = o[j * C + k] * a.pscale[k] + a.pbias[k];
                 }

@@ -12,6 +12,21 @@ __device__ __forceinline__ void wide_store(V* p, const V& v) {
     *p = v;
 }
 
+// float32 -> the 16 bits of a float16 / bfloat16 (warp_rows_planes16): round to nearest, ties to even, subnormal results kept, overflow
+// to infinity.  Plain casts: v_cvt_f16_f32 and v_cvt_pk_bf16_f32 on gfx950.
+struct BitsF16 {
+    __device__ __forceinline__ uint32_t operator()(float v) const {
+        const _Float16 h = (_Float16)v;
+        return __builtin_bit_cast(uint16_t, h);
+    }
+};
+struct BitsBF16 {
+    __device__ __forceinline__ uint32_t operator()(float v) const {
+        const __bf16 h = (__bf16)v;
+        return __builtin_bit_cast(uint16_t, h);
+    }
+};
+
 // ---------------------------------------------------------------------------------------------------
 // Blending.  u8: 15-bit fixed point of the reference == exact integer form
 //   (sum_i p_i * w_i * 32 + 2^14) >> 15  ==  (wy0 * (wx0 p00 + wx1 p01) + wy1 * (wx0 p10 + wx1 p11) + 512) >> 10

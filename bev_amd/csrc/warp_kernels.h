@@ -7,6 +7,7 @@ namespace bevwarp {
 
 constexpr int kNearest = 0;
 constexpr int kLinear = 1;
+constexpr int kPlaneF32 = 1, kPlaneF16 = 2, kPlaneBF16 = 3;  // WarpArgs::planar
 
 struct WarpArgs {
     const uint8_t* src;
@@ -27,8 +28,8 @@ struct WarpArgs {
     int dst_vec_ok;              // destination layout admits the wide stores
     float bval_f[4];
     uint8_t bval_u8[4];
-    // planar float output of 8-bit warps (bevwarp_warp_planar): dst[c][y][x] = float(pixel) * pscale[c] + pbias[c]
-    int planar;
+    // planar float output (bevwarp_warp_planar, bevwarp_warp_planes): dst[c][y][x] = convert(float(pixel) * pscale[c] + pbias[c])
+    int planar;                  // 0: interleaved pixels; kPlaneF32, kPlaneF16, kPlaneBF16: the planes' element type
     int64_t dst_ps;              // bytes between channel planes
     float pscale[4], pbias[4];
     // composite (bevwarp_warp_composite): sources 1 and 2 (foreground, mask) beside src / minv / src_rs / src_h / src_w (background)

@@ -1,5 +1,5 @@
 // warp_kernels.hip -- host side of the warp kernels: launch geometry helpers, dispatch to the per-format translation units
-// (warp_u8_linear.hip, warp_u8_nearest.hip, warp_f32_linear.hip, warp_f32_nearest.hip, warp_composite.hip), and the footprint
+// (warp_u8_linear.hip, warp_u8_nearest.hip, warp_f32_linear.hip, warp_f32_nearest.hip, their _p16 twins, warp_composite.hip), and the footprint
 // kernel (measurement aid).  The kernel itself is warp_rows.h.
 #include "coords.h"
 
@@ -10,6 +10,10 @@ void launch_u8_linear(const WarpArgs& a, int channels, dim3 grid, hipStream_t st
 void launch_u8_nearest(const WarpArgs& a, int channels, dim3 grid, hipStream_t stream);
 void launch_f32_linear(const WarpArgs& a, int channels, dim3 grid, hipStream_t stream);
 void launch_f32_nearest(const WarpArgs& a, int channels, dim3 grid, hipStream_t stream);
+void launch_u8_linear_p16(const WarpArgs& a, int channels, dim3 grid, hipStream_t stream);  // (float16 / bfloat16 planes)
+void launch_u8_nearest_p16(const WarpArgs& a, int channels, dim3 grid, hipStream_t stream);
+void launch_f32_linear_p16(const WarpArgs& a, int channels, dim3 grid, hipStream_t stream);
+void launch_f32_nearest_p16(const WarpArgs& a, int channels, dim3 grid, hipStream_t stream);
 
 namespace {
 
@@ -43,10 +47,12 @@ __global__ void footprint_kernel(unsigned char* __restrict__ touched, int batch,
 
 #ifdef BEVWARP_CLOCK
 hipError_t launch_u8_linear_clock(unsigned long long*, int), launch_u8_nearest_clock(unsigned long long*, int), launch_f32_linear_clock(unsigned long long*, int),
-    launch_f32_nearest_clock(unsigned long long*, int), launch_composite_clock(unsigned long long*, int);
+    launch_f32_nearest_clock(unsigned long long*, int), launch_composite_clock(unsigned long long*, int), launch_u8_linear_p16_clock(unsigned long long*, int),
+    launch_u8_nearest_p16_clock(unsigned long long*, int), launch_f32_linear_p16_clock(unsigned long long*, int), launch_f32_nearest_p16_clock(unsigned long long*, int);
 hipError_t debug_read_clock(unsigned long long* out4, int reset) {  // the sum over the translation units
     for (int i = 0; i < 16; i++) out4[i] = 0;  // (16 words, the size bevwarp_debug_clock's callers pass; words 0 .. 2 are written: warp_rows.h)
-    for (auto fn : {launch_u8_linear_clock, launch_u8_nearest_clock, launch_f32_linear_clock, launch_f32_nearest_clock, launch_composite_clock}) {
+    for (auto fn : {launch_u8_linear_clock, launch_u8_nearest_clock, launch_f32_linear_clock, launch_f32_nearest_clock, launch_composite_clock,
+                    launch_u8_linear_p16_clock, launch_u8_nearest_p16_clock, launch_f32_linear_p16_clock, launch_f32_nearest_p16_clock}) {
         const hipError_t e = fn(out4, reset);
         if (e != hipSuccess) return e;
     }
@@ -72,10 +78,11 @@ int resident_workgroups(int dtype, int channels, int interp) {
 hipError_t launch_warp(const WarpArgs& a, int dtype, int channels, int interp, hipStream_t stream) {
     (void)hipGetLastError();  // a stale error left by the host framework is not this call's
     const dim3 grid((unsigned)(8 * (a.chunk + a.tail_split)));
+    const bool p16 = a.planar == kPlaneF16 || a.planar == kPlaneBF16;
     if (dtype == 0)
-        (interp == kNearest ? launch_u8_nearest : launch_u8_linear)(a, channels, grid, stream);
+        (interp == kNearest ? (p16 ? launch_u8_nearest_p16 : launch_u8_nearest) : (p16 ? launch_u8_linear_p16 : launch_u8_linear))(a, channels, grid, stream);
     else
-        (interp == kNearest ? launch_f32_nearest : launch_f32_linear)(a, channels, grid, stream);
+        (interp == kNearest ? (p16 ? launch_f32_nearest_p16 : launch_f32_nearest) : (p16 ? launch_f32_linear_p16 : launch_f32_linear))(a, channels, grid, stream);
     return hipGetLastError();
 }
 

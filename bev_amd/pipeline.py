@@ -10,7 +10,7 @@ frame travels through three stages that run concurrently on three HIP streams:
 with `depth` slots per stage (default 3), so frame i + 1 uploads and frame i - 1 downloads while frame i is warped; the
 link is full duplex.  The decoder can write straight into the next pinned slot (`next_input()`), which removes the host
 memcpy a pageable `submit(frame)` needs.  Output is the interleaved BEV frame of the source dtype, or -- `planar=True` --
-normalised float32 channel planes (the layout a detector takes), in the same pass.  Results are the resident path's, bit
+normalised channel planes (the layout a detector takes; float32, or float16 / bfloat16 with `plane_dtype`), in the same pass.  Results are the resident path's, bit
 for bit: the same kernel runs on the same bytes.
 """
 import collections
@@ -52,21 +52,27 @@ _H2D, _D2H = 1, 2  # hipMemcpyHostToDevice / hipMemcpyDeviceToHost
 
 class FramePipeline:
     def __init__(self, src_hw, channels, M, dsize, flags=_warp.INTER_LINEAR, depth=3, dtype=torch.uint8, planar=False, scale=1.0 / 255.0, bias=0.0,
-                 download=True, device="cuda", zero_copy_out=True):
+                 download=True, device="cuda", zero_copy_out=True, plane_dtype=torch.float32):
         """src_hw (H, W) of the decoded frames; M the forward homography (as for warpPerspective); dsize (u_size, v_size).
         download=False leaves the BEV frames on the device (results are device tensors valid until `depth` further frames
         have been submitted).  zero_copy_out (with download): the kernel stores the BEV frame straight into the pinned host
         slot over PCIe -- no device copy of it, no D2H copy behind the kernel (on boxes where the two copy directions share an
-        engine that copy serialises with the next frame's upload)."""
+        engine that copy serialises with the next frame's upload).
+        plane_dtype (with planar): torch.float32, torch.float16 or torch.bfloat16 -- the element type of the planes, of the device and
+        of the pinned host slots (warp_to_planar's out_dtype).  numpy has no bfloat16: result() hands such a host slot out as a torch
+        tensor."""
+        if planar and plane_dtype not in _warp._PLANE_DTYPES:
+            raise ValueError("unsupported plane_dtype %s (torch.float32, torch.float16, torch.bfloat16)" % (plane_dtype,))
         if depth < 2:
             raise ValueError("depth must be >= 2 (one slot in flight per stage boundary)")
         self.device = torch.device(device)
         self.H, self.W, self.C = int(src_hw[0]), int(src_hw[1]), int(channels)
         self.dw, self.dh = int(dsize[0]), int(dsize[1])
         self.flags, self.depth, self.planar, self.scale, self.bias, self.download = flags, depth, planar, scale, bias, download
+        self.plane_dtype = plane_dtype
         self.zero_copy_out = bool(zero_copy_out and download)
         out_shape = (self.C, self.dh, self.dw) if planar else (self.dh, self.dw, self.C)
-        out_dtype = torch.float32 if planar else dtype
+        out_dtype = plane_dtype if planar else dtype
         self.h_in = [torch.empty((self.H, self.W, self.C), dtype=dtype, pin_memory=True) for _ in range(depth)]
         self.d_in = [torch.empty((self.H, self.W, self.C), dtype=dtype, device=self.device) for _ in range(depth)]
         self.d_out = [torch.empty(out_shape, dtype=out_dtype, device=self.device) for _ in range(depth)]
@@ -99,10 +105,14 @@ class FramePipeline:
                 sc = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, dtype=np.float64), (self.C,)))
                 bi = np.ascontiguousarray(np.broadcast_to(np.asarray(bias, dtype=np.float64), (self.C,)))
                 self._keep = getattr(self, "_keep", []) + [sc, bi]
-                args = (s.data_ptr(), d.data_ptr(), 1, self.H, self.W, self.dh, self.dw, self.C, s.numel() * esz, s.stride(0) * esz, d.numel() * 4,
-                        d.stride(0) * 4, d.stride(1) * 4, self.minv.data_ptr(), 1, _warp._DTYPES[s.dtype], interp, None,
-                        sc.ctypes.data_as(ctypes.c_void_p), bi.ctypes.data_as(ctypes.c_void_p), self.s_run)
-                self._launch.append((lib.bevwarp_warp_planar, args))
+                psz = d.element_size()
+                args = (s.data_ptr(), d.data_ptr(), 1, self.H, self.W, self.dh, self.dw, self.C, s.numel() * esz, s.stride(0) * esz, d.numel() * psz,
+                        d.stride(0) * psz, d.stride(1) * psz, self.minv.data_ptr(), 1, _warp._DTYPES[s.dtype], interp, None,
+                        sc.ctypes.data_as(ctypes.c_void_p), bi.ctypes.data_as(ctypes.c_void_p))
+                if plane_dtype == torch.float32:
+                    self._launch.append((lib.bevwarp_warp_planar, args + (self.s_run,)))
+                else:
+                    self._launch.append((lib.bevwarp_warp_planes, args + (_warp._PLANE_DTYPES[plane_dtype], self.s_run)))
             else:
                 args = (s.data_ptr(), d.data_ptr(), 1, self.H, self.W, self.dh, self.dw, self.C, s.numel() * esz, s.stride(0) * esz, d.numel() * esz,
                         d.stride(0) * esz, self.minv.data_ptr(), 1, _warp._DTYPES[s.dtype], interp, None, self.s_run)
@@ -142,7 +152,7 @@ class FramePipeline:
         with torch.cuda.stream(stream):
             if self.planar:
                 _warp.warp_to_planar(self.d_in[slot], None, (self.dw, self.dh), scale=self.scale, bias=self.bias, flags=self.flags, out=self.d_out[slot],
-                                     M_inv_device=self.minv)
+                                     M_inv_device=self.minv, out_dtype=self.plane_dtype)
             else:
                 _warp.warp_perspective(self.d_in[slot], None, (self.dw, self.dh), flags=self.flags, out=self.d_out[slot], M_inv_device=self.minv)
 
@@ -186,11 +196,12 @@ class FramePipeline:
 
     def result(self):
         """The oldest frame's BEV: a numpy view of a pinned slot (download=True; valid until `depth` further frames have been
-        committed) or the device tensor.  Blocks until that frame is through."""
+        committed; bfloat16 planes: the pinned tensor itself) or the device tensor.  Blocks until that frame is through."""
         slot = self.pending.popleft()
         if self.download:
             _ok(_hip_rt().hipEventSynchronize((self.ev_run if self.zero_copy_out else self.ev_down)[slot]))
-            return self.h_out[slot].numpy()
+            h = self.h_out[slot]
+            return h if h.dtype == torch.bfloat16 else h.numpy()  # (numpy has no bfloat16)
         _ok(_hip_rt().hipEventSynchronize(self.ev_run[slot]))
         return self.d_out[slot]
 

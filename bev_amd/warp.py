@@ -33,6 +33,7 @@ BORDER_TRANSPARENT = 5
 _BORDER_MODES = (BORDER_CONSTANT, BORDER_REPLICATE, BORDER_REFLECT, BORDER_WRAP, BORDER_REFLECT_101, BORDER_TRANSPARENT)
 
 _DTYPES = {torch.uint8: _lib.U8, torch.float32: _lib.F32}
+_PLANE_DTYPES = {torch.float32: _lib.F32, torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}  # what warp_to_planar writes
 
 
 def invert_homography(M):
@@ -307,18 +308,27 @@ def warp_perspective(src, M, dsize, flags=INTER_LINEAR, border_value=None, out=N
     return d4
 
 
-def warp_to_planar(src, M, dsize, scale=1.0 / 255.0, bias=0.0, flags=INTER_LINEAR, border_value=None, out=None, M_inv_device=None):
-    """Warp uint8 (or float32) frames and write them as normalised float32 channel planes in the same pass (SURVEY.md 8(f2):
+def warp_to_planar(src, M, dsize, scale=1.0 / 255.0, bias=0.0, flags=INTER_LINEAR, border_value=None, out=None, M_inv_device=None,
+                   out_dtype=torch.float32):
+    """Warp uint8 (or float32) frames and write them as normalised channel planes in the same pass (SURVEY.md 8(f2):
     the layout a detector takes, `(B, C, v_size, u_size)`), without materialising the interleaved BEV frame:
 
         out[b, c] = warp_perspective(src, M, dsize)[b, :, :, c].float() * scale[c] + bias[c]      (float32 mul, then add)
 
     src (B, H, W, C) / (H, W, C) / (H, W) uint8 or float32 CUDA tensor; scale / bias scalars or per-channel sequences (e.g.
-    1 / (255 * std) and -mean / std); other arguments as warp_perspective.  Returns (B, C, h, w), or (C, h, w) for a
-    single frame.  Asynchronous on the current stream."""
+    1 / (255 * std) and -mean / std); other arguments as warp_perspective.
+    out_dtype  torch.float32 (default), torch.float16 or torch.bfloat16: the planes' element type.  The 16-bit types hold the float32
+               value above rounded to nearest, ties to even -- bit for bit what `warp_to_planar(...).half()` / `.bfloat16()` gives (NaN
+               payloads aside), without the conversion pass and with half the bytes stored (include/bevwarp.h, bevwarp_warp_planes).
+               A given `out` must have this dtype.
+    Returns (B, C, h, w), or (C, h, w) for a single frame.  Asynchronous on the current stream."""
     interp = int(flags) & 7
     if interp not in (INTER_NEAREST, INTER_LINEAR):  # (no bicubic kernel writes planes)
         raise ValueError("unsupported interpolation flag %d (warp_to_planar: INTER_NEAREST, INTER_LINEAR)" % interp)
+    if out_dtype not in _PLANE_DTYPES:
+        raise ValueError("unsupported out_dtype %s (warp_to_planar: torch.float32, torch.float16, torch.bfloat16)" % (out_dtype,))
+    if out is not None and getattr(out, "dtype", None) != out_dtype:
+        raise ValueError("out must be a %s tensor (out_dtype), got %s" % (out_dtype, getattr(out, "dtype", type(out))))
     if not isinstance(src, torch.Tensor) or not src.is_cuda or src.dtype not in _DTYPES:
         raise ValueError("warp_to_planar needs a uint8 or float32 CUDA (HIP) tensor")
     if src.dim() == 2:
@@ -337,23 +347,30 @@ def warp_to_planar(src, M, dsize, scale=1.0 / 255.0, bias=0.0, flags=INTER_LINEA
         M_inv_device = device_inverse(M, s4.device, inverse_given=bool(int(flags) & WARP_INVERSE_MAP))
     n_m = _check_minv(M_inv_device, s4.device, B)
     if out is None:
-        d4 = torch.empty((B, C, dh, dw), dtype=torch.float32, device=s4.device)
+        d4 = torch.empty((B, C, dh, dw), dtype=out_dtype, device=s4.device)
     else:
-        _check_out(out, torch.float32, s4.device, B * C * dh * dw)
+        _check_out(out, out_dtype, s4.device, B * C * dh * dw)
         d4 = out.reshape(B, C, dh, dw)
         if d4.data_ptr() != out.data_ptr() or d4.stride(3) != 1:
-            raise ValueError("out must be a float32 (B, C, h, w) tensor with contiguous rows")
+            raise ValueError("out must be a %s (B, C, h, w) tensor with contiguous rows" % (out_dtype,))
     def per_channel(v):
         return np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (C,)))
     sc, bi = per_channel(scale), per_channel(bias)
     bv = None if border_value is None else per_channel(border_value)
     stream = torch.cuda.current_stream(s4.device).cuda_stream
     with torch.cuda.device(s4.device):
-        st = _lib.load().bevwarp_warp_planar(
-            s4.data_ptr(), d4.data_ptr(), B, H, W, dh, dw, C, s4.stride(0) * s4.element_size(), s4.stride(1) * s4.element_size(),
-            d4.stride(0) * 4, d4.stride(1) * 4, d4.stride(2) * 4, M_inv_device.data_ptr(), n_m, _DTYPES[s4.dtype], interp,
-            None if bv is None else bv.ctypes.data_as(ctypes.c_void_p), sc.ctypes.data_as(ctypes.c_void_p),
-            bi.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(stream))
+        if out_dtype == torch.float32:
+            st = _lib.load().bevwarp_warp_planar(
+                s4.data_ptr(), d4.data_ptr(), B, H, W, dh, dw, C, s4.stride(0) * s4.element_size(), s4.stride(1) * s4.element_size(),
+                d4.stride(0) * 4, d4.stride(1) * 4, d4.stride(2) * 4, M_inv_device.data_ptr(), n_m, _DTYPES[s4.dtype], interp,
+                None if bv is None else bv.ctypes.data_as(ctypes.c_void_p), sc.ctypes.data_as(ctypes.c_void_p),
+                bi.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(stream))
+        else:  # float16 / bfloat16 planes: the kernels that convert on the way out
+            st = _lib.load().bevwarp_warp_planes(
+                s4.data_ptr(), d4.data_ptr(), B, H, W, dh, dw, C, s4.stride(0) * s4.element_size(), s4.stride(1) * s4.element_size(),
+                d4.stride(0) * 2, d4.stride(1) * 2, d4.stride(2) * 2, M_inv_device.data_ptr(), n_m, _DTYPES[s4.dtype], interp,
+                None if bv is None else bv.ctypes.data_as(ctypes.c_void_p), sc.ctypes.data_as(ctypes.c_void_p),
+                bi.ctypes.data_as(ctypes.c_void_p), _PLANE_DTYPES[out_dtype], ctypes.c_void_p(stream))
     _lib.check(st)
     if out is not None:
         return out

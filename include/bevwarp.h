@@ -15,6 +15,9 @@
  *   bevwarp_warp_planar     the same warp (8-bit or float32 frames), written as normalised float32 channel planes in the same
  *                             pass (the layout step between vis_homo.py:89 and a detector's input;
  *                             the reference leaves it to its callers)
+ *   bevwarp_warp_planes     the same planes as float32, float16 or bfloat16: the layout AND precision step between
+ *                             vis_homo.py:89 and a detector's input (detectors on this hardware run in 16 bits; the `.half()` pass
+ *                             behind bevwarp_warp_planar is folded into the warp's stores)
  *   bevwarp_composite       composite_reg_img(bg, fg, fg_mask), bev/tool/compo.py:5-24 (the blend after the three warps
  *                             of composite_bev_img, :26-49)
  *   bevwarp_warp_composite  composite_bev_img(bg, fg, fg_mask, ...), bev/tool/compo.py:26-49: the three warps and the blend
@@ -63,7 +66,9 @@ typedef enum bevwarp_status {
     BEVWARP_ERR_OVERLAP = -6       /* source and destination share bytes (ABI v5; v4 reported BAD_ARG)   */
 } bevwarp_status;
 
-typedef enum bevwarp_dtype { BEVWARP_U8 = 0, BEVWARP_F32 = 1, BEVWARP_F64 = 2 } bevwarp_dtype;
+/* BEVWARP_F16 (IEEE binary16) and BEVWARP_BF16 (bfloat16) are plane types of bevwarp_warp_planes only: as a pixel or point type every
+ * entry point answers BEVWARP_ERR_UNSUPPORTED for them. */
+typedef enum bevwarp_dtype { BEVWARP_U8 = 0, BEVWARP_F32 = 1, BEVWARP_F64 = 2, BEVWARP_F16 = 3, BEVWARP_BF16 = 4 } bevwarp_dtype;
 
 /* Same numeric values as cv2.INTER_NEAREST / cv2.INTER_LINEAR / cv2.INTER_CUBIC.  BEVWARP_CUBIC is taken by bevwarp_warp and
  * bevwarp_warp_border only; every other entry point with an `interp` returns BEVWARP_ERR_UNSUPPORTED for it. */
@@ -194,6 +199,29 @@ int bevwarp_warp_planar(const void *src, void *dst, int batch, int src_h, int sr
                         int64_t dst_row_stride, const double *M_inv, int m_count, int dtype, int interp,
                         const double *border_value /*HOST*/, const double *scale /*HOST*/, const double *bias /*HOST*/,
                         void *stream);
+
+/*
+ * bevwarp_warp_planar with the planes' element type P = plane_dtype (BEVWARP_F32 | BEVWARP_F16 | BEVWARP_BF16), one pass:
+ *   v               = float32(warp(src[b])[y][x][c]) * float32(scale[c]) + float32(bias[c])
+ *   dst[b][c][y][x] = convert_P(v)
+ * v is exactly the value bevwarp_warp_planar stores: a float32 multiply, then a float32 add, each rounded, no FMA.  The result is what
+ * `bevwarp_warp_planar(...)` followed by a float32 -> P conversion pass gives, double rounding included, without that pass:
+ *   convert_F32   the identity: the call IS bevwarp_warp_planar.
+ *   convert_F16   IEEE binary32 -> binary16, round to nearest, ties to even.  Overflow gives +-inf (65520 is the first value that rounds
+ *                 to inf); subnormal results are kept (2^-24 is representable, the tie 2^-25 goes to 0); -0 stays -0.
+ *   convert_BF16  rounds to the upper 16 bits, nearest, ties to even; the carry may reach inf; float32 subnormals give bfloat16
+ *                 subnormals (not flushed).
+ *   A NaN gives some NaN; its payload and sign are unspecified.
+ *   dst             device; the three destination strides are in BYTES and multiples of the element size (2 for the 16-bit types); base
+ *                   and strides that are all multiples of 8 enable the wide stores of the 16-bit planes (16 for float32).
+ *   plane_dtype     any other value: BEVWARP_ERR_UNSUPPORTED.  interp: BEVWARP_CUBIC is BEVWARP_ERR_UNSUPPORTED, as for bevwarp_warp_planar.
+ * Every other argument, the overlap rule and BEVWARP_ERR_NOT_FINITE for scale and bias are bevwarp_warp_planar's.
+ */
+int bevwarp_warp_planes(const void *src, void *dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int channels,
+                        int64_t src_frame_stride, int64_t src_row_stride, int64_t dst_frame_stride, int64_t dst_plane_stride,
+                        int64_t dst_row_stride, const double *M_inv, int m_count, int dtype, int interp,
+                        const double *border_value /*HOST*/, const double *scale /*HOST*/, const double *bias /*HOST*/,
+                        int plane_dtype, void *stream);
 
 /*
  * out[i] = uint8(min(round_half_even(fg[i] * (mask[i] / 255) + bg[i] * (1 - mask[i] / 255)), 255)) for i in [0, n), computed in

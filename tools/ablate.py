@@ -16,8 +16,9 @@ CSRC = os.path.join(ROOT, "bev_amd", "csrc")
 FLAGS = "-O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -Wno-unused-function -Wno-undefined-internal".split()
 
 
-KERNEL_FILES = ("coords.h", "sample.h", "warp_rows.h", "rows_coords.inc", "rows_sample.inc", "rows_store.inc", "rows_tiles.inc", "rows_run.inc", "warp_kernels.h")
-UNITS = ("warp_kernels", "warp_u8_linear", "warp_u8_nearest", "warp_f32_linear", "warp_f32_nearest", "warp_composite")
+KERNEL_FILES = ("coords.h", "sample.h", "warp_rows.h", "rows_body.inc", "rows_coords.inc", "rows_sample.inc", "rows_store.inc", "rows_tiles.inc", "rows_run.inc", "warp_kernels.h")
+UNITS = ("warp_kernels", "warp_u8_linear", "warp_u8_nearest", "warp_f32_linear", "warp_f32_nearest", "warp_composite",
+         "warp_u8_linear_p16", "warp_u8_nearest_p16", "warp_f32_linear_p16", "warp_f32_nearest_p16")
 
 # snippets of the product source that several specs replace
 TAP_LOOP = "#pragma unroll\n        for (int j = 0; j < PPL; j++) {\n            const uint32_t off = S0[j];\n"  # head of issue_s' loop over a lane's pixels
