@@ -12,6 +12,7 @@
 #include "warp_border.h"
 #include "warp_cubic.h"
 #include "warp_kernels.h"
+#include "warp_nv12.h"
 
 #pragma clang fp contract(off)
 
@@ -189,6 +190,30 @@ int bevwarp_warp_border(const void* src, void* dst, int batch, int src_h, int sr
     if (!cubic) return launched(launch_warp_border(a, dtype, channels, interp, border_mode, p.total_tiles, (hipStream_t)stream));
     if (border_values(border_mode == BEVWARP_BORDER_CONSTANT ? border_value : nullptr, channels, a.cv_f, a.cv_u8) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
     return launched(launch_warp_cubic(a, dtype, channels, border_mode, p.total_tiles, (hipStream_t)stream));
+}
+
+int bevwarp_warp_nv12(const void* y, const void* uv, void* dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int64_t y_frame_stride,
+                      int64_t y_row_stride, int64_t uv_frame_stride, int64_t uv_row_stride, int64_t dst_frame_stride, int64_t dst_row_stride,
+                      const double* M_inv, int m_count, int interp, int rgb_order, const double* border_value, void* stream) {
+    const Nv12Call c = {y, uv, dst, batch, src_h, src_w, dst_h, dst_w, y_frame_stride, y_row_stride, uv_frame_stride, uv_row_stride,
+                        dst_frame_stride, dst_row_stride, M_inv, m_count, interp, rgb_order};
+    const int st = plan::check_warp_nv12(c);
+    if (st != BEVWARP_OK || batch == 0) return st;
+    const TilePlan p = plan::plan_border(batch, dst_h, dst_w, kBorderTileW, kBorderTileH);
+    if (p.status != BEVWARP_OK) return p.status;
+    Nv12Args a;
+    memset(&a, 0, sizeof(a));
+    a.y = (const uint8_t*)y, a.uv = (const uint8_t*)uv, a.dst = (uint8_t*)dst, a.minv = M_inv;
+    a.y_fs = y_frame_stride, a.y_rs = y_row_stride, a.uv_fs = uv_frame_stride, a.uv_rs = uv_row_stride, a.dst_fs = dst_frame_stride, a.dst_rs = dst_row_stride;
+    a.src_h = src_h, a.src_w = src_w, a.dst_h = dst_h, a.dst_w = dst_w;
+    a.m_stride = m_count == 1 ? 0 : 9;
+    copy_grid(a, p);
+    a.dst_vec_ok = plan::wide_stores_ok(c.dst_image(), plan::store_align(BEVWARP_U8, 3, false));
+    float bf[4];
+    uint8_t bu[4];  // (in the destination's channel order, as given: the border value is not converted)
+    if (border_values(border_value, 3, bf, bu) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
+    a.border = (uint32_t)bu[0] | ((uint32_t)bu[1] << 8) | ((uint32_t)bu[2] << 16);
+    return launched(launch_warp_nv12(a, interp, rgb_order, p.total_tiles, (hipStream_t)stream));
 }
 
 int bevwarp_warp_classes(const void* src, void* dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int channels, int64_t src_frame_stride,

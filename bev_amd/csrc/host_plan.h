@@ -149,6 +149,36 @@ inline int check_warp(const WarpCall& c) {
     return regions_overlap(s, d) ? BEVWARP_ERR_OVERLAP : BEVWARP_OK;
 }
 
+// ---- an NV12 warp call (bevwarp_warp_nv12) -------------------------------------------------------------------------------------
+// The source is two images: src_h rows of src_w Y bytes, and src_h / 2 rows of src_w / 2 (U, V) pairs (src_w bytes, 2-byte elements).
+// The destination is 8-bit, 3 channels.
+struct Nv12Call {
+    const void *y, *uv, *dst;
+    int batch, src_h, src_w, dst_h, dst_w;
+    int64_t y_fs, y_rs, uv_fs, uv_rs, dst_fs, dst_rs;
+    const double* minv;
+    int m_count, interp, rgb_order;
+
+    Image y_image() const { return {(uintptr_t)y, src_h, (uint64_t)src_w, y_rs, y_fs, batch}; }
+    Image uv_image() const { return {(uintptr_t)uv, src_h / 2, (uint64_t)src_w, uv_rs, uv_fs, batch}; }
+    Image dst_image() const { return {(uintptr_t)dst, dst_h, (uint64_t)dst_w * 3, dst_rs, dst_fs, batch}; }
+};
+
+// All argument checks of an NV12 warp, in the order the header documents: bad arguments (null pointers, sizes, odd source sides,
+// layouts, matrix count), unsupported interpolation or channel order, source size limits per plane, overlap of the destination with
+// either plane (the planes may overlap each other: both are only read).
+inline int check_warp_nv12(const Nv12Call& c) {
+    if (!c.y || !c.uv || !c.dst || !c.minv) return BEVWARP_ERR_BAD_ARG;
+    if (c.batch < 0 || c.src_h <= 0 || c.src_w <= 0 || c.dst_h <= 0 || c.dst_w <= 0 || (c.src_h & 1) || (c.src_w & 1)) return BEVWARP_ERR_BAD_ARG;
+    const Image y = c.y_image(), uv = c.uv_image(), d = c.dst_image();
+    if (layout_status(y, 1) != BEVWARP_OK || layout_status(uv, 2) != BEVWARP_OK || layout_status(d, 1) != BEVWARP_OK) return BEVWARP_ERR_BAD_ARG;
+    if (c.m_count != 1 && c.m_count != c.batch) return BEVWARP_ERR_BAD_ARG;
+    if ((c.interp != BEVWARP_NEAREST && c.interp != BEVWARP_LINEAR) || (c.rgb_order != 0 && c.rgb_order != 1)) return BEVWARP_ERR_UNSUPPORTED;
+    int st;
+    if ((st = source_size_status(y, c.src_w)) != BEVWARP_OK || (st = source_size_status(uv, c.src_w / 2)) != BEVWARP_OK || c.batch == 0) return st;
+    return (regions_overlap(y, d) || regions_overlap(uv, d)) ? BEVWARP_ERR_OVERLAP : BEVWARP_OK;
+}
+
 // ---- launch geometry ---------------------------------------------------------------------------------------------------------
 struct TilePlan {
     int status;                  // BEVWARP_OK or BEVWARP_ERR_TOO_LARGE (the other fields are then meaningless)

@@ -13,6 +13,7 @@ and leave /root/reference/vis_homo.py:89-91, bev/homo.py:36 and bev/tool/compo.p
     cv2.invert(M) -> (retval, M_inv)                                             the 3x3 step inside warpPerspective
 
     cv2.resize(img, (w, h)[, dst, fx, fy, interpolation])                        vis_homo.py:90 (uint8, INTER_LINEAR only)
+    cv2.cvtColor(nv12, COLOR_YUV2BGR_NV12 | COLOR_YUV2RGB_NV12)                  the conversion behind video.read(), vis_homo.py:86
 
 `cv2.resize` here is OpenCV's own bilinear algorithm (sampling at (d + 0.5) * scale - 0.5, 11-bit coefficients, replicated edge, the
 2 x 2 box-mean rule) as its own device kernel -- round 3 had none, because a resize routed through the WARP kernel (1/32-px
@@ -47,6 +48,8 @@ BORDER_REFLECT_101 = 4
 BORDER_REFLECT101 = 4
 BORDER_DEFAULT = 4
 BORDER_TRANSPARENT = 5
+COLOR_YUV2RGB_NV12 = 90
+COLOR_YUV2BGR_NV12 = 91
 DECOMP_LU = 0
 RANSAC, LMEDS, RHO = 8, 4, 16
 
@@ -64,6 +67,23 @@ def resize(src, dsize, dst=None, fx=0, fy=0, interpolation=INTER_LINEAR):
     """uint8 images of 1-4 channels, INTER_LINEAR (cv2.resize's default; the reference passes none).  Bit-exact with
     oracle/resize_oracle.c (classic OpenCV 3.x-4.x bilinear path, restated from memory: parity unpinned)."""
     return _resize.cv2_resize(src, dsize, dst=dst, fx=fx, fy=fy, interpolation=interpolation)
+
+
+def cvtColor(src, code):
+    """COLOR_YUV2BGR_NV12 / COLOR_YUV2RGB_NV12 only: a `(H * 3 / 2, W)` uint8 array (Y plane, then the rows of (U, V) pairs) -> `(H, W, 3)`.
+    OpenCV's 8-bit BT.601 limited-range fixed point (include/bevwarp.h, bevwarp_warp_nv12; restated from memory: parity unpinned), run as
+    the identity nearest warp of the NV12 kernel.  A camera loop needs no such pass: bev_amd.warp.warp_perspective_nv12 converts inside
+    the warp."""
+    if code not in (COLOR_YUV2BGR_NV12, COLOR_YUV2RGB_NV12):
+        raise NotImplementedError("cvtColor: code %r is not implemented (COLOR_YUV2BGR_NV12 = 91 and COLOR_YUV2RGB_NV12 = 90 only)" % (code,))
+    img = np.asarray(src)
+    if img.dtype != np.uint8 or img.ndim != 2:
+        raise ValueError("cvtColor (NV12): a uint8 array of shape (H * 3 / 2, W) is needed, got %s %s" % (img.dtype, img.shape))
+    import torch
+    y, uv = _warp.split_nv12(torch.from_numpy(np.ascontiguousarray(img)).to("cuda"))  # (one upload; the planes are views of it)
+    H, W = y.shape
+    out = _warp.warp_perspective_nv12(y, uv, np.eye(3), (W, H), flags=INTER_NEAREST, rgb=code == COLOR_YUV2RGB_NV12)
+    return out.cpu().numpy()
 
 
 def findHomography(srcPoints, dstPoints, method=0, ransacReprojThreshold=3.0, mask=None, maxIters=2000, confidence=0.995):

@@ -12,6 +12,9 @@ link is full duplex.  The decoder can write straight into the next pinned slot (
 memcpy a pageable `submit(frame)` needs.  Output is the interleaved BEV frame of the source dtype, or -- `planar=True` --
 normalised channel planes (the layout a detector takes; float32, or float16 / bfloat16 with `plane_dtype`), in the same pass.  Results are the resident path's, bit
 for bit: the same kernel runs on the same bytes.
+
+`src_format="nv12"`: the host slots take what a video decoder produces -- (H * 3 / 2, W) bytes, the Y plane followed by the rows of (U, V)
+pairs -- which halves the upload, and the warp converts each tap to BGR (bev_amd.warp.warp_perspective_nv12; bevwarp_warp_nv12).
 """
 import collections
 import ctypes
@@ -52,7 +55,7 @@ _H2D, _D2H = 1, 2  # hipMemcpyHostToDevice / hipMemcpyDeviceToHost
 
 class FramePipeline:
     def __init__(self, src_hw, channels, M, dsize, flags=_warp.INTER_LINEAR, depth=3, dtype=torch.uint8, planar=False, scale=1.0 / 255.0, bias=0.0,
-                 download=True, device="cuda", zero_copy_out=True, plane_dtype=torch.float32):
+                 download=True, device="cuda", zero_copy_out=True, plane_dtype=torch.float32, src_format="bgr"):
         """src_hw (H, W) of the decoded frames; M the forward homography (as for warpPerspective); dsize (u_size, v_size).
         download=False leaves the BEV frames on the device (results are device tensors valid until `depth` further frames
         have been submitted).  zero_copy_out (with download): the kernel stores the BEV frame straight into the pinned host
@@ -60,7 +63,22 @@ class FramePipeline:
         engine that copy serialises with the next frame's upload).
         plane_dtype (with planar): torch.float32, torch.float16 or torch.bfloat16 -- the element type of the planes, of the device and
         of the pinned host slots (warp_to_planar's out_dtype).  numpy has no bfloat16: result() hands such a host slot out as a torch
-        tensor."""
+        tensor.
+        src_format  "bgr" (default): interleaved (H, W, channels) frames.  "nv12": the input slots are (H * 3 / 2, W) uint8 -- the Y plane,
+        then H / 2 rows of (U, V) pairs -- and the output is the BGR BEV frame; channels must be 3, dtype uint8, H and W
+        even, and planar output is not available (ValueError)."""
+        if src_format not in ("bgr", "nv12"):
+            raise ValueError("unsupported src_format %r (\"bgr\", \"nv12\")" % (src_format,))
+        self.nv12 = src_format == "nv12"
+        if self.nv12:
+            if planar:
+                raise ValueError("src_format=\"nv12\" writes interleaved BGR frames only: planar=True is not available from NV12")
+            if int(channels) != 3 or dtype != torch.uint8:
+                raise ValueError("src_format=\"nv12\" needs channels=3 and dtype=torch.uint8")
+            if int(src_hw[0]) % 2 or int(src_hw[1]) % 2 or int(src_hw[0]) <= 0 or int(src_hw[1]) <= 0:
+                raise ValueError("src_format=\"nv12\" needs even frame sides, got %s" % (tuple(src_hw),))
+            if (int(flags) & 7) not in (_warp.INTER_NEAREST, _warp.INTER_LINEAR):
+                raise ValueError("src_format=\"nv12\": INTER_NEAREST or INTER_LINEAR")
         if planar and plane_dtype not in _warp._PLANE_DTYPES:
             raise ValueError("unsupported plane_dtype %s (torch.float32, torch.float16, torch.bfloat16)" % (plane_dtype,))
         if depth < 2:
@@ -73,8 +91,9 @@ class FramePipeline:
         self.zero_copy_out = bool(zero_copy_out and download)
         out_shape = (self.C, self.dh, self.dw) if planar else (self.dh, self.dw, self.C)
         out_dtype = plane_dtype if planar else dtype
-        self.h_in = [torch.empty((self.H, self.W, self.C), dtype=dtype, pin_memory=True) for _ in range(depth)]
-        self.d_in = [torch.empty((self.H, self.W, self.C), dtype=dtype, device=self.device) for _ in range(depth)]
+        in_shape = (self.H * 3 // 2, self.W) if self.nv12 else (self.H, self.W, self.C)
+        self.h_in = [torch.empty(in_shape, dtype=dtype, pin_memory=True) for _ in range(depth)]
+        self.d_in = [torch.empty(in_shape, dtype=dtype, device=self.device) for _ in range(depth)]
         self.d_out = [torch.empty(out_shape, dtype=out_dtype, device=self.device) for _ in range(depth)]
         self.h_out = [torch.empty(out_shape, dtype=out_dtype, pin_memory=True) for _ in range(depth)] if download else None
         self.minv = _warp.device_inverse(M, self.device, inverse_given=bool(int(flags) & _warp.WARP_INVERSE_MAP))
@@ -101,7 +120,11 @@ class FramePipeline:
         self._launch = []
         for slot in range(depth):
             s, d = self.d_in[slot], (self.h_out[slot] if self.zero_copy_out else self.d_out[slot])  # (pinned host memory is device-addressable)
-            if planar:
+            if self.nv12:  # (one buffer: the (U, V) rows follow the Y rows)
+                args = (s.data_ptr(), s.data_ptr() + self.H * self.W, d.data_ptr(), 1, self.H, self.W, self.dh, self.dw, 0, self.W, 0, self.W, d.numel(),
+                        d.stride(0), self.minv.data_ptr(), 1, interp, 0, None, self.s_run)
+                self._launch.append((lib.bevwarp_warp_nv12, args))
+            elif planar:
                 sc = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, dtype=np.float64), (self.C,)))
                 bi = np.ascontiguousarray(np.broadcast_to(np.asarray(bias, dtype=np.float64), (self.C,)))
                 self._keep = getattr(self, "_keep", []) + [sc, bi]
@@ -150,7 +173,10 @@ class FramePipeline:
     def _launch_py(self, slot, stream):
         """The same launch through bev_amd.warp (argument validation; used once per slot at construction)."""
         with torch.cuda.stream(stream):
-            if self.planar:
+            if self.nv12:
+                y, uv = _warp.split_nv12(self.d_in[slot])
+                _warp.warp_perspective_nv12(y, uv, None, (self.dw, self.dh), flags=self.flags, out=self.d_out[slot], M_inv_device=self.minv)
+            elif self.planar:
                 _warp.warp_to_planar(self.d_in[slot], None, (self.dw, self.dh), scale=self.scale, bias=self.bias, flags=self.flags, out=self.d_out[slot],
                                      M_inv_device=self.minv, out_dtype=self.plane_dtype)
             else:
@@ -158,7 +184,7 @@ class FramePipeline:
 
     # -- input side
     def next_input(self):
-        """The pinned host buffer (numpy view, HWC) the NEXT frame should be decoded into; call commit() when it is filled.
+        """The pinned host buffer (numpy view; HWC, or (H * 3 / 2, W) for NV12) the NEXT frame should be decoded into; call commit() when it is filled.
         Blocks only if that slot's previous frame has not left the device yet."""
         slot = self.n_in % self.depth
         if self.n_in >= self.depth:

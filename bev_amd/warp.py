@@ -377,6 +377,76 @@ def warp_to_planar(src, M, dsize, scale=1.0 / 255.0, bias=0.0, flags=INTER_LINEA
     return d4 if src.dim() == 4 else d4[0]
 
 
+def split_nv12(frame):
+    """(y, uv) views, without a copy, of NV12 frames held in one buffer: a `(H * 3 / 2, W)` or `(B, H * 3 / 2, W)` uint8 tensor (torch, any
+    device; rows contiguous) whose first H rows are the Y plane and whose last H / 2 rows are the interleaved (U, V) pairs.  y is
+    `(H, W)` / `(B, H, W)`, uv is `(H / 2, W / 2, 2)` / `(B, H / 2, W / 2, 2)`: what warp_perspective_nv12 takes."""
+    if not isinstance(frame, torch.Tensor) or frame.dtype != torch.uint8 or frame.dim() not in (2, 3):
+        raise ValueError("split_nv12 needs a uint8 tensor (H * 3 / 2, W) or (B, H * 3 / 2, W)")
+    rows, W = int(frame.shape[-2]), int(frame.shape[-1])
+    if rows <= 0 or W <= 0 or rows % 3 or W % 2:
+        raise ValueError("split_nv12: %d rows x %d bytes is no NV12 frame (rows = H * 3 / 2 with H and W even)" % (rows, W))
+    if frame.stride(-1) != 1:
+        raise ValueError("split_nv12: the rows must be contiguous")
+    H = rows // 3 * 2
+    y = frame[..., :H, :]
+    c = frame[..., H:, :]
+    uv = torch.as_strided(c, tuple(c.shape[:-1]) + (W // 2, 2), tuple(c.stride()[:-1]) + (2, 1), c.storage_offset())
+    return y, uv
+
+
+def warp_perspective_nv12(y, uv, M, dsize, flags=INTER_LINEAR, border_value=None, out=None, M_inv_device=None, rgb=False):
+    """warp_perspective of a video decoder's NV12 frames, converted on the way: bit for bit
+
+        warp_perspective(cvtColor(nv12, COLOR_YUV2BGR_NV12), M, dsize, flags, border_value)       (rgb=True: COLOR_YUV2RGB_NV12)
+
+    in one pass, without the converted frame (include/bevwarp.h, bevwarp_warp_nv12: OpenCV's 8-bit BT.601 limited-range fixed point,
+    restated from memory, parity unpinned).
+
+    y        (H, W) or (B, H, W) uint8 CUDA tensor, H and W even.
+    uv       (H / 2, W / 2, 2) or (B, H / 2, W / 2, 2) uint8 CUDA tensor of (U, V) pairs on the same device.  The last dimension of
+             each must be contiguous (for uv: the pairs and the row of pairs); the other strides are passed through, so the views of
+             split_nv12 and row-padded planes are taken as they are.  The uv base and strides must be even.
+    M, dsize, out, M_inv_device   as warp_perspective; flags INTER_LINEAR (default) or INTER_NEAREST, optionally | WARP_INVERSE_MAP.
+    border_value   scalar or 3 values in the RESULT's channel order (not converted); BORDER_CONSTANT is the only border.
+    Returns (B, h, w, 3), or (h, w, 3) for a single frame.  Asynchronous on the current stream.  No verdict tables, no plan cache."""
+    interp = int(flags) & 7
+    if interp not in (INTER_NEAREST, INTER_LINEAR):
+        raise ValueError("unsupported interpolation flag %d (warp_perspective_nv12: INTER_NEAREST, INTER_LINEAR)" % interp)
+    for name, t in (("y", y), ("uv", uv)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8:
+            raise ValueError("warp_perspective_nv12 needs uint8 CUDA (HIP) tensors; %s is %s" % (name, getattr(t, "dtype", type(t))))
+    if y.dim() not in (2, 3) or uv.dim() != y.dim() + 1 or uv.device != y.device:
+        raise ValueError("y must be (H, W) or (B, H, W) and uv (H/2, W/2, 2) or (B, H/2, W/2, 2) on the same device")
+    y3, uv4 = (y[None], uv[None]) if y.dim() == 2 else (y, uv)
+    B, H, W = y3.shape
+    if H % 2 or W % 2 or tuple(uv4.shape) != (B, H // 2, W // 2, 2):
+        raise ValueError("NV12 needs even sides and uv of shape %s; got y %s, uv %s" % ((B, H // 2, W // 2, 2), tuple(y3.shape), tuple(uv4.shape)))
+    if y3.stride(2) != 1 or uv4.stride(3) != 1 or uv4.stride(2) != 2:
+        raise ValueError("the last dimension of y and of uv (pairs, and the pairs of a row) must be contiguous")
+    dw, dh = int(dsize[0]), int(dsize[1])
+    if M_inv_device is None:
+        M_inv_device = device_inverse(M, y3.device, inverse_given=bool(int(flags) & WARP_INVERSE_MAP))
+    n_m = _check_minv(M_inv_device, y3.device, B)
+    if out is None:
+        d4 = torch.empty((B, dh, dw, 3), dtype=torch.uint8, device=y3.device)
+    else:
+        _check_out(out, torch.uint8, y3.device, B * dh * dw * 3)
+        d4 = out.reshape(B, dh, dw, 3)
+        if d4.data_ptr() != out.data_ptr() or d4.stride(3) != 1 or d4.stride(2) != 3:
+            raise ValueError("out must be a contiguous-row channels-last tensor")
+    bv = _border(border_value, 3)
+    stream = torch.cuda.current_stream(y3.device).cuda_stream
+    with torch.cuda.device(y3.device):
+        st = _lib.load().bevwarp_warp_nv12(y3.data_ptr(), uv4.data_ptr(), d4.data_ptr(), B, H, W, dh, dw, y3.stride(0), y3.stride(1), uv4.stride(0),
+                                           uv4.stride(1), d4.stride(0), d4.stride(1), M_inv_device.data_ptr(), n_m, interp, 1 if rgb else 0,
+                                           None if bv is None else bv.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(stream))
+    _lib.check(st)
+    if out is not None:
+        return out
+    return d4[0] if y.dim() == 2 else d4
+
+
 def footprint(src_hw, M, dsize, batch=None, flags=INTER_LINEAR, device="cuda"):
     """Exact count of distinct in-bounds source pixels the warp reads, per frame.
     Returns (counts int64 tensor [n], touched uint8 tensor [n, H, W])."""

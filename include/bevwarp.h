@@ -18,6 +18,9 @@
  *   bevwarp_warp_planes     the same planes as float32, float16 or bfloat16: the layout AND precision step between
  *                             vis_homo.py:89 and a detector's input (detectors on this hardware run in 16 bits; the `.half()` pass
  *                             behind bevwarp_warp_planar is folded into the warp's stores)
+ *   bevwarp_warp_nv12       `ok, img = video.read()` + cv2.warpPerspective(img, H_bev_img, (u_size, v_size)), vis_homo.py:86-89,
+ *                             without the decoder's colour-conversion pass: the warp samples the decoder's NV12 planes and
+ *                             converts each tap (cv2.cvtColor(nv12, COLOR_YUV2BGR_NV12) never exists in memory)
  *   bevwarp_composite       composite_reg_img(bg, fg, fg_mask), bev/tool/compo.py:5-24 (the blend after the three warps
  *                             of composite_bev_img, :26-49)
  *   bevwarp_warp_composite  composite_bev_img(bg, fg, fg_mask, ...), bev/tool/compo.py:26-49: the three warps and the blend
@@ -222,6 +225,38 @@ int bevwarp_warp_planes(const void *src, void *dst, int batch, int src_h, int sr
                         int64_t dst_row_stride, const double *M_inv, int m_count, int dtype, int interp,
                         const double *border_value /*HOST*/, const double *scale /*HOST*/, const double *bias /*HOST*/,
                         int plane_dtype, void *stream);
+
+/*
+ * dst = bevwarp_warp(cvtColor(nv12, COLOR_YUV2BGR_NV12), ...) for 8-bit pixels, 3 channels, constant border, bit for bit, in one pass:
+ * every tap is converted before the blend and the converted frame is never in memory.  The source is a video decoder's NV12 frame:
+ *   y               device, src_h rows of src_w bytes (y_row_stride >= src_w, y_frame_stride between frames)
+ *   uv              device, src_h / 2 rows of src_w / 2 interleaved (U, V) byte pairs -- src_w bytes per row.  Base, uv_row_stride and
+ *                   uv_frame_stride are even (pairs are read as 16-bit words).  src_h and src_w are even.
+ *                   Pixel (x, y) has Y = y[y][x], U = uv[y >> 1][2 (x >> 1)], V = uv[y >> 1][2 (x >> 1) + 1].
+ *                   Both layouts found in practice fit: one (src_h * 3 / 2) x src_w buffer with uv = y + src_h * y_row_stride, and two
+ *                   allocations.  y and uv may overlap each other (both are only read).
+ *   conversion      OpenCV's 8-bit cvtYUV420sp2RGB: BT.601, limited range, 20-bit fixed point, all in int32, >> arithmetic
+ *                   (restated from memory like the rest of the warp: parity with OpenCV is unpinned):
+ *                       yy = max(0, Y - 16) * 1220542        u = U - 128        v = V - 128
+ *                       R = clamp((yy + 524288 + 1673527 v) >> 20, 0, 255)
+ *                       G = clamp((yy + 524288 -  852492 v - 409993 u) >> 20, 0, 255)
+ *                       B = clamp((yy + 524288 + 2116026 u) >> 20, 0, 255)
+ *   rgb_order       0: dst pixels are B, G, R (COLOR_YUV2BGR_NV12); 1: R, G, B (COLOR_YUV2RGB_NV12).
+ *   interp          BEVWARP_NEAREST | BEVWARP_LINEAR.  Maps, 1/32-px quantisation, tap guards and blend are bevwarp_warp's: a tap inside the
+ *                   frame is the converted pixel, a tap outside is border_value.
+ *   border_value    HOST, 3 doubles in the DESTINATION's channel order (not converted), or NULL = 0.
+ *   dst             device, dst_h x dst_w x 3 bytes; the wide-store rule is bevwarp_warp's.  M_inv, m_count, stream: as bevwarp_warp.
+ * Status, in this order: BEVWARP_ERR_BAD_ARG (null pointer, non-positive size, odd src_w or src_h, a row stride below src_w for either
+ * plane or below 3 dst_w, frames that overlap their successors, an odd uv base / row stride / frame stride, m_count not 1 or batch);
+ * BEVWARP_ERR_UNSUPPORTED (BEVWARP_CUBIC or any other interp; rgb_order outside {0, 1}); BEVWARP_ERR_TOO_LARGE (either plane: a side
+ * > 32767, a row stride >= 16 MiB, a plane >= 2 GiB); BEVWARP_ERR_OVERLAP (dst shares bytes with the y or the uv image, by
+ * bevwarp_warp's rule); BEVWARP_ERR_TOO_LARGE again for a destination side > 2^20 (the launch plan's limit, looked at after the
+ * overlap); BEVWARP_ERR_NOT_FINITE (border_value).  batch == 0 is BEVWARP_OK and launches nothing.
+ */
+int bevwarp_warp_nv12(const void *y, const void *uv, void *dst, int batch, int src_h, int src_w, int dst_h, int dst_w,
+                      int64_t y_frame_stride, int64_t y_row_stride, int64_t uv_frame_stride, int64_t uv_row_stride,
+                      int64_t dst_frame_stride, int64_t dst_row_stride, const double *M_inv, int m_count, int interp,
+                      int rgb_order, const double *border_value /*HOST, 3 doubles or NULL*/, void *stream);
 
 /*
  * out[i] = uint8(min(round_half_even(fg[i] * (mask[i] / 255) + bg[i] * (1 - mask[i] / 255)), 255)) for i in [0, n), computed in
