@@ -10,7 +10,7 @@ import subprocess
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.environ.get("BEVWARP_LIB") or os.path.join(_CSRC, "libbevwarp.so")  # override = A/B builds
 
-U8, F32, F64, F16, BF16 = 0, 1, 2, 3, 4  # (F16, BF16: plane types of bevwarp_warp_planes only)
+U8, F32, F64, F16, BF16 = 0, 1, 2, 3, 4  # (F16, BF16: plane types of bevwarp_warp_planes / _nv12_planes only)
 INTER_NEAREST, INTER_LINEAR, INTER_CUBIC = 0, 1, 2
 ABI_VERSION = 7
 
@@ -40,6 +40,9 @@ SYMBOLS = {
     "bevwarp_warp_nv12": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
                                      _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int,
                                      _c.c_void_p, _c.c_void_p]),
+    "bevwarp_warp_nv12_planes": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
+                                            _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_int, _c.c_int,
+                                            _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p]),
     "bevwarp_composite": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_void_p]),
     "bevwarp_warp_composite": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int64,
                                           _c.c_int64, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int64, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p]),

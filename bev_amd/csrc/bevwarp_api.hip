@@ -216,6 +216,42 @@ int bevwarp_warp_nv12(const void* y, const void* uv, void* dst, int batch, int s
     return launched(launch_warp_nv12(a, interp, rgb_order, p.total_tiles, (hipStream_t)stream));
 }
 
+int bevwarp_warp_nv12_planes(const void* y, const void* uv, void* dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int64_t y_frame_stride,
+                             int64_t y_row_stride, int64_t uv_frame_stride, int64_t uv_row_stride, int64_t dst_frame_stride, int64_t dst_plane_stride,
+                             int64_t dst_row_stride, const double* M_inv, int m_count, int interp, int rgb_order, const double* border_value,
+                             const double* scale, const double* bias, int plane_dtype, void* stream) {
+    const Nv12PlanesCall c = {{y, uv, dst, batch, src_h, src_w, dst_h, dst_w, y_frame_stride, y_row_stride, uv_frame_stride, uv_row_stride,
+                               dst_frame_stride, dst_row_stride, M_inv, m_count, interp, rgb_order},
+                              dst_plane_stride, plane_dtype};
+    const int st = plan::check_warp_nv12_planes(c);
+    if (st != BEVWARP_OK || batch == 0) return st;
+    const TilePlan p = plan::plan_border(batch, dst_h, dst_w, kBorderTileW, kBorderTileH);
+    if (p.status != BEVWARP_OK) return p.status;
+    Nv12PlanesArgs a;
+    memset(&a, 0, sizeof(a));
+    a.y = (const uint8_t*)y, a.uv = (const uint8_t*)uv, a.dst = (uint8_t*)dst, a.minv = M_inv;
+    a.y_fs = y_frame_stride, a.y_rs = y_row_stride, a.uv_fs = uv_frame_stride, a.uv_rs = uv_row_stride, a.dst_fs = dst_frame_stride, a.dst_rs = dst_row_stride;
+    a.src_h = src_h, a.src_w = src_w, a.dst_h = dst_h, a.dst_w = dst_w;
+    a.m_stride = m_count == 1 ? 0 : 9;
+    copy_grid(a, p);
+    a.dst_vec_ok = plan::nv12_planes_wide_stores_ok(c);
+    a.plane = plane_dtype == BEVWARP_F32 ? kPlaneF32 : (plane_dtype == BEVWARP_F16 ? kPlaneF16 : kPlaneBF16);
+    float bf[4];
+    uint8_t bu[4];  // (in the destination's channel order, as given)
+    if (border_values(border_value, 3, bf, bu) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
+    // the kernel samples B, G, R: sampled channel k is the destination's channel k (BGR) or 2 - k (RGB), with that channel's plane,
+    // scale, bias and border value -- the channel order is nothing but this table
+    for (int k = 0; k < 3; k++) {
+        const int ch = rgb_order ? 2 - k : k;
+        const double sc = scale ? scale[ch] : 1.0, bi = bias ? bias[ch] : 0.0;
+        if (!isfinite(sc) || !isfinite(bi)) return BEVWARP_ERR_NOT_FINITE;
+        a.pscale[k] = (float)sc, a.pbias[k] = (float)bi;
+        a.ch_off[k] = (int64_t)ch * dst_plane_stride;
+        a.border |= (uint32_t)bu[ch] << (8 * k);
+    }
+    return launched(launch_warp_nv12_planes(a, interp, p.total_tiles, (hipStream_t)stream));
+}
+
 int bevwarp_warp_classes(const void* src, void* dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int channels, int64_t src_frame_stride,
                          int64_t src_row_stride, int64_t dst_frame_stride, int64_t dst_row_stride, const double* M_inv, int m_count, int dtype, int interp,
                          const double* border_value, void* classes, int mode, void* stream) {

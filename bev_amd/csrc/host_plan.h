@@ -179,6 +179,45 @@ inline int check_warp_nv12(const Nv12Call& c) {
     return (regions_overlap(y, d) || regions_overlap(uv, d)) ? BEVWARP_ERR_OVERLAP : BEVWARP_OK;
 }
 
+// ---- an NV12 warp into channel planes (bevwarp_warp_nv12_planes) ---------------------------------------------------------------------
+// The source is an Nv12Call's; the destination is three planes per frame of dst_h rows of dst_w elements of `plane_dtype`.
+struct Nv12PlanesCall {
+    Nv12Call s;           // (dst, dst_fs, dst_rs: plane 0 of frame 0, the frame stride and a plane's row stride)
+    int64_t dst_ps;       // bytes between the planes of a frame
+    int plane_dtype;      // BEVWARP_F32 | BEVWARP_F16 | BEVWARP_BF16
+
+    // bytes of a plane's element; a plane type the entry point does not take asks no alignment (the layout is looked at first)
+    int elem() const { return plane_dtype == BEVWARP_F32 ? 4 : ((plane_dtype == BEVWARP_F16 || plane_dtype == BEVWARP_BF16) ? 2 : 1); }
+    Image plane_image() const { return {(uintptr_t)s.dst, s.dst_h, (uint64_t)s.dst_w * elem(), s.dst_rs, s.dst_fs, s.batch}; }  // one plane's rows
+    uintptr_t dst_end() const { return plane_image().end() + 2 * (uint64_t)dst_ps; }  // (of the bounding byte range of all planes)
+};
+
+// All argument checks of an NV12 warp into planes, in the order the header documents: check_warp_nv12's bad arguments with the plane
+// layout of check_warp in the destination's place, unsupported interpolation / channel order / plane type, source size limits per plane,
+// overlap of the destination's bounding byte range with either source image.
+inline int check_warp_nv12_planes(const Nv12PlanesCall& c) {
+    const Nv12Call& s = c.s;
+    if (!s.y || !s.uv || !s.dst || !s.minv) return BEVWARP_ERR_BAD_ARG;
+    if (s.batch < 0 || s.src_h <= 0 || s.src_w <= 0 || s.dst_h <= 0 || s.dst_w <= 0 || (s.src_h & 1) || (s.src_w & 1)) return BEVWARP_ERR_BAD_ARG;
+    const Image y = s.y_image(), uv = s.uv_image(), d = c.plane_image();
+    if (layout_status(y, 1) != BEVWARP_OK || layout_status(uv, 2) != BEVWARP_OK) return BEVWARP_ERR_BAD_ARG;
+    // (check_warp's rule for planes: rows in a plane, asked of a lone plane too, and planes in a frame)
+    const Image rows_in_plane = {d.base, d.rows, d.row_bytes, d.rs, c.dst_ps, 2}, planes_in_frame = {d.base, 3, 0, c.dst_ps, d.fs, d.batch};
+    if (layout_status(rows_in_plane, c.elem()) != BEVWARP_OK || layout_status(planes_in_frame, c.elem()) != BEVWARP_OK) return BEVWARP_ERR_BAD_ARG;
+    if (s.m_count != 1 && s.m_count != s.batch) return BEVWARP_ERR_BAD_ARG;
+    if ((s.interp != BEVWARP_NEAREST && s.interp != BEVWARP_LINEAR) || (s.rgb_order != 0 && s.rgb_order != 1)) return BEVWARP_ERR_UNSUPPORTED;
+    if (c.plane_dtype != BEVWARP_F32 && c.plane_dtype != BEVWARP_F16 && c.plane_dtype != BEVWARP_BF16) return BEVWARP_ERR_UNSUPPORTED;
+    int st;
+    if ((st = source_size_status(y, s.src_w)) != BEVWARP_OK || (st = source_size_status(uv, s.src_w / 2)) != BEVWARP_OK || s.batch == 0) return st;
+    const uintptr_t d1 = c.dst_end();
+    return ((y.base < d1 && d.base < y.end()) || (uv.base < d1 && d.base < uv.end())) ? BEVWARP_ERR_OVERLAP : BEVWARP_OK;
+}
+// Does the call's destination admit the wide stores?  call_wide_stores_ok's rule: 4 plane elements per store, the plane stride counts.
+inline bool nv12_planes_wide_stores_ok(const Nv12PlanesCall& c) {
+    const int align = store_align(BEVWARP_U8, 3, true, c.elem());
+    return wide_stores_ok(c.plane_image(), align) && c.dst_ps % align == 0;
+}
+
 // ---- launch geometry ---------------------------------------------------------------------------------------------------------
 struct TilePlan {
     int status;                  // BEVWARP_OK or BEVWARP_ERR_TOO_LARGE (the other fields are then meaningless)

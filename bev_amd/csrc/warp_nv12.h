@@ -1,5 +1,6 @@
-// Internal interface of the NV12 warp (warp_nv12.hip, bevwarp_warp_nv12): a Y plane and a half-resolution plane of (U, V) pairs are
-// sampled and converted tap by tap into an 8-bit BGR / RGB destination.  Constant border, nearest and bilinear.  Not installed.
+// Internal interface of the NV12 warps: a Y plane and a half-resolution plane of (U, V) pairs are sampled and converted tap by tap into an
+// 8-bit BGR / RGB destination (warp_nv12.hip, bevwarp_warp_nv12) or into normalised float32 / float16 / bfloat16 channel planes
+// (warp_nv12_planes.hip, bevwarp_warp_nv12_planes).  Constant border, nearest and bilinear.  Not installed.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -25,5 +26,29 @@ struct Nv12Args {
 };
 
 hipError_t launch_warp_nv12(const Nv12Args& a, int interp, int rgb_order, int64_t items, hipStream_t stream);
+
+// The plane kernel samples in ONE channel order -- B, G, R in bytes 0, 1, 2 of a pixel -- and knows no other: the destination's order is
+// where the host points each sampled channel (plane offset, scale, bias and border byte k belong to sampled channel k).
+struct Nv12PlanesArgs {
+    const uint8_t* y;             // as Nv12Args
+    const uint8_t* uv;
+    uint8_t* dst;                 // plane 0 of frame 0
+    const double* minv;
+    int64_t y_fs, y_rs;           // bytes
+    int64_t uv_fs, uv_rs;
+    int64_t dst_fs, dst_rs;
+    int64_t ch_off[3];            // bytes from a frame's base to the plane sampled channel k (B, G, R) is written to
+    float pscale[3], pbias[3];    // of sampled channel k
+    int src_h, src_w, dst_h, dst_w;
+    int m_stride;
+    int bw0;
+    int tiles_x, tiles_per_frame;
+    uint32_t bw0_magic, tx_magic, tpf_magic;
+    int dst_vec_ok;               // base and the three destination strides admit 4-element stores (16 bytes float32, 8 bytes 16-bit)
+    uint32_t border;              // byte k = the border value of sampled channel k
+    int plane;                    // kPlaneF32, kPlaneF16, kPlaneBF16 (warp_kernels.h)
+};
+
+hipError_t launch_warp_nv12_planes(const Nv12PlanesArgs& a, int interp, int64_t items, hipStream_t stream);
 
 }  // namespace bevwarp

@@ -142,10 +142,12 @@ def _check_out(out, dtype, device, numel):
         raise ValueError("out must be a %s tensor of %d elements on %s" % (dtype, numel, device))
 
 
+def _per_channel(v, C):
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (C,)))
+
+
 def _border(border_value, C):
-    if border_value is None:
-        return None
-    return np.ascontiguousarray(np.broadcast_to(np.asarray(border_value, dtype=np.float64), (C,)))
+    return None if border_value is None else _per_channel(border_value, C)
 
 
 _CLASSES_MAX = 64
@@ -308,6 +310,29 @@ def warp_perspective(src, M, dsize, flags=INTER_LINEAR, border_value=None, out=N
     return d4
 
 
+def _plane_format(who, flags, out_dtype, out):
+    """The interpolation of a call that writes channel planes, once its flags, plane type and `out` are what the plane kernels take."""
+    interp = int(flags) & 7
+    if interp not in (INTER_NEAREST, INTER_LINEAR):  # (no bicubic kernel writes planes)
+        raise ValueError("unsupported interpolation flag %d (%s: INTER_NEAREST, INTER_LINEAR)" % (interp, who))
+    if out_dtype not in _PLANE_DTYPES:
+        raise ValueError("unsupported out_dtype %s (%s: torch.float32, torch.float16, torch.bfloat16)" % (out_dtype, who))
+    if out is not None and getattr(out, "dtype", None) != out_dtype:
+        raise ValueError("out must be a %s tensor (out_dtype), got %s" % (out_dtype, getattr(out, "dtype", type(out))))
+    return interp
+
+
+def _plane_dst(out, out_dtype, device, B, C, dh, dw):
+    """The (B, C, dh, dw) destination of a call that writes channel planes: a new tensor, or the caller's `out` as it is."""
+    if out is None:
+        return torch.empty((B, C, dh, dw), dtype=out_dtype, device=device)
+    _check_out(out, out_dtype, device, B * C * dh * dw)
+    d4 = out.reshape(B, C, dh, dw)
+    if d4.data_ptr() != out.data_ptr() or d4.stride(3) != 1:
+        raise ValueError("out must be a %s (B, C, h, w) tensor with contiguous rows" % (out_dtype,))
+    return d4
+
+
 def warp_to_planar(src, M, dsize, scale=1.0 / 255.0, bias=0.0, flags=INTER_LINEAR, border_value=None, out=None, M_inv_device=None,
                    out_dtype=torch.float32):
     """Warp uint8 (or float32) frames and write them as normalised channel planes in the same pass (SURVEY.md 8(f2):
@@ -322,13 +347,7 @@ def warp_to_planar(src, M, dsize, scale=1.0 / 255.0, bias=0.0, flags=INTER_LINEA
                payloads aside), without the conversion pass and with half the bytes stored (include/bevwarp.h, bevwarp_warp_planes).
                A given `out` must have this dtype.
     Returns (B, C, h, w), or (C, h, w) for a single frame.  Asynchronous on the current stream."""
-    interp = int(flags) & 7
-    if interp not in (INTER_NEAREST, INTER_LINEAR):  # (no bicubic kernel writes planes)
-        raise ValueError("unsupported interpolation flag %d (warp_to_planar: INTER_NEAREST, INTER_LINEAR)" % interp)
-    if out_dtype not in _PLANE_DTYPES:
-        raise ValueError("unsupported out_dtype %s (warp_to_planar: torch.float32, torch.float16, torch.bfloat16)" % (out_dtype,))
-    if out is not None and getattr(out, "dtype", None) != out_dtype:
-        raise ValueError("out must be a %s tensor (out_dtype), got %s" % (out_dtype, getattr(out, "dtype", type(out))))
+    interp = _plane_format("warp_to_planar", flags, out_dtype, out)
     if not isinstance(src, torch.Tensor) or not src.is_cuda or src.dtype not in _DTYPES:
         raise ValueError("warp_to_planar needs a uint8 or float32 CUDA (HIP) tensor")
     if src.dim() == 2:
@@ -346,17 +365,8 @@ def warp_to_planar(src, M, dsize, scale=1.0 / 255.0, bias=0.0, flags=INTER_LINEA
     if M_inv_device is None:
         M_inv_device = device_inverse(M, s4.device, inverse_given=bool(int(flags) & WARP_INVERSE_MAP))
     n_m = _check_minv(M_inv_device, s4.device, B)
-    if out is None:
-        d4 = torch.empty((B, C, dh, dw), dtype=out_dtype, device=s4.device)
-    else:
-        _check_out(out, out_dtype, s4.device, B * C * dh * dw)
-        d4 = out.reshape(B, C, dh, dw)
-        if d4.data_ptr() != out.data_ptr() or d4.stride(3) != 1:
-            raise ValueError("out must be a %s (B, C, h, w) tensor with contiguous rows" % (out_dtype,))
-    def per_channel(v):
-        return np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (C,)))
-    sc, bi = per_channel(scale), per_channel(bias)
-    bv = None if border_value is None else per_channel(border_value)
+    d4 = _plane_dst(out, out_dtype, s4.device, B, C, dh, dw)
+    sc, bi, bv = _per_channel(scale, C), _per_channel(bias, C), _border(border_value, C)
     stream = torch.cuda.current_stream(s4.device).cuda_stream
     with torch.cuda.device(s4.device):
         if out_dtype == torch.float32:
@@ -395,6 +405,25 @@ def split_nv12(frame):
     return y, uv
 
 
+def _nv12_source(who, y, uv, M, flags, M_inv_device):
+    """The planes of an NV12 call as the ABI reads them -- (B, H, W) and (B, H / 2, W / 2, 2) views, strides passed through -- and its
+    matrices: (y3, uv4, M_inv_device, number of matrices)."""
+    for name, t in (("y", y), ("uv", uv)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8:
+            raise ValueError("%s needs uint8 CUDA (HIP) tensors; %s is %s" % (who, name, getattr(t, "dtype", type(t))))
+    if y.dim() not in (2, 3) or uv.dim() != y.dim() + 1 or uv.device != y.device:
+        raise ValueError("y must be (H, W) or (B, H, W) and uv (H/2, W/2, 2) or (B, H/2, W/2, 2) on the same device")
+    y3, uv4 = (y[None], uv[None]) if y.dim() == 2 else (y, uv)
+    B, H, W = y3.shape
+    if H % 2 or W % 2 or tuple(uv4.shape) != (B, H // 2, W // 2, 2):
+        raise ValueError("NV12 needs even sides and uv of shape %s; got y %s, uv %s" % ((B, H // 2, W // 2, 2), tuple(y3.shape), tuple(uv4.shape)))
+    if y3.stride(2) != 1 or uv4.stride(3) != 1 or uv4.stride(2) != 2:
+        raise ValueError("the last dimension of y and of uv (pairs, and the pairs of a row) must be contiguous")
+    if M_inv_device is None:
+        M_inv_device = device_inverse(M, y3.device, inverse_given=bool(int(flags) & WARP_INVERSE_MAP))
+    return y3, uv4, M_inv_device, _check_minv(M_inv_device, y3.device, B)
+
+
 def warp_perspective_nv12(y, uv, M, dsize, flags=INTER_LINEAR, border_value=None, out=None, M_inv_device=None, rgb=False):
     """warp_perspective of a video decoder's NV12 frames, converted on the way: bit for bit
 
@@ -413,21 +442,9 @@ def warp_perspective_nv12(y, uv, M, dsize, flags=INTER_LINEAR, border_value=None
     interp = int(flags) & 7
     if interp not in (INTER_NEAREST, INTER_LINEAR):
         raise ValueError("unsupported interpolation flag %d (warp_perspective_nv12: INTER_NEAREST, INTER_LINEAR)" % interp)
-    for name, t in (("y", y), ("uv", uv)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8:
-            raise ValueError("warp_perspective_nv12 needs uint8 CUDA (HIP) tensors; %s is %s" % (name, getattr(t, "dtype", type(t))))
-    if y.dim() not in (2, 3) or uv.dim() != y.dim() + 1 or uv.device != y.device:
-        raise ValueError("y must be (H, W) or (B, H, W) and uv (H/2, W/2, 2) or (B, H/2, W/2, 2) on the same device")
-    y3, uv4 = (y[None], uv[None]) if y.dim() == 2 else (y, uv)
+    y3, uv4, M_inv_device, n_m = _nv12_source("warp_perspective_nv12", y, uv, M, flags, M_inv_device)
     B, H, W = y3.shape
-    if H % 2 or W % 2 or tuple(uv4.shape) != (B, H // 2, W // 2, 2):
-        raise ValueError("NV12 needs even sides and uv of shape %s; got y %s, uv %s" % ((B, H // 2, W // 2, 2), tuple(y3.shape), tuple(uv4.shape)))
-    if y3.stride(2) != 1 or uv4.stride(3) != 1 or uv4.stride(2) != 2:
-        raise ValueError("the last dimension of y and of uv (pairs, and the pairs of a row) must be contiguous")
     dw, dh = int(dsize[0]), int(dsize[1])
-    if M_inv_device is None:
-        M_inv_device = device_inverse(M, y3.device, inverse_given=bool(int(flags) & WARP_INVERSE_MAP))
-    n_m = _check_minv(M_inv_device, y3.device, B)
     if out is None:
         d4 = torch.empty((B, dh, dw, 3), dtype=torch.uint8, device=y3.device)
     else:
@@ -441,6 +458,44 @@ def warp_perspective_nv12(y, uv, M, dsize, flags=INTER_LINEAR, border_value=None
         st = _lib.load().bevwarp_warp_nv12(y3.data_ptr(), uv4.data_ptr(), d4.data_ptr(), B, H, W, dh, dw, y3.stride(0), y3.stride(1), uv4.stride(0),
                                            uv4.stride(1), d4.stride(0), d4.stride(1), M_inv_device.data_ptr(), n_m, interp, 1 if rgb else 0,
                                            None if bv is None else bv.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(stream))
+    _lib.check(st)
+    if out is not None:
+        return out
+    return d4[0] if y.dim() == 2 else d4
+
+
+def warp_nv12_to_planar(y, uv, M, dsize, scale=1.0 / 255.0, bias=0.0, flags=INTER_LINEAR, border_value=None, out=None, M_inv_device=None,
+                        rgb=False, out_dtype=torch.float32):
+    """A video decoder's NV12 frames warped straight to the normalised channel planes a detector takes, in one launch: bit for bit
+
+        warp_to_planar(warp_perspective_nv12(y, uv, M, dsize, flags, border_value, rgb=rgb), identity, dsize, scale, bias,
+                       flags=INTER_NEAREST, out_dtype=out_dtype)
+
+    without the 8-bit BEV frame in between (include/bevwarp.h, bevwarp_warp_nv12_planes):
+
+        out[b, c] = convert(float32(warp_perspective_nv12(...)[b, :, :, c]) * scale[c] + bias[c])      (float32 mul, then add, then out_dtype)
+
+    y, uv, M, flags, M_inv_device, rgb   as warp_perspective_nv12 (strided planes are passed through; split_nv12's views are taken as they are).
+    scale, bias, border_value   scalars or 3 values in the RESULT's channel order (B, G, R; rgb=True: R, G, B).
+    out_dtype, out   as warp_to_planar: torch.float32 (default), torch.float16 or torch.bfloat16; a given `out` has this dtype and
+                     contiguous rows, and is returned as it is.
+    Returns (B, 3, h, w), or (3, h, w) for a single frame.  Asynchronous on the current stream.  No verdict tables, no plan cache.
+    FramePipeline(src_format="nv12", planar=True) keeps refusing: a streaming caller calls this function with `out=` and `M_inv_device=`
+    on a stream of its own."""
+    interp = _plane_format("warp_nv12_to_planar", flags, out_dtype, out)
+    y3, uv4, M_inv_device, n_m = _nv12_source("warp_nv12_to_planar", y, uv, M, flags, M_inv_device)
+    B, H, W = y3.shape
+    dw, dh = int(dsize[0]), int(dsize[1])
+    d4 = _plane_dst(out, out_dtype, y3.device, B, 3, dh, dw)
+    sc, bi, bv = _per_channel(scale, 3), _per_channel(bias, 3), _border(border_value, 3)
+    esz = d4.element_size()
+    stream = torch.cuda.current_stream(y3.device).cuda_stream
+    with torch.cuda.device(y3.device):
+        st = _lib.load().bevwarp_warp_nv12_planes(
+            y3.data_ptr(), uv4.data_ptr(), d4.data_ptr(), B, H, W, dh, dw, y3.stride(0), y3.stride(1), uv4.stride(0), uv4.stride(1),
+            d4.stride(0) * esz, d4.stride(1) * esz, d4.stride(2) * esz, M_inv_device.data_ptr(), n_m, interp, 1 if rgb else 0,
+            None if bv is None else bv.ctypes.data_as(ctypes.c_void_p), sc.ctypes.data_as(ctypes.c_void_p),
+            bi.ctypes.data_as(ctypes.c_void_p), _PLANE_DTYPES[out_dtype], ctypes.c_void_p(stream))
     _lib.check(st)
     if out is not None:
         return out

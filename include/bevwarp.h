@@ -21,6 +21,9 @@
  *   bevwarp_warp_nv12       `ok, img = video.read()` + cv2.warpPerspective(img, H_bev_img, (u_size, v_size)), vis_homo.py:86-89,
  *                             without the decoder's colour-conversion pass: the warp samples the decoder's NV12 planes and
  *                             converts each tap (cv2.cvtColor(nv12, COLOR_YUV2BGR_NV12) never exists in memory)
+ *   bevwarp_warp_nv12_planes  the same decoder frames, vis_homo.py:86-89, written straight as the detector-input planes of
+ *                             bevwarp_warp_planes (float32, float16 or bfloat16): decoder -> BEV -> detector input in one launch,
+ *                             with neither the converted frame nor the 8-bit BEV frame in memory
  *   bevwarp_composite       composite_reg_img(bg, fg, fg_mask), bev/tool/compo.py:5-24 (the blend after the three warps
  *                             of composite_bev_img, :26-49)
  *   bevwarp_warp_composite  composite_bev_img(bg, fg, fg_mask, ...), bev/tool/compo.py:26-49: the three warps and the blend
@@ -69,8 +72,8 @@ typedef enum bevwarp_status {
     BEVWARP_ERR_OVERLAP = -6       /* source and destination share bytes (ABI v5; v4 reported BAD_ARG)   */
 } bevwarp_status;
 
-/* BEVWARP_F16 (IEEE binary16) and BEVWARP_BF16 (bfloat16) are plane types of bevwarp_warp_planes only: as a pixel or point type every
- * entry point answers BEVWARP_ERR_UNSUPPORTED for them. */
+/* BEVWARP_F16 (IEEE binary16) and BEVWARP_BF16 (bfloat16) are plane types of bevwarp_warp_planes and bevwarp_warp_nv12_planes only: as a
+ * pixel or point type every entry point answers BEVWARP_ERR_UNSUPPORTED for them. */
 typedef enum bevwarp_dtype { BEVWARP_U8 = 0, BEVWARP_F32 = 1, BEVWARP_F64 = 2, BEVWARP_F16 = 3, BEVWARP_BF16 = 4 } bevwarp_dtype;
 
 /* Same numeric values as cv2.INTER_NEAREST / cv2.INTER_LINEAR / cv2.INTER_CUBIC.  BEVWARP_CUBIC is taken by bevwarp_warp and
@@ -257,6 +260,38 @@ int bevwarp_warp_nv12(const void *y, const void *uv, void *dst, int batch, int s
                       int64_t y_frame_stride, int64_t y_row_stride, int64_t uv_frame_stride, int64_t uv_row_stride,
                       int64_t dst_frame_stride, int64_t dst_row_stride, const double *M_inv, int m_count, int interp,
                       int rgb_order, const double *border_value /*HOST, 3 doubles or NULL*/, void *stream);
+
+/*
+ * bevwarp_warp_nv12 and the plane stage of bevwarp_warp_planes in one pass: stands in for `ok, img = video.read()` +
+ * cv2.warpPerspective(img, H_bev_img, (u_size, v_size)), vis_homo.py:86-89, plus the detector-input step of bevwarp_warp_planes (layout and
+ * precision between vis_homo.py:89 and a detector).  For P = plane_dtype (BEVWARP_F32 | BEVWARP_F16 | BEVWARP_BF16) and channel c = 0, 1, 2 in
+ * the DESTINATION's order (rgb_order 0: B, G, R; 1: R, G, B):
+ *   p               = bevwarp_warp_nv12(y, uv, ..., interp, rgb_order, border_value)[b][y][x][c]        (an 8-bit value)
+ *   v               = float32(p) * float32(scale[c]) + float32(bias[c])                              (multiply, then add, each rounded; no FMA)
+ *   dst[b][c][y][x] = convert_P(v)
+ * bit for bit what the two entry points give in sequence, double rounding included; neither the converted frame nor the 8-bit BEV frame
+ * is in memory.  convert_P is exactly bevwarp_warp_planes's (F32: the identity; F16 / BF16: round to nearest, ties to even, overflow to
+ * +-inf, subnormals kept, -0 kept).  A tap outside the frame is the 8-bit border value, as in bevwarp_warp_nv12: a pixel whose taps are
+ * all outside is convert_P(float32(border[c]) * scale[c] + bias[c]).
+ *   y, uv, src_h, src_w, the four source strides, M_inv, m_count, interp, rgb_order, the conversion and the (x >> 1, y >> 1) chroma
+ *                   addressing: bevwarp_warp_nv12's, unchanged (nearest or bilinear, constant border, even source sides).
+ *   dst             device, three planes per frame of dst_h rows of dst_w elements of P; dst_frame_stride, dst_plane_stride and
+ *                   dst_row_stride in BYTES, multiples of the element size.  A base and strides that are all multiples of 4 elements
+ *                   (16 bytes float32, 8 bytes 16-bit) enable the wide stores.
+ *   border_value, scale, bias   HOST, 3 doubles each in the DESTINATION's channel order, or NULL = 0, 1 and 0.
+ * Status, in this order: BEVWARP_ERR_BAD_ARG (everything bevwarp_warp_nv12 lists for y / uv / m_count; a destination base or stride that is
+ * no multiple of the element size -- for a plane_dtype outside the three no alignment is asked --, a row stride below dst_w elements,
+ * planes or frames that overlap their successors); BEVWARP_ERR_UNSUPPORTED (interp other than nearest / linear, rgb_order outside {0, 1},
+ * plane_dtype outside {F32, F16, BF16}); BEVWARP_ERR_TOO_LARGE (either source plane, as bevwarp_warp_nv12); BEVWARP_ERR_OVERLAP (the bounding
+ * byte range of all destination planes meets the y or the uv image's); BEVWARP_ERR_TOO_LARGE again for a destination side > 2^20;
+ * BEVWARP_ERR_NOT_FINITE (border_value, scale, bias).  batch == 0 is BEVWARP_OK and launches nothing.
+ */
+int bevwarp_warp_nv12_planes(const void *y, const void *uv, void *dst, int batch, int src_h, int src_w, int dst_h, int dst_w,
+                             int64_t y_frame_stride, int64_t y_row_stride, int64_t uv_frame_stride, int64_t uv_row_stride,
+                             int64_t dst_frame_stride, int64_t dst_plane_stride, int64_t dst_row_stride,
+                             const double *M_inv, int m_count, int interp, int rgb_order,
+                             const double *border_value /*HOST, 3 or NULL*/, const double *scale /*HOST, 3 or NULL = 1*/,
+                             const double *bias /*HOST, 3 or NULL = 0*/, int plane_dtype, void *stream);
 
 /*
  * out[i] = uint8(min(round_half_even(fg[i] * (mask[i] / 255) + bg[i] * (1 - mask[i] / 255)), 255)) for i in [0, n), computed in
