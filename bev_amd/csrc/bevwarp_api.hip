@@ -30,23 +30,35 @@ int launched(hipError_t e) { return e == hipSuccess ? BEVWARP_OK : hip_fail(e); 
 using namespace bevwarp;
 using namespace bevwarp::plan;
 
-// a call's and a plan's fields in the kernel arguments (WarpArgs and BorderArgs name the common ones alike)
-template <class Args>
-void copy_call(Args& a, const WarpCall& c) {
+// a call's and a plan's fields in the row kernel's arguments
+void copy_call(WarpArgs& a, const WarpCall& c) {
     memset(&a, 0, sizeof(a));
     a.src = (const uint8_t*)c.src.base, a.dst = (uint8_t*)c.dst.base, a.minv = c.minv;
     a.src_fs = c.src.fs, a.src_rs = c.src.rs, a.dst_fs = c.dst.fs, a.dst_rs = c.dst.rs;
     a.src_h = c.src.h, a.src_w = c.src.w, a.dst_h = c.dst.h, a.dst_w = c.dst.w;
     a.m_stride = c.m_count == 1 ? 0 : 9;
 }
-template <class Args>
-void copy_grid(Args& a, const TilePlan& p) {
+void copy_plan(WarpArgs& a, const TilePlan& p) {
+    a.bw0 = p.bw0, a.tiles_x = p.tiles_x, a.tiles_per_frame = p.tiles_per_frame;
+    a.tpf_magic = p.tpf_magic, a.tx_magic = p.tx_magic, a.bw0_magic = p.bw0_magic;
+    a.tile_h = p.tile_h, a.total_tiles = p.total_tiles, a.chunk = p.chunk, a.stagger = p.stagger, a.tail_split = p.tail_split;
+}
+// The shared frame's part (flat_frame.h) of the border, bicubic and NV12 kernels' arguments, which the caller has zeroed: the
+// destination, the matrices and plan_border's grid.  (dst_vec_ok follows each entry point's own layout rule.)
+void fill_frame(FrameArgs& a, const Frames& dst, const double* minv, int m_count, const TilePlan& p) {
+    a.dst = (uint8_t*)dst.base, a.minv = minv;
+    a.dst_fs = dst.fs, a.dst_rs = dst.rs, a.dst_h = dst.h, a.dst_w = dst.w;
+    a.m_stride = m_count == 1 ? 0 : 9;
     a.bw0 = p.bw0, a.tiles_x = p.tiles_x, a.tiles_per_frame = p.tiles_per_frame;
     a.tpf_magic = p.tpf_magic, a.tx_magic = p.tx_magic, a.bw0_magic = p.bw0_magic;
 }
-void copy_plan(WarpArgs& a, const TilePlan& p) {
-    copy_grid(a, p);
-    a.tile_h = p.tile_h, a.total_tiles = p.total_tiles, a.chunk = p.chunk, a.stagger = p.stagger, a.tail_split = p.tail_split;
+// ... and the NV12 kernels' own part: the frame, the two source planes and the border value, `bu` = its bytes per SAMPLED channel
+void fill_nv12(Nv12Args& a, const Nv12Call& c, const TilePlan& p, const uint8_t* bu) {
+    fill_frame(a, {c.dst, c.dst_h, c.dst_w, c.dst_fs, c.dst_rs}, c.minv, c.m_count, p);
+    a.y = (const uint8_t*)c.y, a.uv = (const uint8_t*)c.uv;
+    a.y_fs = c.y_fs, a.y_rs = c.y_rs, a.uv_fs = c.uv_fs, a.uv_rs = c.uv_rs;
+    a.src_h = c.src_h, a.src_w = c.src_w;
+    a.border = (uint32_t)bu[0] | ((uint32_t)bu[1] << 8) | ((uint32_t)bu[2] << 16);
 }
 // border_value (HOST, `channels` doubles or NULL) as the kernels take it: float32, and saturate_cast<uchar> (round half to even, clamp)
 template <class U8>
@@ -178,8 +190,9 @@ int bevwarp_warp_border(const void* src, void* dst, int batch, int src_h, int sr
     const TilePlan p = plan::plan_border(batch, dst_h, dst_w, kBorderTileW, kBorderTileH);
     if (p.status != BEVWARP_OK) return p.status;
     CubicArgs a;  // (the border kernel takes its BorderArgs part)
-    copy_call(a, c);
-    copy_grid(a, p);
+    memset(&a, 0, sizeof(a));
+    fill_frame(a, c.dst, c.minv, c.m_count, p);
+    a.src = (const uint8_t*)src, a.src_fs = src_frame_stride, a.src_rs = src_row_stride, a.src_h = src_h, a.src_w = src_w;
     // the 4 taps of a bicubic window reach one index beyond a saturated one: a period plan of their own
     const plan::BorderPeriod px = cubic ? cubic::window_period(border_mode, src_w) : plan::border_period(border_mode, src_w);
     const plan::BorderPeriod py = cubic ? cubic::window_period(border_mode, src_h) : plan::border_period(border_mode, src_h);
@@ -201,18 +214,13 @@ int bevwarp_warp_nv12(const void* y, const void* uv, void* dst, int batch, int s
     if (st != BEVWARP_OK || batch == 0) return st;
     const TilePlan p = plan::plan_border(batch, dst_h, dst_w, kBorderTileW, kBorderTileH);
     if (p.status != BEVWARP_OK) return p.status;
-    Nv12Args a;
-    memset(&a, 0, sizeof(a));
-    a.y = (const uint8_t*)y, a.uv = (const uint8_t*)uv, a.dst = (uint8_t*)dst, a.minv = M_inv;
-    a.y_fs = y_frame_stride, a.y_rs = y_row_stride, a.uv_fs = uv_frame_stride, a.uv_rs = uv_row_stride, a.dst_fs = dst_frame_stride, a.dst_rs = dst_row_stride;
-    a.src_h = src_h, a.src_w = src_w, a.dst_h = dst_h, a.dst_w = dst_w;
-    a.m_stride = m_count == 1 ? 0 : 9;
-    copy_grid(a, p);
-    a.dst_vec_ok = plan::wide_stores_ok(c.dst_image(), plan::store_align(BEVWARP_U8, 3, false));
     float bf[4];
     uint8_t bu[4];  // (in the destination's channel order, as given: the border value is not converted)
     if (border_values(border_value, 3, bf, bu) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
-    a.border = (uint32_t)bu[0] | ((uint32_t)bu[1] << 8) | ((uint32_t)bu[2] << 16);
+    Nv12Args a;
+    memset(&a, 0, sizeof(a));
+    fill_nv12(a, c, p, bu);
+    a.dst_vec_ok = plan::wide_stores_ok(c.dst_image(), plan::store_align(BEVWARP_U8, 3, false));
     return launched(launch_warp_nv12(a, interp, rgb_order, p.total_tiles, (hipStream_t)stream));
 }
 
@@ -227,28 +235,25 @@ int bevwarp_warp_nv12_planes(const void* y, const void* uv, void* dst, int batch
     if (st != BEVWARP_OK || batch == 0) return st;
     const TilePlan p = plan::plan_border(batch, dst_h, dst_w, kBorderTileW, kBorderTileH);
     if (p.status != BEVWARP_OK) return p.status;
-    Nv12PlanesArgs a;
-    memset(&a, 0, sizeof(a));
-    a.y = (const uint8_t*)y, a.uv = (const uint8_t*)uv, a.dst = (uint8_t*)dst, a.minv = M_inv;
-    a.y_fs = y_frame_stride, a.y_rs = y_row_stride, a.uv_fs = uv_frame_stride, a.uv_rs = uv_row_stride, a.dst_fs = dst_frame_stride, a.dst_rs = dst_row_stride;
-    a.src_h = src_h, a.src_w = src_w, a.dst_h = dst_h, a.dst_w = dst_w;
-    a.m_stride = m_count == 1 ? 0 : 9;
-    copy_grid(a, p);
-    a.dst_vec_ok = plan::nv12_planes_wide_stores_ok(c);
-    a.plane = plane_dtype == BEVWARP_F32 ? kPlaneF32 : (plane_dtype == BEVWARP_F16 ? kPlaneF16 : kPlaneBF16);
     float bf[4];
     uint8_t bu[4];  // (in the destination's channel order, as given)
     if (border_values(border_value, 3, bf, bu) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
+    Nv12PlanesArgs a;
+    memset(&a, 0, sizeof(a));
+    a.dst_vec_ok = plan::nv12_planes_wide_stores_ok(c);
+    a.plane = plane_dtype == BEVWARP_F32 ? kPlaneF32 : (plane_dtype == BEVWARP_F16 ? kPlaneF16 : kPlaneBF16);
     // the kernel samples B, G, R: sampled channel k is the destination's channel k (BGR) or 2 - k (RGB), with that channel's plane,
     // scale, bias and border value -- the channel order is nothing but this table
+    uint8_t bs[3];
     for (int k = 0; k < 3; k++) {
         const int ch = rgb_order ? 2 - k : k;
         const double sc = scale ? scale[ch] : 1.0, bi = bias ? bias[ch] : 0.0;
         if (!isfinite(sc) || !isfinite(bi)) return BEVWARP_ERR_NOT_FINITE;
         a.pscale[k] = (float)sc, a.pbias[k] = (float)bi;
         a.ch_off[k] = (int64_t)ch * dst_plane_stride;
-        a.border |= (uint32_t)bu[ch] << (8 * k);
+        bs[k] = bu[ch];
     }
+    fill_nv12(a, c.s, p, bs);
     return launched(launch_warp_nv12_planes(a, interp, p.total_tiles, (hipStream_t)stream));
 }
 

@@ -164,21 +164,6 @@ struct Nv12Call {
     Image dst_image() const { return {(uintptr_t)dst, dst_h, (uint64_t)dst_w * 3, dst_rs, dst_fs, batch}; }
 };
 
-// All argument checks of an NV12 warp, in the order the header documents: bad arguments (null pointers, sizes, odd source sides,
-// layouts, matrix count), unsupported interpolation or channel order, source size limits per plane, overlap of the destination with
-// either plane (the planes may overlap each other: both are only read).
-inline int check_warp_nv12(const Nv12Call& c) {
-    if (!c.y || !c.uv || !c.dst || !c.minv) return BEVWARP_ERR_BAD_ARG;
-    if (c.batch < 0 || c.src_h <= 0 || c.src_w <= 0 || c.dst_h <= 0 || c.dst_w <= 0 || (c.src_h & 1) || (c.src_w & 1)) return BEVWARP_ERR_BAD_ARG;
-    const Image y = c.y_image(), uv = c.uv_image(), d = c.dst_image();
-    if (layout_status(y, 1) != BEVWARP_OK || layout_status(uv, 2) != BEVWARP_OK || layout_status(d, 1) != BEVWARP_OK) return BEVWARP_ERR_BAD_ARG;
-    if (c.m_count != 1 && c.m_count != c.batch) return BEVWARP_ERR_BAD_ARG;
-    if ((c.interp != BEVWARP_NEAREST && c.interp != BEVWARP_LINEAR) || (c.rgb_order != 0 && c.rgb_order != 1)) return BEVWARP_ERR_UNSUPPORTED;
-    int st;
-    if ((st = source_size_status(y, c.src_w)) != BEVWARP_OK || (st = source_size_status(uv, c.src_w / 2)) != BEVWARP_OK || c.batch == 0) return st;
-    return (regions_overlap(y, d) || regions_overlap(uv, d)) ? BEVWARP_ERR_OVERLAP : BEVWARP_OK;
-}
-
 // ---- an NV12 warp into channel planes (bevwarp_warp_nv12_planes) ---------------------------------------------------------------------
 // The source is an Nv12Call's; the destination is three planes per frame of dst_h rows of dst_w elements of `plane_dtype`.
 struct Nv12PlanesCall {
@@ -192,26 +177,35 @@ struct Nv12PlanesCall {
     uintptr_t dst_end() const { return plane_image().end() + 2 * (uint64_t)dst_ps; }  // (of the bounding byte range of all planes)
 };
 
-// All argument checks of an NV12 warp into planes, in the order the header documents: check_warp_nv12's bad arguments with the plane
-// layout of check_warp in the destination's place, unsupported interpolation / channel order / plane type, source size limits per plane,
-// overlap of the destination's bounding byte range with either source image.
-inline int check_warp_nv12_planes(const Nv12PlanesCall& c) {
-    const Nv12Call& s = c.s;
-    if (!s.y || !s.uv || !s.dst || !s.minv) return BEVWARP_ERR_BAD_ARG;
-    if (s.batch < 0 || s.src_h <= 0 || s.src_w <= 0 || s.dst_h <= 0 || s.dst_w <= 0 || (s.src_h & 1) || (s.src_w & 1)) return BEVWARP_ERR_BAD_ARG;
-    const Image y = s.y_image(), uv = s.uv_image(), d = c.plane_image();
+// All argument checks of the two NV12 warps (`planes`: the call into planes, or null), in the order the header documents: bad arguments
+// (null pointers, sizes, odd source sides, layouts -- the interleaved destination's, or check_warp's rule for planes: rows in a plane,
+// asked of a lone plane too, and planes in a frame -- then the matrix count), unsupported interpolation, channel order or plane type,
+// source size limits per plane, overlap of the destination with either source plane (the planes may overlap each other: both are only
+// read; a destination of planes is taken as its bounding byte range).
+inline int check_nv12(const Nv12Call& c, const Nv12PlanesCall* planes) {
+    if (!c.y || !c.uv || !c.dst || !c.minv) return BEVWARP_ERR_BAD_ARG;
+    if (c.batch < 0 || c.src_h <= 0 || c.src_w <= 0 || c.dst_h <= 0 || c.dst_w <= 0 || (c.src_h & 1) || (c.src_w & 1)) return BEVWARP_ERR_BAD_ARG;
+    const Image y = c.y_image(), uv = c.uv_image(), d = planes ? planes->plane_image() : c.dst_image();
     if (layout_status(y, 1) != BEVWARP_OK || layout_status(uv, 2) != BEVWARP_OK) return BEVWARP_ERR_BAD_ARG;
-    // (check_warp's rule for planes: rows in a plane, asked of a lone plane too, and planes in a frame)
-    const Image rows_in_plane = {d.base, d.rows, d.row_bytes, d.rs, c.dst_ps, 2}, planes_in_frame = {d.base, 3, 0, c.dst_ps, d.fs, d.batch};
-    if (layout_status(rows_in_plane, c.elem()) != BEVWARP_OK || layout_status(planes_in_frame, c.elem()) != BEVWARP_OK) return BEVWARP_ERR_BAD_ARG;
-    if (s.m_count != 1 && s.m_count != s.batch) return BEVWARP_ERR_BAD_ARG;
-    if ((s.interp != BEVWARP_NEAREST && s.interp != BEVWARP_LINEAR) || (s.rgb_order != 0 && s.rgb_order != 1)) return BEVWARP_ERR_UNSUPPORTED;
-    if (c.plane_dtype != BEVWARP_F32 && c.plane_dtype != BEVWARP_F16 && c.plane_dtype != BEVWARP_BF16) return BEVWARP_ERR_UNSUPPORTED;
+    if (planes) {
+        const Image rows_in_plane = {d.base, d.rows, d.row_bytes, d.rs, planes->dst_ps, 2}, planes_in_frame = {d.base, 3, 0, planes->dst_ps, d.fs, d.batch};
+        if (layout_status(rows_in_plane, planes->elem()) != BEVWARP_OK || layout_status(planes_in_frame, planes->elem()) != BEVWARP_OK) return BEVWARP_ERR_BAD_ARG;
+    } else if (layout_status(d, 1) != BEVWARP_OK) {
+        return BEVWARP_ERR_BAD_ARG;
+    }
+    if (c.m_count != 1 && c.m_count != c.batch) return BEVWARP_ERR_BAD_ARG;
+    if ((c.interp != BEVWARP_NEAREST && c.interp != BEVWARP_LINEAR) || (c.rgb_order != 0 && c.rgb_order != 1)) return BEVWARP_ERR_UNSUPPORTED;
+    if (planes && planes->plane_dtype != BEVWARP_F32 && planes->plane_dtype != BEVWARP_F16 && planes->plane_dtype != BEVWARP_BF16) return BEVWARP_ERR_UNSUPPORTED;
     int st;
-    if ((st = source_size_status(y, s.src_w)) != BEVWARP_OK || (st = source_size_status(uv, s.src_w / 2)) != BEVWARP_OK || s.batch == 0) return st;
-    const uintptr_t d1 = c.dst_end();
-    return ((y.base < d1 && d.base < y.end()) || (uv.base < d1 && d.base < uv.end())) ? BEVWARP_ERR_OVERLAP : BEVWARP_OK;
+    if ((st = source_size_status(y, c.src_w)) != BEVWARP_OK || (st = source_size_status(uv, c.src_w / 2)) != BEVWARP_OK || c.batch == 0) return st;
+    if (planes) {
+        const uintptr_t d1 = planes->dst_end();
+        return ((y.base < d1 && d.base < y.end()) || (uv.base < d1 && d.base < uv.end())) ? BEVWARP_ERR_OVERLAP : BEVWARP_OK;
+    }
+    return (regions_overlap(y, d) || regions_overlap(uv, d)) ? BEVWARP_ERR_OVERLAP : BEVWARP_OK;
 }
+inline int check_warp_nv12(const Nv12Call& c) { return check_nv12(c, nullptr); }
+inline int check_warp_nv12_planes(const Nv12PlanesCall& c) { return check_nv12(c.s, &c); }
 // Does the call's destination admit the wide stores?  call_wide_stores_ok's rule: 4 plane elements per store, the plane stride counts.
 inline bool nv12_planes_wide_stores_ok(const Nv12PlanesCall& c) {
     const int align = store_align(BEVWARP_U8, 3, true, c.elem());

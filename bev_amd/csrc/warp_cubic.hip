@@ -2,12 +2,11 @@
 // border modes.  OpenCV 3.x-4.x's remapBicubic restated from memory (parity unpinned, like the rest of the warp); the definition is
 // in include/bevwarp.h and DESIGN.md section 4.10, the tables in cubic_tab.h.
 //
-// The frame of the border kernel (warp_border.hip): a flat grid, a lane owns 4 consecutive pixels of one destination row, the
-// exact float64 coordinate chain per pixel, int16 saturation before anything else, wide stores for lanes that write all 4 pixels.
-// What is new is the sampler, in two paths.  An INLIER (all 16 taps inside the source) loads each of its four tap rows as ONE window
+// The frame is flat_frame.h's, shared with the border and NV12 kernels: a flat grid, a lane owns 4 consecutive pixels of one destination
+// row, the exact float64 coordinate chain per pixel, int16 saturation before anything else, wide stores for lanes that write all 4
+// pixels.  This unit holds the sampler, in two paths.  An INLIER (all 16 taps inside the source) loads each of its four tap rows as ONE window
 // of exactly 4 C values and sums them row by row.  Every other written pixel takes the general path: eight index remaps, sixteen
 // per-pixel loads, one tap at a time around the border value.  A wave diverges where a row segment crosses the frame's edge.
-#include "border_device.h"
 #include "cubic_tab.h"
 #include "warp_cubic.h"
 
@@ -173,37 +172,23 @@ __global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(kWavesPerSi
     constexpr int PPL = kBorderPPL;
     constexpr bool kTransparent = MODE == BEVWARP_BORDER_TRANSPARENT;
     constexpr int kRemap = kTransparent ? BEVWARP_BORDER_REFLECT_101 : MODE;
-    const uint32_t t = blockIdx.x;
-    const uint32_t b = fast_div(t, a.tpf_magic, (uint32_t)a.tiles_per_frame);
-    const uint32_t r = t - b * (uint32_t)a.tiles_per_frame;
-    const uint32_t ty = fast_div(r, a.tx_magic, (uint32_t)a.tiles_x);
-    const uint32_t tx = r - ty * (uint32_t)a.tiles_x;
-    const int y = (int)ty * kBorderTileH + (int)(threadIdx.x >> 6);
-    const int xs = (int)tx * kBorderTileW + (int)(threadIdx.x & 63) * PPL;  // the lane's first pixel
-    if (y >= a.dst_h || xs >= a.dst_w) return;
-    const double* M = a.minv + (int64_t)b * a.m_stride;
-    double Mr[9];
-#pragma unroll
-    for (int i = 0; i < 9; i++) Mr[i] = M[i];
+    uint32_t b;
+    int y, xs;  // frame, row, the lane's first pixel
+    if (!lane_position(a, b, y, xs)) return;
+    RowWalk walk(a, b, y);
     const uint8_t* frame = a.src + (int64_t)b * a.src_fs;
     // all 16 taps inside: 0 <= sx < max(w - 3, 0) and 0 <= sy < max(h - 3, 0)
     const unsigned in_w = (unsigned)max(a.src_w - 3, 0), in_h = (unsigned)max(a.src_h - 3, 0);
 
     Pixel<T, C> px[PPL];
     bool wr[PPL];
-    int bx = -1;
-    double X0 = 0.0, Y0 = 0.0, W0 = 0.0;
 #pragma unroll
     for (int j = 0; j < PPL; j++) {
         const int x = xs + j;
-        const int bxj = (int)fast_div((uint32_t)x, a.bw0_magic, (uint32_t)a.bw0) * a.bw0;
-        if (bxj != bx) {  // (the lane's 4 pixels share an evaluation block unless its width is not a multiple of 4)
-            bx = bxj;
-            row_terms(Mr, bx, y, X0, Y0, W0);
-        }
-        const double x1 = (double)(x - bx);
+        double Xn, Yn, Wn;
+        walk.pixel(a, x, Xn, Yn, Wn);
         int X, Y;
-        map_pixel_exact_nan_max<kLinear>(X0 + Mr[0] * x1, Y0 + Mr[3] * x1, W0 + Mr[6] * x1, X, Y);  // the bilinear warp's maps
+        map_pixel_exact_nan_max<kLinear>(Xn, Yn, Wn, X, Y);  // the bilinear warp's maps
         // the window starts one pixel before the map's position, AFTER its int16 saturation
         const int sx = sat16(X >> kInterBits) - 1, sy = sat16(Y >> kInterBits) - 1;
         const bool inl = (unsigned)sx < in_w && (unsigned)sy < in_h;
@@ -217,8 +202,7 @@ __global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(kWavesPerSi
         else
             px[j] = sample_general<T, C, kRemap>(a, frame, sx, sy, W);
     }
-    uint8_t* drow = a.dst + (int64_t)b * a.dst_fs + (int64_t)y * a.dst_rs;
-    store_lane_pixels<T, C, true>(drow, xs, px, wr, a.dst_vec_ok);
+    store_lane_pixels<T, C, true>(a, b, y, xs, px, wr);
 }
 
 template <typename T, int MODE>

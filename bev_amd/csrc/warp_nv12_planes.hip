@@ -2,12 +2,12 @@
 // (bevwarp_warp_nv12_planes): what bevwarp_warp_nv12 followed by the plane stage of bevwarp_warp_planes gives, bit for bit, in one pass --
 // neither the converted frame nor the 8-bit BEV frame exists.  Constant border, nearest and bilinear.  See DESIGN.md section 4.13.
 //
-// warp_nv12_kernel's structure (warp_nv12.hip) and its sampler (nv12_sample.h); the store stage is the plane stage of the row kernel's
-// 8-bit sources (rows_store.inc): per channel the lane converts its 4 values and writes them with one 16-byte (float32) or 8-byte (16-bit)
-// store into that channel's plane row, so a wave writes 1024 / 512 contiguous bytes per instruction.  The kernel samples B, G, R and
-// never learns the destination's channel order: the host hands it a plane offset, scale, bias and border byte per SAMPLED channel.
+// The frame is flat_frame.h's and the sampler warp_nv12_kernel's (nv12_sample.h); the store stage, which has no twin in the frame, is
+// the plane stage of the row kernel's 8-bit sources (rows_store.inc): per channel the lane converts its 4 values and writes them with
+// one 16-byte (float32) or 8-byte (16-bit) store into that channel's plane row, so a wave writes 1024 / 512 contiguous bytes per
+// instruction.  The kernel samples B, G, R and never learns the destination's channel order: the host hands it a plane offset, scale,
+// bias and border byte per SAMPLED channel.
 #include "nv12_sample.h"
-#include "warp_border.h"
 #include "warp_kernels.h"
 #include "warp_nv12.h"
 
@@ -18,43 +18,28 @@ namespace {
 template <int INTERP, bool WIDE16>
 __global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(kWavesPerSimd, 8))) void nv12_planes_kernel(const Nv12PlanesArgs a) {
     constexpr int PPL = kBorderPPL;
-    const uint32_t t = blockIdx.x;
-    const uint32_t b = fast_div(t, a.tpf_magic, (uint32_t)a.tiles_per_frame);
-    const uint32_t r = t - b * (uint32_t)a.tiles_per_frame;
-    const uint32_t ty = fast_div(r, a.tx_magic, (uint32_t)a.tiles_x);
-    const uint32_t tx = r - ty * (uint32_t)a.tiles_x;
-    const int y = (int)ty * kBorderTileH + (int)(threadIdx.x >> 6);
-    const int xs = (int)tx * kBorderTileW + (int)(threadIdx.x & 63) * PPL;  // the lane's first pixel
-    if (y >= a.dst_h || xs >= a.dst_w) return;
-    const double* M = a.minv + (int64_t)b * a.m_stride;
-    double Mr[9];
-#pragma unroll
-    for (int i = 0; i < 9; i++) Mr[i] = M[i];
+    uint32_t b;
+    int y, xs;  // frame, row, the lane's first pixel
+    if (!lane_position(a, b, y, xs)) return;
+    RowWalk walk(a, b, y);
     const uint8_t* yf = a.y + (int64_t)b * a.y_fs;
     const uint8_t* uvf = a.uv + (int64_t)b * a.uv_fs;
 
     uint32_t p[PPL];
-    int bx = -1;
-    double X0 = 0.0, Y0 = 0.0, W0 = 0.0;
 #pragma unroll
     for (int j = 0; j < PPL; j++) {
         // pixels past the row's end are computed like any other (their taps are clamped into the planes too) and not stored
-        const int x = xs + j;
-        const int bxj = (int)fast_div((uint32_t)x, a.bw0_magic, (uint32_t)a.bw0) * a.bw0;
-        if (bxj != bx) {  // (the lane's 4 pixels share an evaluation block unless its width is not a multiple of 4)
-            bx = bxj;
-            row_terms(Mr, bx, y, X0, Y0, W0);
-        }
-        const double x1 = (double)(x - bx);
+        double Xn, Yn, W;
+        walk.pixel(a, xs + j, Xn, Yn, W);
         int X, Y;
-        map_pixel_exact<INTERP>(X0 + Mr[0] * x1, Y0 + Mr[3] * x1, W0 + Mr[6] * x1, X, Y);
+        map_pixel_exact<INTERP>(Xn, Yn, W, X, Y);
         p[j] = sample_nv12<INTERP, 0>(yf, uvf, a.y_rs, a.uv_rs, a.src_w, a.src_h, a.border, X, Y);
     }
 
     // the plane stores: per sampled channel the 8-bit value as float32, times scale, plus bias (each rounded), converted; 4 elements of
     // a plane row in one store for a lane whose 4 pixels lie in the row, element stores otherwise
     constexpr int ELEM = WIDE16 ? 2 : 4;
-    uint8_t* d = a.dst + (int64_t)b * a.dst_fs + (int64_t)y * a.dst_rs + (int64_t)xs * ELEM;
+    uint8_t* d = dst_row(a, b, y) + (int64_t)xs * ELEM;
     const int lane_px = min(PPL, a.dst_w - xs);
     const bool lane_vec = a.dst_vec_ok && lane_px == PPL;
     if constexpr (WIDE16) {

@@ -2,9 +2,6 @@
 oracle and against known answers, the C ABI's argument checks, the cv2-compatible constants, and the new kernels' code objects."""
 import ctypes
 import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,6 +9,7 @@ import pytest
 from bev_amd import _lib
 from oracle import warp_numpy as wn
 from tests import border_ref as BR
+from tests import codeobj
 from tests import workloads as wl
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -166,28 +164,7 @@ def test_cv2_compat_rejects_unknown_border_before_the_device():
 
 # ---- the code objects of the new kernels: no scratch, at most 128 VGPRs each ----
 
-def _makefile_flags():
-    with open(os.path.join(ROOT, "bev_amd", "csrc", "Makefile")) as f:
-        text = f.read()
-    flags = re.search(r"^CXXFLAGS \?= (.*)$", text, re.M).group(1)
-    return flags.replace("$(ARCH)", "gfx950").split()
-
-
 def test_border_kernels_code_object(tmp_path):
-    hipcc = shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
-    if hipcc is None:
-        pytest.skip("hipcc is absent")
-    readelf = os.path.join(os.path.dirname(os.path.realpath(hipcc)), "..", "llvm", "bin", "llvm-readelf")
-    if not os.path.exists(readelf):
-        readelf = shutil.which("llvm-readelf") or "/opt/rocm/llvm/bin/llvm-readelf"
-    co = str(tmp_path / "warp_border.co")
-    subprocess.check_call([hipcc] + _makefile_flags() + ["--cuda-device-only", "--no-gpu-bundle-output", "-c", "warp_border.hip", "-o", co],
-                          cwd=os.path.join(ROOT, "bev_amd", "csrc"))
-    notes = subprocess.check_output([readelf, "--notes", co], text=True)
-    parts = re.split(r"^\s*\.name:\s+(\S*warp_border_kernel\S*)\s*$", notes, flags=re.M)
-    kernels = dict(zip(parts[1::2], parts[2::2]))
+    kernels = {n: k for n, k in codeobj.kernels("warp_border.hip", tmp_path).items() if "warp_border_kernel" in n}
     assert len(kernels) == 2 * 2 * 4 * 5, len(kernels)  # dtype x interpolation x channels x mode
-    for name, meta in kernels.items():
-        scratch = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", meta).group(1))
-        vgprs = int(re.search(r"\.vgpr_count:\s+(\d+)", meta).group(1))
-        assert scratch == 0 and vgprs <= 128, (name, scratch, vgprs)
+    codeobj.assert_lean(kernels)

@@ -3,8 +3,6 @@
 checks, the cv2-compatible constant, and the kernels' code object.  OpenCV's remapBicubic restated from memory: parity unpinned."""
 import ctypes
 import os
-import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -12,6 +10,7 @@ import pytest
 
 from bev_amd import _lib
 from tests import border_ref as BR
+from tests import codeobj
 from tests import cubic_ref as CR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -245,28 +244,7 @@ def test_warp_to_planar_keeps_rejecting_cubic():
 
 # ---- the code object: at least one kernel, no scratch, at most 128 VGPRs (4 waves per SIMD, the border kernels' bound) ----
 
-def _makefile_flags():
-    with open(os.path.join(ROOT, "bev_amd", "csrc", "Makefile")) as f:
-        text = f.read()
-    flags = re.search(r"^CXXFLAGS \?= (.*)$", text, re.M).group(1)
-    return flags.replace("$(ARCH)", "gfx950").split()
-
-
 def test_cubic_kernels_code_object(tmp_path):
-    hipcc = shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
-    if hipcc is None:
-        pytest.skip("hipcc is absent")
-    readelf = os.path.join(os.path.dirname(os.path.realpath(hipcc)), "..", "llvm", "bin", "llvm-readelf")
-    if not os.path.exists(readelf):
-        readelf = shutil.which("llvm-readelf") or "/opt/rocm/llvm/bin/llvm-readelf"
-    co = str(tmp_path / "warp_cubic.co")
-    subprocess.check_call([hipcc] + _makefile_flags() + ["--cuda-device-only", "--no-gpu-bundle-output", "-c", "warp_cubic.hip", "-o", co],
-                          cwd=os.path.join(ROOT, "bev_amd", "csrc"))
-    notes = subprocess.check_output([readelf, "--notes", co], text=True)
-    parts = re.split(r"^\s*\.name:\s+(\S*warp_cubic_kernel\S*)\s*$", notes, flags=re.M)
-    kernels = dict(zip(parts[1::2], parts[2::2]))
+    kernels = {n: k for n, k in codeobj.kernels("warp_cubic.hip", tmp_path).items() if "warp_cubic_kernel" in n}
     assert len(kernels) == 2 * 4 * 6, len(kernels)  # dtype x channels x mode
-    for name, meta in kernels.items():
-        scratch = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", meta).group(1))
-        vgprs = int(re.search(r"\.vgpr_count:\s+(\d+)", meta).group(1))
-        assert scratch == 0 and vgprs <= 128, (name, scratch, vgprs)
+    codeobj.assert_lean(kernels)

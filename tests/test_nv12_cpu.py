@@ -4,8 +4,6 @@ argument errors, host_plan.h's check_warp_nv12 at its limits in a stand-alone dr
 sanitizers (tests/nv12_plan_driver.cpp), and the compiled kernels' register and scratch figures."""
 import ctypes
 import os
-import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -13,6 +11,7 @@ import pytest
 import torch
 
 from bev_amd import _lib
+from tests import codeobj
 from tests import nv12_ref as R
 from tests.test_abi import declared_symbols
 
@@ -347,31 +346,8 @@ def test_check_warp_nv12_at_its_limits_under_the_sanitizer(driver):
 
 
 # ---- the compiled kernels ---------------------------------------------------------------------------------------------------------------
-def _makefile_flags():
-    with open(os.path.join(ROOT, "bev_amd", "csrc", "Makefile")) as f:
-        text = f.read()
-    assert "warp_nv12.hip" in re.search(r"^SRCS = (.*)$", text, re.M).group(1) and "warp_nv12.h" in re.search(r"^KERNEL_HDRS = (.*)$", text, re.M).group(1)
-    flags = re.search(r"^CXXFLAGS \?= (.*)$", text, re.M).group(1)
-    assert "-ffp-contract=off" in flags
-    return flags.replace("$(ARCH)", "gfx950").split()
-
-
 def test_nv12_kernels_code_object(tmp_path):
-    hipcc = shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
-    if hipcc is None:
-        pytest.skip("hipcc is absent")
-    readelf = os.path.join(os.path.dirname(os.path.realpath(hipcc)), "..", "llvm", "bin", "llvm-readelf")
-    if not os.path.exists(readelf):
-        readelf = shutil.which("llvm-readelf") or "/opt/rocm/llvm/bin/llvm-readelf"
-    co = str(tmp_path / "warp_nv12.co")
-    subprocess.check_call([hipcc] + _makefile_flags() + ["--cuda-device-only", "--no-gpu-bundle-output", "-c", "warp_nv12.hip", "-o", co],
-                          cwd=os.path.join(ROOT, "bev_amd", "csrc"))
-    notes = subprocess.check_output([readelf, "--notes", co], text=True)
-    parts = re.split(r"^\s*\.name:\s+(\S*warp_nv12_kernel\S*)\s*$", notes, flags=re.M)
-    kernels = dict(zip(parts[1::2], parts[2::2]))
-    assert len(kernels) == 2 * 2, sorted(kernels)  # interpolation x channel order
-    for name, meta in kernels.items():
-        scratch = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", meta).group(1))
-        vgprs = int(re.search(r"\.vgpr_count:\s+(\d+)", meta).group(1))
-        assert scratch == 0 and vgprs <= 128, (name, scratch, vgprs)
-    assert [int(v) for v in re.findall(r"\.group_segment_fixed_size:\s+(\d+)", notes)] == [0] * 4  # no LDS
+    unit = codeobj.kernels("warp_nv12.hip", tmp_path, header="warp_nv12.h")
+    kernels = {n: k for n, k in unit.items() if "warp_nv12_kernel" in n}
+    assert len(kernels) == len(unit) == 2 * 2, sorted(unit)  # interpolation x channel order, and nothing else in the unit
+    codeobj.assert_lean(kernels)

@@ -6,7 +6,6 @@ figures."""
 import ctypes
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -14,6 +13,7 @@ import pytest
 import torch
 
 from bev_amd import _lib
+from tests import codeobj
 from tests.test_abi import declared_symbols
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -317,35 +317,10 @@ def test_check_warp_nv12_planes_at_its_limits_under_the_sanitizer(driver):
 
 
 # ---- the compiled kernels ---------------------------------------------------------------------------------------------------------------
-def _makefile_flags():
-    with open(os.path.join(ROOT, "bev_amd", "csrc", "Makefile")) as f:
-        text = f.read()
-    assert "warp_nv12_planes.hip" in re.search(r"^SRCS = (.*)$", text, re.M).group(1) and "nv12_sample.h" in re.search(r"^KERNEL_HDRS = (.*)$", text, re.M).group(1)
-    flags = re.search(r"^CXXFLAGS \?= (.*)$", text, re.M).group(1)
-    assert "-ffp-contract=off" in flags
-    return flags.replace("$(ARCH)", "gfx950").split()
-
-
 def test_nv12_planes_kernels_code_object(tmp_path):
-    hipcc = shutil.which("hipcc") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else None)
-    if hipcc is None:
-        pytest.skip("hipcc is absent")
-    readelf = os.path.join(os.path.dirname(os.path.realpath(hipcc)), "..", "llvm", "bin", "llvm-readelf")
-    if not os.path.exists(readelf):
-        readelf = shutil.which("llvm-readelf") or "/opt/rocm/llvm/bin/llvm-readelf"
-    co = str(tmp_path / "warp_nv12_planes.co")
-    subprocess.check_call([hipcc] + _makefile_flags() + ["--cuda-device-only", "--no-gpu-bundle-output", "-c", "warp_nv12_planes.hip", "-o", co],
-                          cwd=os.path.join(ROOT, "bev_amd", "csrc"))
-    notes = subprocess.check_output([readelf, "--notes", co], text=True)
-    parts = re.split(r"^\s*\.name:\s+(\S+)\s*$", notes, flags=re.M)
-    kernels = {n: m for n, m in zip(parts[1::2], parts[2::2]) if ".private_segment_fixed_size" in m}  # (argument names have no such field)
+    kernels = codeobj.kernels("warp_nv12_planes.hip", tmp_path, header="nv12_sample.h")
     with open(os.path.join(ROOT, "DESIGN.md")) as f:
         stated = re.search(r"warp_nv12_planes\.hip[^\n]*?\b(\d+) kernels", f.read())
     assert stated and len(kernels) == int(stated.group(1)) == 2 * 2, (sorted(kernels), stated)  # interpolation x (float32 | 16-bit planes)
     assert all("nv12_planes_kernel" in n and "warp_nv12_kernel" not in n for n in kernels), sorted(kernels)
-    for name, meta in kernels.items():
-        scratch = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", meta).group(1))
-        vgprs = int(re.search(r"\.vgpr_count:\s+(\d+)", meta).group(1))
-        assert scratch == 0 and vgprs <= 128, (name, scratch, vgprs)
-    assert [int(v) for v in re.findall(r"\.group_segment_fixed_size:\s+(\d+)", notes)] == [0] * len(kernels)  # no LDS (the field precedes a kernel's name)
-    assert [int(v) for v in re.findall(r"\.private_segment_fixed_size:\s+(\d+)", notes)] == [0] * len(kernels)
+    codeobj.assert_lean(kernels)
