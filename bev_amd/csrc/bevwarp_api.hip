@@ -13,6 +13,7 @@
 #include "warp_cubic.h"
 #include "warp_kernels.h"
 #include "warp_nv12.h"
+#include "warp_nv12_out.h"
 
 #pragma clang fp contract(off)
 
@@ -255,6 +256,60 @@ int bevwarp_warp_nv12_planes(const void* y, const void* uv, void* dst, int batch
     }
     fill_nv12(a, c.s, p, bs);
     return launched(launch_warp_nv12_planes(a, interp, p.total_tiles, (hipStream_t)stream));
+}
+
+}  // extern "C"
+
+namespace {
+// bevwarp_warp_to_nv12 and bevwarp_warp_nv12_to_nv12: the checks, plan_border's grid, the border pixel, one launch
+int warp_nv12_out_impl(const Nv12OutCall& c, const double* border_value, void* stream) {
+    const int st = c.nv12_src ? plan::check_warp_nv12_to_nv12(c) : plan::check_warp_to_nv12(c);
+    if (st != BEVWARP_OK || c.batch == 0) return st;
+    const TilePlan p = plan::plan_border(c.batch, c.dst_h, c.dst_w, kBorderTileW, kBorderTileH);
+    if (p.status != BEVWARP_OK) return p.status;
+    float bf[4];
+    uint8_t bu[4];  // (in the warped pixel's channel order: a pixel value, converted by the kernel like any other)
+    if (border_values(border_value, 3, bf, bu) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
+    Nv12OutArgs a;
+    memset(&a, 0, sizeof(a));
+    fill_frame(a, {c.dst_y, c.dst_h, c.dst_w, c.dy_fs, c.dy_rs}, c.minv, c.m_count, p);
+    a.dst_uv = (uint8_t*)c.dst_uv, a.duv_fs = c.duv_fs, a.duv_rs = c.duv_rs;
+    a.dst_vec_ok = plan::nv12_out_wide_stores_ok(c.dst_y_image());
+    a.uv_vec_ok = plan::nv12_out_wide_stores_ok(c.dst_uv_image());
+    a.src = (const uint8_t*)c.src, a.src_fs = c.src_fs, a.src_rs = c.src_rs;
+    a.y = (const uint8_t*)c.y, a.uv = (const uint8_t*)c.uv;
+    a.y_fs = c.y_fs, a.y_rs = c.y_rs, a.uv_fs = c.uv_fs, a.uv_rs = c.uv_rs;
+    a.src_h = c.src_h, a.src_w = c.src_w;
+    a.border = (uint32_t)bu[0] | ((uint32_t)bu[1] << 8) | ((uint32_t)bu[2] << 16);
+    return launched(launch_warp_nv12_out(a, c.nv12_src, c.interp, c.rgb_order, p.total_tiles, (hipStream_t)stream));
+}
+}  // namespace
+
+extern "C" {
+
+int bevwarp_warp_to_nv12(const void* src, void* dst_y, void* dst_uv, int batch, int src_h, int src_w, int dst_h, int dst_w, int64_t src_frame_stride,
+                         int64_t src_row_stride, int64_t y_frame_stride, int64_t y_row_stride, int64_t uv_frame_stride, int64_t uv_row_stride,
+                         const double* M_inv, int m_count, int interp, int rgb_order, const double* border_value, void* stream) {
+    Nv12OutCall c = {};
+    c.nv12_src = false, c.src = src, c.dst_y = dst_y, c.dst_uv = dst_uv;
+    c.batch = batch, c.src_h = src_h, c.src_w = src_w, c.dst_h = dst_h, c.dst_w = dst_w;
+    c.src_fs = src_frame_stride, c.src_rs = src_row_stride;
+    c.dy_fs = y_frame_stride, c.dy_rs = y_row_stride, c.duv_fs = uv_frame_stride, c.duv_rs = uv_row_stride;
+    c.minv = M_inv, c.m_count = m_count, c.interp = interp, c.rgb_order = rgb_order;
+    return warp_nv12_out_impl(c, border_value, stream);
+}
+
+int bevwarp_warp_nv12_to_nv12(const void* y, const void* uv, void* dst_y, void* dst_uv, int batch, int src_h, int src_w, int dst_h, int dst_w,
+                              int64_t y_frame_stride, int64_t y_row_stride, int64_t uv_frame_stride, int64_t uv_row_stride, int64_t dst_y_frame_stride,
+                              int64_t dst_y_row_stride, int64_t dst_uv_frame_stride, int64_t dst_uv_row_stride, const double* M_inv, int m_count,
+                              int interp, const double* border_value, void* stream) {
+    Nv12OutCall c = {};
+    c.nv12_src = true, c.y = y, c.uv = uv, c.dst_y = dst_y, c.dst_uv = dst_uv;
+    c.batch = batch, c.src_h = src_h, c.src_w = src_w, c.dst_h = dst_h, c.dst_w = dst_w;
+    c.y_fs = y_frame_stride, c.y_rs = y_row_stride, c.uv_fs = uv_frame_stride, c.uv_rs = uv_row_stride;
+    c.dy_fs = dst_y_frame_stride, c.dy_rs = dst_y_row_stride, c.duv_fs = dst_uv_frame_stride, c.duv_rs = dst_uv_row_stride;
+    c.minv = M_inv, c.m_count = m_count, c.interp = interp, c.rgb_order = 0;
+    return warp_nv12_out_impl(c, border_value, stream);
 }
 
 int bevwarp_warp_classes(const void* src, void* dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int channels, int64_t src_frame_stride,

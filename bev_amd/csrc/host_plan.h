@@ -212,6 +212,72 @@ inline bool nv12_planes_wide_stores_ok(const Nv12PlanesCall& c) {
     return wide_stores_ok(c.plane_image(), align) && c.dst_ps % align == 0;
 }
 
+// ---- a warp into NV12 (bevwarp_warp_to_nv12, bevwarp_warp_nv12_to_nv12) -------------------------------------------------------------
+// The destination is two images, laid out like an Nv12Call's source: dst_h rows of dst_w Y bytes, and dst_h / 2 rows of dst_w / 2 (U, V)
+// pairs (dst_w bytes, 2-byte elements).  The source is 8-bit, 3 channels (`src`) or, with `nv12_src`, the two planes of an Nv12Call.
+struct Nv12OutCall {
+    bool nv12_src;
+    const void *src, *y, *uv;     // src (BGR / RGB frames) or y and uv; the other side is unused
+    const void *dst_y, *dst_uv;
+    int batch, src_h, src_w, dst_h, dst_w;
+    int64_t src_fs, src_rs;       // of src
+    int64_t y_fs, y_rs, uv_fs, uv_rs;  // of y and uv
+    int64_t dy_fs, dy_rs, duv_fs, duv_rs;
+    const double* minv;
+    int m_count, interp, rgb_order;   // (rgb_order: of src; an NV12 source is sampled as B, G, R and passes 0)
+
+    Image src_image() const { return {(uintptr_t)src, src_h, (uint64_t)src_w * 3, src_rs, src_fs, batch}; }
+    Image y_image() const { return {(uintptr_t)y, src_h, (uint64_t)src_w, y_rs, y_fs, batch}; }
+    Image uv_image() const { return {(uintptr_t)uv, src_h / 2, (uint64_t)src_w, uv_rs, uv_fs, batch}; }
+    Image dst_y_image() const { return {(uintptr_t)dst_y, dst_h, (uint64_t)dst_w, dy_rs, dy_fs, batch}; }
+    Image dst_uv_image() const { return {(uintptr_t)dst_uv, dst_h / 2, (uint64_t)dst_w, duv_rs, duv_fs, batch}; }
+};
+
+// Do the two planes a launch WRITES share bytes?  regions_overlap's rule, with one more refinement: in a batch of single-buffer frames
+// (Y rows, then the rows of pairs, frame after frame) the Y images' bounding range spans every frame's pairs.  Where both planes walk
+// the frames with one stride and a frame's two planes lie within one such stride of each other, planes of different frames cannot meet
+// and frame 0 decides.
+inline bool written_planes_overlap(const Image& a, const Image& b) {
+    if (a.batch > 1 && a.fs == b.fs) {
+        Image a0 = a, b0 = b;
+        a0.batch = b0.batch = 1;
+        const uintptr_t lo = a0.base < b0.base ? a0.base : b0.base, a1 = a0.end(), b1 = b0.end(), hi = a1 > b1 ? a1 : b1;
+        if ((uint64_t)(hi - lo) <= (uint64_t)a.fs) return regions_overlap(a0, b0);
+    }
+    return regions_overlap(a, b);
+}
+
+// All argument checks of the two warps into NV12, in the order the header documents: bad arguments (null pointers, sizes, odd destination
+// sides, odd sides of an NV12 source, the layout of every image -- the pairs' planes with 2-byte elements --, the matrix count), unsupported
+// interpolation or channel order, the source's size limits, overlap of either destination plane with any source image and of the two
+// destination planes with each other (source planes may overlap each other: both are only read).
+inline int check_nv12_out(const Nv12OutCall& c) {
+    if (c.nv12_src ? (!c.y || !c.uv) : !c.src) return BEVWARP_ERR_BAD_ARG;
+    if (!c.dst_y || !c.dst_uv || !c.minv) return BEVWARP_ERR_BAD_ARG;
+    if (c.batch < 0 || c.src_h <= 0 || c.src_w <= 0 || c.dst_h <= 0 || c.dst_w <= 0 || (c.dst_h & 1) || (c.dst_w & 1)) return BEVWARP_ERR_BAD_ARG;
+    if (c.nv12_src && ((c.src_h & 1) || (c.src_w & 1))) return BEVWARP_ERR_BAD_ARG;
+    const Image s = c.src_image(), y = c.y_image(), uv = c.uv_image(), dy = c.dst_y_image(), duv = c.dst_uv_image();
+    if (c.nv12_src ? (layout_status(y, 1) != BEVWARP_OK || layout_status(uv, 2) != BEVWARP_OK) : layout_status(s, 1) != BEVWARP_OK) return BEVWARP_ERR_BAD_ARG;
+    if (layout_status(dy, 1) != BEVWARP_OK || layout_status(duv, 2) != BEVWARP_OK) return BEVWARP_ERR_BAD_ARG;
+    if (c.m_count != 1 && c.m_count != c.batch) return BEVWARP_ERR_BAD_ARG;
+    if ((c.interp != BEVWARP_NEAREST && c.interp != BEVWARP_LINEAR) || (c.rgb_order != 0 && c.rgb_order != 1)) return BEVWARP_ERR_UNSUPPORTED;
+    int st;
+    if (c.nv12_src) {
+        if ((st = source_size_status(y, c.src_w)) != BEVWARP_OK || (st = source_size_status(uv, c.src_w / 2)) != BEVWARP_OK) return st;
+    } else if ((st = source_size_status(s, c.src_w)) != BEVWARP_OK) {
+        return st;
+    }
+    if (c.batch == 0) return BEVWARP_OK;
+    const bool meets_source = c.nv12_src ? (regions_overlap(y, dy) || regions_overlap(uv, dy) || regions_overlap(y, duv) || regions_overlap(uv, duv))
+                                         : (regions_overlap(s, dy) || regions_overlap(s, duv));
+    return (meets_source || written_planes_overlap(dy, duv)) ? BEVWARP_ERR_OVERLAP : BEVWARP_OK;
+}
+inline int check_warp_to_nv12(const Nv12OutCall& c) { return c.nv12_src ? BEVWARP_ERR_BAD_ARG : check_nv12_out(c); }
+inline int check_warp_nv12_to_nv12(const Nv12OutCall& c) { return c.nv12_src ? check_nv12_out(c) : BEVWARP_ERR_BAD_ARG; }
+// Wide stores, per plane: a lane's 4 Y bytes, and its two pairs, go out as one dword each where the plane's base and both strides are
+// multiples of 4 (the frame stride counts even for a single frame).
+inline bool nv12_out_wide_stores_ok(const Image& plane) { return wide_stores_ok(plane, 4); }
+
 // ---- launch geometry ---------------------------------------------------------------------------------------------------------
 struct TilePlan {
     int status;                  // BEVWARP_OK or BEVWARP_ERR_TOO_LARGE (the other fields are then meaningless)

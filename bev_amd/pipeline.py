@@ -15,6 +15,10 @@ for bit: the same kernel runs on the same bytes.
 
 `src_format="nv12"`: the host slots take what a video decoder produces -- (H * 3 / 2, W) bytes, the Y plane followed by the rows of (U, V)
 pairs -- which halves the upload, and the warp converts each tap to BGR (bev_amd.warp.warp_perspective_nv12; bevwarp_warp_nv12).
+
+`dst_format="nv12"`: the output slots are what a video encoder takes -- (dh * 3 / 2, dw) bytes, the BEV frame's Y plane followed by its rows of
+(U, V) pairs -- which halves the download and removes the writer's colour conversion; the warp converts each pixel as it stores it
+(bev_amd.warp.warp_perspective_to_nv12, warp_nv12_to_nv12; bevwarp_warp_to_nv12, bevwarp_warp_nv12_to_nv12).
 """
 import collections
 import ctypes
@@ -55,7 +59,7 @@ _H2D, _D2H = 1, 2  # hipMemcpyHostToDevice / hipMemcpyDeviceToHost
 
 class FramePipeline:
     def __init__(self, src_hw, channels, M, dsize, flags=_warp.INTER_LINEAR, depth=3, dtype=torch.uint8, planar=False, scale=1.0 / 255.0, bias=0.0,
-                 download=True, device="cuda", zero_copy_out=True, plane_dtype=torch.float32, src_format="bgr"):
+                 download=True, device="cuda", zero_copy_out=True, plane_dtype=torch.float32, src_format="bgr", dst_format="bgr"):
         """src_hw (H, W) of the decoded frames; M the forward homography (as for warpPerspective); dsize (u_size, v_size).
         download=False leaves the BEV frames on the device (results are device tensors valid until `depth` further frames
         have been submitted).  zero_copy_out (with download): the kernel stores the BEV frame straight into the pinned host
@@ -65,8 +69,12 @@ class FramePipeline:
         of the pinned host slots (warp_to_planar's out_dtype).  numpy has no bfloat16: result() hands such a host slot out as a torch
         tensor.
         src_format  "bgr" (default): interleaved (H, W, channels) frames.  "nv12": the input slots are (H * 3 / 2, W) uint8 -- the Y plane,
-        then H / 2 rows of (U, V) pairs -- and the output is the BGR BEV frame; channels must be 3, dtype uint8, H and W
-        even, and planar output is not available (ValueError)."""
+        then H / 2 rows of (U, V) pairs -- and the output is the BGR BEV frame (or, with dst_format, its NV12 form); channels must be 3, dtype uint8, H and W
+        even, and planar output is not available (ValueError).
+        dst_format  "bgr" (default): the interleaved BEV frame (or planes, with planar).  "nv12": the device and pinned output slots are
+        (dh * 3 / 2, dw) uint8 -- the BEV frame's Y plane, then dh / 2 rows of (U, V) pairs, BT.601 limited range -- from either source
+        format, with download on or off and with zero_copy_out; channels must be 3, dtype uint8, dsize even, flags INTER_NEAREST or
+        INTER_LINEAR, and planar output is not available (ValueError).  The input frames are taken as B, G, R."""
         if src_format not in ("bgr", "nv12"):
             raise ValueError("unsupported src_format %r (\"bgr\", \"nv12\")" % (src_format,))
         self.nv12 = src_format == "nv12"
@@ -79,6 +87,18 @@ class FramePipeline:
                 raise ValueError("src_format=\"nv12\" needs even frame sides, got %s" % (tuple(src_hw),))
             if (int(flags) & 7) not in (_warp.INTER_NEAREST, _warp.INTER_LINEAR):
                 raise ValueError("src_format=\"nv12\": INTER_NEAREST or INTER_LINEAR")
+        if dst_format not in ("bgr", "nv12"):
+            raise ValueError("unsupported dst_format %r (\"bgr\", \"nv12\")" % (dst_format,))
+        self.nv12_out = dst_format == "nv12"
+        if self.nv12_out:
+            if planar:
+                raise ValueError("dst_format=\"nv12\" writes NV12 frames only: planar=True is not available with it")
+            if int(channels) != 3 or dtype != torch.uint8:
+                raise ValueError("dst_format=\"nv12\" needs channels=3 and dtype=torch.uint8")
+            if int(dsize[0]) % 2 or int(dsize[1]) % 2 or int(dsize[0]) <= 0 or int(dsize[1]) <= 0:
+                raise ValueError("dst_format=\"nv12\" needs an even dsize, got %s" % (tuple(dsize),))
+            if (int(flags) & 7) not in (_warp.INTER_NEAREST, _warp.INTER_LINEAR):
+                raise ValueError("dst_format=\"nv12\": INTER_NEAREST or INTER_LINEAR")
         if planar and plane_dtype not in _warp._PLANE_DTYPES:
             raise ValueError("unsupported plane_dtype %s (torch.float32, torch.float16, torch.bfloat16)" % (plane_dtype,))
         if depth < 2:
@@ -90,6 +110,8 @@ class FramePipeline:
         self.plane_dtype = plane_dtype
         self.zero_copy_out = bool(zero_copy_out and download)
         out_shape = (self.C, self.dh, self.dw) if planar else (self.dh, self.dw, self.C)
+        if self.nv12_out:
+            out_shape = (self.dh * 3 // 2, self.dw)
         out_dtype = plane_dtype if planar else dtype
         in_shape = (self.H * 3 // 2, self.W) if self.nv12 else (self.H, self.W, self.C)
         self.h_in = [torch.empty(in_shape, dtype=dtype, pin_memory=True) for _ in range(depth)]
@@ -120,7 +142,18 @@ class FramePipeline:
         self._launch = []
         for slot in range(depth):
             s, d = self.d_in[slot], (self.h_out[slot] if self.zero_copy_out else self.d_out[slot])  # (pinned host memory is device-addressable)
-            if self.nv12:  # (one buffer: the (U, V) rows follow the Y rows)
+            if self.nv12_out:  # (one buffer per side: the (U, V) rows follow the Y rows)
+                dst = (d.data_ptr(), d.data_ptr() + self.dh * self.dw)
+                tail = (self.minv.data_ptr(), 1, interp)
+                if self.nv12:
+                    args = (s.data_ptr(), s.data_ptr() + self.H * self.W) + dst + (1, self.H, self.W, self.dh, self.dw, 0, self.W, 0, self.W, 0, self.dw, 0,
+                                                                                 self.dw) + tail + (None, self.s_run)
+                    self._launch.append((lib.bevwarp_warp_nv12_to_nv12, args))
+                else:
+                    args = (s.data_ptr(),) + dst + (1, self.H, self.W, self.dh, self.dw, s.numel() * esz, s.stride(0) * esz, 0, self.dw, 0, self.dw) + tail + (
+                        0, None, self.s_run)
+                    self._launch.append((lib.bevwarp_warp_to_nv12, args))
+            elif self.nv12:  # (one buffer: the (U, V) rows follow the Y rows)
                 args = (s.data_ptr(), s.data_ptr() + self.H * self.W, d.data_ptr(), 1, self.H, self.W, self.dh, self.dw, 0, self.W, 0, self.W, d.numel(),
                         d.stride(0), self.minv.data_ptr(), 1, interp, 0, None, self.s_run)
                 self._launch.append((lib.bevwarp_warp_nv12, args))
@@ -173,7 +206,12 @@ class FramePipeline:
     def _launch_py(self, slot, stream):
         """The same launch through bev_amd.warp (argument validation; used once per slot at construction)."""
         with torch.cuda.stream(stream):
-            if self.nv12:
+            if self.nv12_out and self.nv12:
+                y, uv = _warp.split_nv12(self.d_in[slot])
+                _warp.warp_nv12_to_nv12(y, uv, None, (self.dw, self.dh), flags=self.flags, out=self.d_out[slot], M_inv_device=self.minv)
+            elif self.nv12_out:
+                _warp.warp_perspective_to_nv12(self.d_in[slot], None, (self.dw, self.dh), flags=self.flags, out=self.d_out[slot], M_inv_device=self.minv)
+            elif self.nv12:
                 y, uv = _warp.split_nv12(self.d_in[slot])
                 _warp.warp_perspective_nv12(y, uv, None, (self.dw, self.dh), flags=self.flags, out=self.d_out[slot], M_inv_device=self.minv)
             elif self.planar:

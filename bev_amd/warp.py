@@ -502,6 +502,110 @@ def warp_nv12_to_planar(y, uv, M, dsize, scale=1.0 / 255.0, bias=0.0, flags=INTE
     return d4[0] if y.dim() == 2 else d4
 
 
+def _nv12_out_format(who, flags, dsize):
+    """What the warps into NV12 check before they look at a tensor: (interp, dw, dh)."""
+    interp = int(flags) & 7
+    if interp not in (INTER_NEAREST, INTER_LINEAR):
+        raise ValueError("unsupported interpolation flag %d (%s: INTER_NEAREST, INTER_LINEAR)" % (interp, who))
+    dw, dh = int(dsize[0]), int(dsize[1])
+    if dw <= 0 or dh <= 0 or dw % 2 or dh % 2:
+        raise ValueError("%s: an NV12 frame has even sides, got dsize %s" % (who, (dw, dh)))
+    return interp, dw, dh
+
+
+def _nv12_dst(who, out, device, B, dh, dw, single):
+    """The destination planes of a warp into NV12 as the ABI writes them -- (B, dh, dw) and (B, dh / 2, dw / 2, 2) views, strides passed
+    through -- and what the call returns: `out` itself, or a new joined (dh * 3 / 2, dw) / (B, dh * 3 / 2, dw) buffer."""
+    if out is None:
+        out = torch.empty((dh * 3 // 2, dw) if single else (B, dh * 3 // 2, dw), dtype=torch.uint8, device=device)
+        y, uv = split_nv12(out)
+    elif isinstance(out, (tuple, list)):
+        if len(out) != 2:
+            raise ValueError("%s: out is a joined (dh * 3 / 2, dw) buffer or a (y, uv) pair" % who)
+        y, uv = out
+    else:
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.dim() not in (2, 3) or tuple(out.shape[-2:]) != (dh * 3 // 2, dw):
+            raise ValueError("%s: a joined out must be a uint8 tensor (..., %d, %d)" % (who, dh * 3 // 2, dw))
+        y, uv = split_nv12(out)
+    for name, t in (("y", y), ("uv", uv)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.device != device:
+            raise ValueError("%s: the %s plane of out must be a uint8 tensor on %s" % (who, name, device))
+    if y.dim() not in (2, 3) or uv.dim() != y.dim() + 1:
+        raise ValueError("%s: out planes must be y (dh, dw) or (B, dh, dw) and uv (dh/2, dw/2, 2) or (B, dh/2, dw/2, 2)" % who)
+    y3, uv4 = (y[None], uv[None]) if y.dim() == 2 else (y, uv)
+    if tuple(y3.shape) != (B, dh, dw) or tuple(uv4.shape) != (B, dh // 2, dw // 2, 2):
+        raise ValueError("%s: out planes must be %s and %s; got y %s, uv %s" % (who, (B, dh, dw), (B, dh // 2, dw // 2, 2), tuple(y3.shape), tuple(uv4.shape)))
+    if y3.stride(2) != 1 or uv4.stride(3) != 1 or uv4.stride(2) != 2:
+        raise ValueError("%s: the last dimension of out's y and of its uv (pairs, and the pairs of a row) must be contiguous" % who)
+    return y3, uv4, out
+
+
+def warp_perspective_to_nv12(src, M, dsize, flags=INTER_LINEAR, border_value=None, out=None, M_inv_device=None, rgb=False):
+    """warp_perspective of 8-bit BGR frames, written as the NV12 frame a video encoder takes: bit for bit
+
+        BGR->NV12(warp_perspective(src, M, dsize, flags, border_value))               (rgb=True: the frames are R, G, B)
+
+    in one pass, without the warped BGR frame (include/bevwarp.h, bevwarp_warp_to_nv12: OpenCV's 8-bit BT.601 limited-range RGB -> YUV 4:2:0
+    fixed point, restated from memory, parity unpinned; a (U, V) pair is that of its 2 x 2 block's top-left pixel, nothing is averaged).
+
+    src      (B, H, W, 3) or (H, W, 3) uint8 CUDA tensor, channels-last, rows contiguous.
+    M, M_inv_device   as warp_perspective; flags INTER_LINEAR (default) or INTER_NEAREST, optionally | WARP_INVERSE_MAP.
+    dsize    (width, height), both even.
+    border_value   scalar or 3 values in the SOURCE's channel order: a pixel, converted like any other ((0, 0, 0) gives (16, 128, 128)).
+    out      a joined uint8 buffer (dh * 3 / 2, dw) or (B, dh * 3 / 2, dw) -- the Y rows, then the rows of (U, V) pairs; split with
+             split_nv12 -- or a (y, uv) pair of planes, (B, dh, dw) and (B, dh / 2, dw / 2, 2), whose strides are passed through (the uv
+             base and strides must be even): exactly what warp_perspective_nv12 takes as its source.
+    Returns `out` if given, otherwise a new joined buffer.  Asynchronous on the current stream.  No verdict tables, no plan cache."""
+    interp, dw, dh = _nv12_out_format("warp_perspective_to_nv12", flags, dsize)
+    if not isinstance(src, torch.Tensor) or not src.is_cuda or src.dtype != torch.uint8:
+        raise ValueError("warp_perspective_to_nv12 needs a uint8 CUDA (HIP) tensor; src is %s" % (getattr(src, "dtype", type(src)),))
+    if src.dim() not in (3, 4) or src.shape[-1] != 3:
+        raise ValueError("src must be (B, H, W, 3) or (H, W, 3)")
+    s4 = src[None] if src.dim() == 3 else src
+    if s4.stride(3) != 1 or s4.stride(2) != 3:
+        s4 = s4.contiguous()
+    B, H, W, _ = s4.shape
+    if M_inv_device is None:
+        M_inv_device = device_inverse(M, s4.device, inverse_given=bool(int(flags) & WARP_INVERSE_MAP))
+    n_m = _check_minv(M_inv_device, s4.device, B)
+    y3, uv4, ret = _nv12_dst("warp_perspective_to_nv12", out, s4.device, B, dh, dw, src.dim() == 3)
+    bv = _border(border_value, 3)
+    stream = torch.cuda.current_stream(s4.device).cuda_stream
+    with torch.cuda.device(s4.device):
+        st = _lib.load().bevwarp_warp_to_nv12(s4.data_ptr(), y3.data_ptr(), uv4.data_ptr(), B, H, W, dh, dw, s4.stride(0), s4.stride(1), y3.stride(0),
+                                              y3.stride(1), uv4.stride(0), uv4.stride(1), M_inv_device.data_ptr(), n_m, interp, 1 if rgb else 0,
+                                              None if bv is None else bv.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(stream))
+    _lib.check(st)
+    return ret
+
+
+def warp_nv12_to_nv12(y, uv, M, dsize, flags=INTER_LINEAR, border_value=None, out=None, M_inv_device=None):
+    """A video decoder's NV12 frames warped straight to the NV12 frames a video encoder takes, in one launch: bit for bit
+
+        BGR->NV12(warp_perspective_nv12(y, uv, M, dsize, flags, border_value))
+
+    with no BGR frame in memory on either side (include/bevwarp.h, bevwarp_warp_nv12_to_nv12).  This is not a warp of the Y and UV planes:
+    every tap is converted to BGR, blended there, and the blended pixel converted back.
+
+    y, uv, M, flags, M_inv_device   as warp_perspective_nv12.  dsize (width, height), both even.
+    border_value   scalar or 3 values in B, G, R order: a pixel, converted like any other.
+    out      as warp_perspective_to_nv12: a joined buffer or a (y, uv) pair.
+    Returns `out` if given, otherwise a new joined buffer.  Asynchronous on the current stream.  No verdict tables, no plan cache."""
+    interp, dw, dh = _nv12_out_format("warp_nv12_to_nv12", flags, dsize)
+    y3, uv4, M_inv_device, n_m = _nv12_source("warp_nv12_to_nv12", y, uv, M, flags, M_inv_device)
+    B, H, W = y3.shape
+    dy3, duv4, ret = _nv12_dst("warp_nv12_to_nv12", out, y3.device, B, dh, dw, y.dim() == 2)
+    bv = _border(border_value, 3)
+    stream = torch.cuda.current_stream(y3.device).cuda_stream
+    with torch.cuda.device(y3.device):
+        st = _lib.load().bevwarp_warp_nv12_to_nv12(y3.data_ptr(), uv4.data_ptr(), dy3.data_ptr(), duv4.data_ptr(), B, H, W, dh, dw, y3.stride(0), y3.stride(1),
+                                                   uv4.stride(0), uv4.stride(1), dy3.stride(0), dy3.stride(1), duv4.stride(0), duv4.stride(1),
+                                                   M_inv_device.data_ptr(), n_m, interp, None if bv is None else bv.ctypes.data_as(ctypes.c_void_p),
+                                                   ctypes.c_void_p(stream))
+    _lib.check(st)
+    return ret
+
+
 def footprint(src_hw, M, dsize, batch=None, flags=INTER_LINEAR, device="cuda"):
     """Exact count of distinct in-bounds source pixels the warp reads, per frame.
     Returns (counts int64 tensor [n], touched uint8 tensor [n, H, W])."""

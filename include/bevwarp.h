@@ -24,6 +24,11 @@
  *   bevwarp_warp_nv12_planes  the same decoder frames, vis_homo.py:86-89, written straight as the detector-input planes of
  *                             bevwarp_warp_planes (float32, float16 or bfloat16): decoder -> BEV -> detector input in one launch,
  *                             with neither the converted frame nor the 8-bit BEV frame in memory
+ *   bevwarp_warp_to_nv12    cv2.warpPerspective(img, H_bev_img, (u_size, v_size)) + `writer.write(bev)`, vis_homo.py:109-111 and
+ *                             bev/io/utils.py:89-99, without the BGR -> YUV 4:2:0 pass a video writer hides inside write(): the warp
+ *                             stores the BEV frame as NV12, what an encoder takes (the tracker tools read the encoded bev.avi)
+ *   bevwarp_warp_nv12_to_nv12  the same egress from a decoder's NV12 frames, vis_homo.py:85-111 and bev/io/utils.py:89-99:
+ *                             decoder -> BEV -> encoder in one launch, with no BGR frame in memory on either side
  *   bevwarp_composite       composite_reg_img(bg, fg, fg_mask), bev/tool/compo.py:5-24 (the blend after the three warps
  *                             of composite_bev_img, :26-49)
  *   bevwarp_warp_composite  composite_bev_img(bg, fg, fg_mask, ...), bev/tool/compo.py:26-49: the three warps and the blend
@@ -292,6 +297,65 @@ int bevwarp_warp_nv12_planes(const void *y, const void *uv, void *dst, int batch
                              const double *M_inv, int m_count, int interp, int rgb_order,
                              const double *border_value /*HOST, 3 or NULL*/, const double *scale /*HOST, 3 or NULL = 1*/,
                              const double *bias /*HOST, 3 or NULL = 0*/, int plane_dtype, void *stream);
+
+/*
+ * The warp written as NV12 for a video encoder, in one pass: stands in for cv2.warpPerspective(img, H_bev_img, (u_size, v_size)) followed by
+ * `writer.write(bev)`, vis_homo.py:109-111 and bev/io/utils.py:89-99, whose writer converts every BGR frame to YUV 4:2:0 on the host.
+ * Bit for bit
+ *   (dst_y, dst_uv) = BGR->NV12( bevwarp_warp(src, ..., 3 channels, BEVWARP_U8, interp, border_value) )
+ * and the warped BGR / RGB frame is never in memory.  With p the 8-bit warped pixel and R, G, B its channels as rgb_order names them:
+ *       Y = ( 269484 R + 528482 G + 102760 B + (16  << 20) + (1 << 19)) >> 20
+ *       U = (-155188 R - 305135 G + 460324 B + (128 << 20) + (1 << 19)) >> 20
+ *       V = ( 460324 R - 385875 G -  74448 B + (128 << 20) + (1 << 19)) >> 20              (int32, >> arithmetic)
+ *       dst_y [b][y][x]         = Y(p[b][y][x])                              every x, y
+ *       dst_uv[b][y / 2][x / 2] = (U(p[b][y][x]), V(p[b][y][x]))             x even and y even only: no averaging over the 2 x 2 block
+ *   conversion      OpenCV's 8-bit RGB -> YUV 4:2:0 two-plane path: BT.601, limited range, 20-bit fixed point (restated from memory like the
+ *                   rest of the warp: parity with OpenCV is unpinned).  Over all 2^24 pixels the sums span 17,301,504 ... 246,986,634 (Y)
+ *                   and 17,359,651 ... 252,124,636 (U, V), Y spans 16 ... 235 and U, V span 16 ... 240: int32 holds every sum and no
+ *                   value is clamped.
+ *   src             device, 8-bit, 3 channels, src_h x src_w pixels.  rgb_order 0: its pixels are B, G, R (what VideoCapture gives); 1: R, G, B.
+ *   interp          BEVWARP_NEAREST | BEVWARP_LINEAR; maps, tap guards and blend are bevwarp_warp's.
+ *   border_value    HOST, 3 doubles in the SOURCE pixel's channel order, or NULL = 0: a pixel value like any other, converted with the
+ *                   pixel -- (0, 0, 0) gives Y, U, V = (16, 128, 128).
+ *   dst_y, dst_uv   device; dst_h and dst_w are even.  The layout is bevwarp_warp_nv12's source layout, so a frame written here is accepted
+ *                   there: dst_h rows of dst_w Y bytes (y_row_stride >= dst_w), dst_h / 2 rows of dst_w / 2 (U, V) byte pairs -- dst_w
+ *                   bytes per row; the uv base, uv_row_stride and uv_frame_stride are even.  One (dst_h * 3 / 2) x dst_w buffer with
+ *                   dst_uv = dst_y + dst_h * y_row_stride, and two allocations, both fit.  A plane whose base and both strides are
+ *                   multiples of 4 is written with 4-byte stores (each plane by its own layout).
+ * Status, in this order: BEVWARP_ERR_BAD_ARG (null pointer, non-positive size, odd dst_w or dst_h, a row stride below 3 src_w or below
+ * dst_w for either destination plane, frames that overlap their successors, an odd uv base / row stride / frame stride, m_count not 1 or
+ * batch); BEVWARP_ERR_UNSUPPORTED (interp other than nearest / linear; rgb_order outside {0, 1}); BEVWARP_ERR_TOO_LARGE (the source limits
+ * of bevwarp_warp); BEVWARP_ERR_OVERLAP (either destination plane shares bytes with the source, by bevwarp_warp's rule, or the two
+ * destination planes share bytes with each other -- both are written; the single-buffer layout is adjacent, not overlapping);
+ * BEVWARP_ERR_TOO_LARGE again for a destination side > 2^20; BEVWARP_ERR_NOT_FINITE (border_value).  batch == 0 is BEVWARP_OK and
+ * launches nothing.
+ * Warping the Y and the UV plane separately (two bevwarp_warp calls of 1 and 2 channels) is NOT this: it blends in YUV.
+ */
+int bevwarp_warp_to_nv12(const void *src, void *dst_y, void *dst_uv, int batch, int src_h, int src_w, int dst_h, int dst_w,
+                         int64_t src_frame_stride, int64_t src_row_stride,
+                         int64_t y_frame_stride, int64_t y_row_stride, int64_t uv_frame_stride, int64_t uv_row_stride,
+                         const double *M_inv, int m_count, int interp, int rgb_order,
+                         const double *border_value /*HOST, 3 or NULL*/, void *stream);
+
+/*
+ * The same egress from a video decoder's NV12 frames: `video.read()` -> cv2.warpPerspective -> `writer.write(bev)`, vis_homo.py:85-111 and
+ * bev/io/utils.py:89-99, in one launch with no BGR frame in memory on either side.  Bit for bit
+ *   (dst_y, dst_uv) = BGR->NV12( bevwarp_warp_nv12(y, uv, ..., interp, rgb_order = 0, border_value) )
+ * with bevwarp_warp_to_nv12's conversion and destination and bevwarp_warp_nv12's source (even src_h and src_w, every tap converted to B, G, R
+ * before the blend).  border_value: HOST, 3 doubles in B, G, R order, or NULL = 0; converted with the pixel.  The intermediate channel
+ * order changes nothing else.
+ * Status, in this order: BEVWARP_ERR_BAD_ARG (null pointer, non-positive size, odd dst_w, dst_h, src_w or src_h, a row stride below src_w
+ * for either source plane or below dst_w for either destination plane, frames that overlap their successors, an odd uv base / row stride /
+ * frame stride -- source and destination alike --, m_count not 1 or batch); BEVWARP_ERR_UNSUPPORTED (interp other than nearest / linear);
+ * BEVWARP_ERR_TOO_LARGE (either source plane, as bevwarp_warp_nv12); BEVWARP_ERR_OVERLAP (either destination plane shares bytes with either
+ * source plane, or the destination planes with each other; the source planes may overlap each other); BEVWARP_ERR_TOO_LARGE again for a
+ * destination side > 2^20; BEVWARP_ERR_NOT_FINITE (border_value).  batch == 0 is BEVWARP_OK and launches nothing.
+ */
+int bevwarp_warp_nv12_to_nv12(const void *y, const void *uv, void *dst_y, void *dst_uv, int batch, int src_h, int src_w,
+                              int dst_h, int dst_w, int64_t y_frame_stride, int64_t y_row_stride, int64_t uv_frame_stride,
+                              int64_t uv_row_stride, int64_t dst_y_frame_stride, int64_t dst_y_row_stride,
+                              int64_t dst_uv_frame_stride, int64_t dst_uv_row_stride, const double *M_inv, int m_count,
+                              int interp, const double *border_value /*HOST, 3 (B, G, R) or NULL*/, void *stream);
 
 /*
  * out[i] = uint8(min(round_half_even(fg[i] * (mask[i] / 255) + bg[i] * (1 - mask[i] / 255)), 255)) for i in [0, n), computed in
