@@ -31,35 +31,39 @@ int launched(hipError_t e) { return e == hipSuccess ? BEVWARP_OK : hip_fail(e); 
 using namespace bevwarp;
 using namespace bevwarp::plan;
 
-// a call's and a plan's fields in the row kernel's arguments
-void copy_call(WarpArgs& a, const WarpCall& c) {
-    memset(&a, 0, sizeof(a));
-    a.src = (const uint8_t*)c.src.base, a.dst = (uint8_t*)c.dst.base, a.minv = c.minv;
-    a.src_fs = c.src.fs, a.src_rs = c.src.rs, a.dst_fs = c.dst.fs, a.dst_rs = c.dst.rs;
-    a.src_h = c.src.h, a.src_w = c.src.w, a.dst_h = c.dst.h, a.dst_w = c.dst.w;
-    a.m_stride = c.m_count == 1 ? 0 : 9;
-}
+// a plan's fields in the row kernel's arguments
 void copy_plan(WarpArgs& a, const TilePlan& p) {
     a.bw0 = p.bw0, a.tiles_x = p.tiles_x, a.tiles_per_frame = p.tiles_per_frame;
     a.tpf_magic = p.tpf_magic, a.tx_magic = p.tx_magic, a.bw0_magic = p.bw0_magic;
     a.tile_h = p.tile_h, a.total_tiles = p.total_tiles, a.chunk = p.chunk, a.stagger = p.stagger, a.tail_split = p.tail_split;
 }
-// The shared frame's part (flat_frame.h) of the border, bicubic and NV12 kernels' arguments, which the caller has zeroed: the
-// destination, the matrices and plan_border's grid.  (dst_vec_ok follows each entry point's own layout rule.)
-void fill_frame(FrameArgs& a, const Frames& dst, const double* minv, int m_count, const TilePlan& p) {
-    a.dst = (uint8_t*)dst.base, a.minv = minv;
-    a.dst_fs = dst.fs, a.dst_rs = dst.rs, a.dst_h = dst.h, a.dst_w = dst.w;
-    a.m_stride = m_count == 1 ? 0 : 9;
+// What the flat-grid entry points (border, bicubic, NV12, NV12 planes, into NV12) share: the checks, plan_border's grid, and in the zeroed
+// arguments the shared frame's part (flat_frame.h) -- the first written image, the matrices, the grid -- and the source's sides.
+// items = 0: nothing to launch, the status is the call's.  (dst_vec_ok follows each entry point's own layout rule.)
+template <class Args>
+int flat_grid_args(const Call& c, Args& a, int64_t& items) {
+    items = 0;
+    const int st = plan::check_call(c);
+    if (st != BEVWARP_OK || c.batch == 0) return st;
+    const TilePlan p = plan::plan_border(c.batch, c.dst_h, c.dst_w, kBorderTileW, kBorderTileH);
+    if (p.status != BEVWARP_OK) return p.status;
+    memset(&a, 0, sizeof(a));
+    const Image& d = c.writes[0].im;
+    a.dst = (uint8_t*)d.base, a.minv = c.minv;
+    a.dst_fs = d.fs, a.dst_rs = d.rs, a.dst_h = c.dst_h, a.dst_w = c.dst_w;
+    a.m_stride = c.m_count == 1 ? 0 : 9;
     a.bw0 = p.bw0, a.tiles_x = p.tiles_x, a.tiles_per_frame = p.tiles_per_frame;
     a.tpf_magic = p.tpf_magic, a.tx_magic = p.tx_magic, a.bw0_magic = p.bw0_magic;
-}
-// ... and the NV12 kernels' own part: the frame, the two source planes and the border value, `bu` = its bytes per SAMPLED channel
-void fill_nv12(Nv12Args& a, const Nv12Call& c, const TilePlan& p, const uint8_t* bu) {
-    fill_frame(a, {c.dst, c.dst_h, c.dst_w, c.dst_fs, c.dst_rs}, c.minv, c.m_count, p);
-    a.y = (const uint8_t*)c.y, a.uv = (const uint8_t*)c.uv;
-    a.y_fs = c.y_fs, a.y_rs = c.y_rs, a.uv_fs = c.uv_fs, a.uv_rs = c.uv_rs;
     a.src_h = c.src_h, a.src_w = c.src_w;
-    a.border = (uint32_t)bu[0] | ((uint32_t)bu[1] << 8) | ((uint32_t)bu[2] << 16);
+    items = p.total_tiles;
+    return BEVWARP_OK;
+}
+// ... and the NV12 kernels' source: the two planes the call reads
+template <class Args>
+void fill_nv12_source(Args& a, const Call& c) {
+    const Image &y = c.reads[0].im, &uv = c.reads[1].im;
+    a.y = (const uint8_t*)y.base, a.uv = (const uint8_t*)uv.base;
+    a.y_fs = y.fs, a.y_rs = y.rs, a.uv_fs = uv.fs, a.uv_rs = uv.rs;
 }
 // border_value (HOST, `channels` doubles or NULL) as the kernels take it: float32, and saturate_cast<uchar> (round half to even, clamp)
 template <class U8>
@@ -73,6 +77,12 @@ int border_values(const double* border_value, int channels, float* f, U8* u8) {
     }
     return BEVWARP_OK;
 }
+// ... and of the NV12 entry points' 3 channels: the 8-bit values (bu[4]), which the kernels take packed, byte k = channel k
+int border_bytes(const double* border_value, uint8_t* bu) {
+    float bf[4];
+    return border_values(border_value, 3, bf, bu);
+}
+uint32_t packed3(const uint8_t* b) { return (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16); }
 }  // namespace
 
 #ifdef BEVWARP_CLOCK
@@ -129,36 +139,43 @@ int bevwarp_invert_homography(const double* S, double* D, int n) {
 
 namespace {
 // bevwarp_warp and its planar and verdict-table variants (plane_format: WarpArgs::planar of a planar call)
-int warp_impl(const WarpCall& c, int plane_format = kPlaneF32) {
-    const int st = plan::check_warp(c);
+int warp_impl(const Call& c, int channels, int dtype, int interp, const double* border_value, void* stream, int plane_format = 0, const double* scale = nullptr,
+              const double* bias = nullptr, void* classes = nullptr, int classes_mode = 0) {
+    const int st = plan::check_call(c);
     if (st != BEVWARP_OK || c.batch == 0) return st;
-    const TilePlan p = plan::plan_rows(c.batch, c.dst.h, c.dst.w, c.dtype, tile_width(c.dtype), rows_per_pass(), resident_workgroups(c.dtype, c.channels, c.interp));
+    const TilePlan p = plan::plan_rows(c.batch, c.dst_h, c.dst_w, dtype, tile_width(dtype), rows_per_pass(), resident_workgroups(dtype, channels, interp));
     if (p.status != BEVWARP_OK) return p.status;
 
+    const Image& s = c.reads[0].im;
+    const WrittenImage& d = c.writes[0];
     WarpArgs a;
-    copy_call(a, c);
+    memset(&a, 0, sizeof(a));
+    a.src = (const uint8_t*)s.base, a.dst = (uint8_t*)d.im.base, a.minv = c.minv;
+    a.src_fs = s.fs, a.src_rs = s.rs, a.dst_fs = d.im.fs, a.dst_rs = d.im.rs;
+    a.src_h = c.src_h, a.src_w = c.src_w, a.dst_h = c.dst_h, a.dst_w = c.dst_w;
+    a.m_stride = c.m_count == 1 ? 0 : 9;
     a.batch = c.batch;
     copy_plan(a, p);
-    a.dst_vec_ok = plan::call_wide_stores_ok(c);
-    if (c.planar) {
+    a.dst_vec_ok = plan::wide_stores_ok(d, plan::store_align(dtype, channels, d.planar, d.elem));
+    if (d.planar) {
         a.planar = plane_format;
-        a.dst_ps = c.plane_stride;
+        a.dst_ps = d.plane_stride;
         for (int k = 0; k < 4; k++) {
-            const double sc = (c.scale && k < c.channels) ? c.scale[k] : 1.0, bi = (c.bias && k < c.channels) ? c.bias[k] : 0.0;
+            const double sc = (scale && k < channels) ? scale[k] : 1.0, bi = (bias && k < channels) ? bias[k] : 0.0;
             if (!isfinite(sc) || !isfinite(bi)) return BEVWARP_ERR_NOT_FINITE;
             a.pscale[k] = (float)sc;
             a.pbias[k] = (float)bi;
         }
     }
-    if (border_values(c.border_value, c.channels, a.bval_f, a.bval_u8) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
-    if (c.classes) {
-        if ((uintptr_t)c.classes % 4) return BEVWARP_ERR_BAD_ARG;
-        if (c.classes_mode == BEVWARP_CLASSES_FILL)
-            a.classify_out = (uint32_t*)c.classes;
+    if (border_values(border_value, channels, a.bval_f, a.bval_u8) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
+    if (classes) {
+        if ((uintptr_t)classes % 4) return BEVWARP_ERR_BAD_ARG;
+        if (classes_mode == BEVWARP_CLASSES_FILL)
+            a.classify_out = (uint32_t*)classes;
         else
-            a.tile_class = (const uint32_t*)c.classes;
+            a.tile_class = (const uint32_t*)classes;
     }
-    return launched(launch_warp(a, c.dtype, c.channels, c.interp, (hipStream_t)c.stream));
+    return launched(launch_warp(a, dtype, channels, interp, (hipStream_t)stream));
 }
 }  // namespace
 
@@ -170,8 +187,9 @@ int bevwarp_warp(const void* src, void* dst, int batch, int src_h, int src_w, in
     if (interp == BEVWARP_CUBIC)  // the bicubic kernel has every border, the constant one included
         return bevwarp_warp_border(src, dst, batch, src_h, src_w, dst_h, dst_w, channels, src_frame_stride, src_row_stride, dst_frame_stride, dst_row_stride,
                                    M_inv, m_count, dtype, interp, BEVWARP_BORDER_CONSTANT, border_value, stream);
-    return warp_impl({{src, src_h, src_w, src_frame_stride, src_row_stride}, {dst, dst_h, dst_w, dst_frame_stride, dst_row_stride}, batch, channels, dtype, interp,
-                      M_inv, m_count, border_value, stream});
+    return warp_impl(plan::warp_call({src, src_frame_stride, src_row_stride}, {dst, dst_frame_stride, dst_row_stride}, {batch, src_h, src_w, dst_h, dst_w, m_count, M_inv},
+                                     channels, dtype, interp, false),
+                     channels, dtype, interp, border_value, stream);
 }
 
 int bevwarp_warp_border(const void* src, void* dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int channels,
@@ -183,65 +201,55 @@ int bevwarp_warp_border(const void* src, void* dst, int batch, int src_h, int sr
                             M_inv, m_count, dtype, interp, border_value, stream);
     if (border_mode < BEVWARP_BORDER_CONSTANT || border_mode > BEVWARP_BORDER_TRANSPARENT) return BEVWARP_ERR_UNSUPPORTED;  // (BORDER_ISOLATED too)
     // (border_value is read by no mode but the constant one, as in OpenCV)
-    WarpCall c = {{src, src_h, src_w, src_frame_stride, src_row_stride}, {dst, dst_h, dst_w, dst_frame_stride, dst_row_stride}, batch, channels, dtype, interp,
-                  M_inv, m_count, nullptr, stream};
-    c.cubic_ok = true;
-    const int st = plan::check_warp(c);
-    if (st != BEVWARP_OK || batch == 0) return st;
-    const TilePlan p = plan::plan_border(batch, dst_h, dst_w, kBorderTileW, kBorderTileH);
-    if (p.status != BEVWARP_OK) return p.status;
+    const Call c = plan::warp_call({src, src_frame_stride, src_row_stride}, {dst, dst_frame_stride, dst_row_stride}, {batch, src_h, src_w, dst_h, dst_w, m_count, M_inv},
+                                   channels, dtype, interp, true);
     CubicArgs a;  // (the border kernel takes its BorderArgs part)
-    memset(&a, 0, sizeof(a));
-    fill_frame(a, c.dst, c.minv, c.m_count, p);
-    a.src = (const uint8_t*)src, a.src_fs = src_frame_stride, a.src_rs = src_row_stride, a.src_h = src_h, a.src_w = src_w;
+    int64_t items;
+    const int st = flat_grid_args(c, a, items);
+    if (!items) return st;
+    a.src = (const uint8_t*)src, a.src_fs = src_frame_stride, a.src_rs = src_row_stride;
     // the 4 taps of a bicubic window reach one index beyond a saturated one: a period plan of their own
     const plan::BorderPeriod px = cubic ? cubic::window_period(border_mode, src_w) : plan::border_period(border_mode, src_w);
     const plan::BorderPeriod py = cubic ? cubic::window_period(border_mode, src_h) : plan::border_period(border_mode, src_h);
     a.per_x = px.per, a.off_x = px.off, a.mag_x = px.mag;
     a.per_y = py.per, a.off_y = py.off, a.mag_y = py.mag;
-    a.dst_vec_ok = plan::wide_stores_ok(c.dst_image(), plan::store_align(dtype, channels, false));
-    a.src_vec_ok = plan::pixel_loads_ok(c.src_image(), plan::pixel_load_align(dtype, channels));
-    if (!cubic) return launched(launch_warp_border(a, dtype, channels, interp, border_mode, p.total_tiles, (hipStream_t)stream));
+    a.dst_vec_ok = plan::wide_stores_ok(c.writes[0], plan::store_align(dtype, channels, false));
+    a.src_vec_ok = plan::pixel_loads_ok(c.reads[0].im, plan::pixel_load_align(dtype, channels));
+    if (!cubic) return launched(launch_warp_border(a, dtype, channels, interp, border_mode, items, (hipStream_t)stream));
     if (border_values(border_mode == BEVWARP_BORDER_CONSTANT ? border_value : nullptr, channels, a.cv_f, a.cv_u8) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
-    return launched(launch_warp_cubic(a, dtype, channels, border_mode, p.total_tiles, (hipStream_t)stream));
+    return launched(launch_warp_cubic(a, dtype, channels, border_mode, items, (hipStream_t)stream));
 }
 
 int bevwarp_warp_nv12(const void* y, const void* uv, void* dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int64_t y_frame_stride,
                       int64_t y_row_stride, int64_t uv_frame_stride, int64_t uv_row_stride, int64_t dst_frame_stride, int64_t dst_row_stride,
                       const double* M_inv, int m_count, int interp, int rgb_order, const double* border_value, void* stream) {
-    const Nv12Call c = {y, uv, dst, batch, src_h, src_w, dst_h, dst_w, y_frame_stride, y_row_stride, uv_frame_stride, uv_row_stride,
-                        dst_frame_stride, dst_row_stride, M_inv, m_count, interp, rgb_order};
-    const int st = plan::check_warp_nv12(c);
-    if (st != BEVWARP_OK || batch == 0) return st;
-    const TilePlan p = plan::plan_border(batch, dst_h, dst_w, kBorderTileW, kBorderTileH);
-    if (p.status != BEVWARP_OK) return p.status;
-    float bf[4];
-    uint8_t bu[4];  // (in the destination's channel order, as given: the border value is not converted)
-    if (border_values(border_value, 3, bf, bu) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
+    const Call c = plan::nv12_call({y, y_frame_stride, y_row_stride}, {uv, uv_frame_stride, uv_row_stride}, {dst, dst_frame_stride, dst_row_stride},
+                                   {batch, src_h, src_w, dst_h, dst_w, m_count, M_inv}, interp, rgb_order);
     Nv12Args a;
-    memset(&a, 0, sizeof(a));
-    fill_nv12(a, c, p, bu);
-    a.dst_vec_ok = plan::wide_stores_ok(c.dst_image(), plan::store_align(BEVWARP_U8, 3, false));
-    return launched(launch_warp_nv12(a, interp, rgb_order, p.total_tiles, (hipStream_t)stream));
+    int64_t items;
+    const int st = flat_grid_args(c, a, items);
+    if (!items) return st;
+    uint8_t bu[4];  // (in the destination's channel order, as given: the border value is not converted)
+    if (border_bytes(border_value, bu) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
+    fill_nv12_source(a, c);
+    a.border = packed3(bu);
+    a.dst_vec_ok = plan::wide_stores_ok(c.writes[0], plan::store_align(BEVWARP_U8, 3, false));
+    return launched(launch_warp_nv12(a, interp, rgb_order, items, (hipStream_t)stream));
 }
 
 int bevwarp_warp_nv12_planes(const void* y, const void* uv, void* dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int64_t y_frame_stride,
                              int64_t y_row_stride, int64_t uv_frame_stride, int64_t uv_row_stride, int64_t dst_frame_stride, int64_t dst_plane_stride,
                              int64_t dst_row_stride, const double* M_inv, int m_count, int interp, int rgb_order, const double* border_value,
                              const double* scale, const double* bias, int plane_dtype, void* stream) {
-    const Nv12PlanesCall c = {{y, uv, dst, batch, src_h, src_w, dst_h, dst_w, y_frame_stride, y_row_stride, uv_frame_stride, uv_row_stride,
-                               dst_frame_stride, dst_row_stride, M_inv, m_count, interp, rgb_order},
-                              dst_plane_stride, plane_dtype};
-    const int st = plan::check_warp_nv12_planes(c);
-    if (st != BEVWARP_OK || batch == 0) return st;
-    const TilePlan p = plan::plan_border(batch, dst_h, dst_w, kBorderTileW, kBorderTileH);
-    if (p.status != BEVWARP_OK) return p.status;
-    float bf[4];
-    uint8_t bu[4];  // (in the destination's channel order, as given)
-    if (border_values(border_value, 3, bf, bu) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
+    const Call c = plan::nv12_planes_call({y, y_frame_stride, y_row_stride}, {uv, uv_frame_stride, uv_row_stride}, {dst, dst_frame_stride, dst_row_stride},
+                                          dst_plane_stride, {batch, src_h, src_w, dst_h, dst_w, m_count, M_inv}, interp, rgb_order, plane_dtype);
     Nv12PlanesArgs a;
-    memset(&a, 0, sizeof(a));
-    a.dst_vec_ok = plan::nv12_planes_wide_stores_ok(c);
+    int64_t items;
+    const int st = flat_grid_args(c, a, items);
+    if (!items) return st;
+    uint8_t bu[4];  // (in the destination's channel order, as given)
+    if (border_bytes(border_value, bu) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
+    a.dst_vec_ok = plan::wide_stores_ok(c.writes[0], plan::store_align(BEVWARP_U8, 3, true, c.writes[0].elem));
     a.plane = plane_dtype == BEVWARP_F32 ? kPlaneF32 : (plane_dtype == BEVWARP_F16 ? kPlaneF16 : kPlaneBF16);
     // the kernel samples B, G, R: sampled channel k is the destination's channel k (BGR) or 2 - k (RGB), with that channel's plane,
     // scale, bias and border value -- the channel order is nothing but this table
@@ -254,34 +262,33 @@ int bevwarp_warp_nv12_planes(const void* y, const void* uv, void* dst, int batch
         a.ch_off[k] = (int64_t)ch * dst_plane_stride;
         bs[k] = bu[ch];
     }
-    fill_nv12(a, c.s, p, bs);
-    return launched(launch_warp_nv12_planes(a, interp, p.total_tiles, (hipStream_t)stream));
+    fill_nv12_source(a, c);
+    a.border = packed3(bs);
+    return launched(launch_warp_nv12_planes(a, interp, items, (hipStream_t)stream));
 }
 
 }  // extern "C"
 
 namespace {
-// bevwarp_warp_to_nv12 and bevwarp_warp_nv12_to_nv12: the checks, plan_border's grid, the border pixel, one launch
-int warp_nv12_out_impl(const Nv12OutCall& c, const double* border_value, void* stream) {
-    const int st = c.nv12_src ? plan::check_warp_nv12_to_nv12(c) : plan::check_warp_to_nv12(c);
-    if (st != BEVWARP_OK || c.batch == 0) return st;
-    const TilePlan p = plan::plan_border(c.batch, c.dst_h, c.dst_w, kBorderTileW, kBorderTileH);
-    if (p.status != BEVWARP_OK) return p.status;
-    float bf[4];
-    uint8_t bu[4];  // (in the warped pixel's channel order: a pixel value, converted by the kernel like any other)
-    if (border_values(border_value, 3, bf, bu) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
+// bevwarp_warp_to_nv12 and bevwarp_warp_nv12_to_nv12 (the call reads two images): the checks, plan_border's grid, the border pixel, one launch
+int warp_nv12_out_impl(const Call& c, int interp, int rgb_order, const double* border_value, void* stream) {
     Nv12OutArgs a;
-    memset(&a, 0, sizeof(a));
-    fill_frame(a, {c.dst_y, c.dst_h, c.dst_w, c.dy_fs, c.dy_rs}, c.minv, c.m_count, p);
-    a.dst_uv = (uint8_t*)c.dst_uv, a.duv_fs = c.duv_fs, a.duv_rs = c.duv_rs;
-    a.dst_vec_ok = plan::nv12_out_wide_stores_ok(c.dst_y_image());
-    a.uv_vec_ok = plan::nv12_out_wide_stores_ok(c.dst_uv_image());
-    a.src = (const uint8_t*)c.src, a.src_fs = c.src_fs, a.src_rs = c.src_rs;
-    a.y = (const uint8_t*)c.y, a.uv = (const uint8_t*)c.uv;
-    a.y_fs = c.y_fs, a.y_rs = c.y_rs, a.uv_fs = c.uv_fs, a.uv_rs = c.uv_rs;
-    a.src_h = c.src_h, a.src_w = c.src_w;
-    a.border = (uint32_t)bu[0] | ((uint32_t)bu[1] << 8) | ((uint32_t)bu[2] << 16);
-    return launched(launch_warp_nv12_out(a, c.nv12_src, c.interp, c.rgb_order, p.total_tiles, (hipStream_t)stream));
+    int64_t items;
+    const int st = flat_grid_args(c, a, items);
+    if (!items) return st;
+    uint8_t bu[4];  // (in the warped pixel's channel order: a pixel value, converted by the kernel like any other)
+    if (border_bytes(border_value, bu) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
+    const Image& duv = c.writes[1].im;
+    a.dst_uv = (uint8_t*)duv.base, a.duv_fs = duv.fs, a.duv_rs = duv.rs;
+    a.dst_vec_ok = plan::wide_stores_ok(c.writes[0], 4);  // per plane: a lane's 4 Y bytes, and its two pairs, go out as one dword each
+    a.uv_vec_ok = plan::wide_stores_ok(c.writes[1], 4);
+    const bool nv12_src = c.n_reads == 2;
+    if (nv12_src)
+        fill_nv12_source(a, c);
+    else
+        a.src = (const uint8_t*)c.reads[0].im.base, a.src_fs = c.reads[0].im.fs, a.src_rs = c.reads[0].im.rs;
+    a.border = packed3(bu);
+    return launched(launch_warp_nv12_out(a, nv12_src, interp, rgb_order, items, (hipStream_t)stream));
 }
 }  // namespace
 
@@ -290,46 +297,37 @@ extern "C" {
 int bevwarp_warp_to_nv12(const void* src, void* dst_y, void* dst_uv, int batch, int src_h, int src_w, int dst_h, int dst_w, int64_t src_frame_stride,
                          int64_t src_row_stride, int64_t y_frame_stride, int64_t y_row_stride, int64_t uv_frame_stride, int64_t uv_row_stride,
                          const double* M_inv, int m_count, int interp, int rgb_order, const double* border_value, void* stream) {
-    Nv12OutCall c = {};
-    c.nv12_src = false, c.src = src, c.dst_y = dst_y, c.dst_uv = dst_uv;
-    c.batch = batch, c.src_h = src_h, c.src_w = src_w, c.dst_h = dst_h, c.dst_w = dst_w;
-    c.src_fs = src_frame_stride, c.src_rs = src_row_stride;
-    c.dy_fs = y_frame_stride, c.dy_rs = y_row_stride, c.duv_fs = uv_frame_stride, c.duv_rs = uv_row_stride;
-    c.minv = M_inv, c.m_count = m_count, c.interp = interp, c.rgb_order = rgb_order;
-    return warp_nv12_out_impl(c, border_value, stream);
+    return warp_nv12_out_impl(plan::to_nv12_call({src, src_frame_stride, src_row_stride}, {dst_y, y_frame_stride, y_row_stride}, {dst_uv, uv_frame_stride, uv_row_stride},
+                                                 {batch, src_h, src_w, dst_h, dst_w, m_count, M_inv}, interp, rgb_order),
+                              interp, rgb_order, border_value, stream);
 }
 
 int bevwarp_warp_nv12_to_nv12(const void* y, const void* uv, void* dst_y, void* dst_uv, int batch, int src_h, int src_w, int dst_h, int dst_w,
                               int64_t y_frame_stride, int64_t y_row_stride, int64_t uv_frame_stride, int64_t uv_row_stride, int64_t dst_y_frame_stride,
                               int64_t dst_y_row_stride, int64_t dst_uv_frame_stride, int64_t dst_uv_row_stride, const double* M_inv, int m_count,
                               int interp, const double* border_value, void* stream) {
-    Nv12OutCall c = {};
-    c.nv12_src = true, c.y = y, c.uv = uv, c.dst_y = dst_y, c.dst_uv = dst_uv;
-    c.batch = batch, c.src_h = src_h, c.src_w = src_w, c.dst_h = dst_h, c.dst_w = dst_w;
-    c.y_fs = y_frame_stride, c.y_rs = y_row_stride, c.uv_fs = uv_frame_stride, c.uv_rs = uv_row_stride;
-    c.dy_fs = dst_y_frame_stride, c.dy_rs = dst_y_row_stride, c.duv_fs = dst_uv_frame_stride, c.duv_rs = dst_uv_row_stride;
-    c.minv = M_inv, c.m_count = m_count, c.interp = interp, c.rgb_order = 0;
-    return warp_nv12_out_impl(c, border_value, stream);
+    return warp_nv12_out_impl(plan::nv12_to_nv12_call({y, y_frame_stride, y_row_stride}, {uv, uv_frame_stride, uv_row_stride}, {dst_y, dst_y_frame_stride, dst_y_row_stride},
+                                                      {dst_uv, dst_uv_frame_stride, dst_uv_row_stride}, {batch, src_h, src_w, dst_h, dst_w, m_count, M_inv}, interp),
+                              interp, 0, border_value, stream);
 }
 
 int bevwarp_warp_classes(const void* src, void* dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int channels, int64_t src_frame_stride,
                          int64_t src_row_stride, int64_t dst_frame_stride, int64_t dst_row_stride, const double* M_inv, int m_count, int dtype, int interp,
                          const double* border_value, void* classes, int mode, void* stream) {
     if (!classes || (mode != BEVWARP_CLASSES_USE && mode != BEVWARP_CLASSES_FILL)) return BEVWARP_ERR_BAD_ARG;
-    return warp_impl({{src, src_h, src_w, src_frame_stride, src_row_stride}, {dst, dst_h, dst_w, dst_frame_stride, dst_row_stride}, batch, channels, dtype, interp,
-                      M_inv, m_count, border_value, stream, false, 0, nullptr, nullptr, classes, mode});
+    return warp_impl(plan::warp_call({src, src_frame_stride, src_row_stride}, {dst, dst_frame_stride, dst_row_stride}, {batch, src_h, src_w, dst_h, dst_w, m_count, M_inv},
+                                     channels, dtype, interp, false),
+                     channels, dtype, interp, border_value, stream, 0, nullptr, nullptr, classes, mode);
 }
 
 // The table of a launch geometry -- full tile, upper half, lower half per tile -- or the status of the warp it describes (tightly
 // packed frames, one matrix).  Sizes and format only: no pointer is involved.
 int64_t bevwarp_tile_classes_bytes(int batch, int src_h, int src_w, int dst_h, int dst_w, int channels, int dtype, int interp) {
     if (batch <= 0) return 0;
-    const WarpCall c = {{nullptr, src_h, src_w, 0, 0}, {nullptr, dst_h, dst_w, 0, 0}, batch, channels, dtype, interp, nullptr, 1};
-    int st = plan::format_status(c);
-    if (st != BEVWARP_OK) return st;
-    Image s = c.src_image();
-    s.rs = (int64_t)s.row_bytes;
-    if ((st = plan::source_size_status(s, src_w)) != BEVWARP_OK) return st;
+    Call c = plan::warp_call({}, {}, {batch, src_h, src_w, dst_h, dst_w, 1, nullptr}, channels, dtype, interp, false);
+    c.reads[0].im.rs = (int64_t)c.reads[0].im.row_bytes;
+    int st;
+    if ((st = plan::sides_status(c)) != BEVWARP_OK || (st = plan::format_status(c)) != BEVWARP_OK || (st = plan::source_sizes_status(c)) != BEVWARP_OK) return st;
     const TilePlan p = plan::plan_rows(batch, dst_h, dst_w, dtype, tile_width(dtype), rows_per_pass(), resident_workgroups(dtype, channels, interp));
     return p.status != BEVWARP_OK ? (int64_t)p.status : 3 * p.total_tiles * (int64_t)sizeof(uint32_t);
 }
@@ -338,22 +336,19 @@ int bevwarp_warp_planar(const void* src, void* dst, int batch, int src_h, int sr
                         int64_t src_frame_stride, int64_t src_row_stride, int64_t dst_frame_stride, int64_t dst_plane_stride,
                         int64_t dst_row_stride, const double* M_inv, int m_count, int dtype, int interp, const double* border_value,
                         const double* scale, const double* bias, void* stream) {
-    return warp_impl({{src, src_h, src_w, src_frame_stride, src_row_stride}, {dst, dst_h, dst_w, dst_frame_stride, dst_row_stride}, batch, channels, dtype, interp,
-                      M_inv, m_count, border_value, stream, true, dst_plane_stride, scale, bias});
+    return bevwarp_warp_planes(src, dst, batch, src_h, src_w, dst_h, dst_w, channels, src_frame_stride, src_row_stride, dst_frame_stride, dst_plane_stride,
+                               dst_row_stride, M_inv, m_count, dtype, interp, border_value, scale, bias, BEVWARP_F32, stream);
 }
 
 int bevwarp_warp_planes(const void* src, void* dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int channels,
                         int64_t src_frame_stride, int64_t src_row_stride, int64_t dst_frame_stride, int64_t dst_plane_stride,
                         int64_t dst_row_stride, const double* M_inv, int m_count, int dtype, int interp, const double* border_value,
                         const double* scale, const double* bias, int plane_dtype, void* stream) {
-    if (plane_dtype == BEVWARP_F32)  // float32 planes are bevwarp_warp_planar itself
-        return bevwarp_warp_planar(src, dst, batch, src_h, src_w, dst_h, dst_w, channels, src_frame_stride, src_row_stride, dst_frame_stride, dst_plane_stride,
-                                   dst_row_stride, M_inv, m_count, dtype, interp, border_value, scale, bias, stream);
-    if (plane_dtype != BEVWARP_F16 && plane_dtype != BEVWARP_BF16) return BEVWARP_ERR_UNSUPPORTED;
-    WarpCall c = {{src, src_h, src_w, src_frame_stride, src_row_stride}, {dst, dst_h, dst_w, dst_frame_stride, dst_row_stride}, batch, channels, dtype, interp,
-                  M_inv, m_count, border_value, stream, true, dst_plane_stride, scale, bias};
-    c.plane_elem = 2;
-    return warp_impl(c, plane_dtype == BEVWARP_F16 ? kPlaneF16 : kPlaneBF16);
+    if (plane_dtype != BEVWARP_F32 && plane_dtype != BEVWARP_F16 && plane_dtype != BEVWARP_BF16) return BEVWARP_ERR_UNSUPPORTED;
+    const int plane_elem = plane_dtype == BEVWARP_F32 ? 4 : 2;
+    return warp_impl(plan::warp_call({src, src_frame_stride, src_row_stride}, {dst, dst_frame_stride, dst_row_stride}, {batch, src_h, src_w, dst_h, dst_w, m_count, M_inv},
+                                     channels, dtype, interp, false, plane_elem, dst_plane_stride),
+                     channels, dtype, interp, border_value, stream, plane_dtype == BEVWARP_F32 ? kPlaneF32 : (plane_dtype == BEVWARP_F16 ? kPlaneF16 : kPlaneBF16), scale, bias);
 }
 
 int bevwarp_composite(const void* bg, const void* fg, const void* mask, void* out, int64_t n, void* stream) {

@@ -78,160 +78,74 @@ inline int store_align(int dtype, int channels, bool planar, int plane_elem = 4)
     return dtype == BEVWARP_U8 ? (channels == 4 ? 16 : (channels == 2 ? 8 : 4)) : 16;
 }
 inline bool wide_stores_ok(const Image& d, int align) { return d.base % align == 0 && d.rs % align == 0 && d.fs % align == 0; }
-// (a planar call's wide stores: call_wide_stores_ok below -- the plane stride counts as well)
+// (a written image of planes: the overload below -- the plane stride counts as well)
 // The border kernel's whole-pixel loads: 8-bit pixels of 2 / 4 channels that are all 2- / 4-byte aligned (one load per tap).
 inline int pixel_load_align(int dtype, int channels) { return (dtype == BEVWARP_U8 && (channels == 2 || channels == 4)) ? channels : (dtype == BEVWARP_U8 ? 1 : 4); }
 inline bool pixel_loads_ok(const Image& s, int align) { return s.base % align == 0 && s.rs % align == 0 && (s.batch == 1 || s.fs % align == 0); }
 
-// ---- a warp call (bevwarp_warp, _classes, _planar, _border) -----------------------------------------------------------------
+// ---- a call: the images it reads and the images it writes ------------------------------------------------------------------------
 struct Frames {  // an image batch as the ABI passes it
     const void* base;
-    int h, w;
     int64_t fs, rs;
+    Image image(int rows, uint64_t row_bytes, int batch) const { return {(uintptr_t)base, rows, row_bytes, rs, fs, batch}; }
 };
-struct WarpCall {  // (an aggregate: every entry point fills it once, the optional parts default to none)
-    Frames src, dst;
-    int batch, channels, dtype, interp;
+struct ReadImage {
+    Image im;
+    int cols, elem;  // pixels of a row, for the size limits; bytes of an element: 1, 2 (a (U, V) pair) or 4 (float32)
+};
+struct WrittenImage {
+    Image im;  // (planar: one plane's rows)
+    int elem;
+    bool planar;           // channel planes instead of interleaved pixels: `planes` per frame (interleaved: 1) ...
+    int planes;
+    int64_t plane_stride;  // ... this many bytes apart
+    uintptr_t end() const { return im.end() + (uint64_t)(planes - 1) * plane_stride; }  // (of the bounding byte range of all planes)
+};
+// The two images of a batch of NV12 frames: h rows of w Y bytes, and h / 2 rows of w / 2 (U, V) pairs (w bytes, 2-byte elements).
+struct Nv12Images {
+    Image y, uv;
+};
+inline Nv12Images nv12_images(Frames y, Frames uv, int h, int w, int batch) { return {y.image(h, (uint64_t)w, batch), uv.image(h / 2, (uint64_t)w, batch)}; }
+
+// What the checks need of one entry point's arguments.  The functions of the last part of this section describe the nine entry points in
+// these terms; bevwarp_api.hip and tests/host_plan_driver.cpp both build their calls with them.
+struct Sizes {  // (what every entry point passes besides its images and its format)
+    int batch, src_h, src_w, dst_h, dst_w, m_count;
     const double* minv;
-    int m_count;
-    const double* border_value;
-    void* stream;
-    bool planar;  // bevwarp_warp_planar, _planes: channel planes, plane_stride bytes apart, instead of interleaved pixels of the source type
-    int64_t plane_stride;
-    const double *scale, *bias;
-    void* classes;  // bevwarp_warp_classes
-    int classes_mode;
-    bool cubic_ok;  // bevwarp_warp, bevwarp_warp_border: the entry points behind which a bicubic kernel stands
-    int plane_elem = 4;  // bytes of a plane's element: 4 (float32), 2 (bevwarp_warp_planes: float16, bfloat16)
+};
+struct Call : Sizes {
+    bool format_ok;     // the entry point takes this dtype, channel count, interpolation, channel order and plane type ...
+    bool format_first;  // ... which is asked before the layouts (bevwarp_warp and its kin) or after the matrix count (the NV12 entry points)
+    bool even_src, even_dst;  // NV12 frames have even sides
+    int n_reads, n_writes;
+    ReadImage reads[2];
+    WrittenImage writes[2];
 
-    int elem() const { return dtype == BEVWARP_U8 ? 1 : 4; }
-    Image src_image() const { return {(uintptr_t)src.base, src.h, (uint64_t)src.w * channels * elem(), src.rs, src.fs, batch}; }
-    // (planar: one plane's rows; the planes of a frame are plane_stride apart)
-    Image dst_image() const { return {(uintptr_t)dst.base, dst.h, (uint64_t)dst.w * (planar ? plane_elem : channels * elem()), dst.rs, dst.fs, batch}; }
+    void read(const Image& im, int cols, int elem) { reads[n_reads++] = {im, cols, elem}; }
+    void write(const Image& im, int elem) { writes[n_writes++] = {im, elem, false, 1, 0}; }
+    void write_planes(const Image& im, int elem, int planes, int64_t plane_stride) { writes[n_writes++] = {im, elem, true, planes, plane_stride}; }
+    void read_nv12(Frames y, Frames uv) {
+        const Nv12Images f = nv12_images(y, uv, src_h, src_w, batch);
+        even_src = true, read(f.y, src_w, 1), read(f.uv, src_w / 2, 2);
+    }
+    void write_nv12(Frames y, Frames uv) {
+        const Nv12Images f = nv12_images(y, uv, dst_h, dst_w, batch);
+        even_dst = true, write(f.y, 1), write(f.uv, 2);
+    }
 };
 
-// Does the call's destination admit the wide stores?  (planes: 4 elements per store, and the plane stride is a stride like the others)
-inline bool call_wide_stores_ok(const WarpCall& c) {
-    const int align = store_align(c.dtype, c.channels, c.planar, c.plane_elem);
-    return wide_stores_ok(c.dst_image(), align) && (!c.planar || c.plane_stride % align == 0);
-}
-
-// The checks that need no pointer, in the order their statuses are documented: sizes, format, matrix count.
-inline int format_status(const WarpCall& c) {
-    if (c.batch < 0 || c.src.h <= 0 || c.src.w <= 0 || c.dst.h <= 0 || c.dst.w <= 0) return BEVWARP_ERR_BAD_ARG;
-    const bool interp_ok = c.interp == BEVWARP_NEAREST || c.interp == BEVWARP_LINEAR || (c.interp == BEVWARP_CUBIC && c.cubic_ok);
-    if ((c.dtype != BEVWARP_U8 && c.dtype != BEVWARP_F32) || !interp_ok || c.channels < 1 || c.channels > 4) return BEVWARP_ERR_UNSUPPORTED;
-    if (c.m_count != 1 && c.m_count != c.batch) return BEVWARP_ERR_BAD_ARG;
-    return BEVWARP_OK;
-}
+// Wide stores of a written image: with planes, the plane stride is a stride like the others.
+inline bool wide_stores_ok(const WrittenImage& w, int align) { return wide_stores_ok(w.im, align) && (!w.planar || w.plane_stride % align == 0); }
 
 // The source limits of the warp kernels: sides of at most 32767 px (saturated 16-bit tap indices) and 24-bit multiplies.
 inline int source_size_status(const Image& src, int cols) { return size_status(src, cols, 32767, 32767, true); }
 
-// All argument checks of a warp: BEVWARP_OK or the status to return.  Null pointers, then format, layout, size, overlap.
-inline int check_warp(const WarpCall& c) {
-    if (!c.src.base || !c.dst.base || !c.minv) return BEVWARP_ERR_BAD_ARG;
-    int st = format_status(c);
-    if (st != BEVWARP_OK) return st;
-    const Image s = c.src_image(), d = c.dst_image();
-    if ((st = layout_status(s, c.elem())) != BEVWARP_OK) return st;
-    if (c.planar) {  // destination: `channels` planes per frame -- the rule twice: rows in a plane (asked of a lone plane too), planes in a frame
-        const Image rows_in_plane = {d.base, d.rows, d.row_bytes, d.rs, c.plane_stride, 2}, planes_in_frame = {d.base, c.channels, 0, c.plane_stride, d.fs, d.batch};
-        if (layout_status(rows_in_plane, c.plane_elem) != BEVWARP_OK || layout_status(planes_in_frame, c.plane_elem) != BEVWARP_OK) return BEVWARP_ERR_BAD_ARG;
-    } else if ((st = layout_status(d, c.elem())) != BEVWARP_OK) {
-        return st;
-    }
-    if ((st = source_size_status(s, c.src.w)) != BEVWARP_OK || c.batch == 0) return st;
-    if (c.planar) {  // (planes: bounding ranges only -- a frame's planes need not share the rows' stride)
-        const uintptr_t d1 = d.end() + (uint64_t)(c.channels - 1) * c.plane_stride;
-        return (s.base < d1 && d.base < s.end()) ? BEVWARP_ERR_OVERLAP : BEVWARP_OK;
-    }
-    return regions_overlap(s, d) ? BEVWARP_ERR_OVERLAP : BEVWARP_OK;
+// The layout of a written image.  Planes: the rule twice -- rows in a plane (asked of a lone plane too), planes in a frame.
+inline int layout_status(const WrittenImage& w) {
+    if (!w.planar) return layout_status(w.im, w.elem);
+    const Image &d = w.im, rows_in_plane = {d.base, d.rows, d.row_bytes, d.rs, w.plane_stride, 2}, planes_in_frame = {d.base, w.planes, 0, w.plane_stride, d.fs, d.batch};
+    return (layout_status(rows_in_plane, w.elem) != BEVWARP_OK || layout_status(planes_in_frame, w.elem) != BEVWARP_OK) ? BEVWARP_ERR_BAD_ARG : BEVWARP_OK;
 }
-
-// ---- an NV12 warp call (bevwarp_warp_nv12) -------------------------------------------------------------------------------------
-// The source is two images: src_h rows of src_w Y bytes, and src_h / 2 rows of src_w / 2 (U, V) pairs (src_w bytes, 2-byte elements).
-// The destination is 8-bit, 3 channels.
-struct Nv12Call {
-    const void *y, *uv, *dst;
-    int batch, src_h, src_w, dst_h, dst_w;
-    int64_t y_fs, y_rs, uv_fs, uv_rs, dst_fs, dst_rs;
-    const double* minv;
-    int m_count, interp, rgb_order;
-
-    Image y_image() const { return {(uintptr_t)y, src_h, (uint64_t)src_w, y_rs, y_fs, batch}; }
-    Image uv_image() const { return {(uintptr_t)uv, src_h / 2, (uint64_t)src_w, uv_rs, uv_fs, batch}; }
-    Image dst_image() const { return {(uintptr_t)dst, dst_h, (uint64_t)dst_w * 3, dst_rs, dst_fs, batch}; }
-};
-
-// ---- an NV12 warp into channel planes (bevwarp_warp_nv12_planes) ---------------------------------------------------------------------
-// The source is an Nv12Call's; the destination is three planes per frame of dst_h rows of dst_w elements of `plane_dtype`.
-struct Nv12PlanesCall {
-    Nv12Call s;           // (dst, dst_fs, dst_rs: plane 0 of frame 0, the frame stride and a plane's row stride)
-    int64_t dst_ps;       // bytes between the planes of a frame
-    int plane_dtype;      // BEVWARP_F32 | BEVWARP_F16 | BEVWARP_BF16
-
-    // bytes of a plane's element; a plane type the entry point does not take asks no alignment (the layout is looked at first)
-    int elem() const { return plane_dtype == BEVWARP_F32 ? 4 : ((plane_dtype == BEVWARP_F16 || plane_dtype == BEVWARP_BF16) ? 2 : 1); }
-    Image plane_image() const { return {(uintptr_t)s.dst, s.dst_h, (uint64_t)s.dst_w * elem(), s.dst_rs, s.dst_fs, s.batch}; }  // one plane's rows
-    uintptr_t dst_end() const { return plane_image().end() + 2 * (uint64_t)dst_ps; }  // (of the bounding byte range of all planes)
-};
-
-// All argument checks of the two NV12 warps (`planes`: the call into planes, or null), in the order the header documents: bad arguments
-// (null pointers, sizes, odd source sides, layouts -- the interleaved destination's, or check_warp's rule for planes: rows in a plane,
-// asked of a lone plane too, and planes in a frame -- then the matrix count), unsupported interpolation, channel order or plane type,
-// source size limits per plane, overlap of the destination with either source plane (the planes may overlap each other: both are only
-// read; a destination of planes is taken as its bounding byte range).
-inline int check_nv12(const Nv12Call& c, const Nv12PlanesCall* planes) {
-    if (!c.y || !c.uv || !c.dst || !c.minv) return BEVWARP_ERR_BAD_ARG;
-    if (c.batch < 0 || c.src_h <= 0 || c.src_w <= 0 || c.dst_h <= 0 || c.dst_w <= 0 || (c.src_h & 1) || (c.src_w & 1)) return BEVWARP_ERR_BAD_ARG;
-    const Image y = c.y_image(), uv = c.uv_image(), d = planes ? planes->plane_image() : c.dst_image();
-    if (layout_status(y, 1) != BEVWARP_OK || layout_status(uv, 2) != BEVWARP_OK) return BEVWARP_ERR_BAD_ARG;
-    if (planes) {
-        const Image rows_in_plane = {d.base, d.rows, d.row_bytes, d.rs, planes->dst_ps, 2}, planes_in_frame = {d.base, 3, 0, planes->dst_ps, d.fs, d.batch};
-        if (layout_status(rows_in_plane, planes->elem()) != BEVWARP_OK || layout_status(planes_in_frame, planes->elem()) != BEVWARP_OK) return BEVWARP_ERR_BAD_ARG;
-    } else if (layout_status(d, 1) != BEVWARP_OK) {
-        return BEVWARP_ERR_BAD_ARG;
-    }
-    if (c.m_count != 1 && c.m_count != c.batch) return BEVWARP_ERR_BAD_ARG;
-    if ((c.interp != BEVWARP_NEAREST && c.interp != BEVWARP_LINEAR) || (c.rgb_order != 0 && c.rgb_order != 1)) return BEVWARP_ERR_UNSUPPORTED;
-    if (planes && planes->plane_dtype != BEVWARP_F32 && planes->plane_dtype != BEVWARP_F16 && planes->plane_dtype != BEVWARP_BF16) return BEVWARP_ERR_UNSUPPORTED;
-    int st;
-    if ((st = source_size_status(y, c.src_w)) != BEVWARP_OK || (st = source_size_status(uv, c.src_w / 2)) != BEVWARP_OK || c.batch == 0) return st;
-    if (planes) {
-        const uintptr_t d1 = planes->dst_end();
-        return ((y.base < d1 && d.base < y.end()) || (uv.base < d1 && d.base < uv.end())) ? BEVWARP_ERR_OVERLAP : BEVWARP_OK;
-    }
-    return (regions_overlap(y, d) || regions_overlap(uv, d)) ? BEVWARP_ERR_OVERLAP : BEVWARP_OK;
-}
-inline int check_warp_nv12(const Nv12Call& c) { return check_nv12(c, nullptr); }
-inline int check_warp_nv12_planes(const Nv12PlanesCall& c) { return check_nv12(c.s, &c); }
-// Does the call's destination admit the wide stores?  call_wide_stores_ok's rule: 4 plane elements per store, the plane stride counts.
-inline bool nv12_planes_wide_stores_ok(const Nv12PlanesCall& c) {
-    const int align = store_align(BEVWARP_U8, 3, true, c.elem());
-    return wide_stores_ok(c.plane_image(), align) && c.dst_ps % align == 0;
-}
-
-// ---- a warp into NV12 (bevwarp_warp_to_nv12, bevwarp_warp_nv12_to_nv12) -------------------------------------------------------------
-// The destination is two images, laid out like an Nv12Call's source: dst_h rows of dst_w Y bytes, and dst_h / 2 rows of dst_w / 2 (U, V)
-// pairs (dst_w bytes, 2-byte elements).  The source is 8-bit, 3 channels (`src`) or, with `nv12_src`, the two planes of an Nv12Call.
-struct Nv12OutCall {
-    bool nv12_src;
-    const void *src, *y, *uv;     // src (BGR / RGB frames) or y and uv; the other side is unused
-    const void *dst_y, *dst_uv;
-    int batch, src_h, src_w, dst_h, dst_w;
-    int64_t src_fs, src_rs;       // of src
-    int64_t y_fs, y_rs, uv_fs, uv_rs;  // of y and uv
-    int64_t dy_fs, dy_rs, duv_fs, duv_rs;
-    const double* minv;
-    int m_count, interp, rgb_order;   // (rgb_order: of src; an NV12 source is sampled as B, G, R and passes 0)
-
-    Image src_image() const { return {(uintptr_t)src, src_h, (uint64_t)src_w * 3, src_rs, src_fs, batch}; }
-    Image y_image() const { return {(uintptr_t)y, src_h, (uint64_t)src_w, y_rs, y_fs, batch}; }
-    Image uv_image() const { return {(uintptr_t)uv, src_h / 2, (uint64_t)src_w, uv_rs, uv_fs, batch}; }
-    Image dst_y_image() const { return {(uintptr_t)dst_y, dst_h, (uint64_t)dst_w, dy_rs, dy_fs, batch}; }
-    Image dst_uv_image() const { return {(uintptr_t)dst_uv, dst_h / 2, (uint64_t)dst_w, duv_rs, duv_fs, batch}; }
-};
 
 // Do the two planes a launch WRITES share bytes?  regions_overlap's rule, with one more refinement: in a batch of single-buffer frames
 // (Y rows, then the rows of pairs, frame after frame) the Y images' bounding range spans every frame's pairs.  Where both planes walk
@@ -247,36 +161,102 @@ inline bool written_planes_overlap(const Image& a, const Image& b) {
     return regions_overlap(a, b);
 }
 
-// All argument checks of the two warps into NV12, in the order the header documents: bad arguments (null pointers, sizes, odd destination
-// sides, odd sides of an NV12 source, the layout of every image -- the pairs' planes with 2-byte elements --, the matrix count), unsupported
-// interpolation or channel order, the source's size limits, overlap of either destination plane with any source image and of the two
-// destination planes with each other (source planes may overlap each other: both are only read).
-inline int check_nv12_out(const Nv12OutCall& c) {
-    if (c.nv12_src ? (!c.y || !c.uv) : !c.src) return BEVWARP_ERR_BAD_ARG;
-    if (!c.dst_y || !c.dst_uv || !c.minv) return BEVWARP_ERR_BAD_ARG;
-    if (c.batch < 0 || c.src_h <= 0 || c.src_w <= 0 || c.dst_h <= 0 || c.dst_w <= 0 || (c.dst_h & 1) || (c.dst_w & 1)) return BEVWARP_ERR_BAD_ARG;
-    if (c.nv12_src && ((c.src_h & 1) || (c.src_w & 1))) return BEVWARP_ERR_BAD_ARG;
-    const Image s = c.src_image(), y = c.y_image(), uv = c.uv_image(), dy = c.dst_y_image(), duv = c.dst_uv_image();
-    if (c.nv12_src ? (layout_status(y, 1) != BEVWARP_OK || layout_status(uv, 2) != BEVWARP_OK) : layout_status(s, 1) != BEVWARP_OK) return BEVWARP_ERR_BAD_ARG;
-    if (layout_status(dy, 1) != BEVWARP_OK || layout_status(duv, 2) != BEVWARP_OK) return BEVWARP_ERR_BAD_ARG;
-    if (c.m_count != 1 && c.m_count != c.batch) return BEVWARP_ERR_BAD_ARG;
-    if ((c.interp != BEVWARP_NEAREST && c.interp != BEVWARP_LINEAR) || (c.rgb_order != 0 && c.rgb_order != 1)) return BEVWARP_ERR_UNSUPPORTED;
-    int st;
-    if (c.nv12_src) {
-        if ((st = source_size_status(y, c.src_w)) != BEVWARP_OK || (st = source_size_status(uv, c.src_w / 2)) != BEVWARP_OK) return st;
-    } else if ((st = source_size_status(s, c.src_w)) != BEVWARP_OK) {
-        return st;
-    }
-    if (c.batch == 0) return BEVWARP_OK;
-    const bool meets_source = c.nv12_src ? (regions_overlap(y, dy) || regions_overlap(uv, dy) || regions_overlap(y, duv) || regions_overlap(uv, duv))
-                                         : (regions_overlap(s, dy) || regions_overlap(s, duv));
-    return (meets_source || written_planes_overlap(dy, duv)) ? BEVWARP_ERR_OVERLAP : BEVWARP_OK;
+// ---- the checks: one routine per phase, each over all images of the call ---------------------------------------------------------------
+inline int null_status(const Call& c) {
+    bool null = !c.minv;
+    for (int i = 0; i < c.n_reads; i++) null |= !c.reads[i].im.base;
+    for (int i = 0; i < c.n_writes; i++) null |= !c.writes[i].im.base;
+    return null ? BEVWARP_ERR_BAD_ARG : BEVWARP_OK;
 }
-inline int check_warp_to_nv12(const Nv12OutCall& c) { return c.nv12_src ? BEVWARP_ERR_BAD_ARG : check_nv12_out(c); }
-inline int check_warp_nv12_to_nv12(const Nv12OutCall& c) { return c.nv12_src ? check_nv12_out(c) : BEVWARP_ERR_BAD_ARG; }
-// Wide stores, per plane: a lane's 4 Y bytes, and its two pairs, go out as one dword each where the plane's base and both strides are
-// multiples of 4 (the frame stride counts even for a single frame).
-inline bool nv12_out_wide_stores_ok(const Image& plane) { return wide_stores_ok(plane, 4); }
+inline int sides_status(const Call& c) {
+    if (c.batch < 0 || c.src_h <= 0 || c.src_w <= 0 || c.dst_h <= 0 || c.dst_w <= 0) return BEVWARP_ERR_BAD_ARG;
+    return ((c.even_src && ((c.src_h | c.src_w) & 1)) || (c.even_dst && ((c.dst_h | c.dst_w) & 1))) ? BEVWARP_ERR_BAD_ARG : BEVWARP_OK;
+}
+inline int layouts_status(const Call& c) {
+    int st = BEVWARP_OK;
+    for (int i = 0; i < c.n_reads && st == BEVWARP_OK; i++) st = layout_status(c.reads[i].im, c.reads[i].elem);
+    for (int i = 0; i < c.n_writes && st == BEVWARP_OK; i++) st = layout_status(c.writes[i]);
+    return st;
+}
+inline int matrix_count_status(const Call& c) { return (c.m_count != 1 && c.m_count != c.batch) ? BEVWARP_ERR_BAD_ARG : BEVWARP_OK; }
+inline int format_status(const Call& c) { return c.format_ok ? BEVWARP_OK : BEVWARP_ERR_UNSUPPORTED; }
+inline int source_sizes_status(const Call& c) {
+    int st = BEVWARP_OK;
+    for (int i = 0; i < c.n_reads && st == BEVWARP_OK; i++) st = source_size_status(c.reads[i].im, c.reads[i].cols);
+    return st;
+}
+// Every written image against every read one, and the written ones against each other; read images may overlap each other.  An image of
+// planes is taken as its bounding byte range: a frame's planes need not share the rows' stride.
+inline int overlap_status(const Call& c) {
+    for (int i = 0; i < c.n_writes; i++)
+        for (int k = 0; k < c.n_reads; k++) {
+            const WrittenImage& w = c.writes[i];
+            const Image& r = c.reads[k].im;
+            if (w.planar ? (r.base < w.end() && w.im.base < r.end()) : regions_overlap(r, w.im)) return BEVWARP_ERR_OVERLAP;
+        }
+    return (c.n_writes == 2 && written_planes_overlap(c.writes[0].im, c.writes[1].im)) ? BEVWARP_ERR_OVERLAP : BEVWARP_OK;
+}
+
+// All argument checks of a call, in either order include/bevwarp.h documents: BEVWARP_OK or the status to return.  (An empty batch ends
+// the checks before the overlap: the caller returns on it as well.)
+inline int check_call(const Call& c) {
+    int (*const format_first[])(const Call&) = {null_status, sides_status, format_status, matrix_count_status, layouts_status, source_sizes_status};
+    int (*const layouts_first[])(const Call&) = {null_status, sides_status, layouts_status, matrix_count_status, format_status, source_sizes_status};
+    for (auto phase : c.format_first ? format_first : layouts_first) {
+        const int st = phase(c);
+        if (st != BEVWARP_OK) return st;
+    }
+    return c.batch == 0 ? BEVWARP_OK : overlap_status(c);
+}
+
+// ---- the entry points' calls -------------------------------------------------------------------------------------------------------------
+// bevwarp_warp, _warp_border (cubic_ok: a bicubic kernel stands behind them), _warp_classes, and with plane_elem = 4 / 2 bevwarp_warp_planar /
+// _warp_planes: `channels` planes of float32 / 16-bit elements, dst_ps apart, instead of interleaved pixels of the source type.
+inline Call warp_call(Frames src, Frames dst, const Sizes& z, int channels, int dtype, int interp, bool cubic_ok, int plane_elem = 0, int64_t dst_ps = 0) {
+    const int elem = dtype == BEVWARP_U8 ? 1 : 4;
+    const bool interp_ok = interp == BEVWARP_NEAREST || interp == BEVWARP_LINEAR || (interp == BEVWARP_CUBIC && cubic_ok);
+    Call c = {z, (dtype == BEVWARP_U8 || dtype == BEVWARP_F32) && interp_ok && channels >= 1 && channels <= 4, true};
+    c.read(src.image(z.src_h, (uint64_t)z.src_w * channels * elem, z.batch), z.src_w, elem);
+    if (plane_elem)
+        c.write_planes(dst.image(z.dst_h, (uint64_t)z.dst_w * plane_elem, z.batch), plane_elem, channels, dst_ps);
+    else
+        c.write(dst.image(z.dst_h, (uint64_t)z.dst_w * channels * elem, z.batch), elem);
+    return c;
+}
+// What the four NV12 entry points share: nearest or bilinear, B, G, R or R, G, B.  Each adds its images.
+inline Call nv12_family_call(const Sizes& z, int interp, int rgb_order, bool plane_ok = true) {
+    return {z, (interp == BEVWARP_NEAREST || interp == BEVWARP_LINEAR) && (rgb_order == 0 || rgb_order == 1) && plane_ok, false};
+}
+// bevwarp_warp_nv12: to 8-bit pixels of 3 channels
+inline Call nv12_call(Frames y, Frames uv, Frames dst, const Sizes& z, int interp, int rgb_order) {
+    Call c = nv12_family_call(z, interp, rgb_order);
+    c.read_nv12(y, uv);
+    c.write(dst.image(z.dst_h, (uint64_t)z.dst_w * 3, z.batch), 1);
+    return c;
+}
+// bevwarp_warp_nv12_planes: to three planes of `plane_dtype` (BEVWARP_F32 | BEVWARP_F16 | BEVWARP_BF16), dst_ps apart.  A plane type the entry
+// point does not take has 1-byte elements here: it asks no alignment, because the layout is looked at first.
+inline Call nv12_planes_call(Frames y, Frames uv, Frames dst, int64_t dst_ps, const Sizes& z, int interp, int rgb_order, int plane_dtype) {
+    const int elem = plane_dtype == BEVWARP_F32 ? 4 : ((plane_dtype == BEVWARP_F16 || plane_dtype == BEVWARP_BF16) ? 2 : 1);
+    Call c = nv12_family_call(z, interp, rgb_order, elem != 1);  // (1: none of the three)
+    c.read_nv12(y, uv);
+    c.write_planes(dst.image(z.dst_h, (uint64_t)z.dst_w * elem, z.batch), elem, 3, dst_ps);
+    return c;
+}
+// bevwarp_warp_to_nv12: from 8-bit pixels of 3 channels
+inline Call to_nv12_call(Frames src, Frames dst_y, Frames dst_uv, const Sizes& z, int interp, int rgb_order) {
+    Call c = nv12_family_call(z, interp, rgb_order);
+    c.read(src.image(z.src_h, (uint64_t)z.src_w * 3, z.batch), z.src_w, 1);
+    c.write_nv12(dst_y, dst_uv);
+    return c;
+}
+// bevwarp_warp_nv12_to_nv12 (the source is sampled as B, G, R)
+inline Call nv12_to_nv12_call(Frames y, Frames uv, Frames dst_y, Frames dst_uv, const Sizes& z, int interp) {
+    Call c = nv12_family_call(z, interp, 0);
+    c.read_nv12(y, uv);
+    c.write_nv12(dst_y, dst_uv);
+    return c;
+}
 
 // ---- launch geometry ---------------------------------------------------------------------------------------------------------
 struct TilePlan {

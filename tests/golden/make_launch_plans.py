@@ -109,9 +109,8 @@ def main():
     if len(sys.argv) == 3 and sys.argv[1] == "--recorder":
         recorded = record(os.path.abspath(sys.argv[2]))
     else:
-        from tests import test_host_plan as t
-        with tempfile.TemporaryDirectory() as tmp:
-            recorded = t.plans_from_driver(t.build_driver(tmp), cases())
+        from tests import hostplan, test_host_plan as t
+        recorded = t.plans_from_driver(hostplan.build_driver(), cases())
     with open(OUT, "w") as f:
         f.write('{"cases": [\n' + ",\n".join(json.dumps(c) for c in recorded) + "\n]}\n")
     print("%d cases -> %s" % (len(recorded), OUT))

@@ -4,6 +4,7 @@ float_frame            float32 frames over the whole format: both signs, every b
                        signalling NaNs, +-FLT_MAX (the frames of tests/workloads.py lie in [0, 1))
 same_float             the comparison that goes with them: by bit pattern, so -0.0 != +0.0 and a NaN equals only a NaN
 padded_source          frames inside one larger allocation whose every other byte holds a fill value that is not the border value
+strided                an array in an allocation of its own in which every outer stride is padded by an amount of the caller's choice
 canaried_out,          a destination view inside a holder of canary bytes, and the check that the bytes around the view are intact
 assert_canaries_intact
 
@@ -141,6 +142,22 @@ def padded_source(frames_np, fill, offset=0, pad_rows=2, device="cuda"):
     view = torch.as_strided(buf, (B, H, W, C), (fs, rs, C, 1), pad_rows * rs + side + offset)
     view.copy_(torch.from_numpy(f4).to(device))
     return view if f.ndim == 4 else view[0]
+
+
+def strided(a_np, pads, fill=U8_FILL, device="cuda"):
+    """A CUDA view holding `a_np` in one allocation of its own (every other element is `fill`) in which the stride of dimension k, for
+    k < len(pads), is pads[k] elements more than the dimensions inside it need; the remaining dimensions are contiguous.  A caller that
+    gives every image of a call pads of its own gets row, plane and frame strides that all differ from the tight ones and from each other:
+    an entry point that swaps or drops one of them then reads or writes the wrong elements, and the comparison shows it."""
+    import torch
+    a = np.ascontiguousarray(a_np)
+    strides = [1] * a.ndim
+    for k in reversed(range(a.ndim - 1)):
+        strides[k] = a.shape[k + 1] * strides[k + 1] + (pads[k] if k < len(pads) else 0)
+    buf = _filled(a.shape[0] * strides[0], torch.from_numpy(a).dtype, fill, device)
+    view = torch.as_strided(buf, a.shape, strides)
+    view.copy_(torch.from_numpy(a).to(device))
+    return view
 
 
 def canaried_out(shape, dtype, pad, canvas=77, align=16, planar=False, gap_rows=2, device="cuda"):

@@ -9,15 +9,14 @@ import pytest
 
 from bev_amd import _lib
 from oracle import cpu_oracle as co
+from tests import hostplan
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    return _lib.load()
+    return hostplan.built_lib()
 
 
 def declared_symbols():

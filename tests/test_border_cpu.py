@@ -10,6 +10,7 @@ from bev_amd import _lib
 from oracle import warp_numpy as wn
 from tests import border_ref as BR
 from tests import codeobj
+from tests import hostplan
 from tests import workloads as wl
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -105,9 +106,7 @@ def test_int16_saturation_and_nan_coordinates():
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    return _lib.load()
+    return hostplan.built_lib()
 
 
 def test_abi_entry_validates_like_bevwarp_warp(lib):

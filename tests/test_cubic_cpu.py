@@ -12,6 +12,7 @@ from bev_amd import _lib
 from tests import border_ref as BR
 from tests import codeobj
 from tests import cubic_ref as CR
+from tests import hostplan
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -157,9 +158,7 @@ def test_float_inlier_and_general_orders_differ():
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    return _lib.load()
+    return hostplan.built_lib()
 
 
 CUBIC = 2

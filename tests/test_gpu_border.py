@@ -163,6 +163,25 @@ def test_strided_batch_and_unaligned_output(W):
             np.testing.assert_array_equal(got[i], exp, err_msg="%s frame %d" % (BR.NAMES[mode], i))
 
 
+@pytest.mark.parametrize("interp", [NEAREST, LINEAR])
+def test_two_frames_two_matrices_every_stride_padded(W, interp):
+    """What an entry point's argument filling can get wrong -- a swapped or dropped stride or pointer -- in the smallest shape that shows
+    it: two frames with a matrix each, row and frame strides of source and destination that all differ from the tight ones and from each
+    other, a destination of two tile columns (260 > 256) and two tile rows (6 > 4)."""
+    from tests import pixels as PX
+    sw, sh, dw, dh = 12, 10, 260, 6
+    host = _src((2, sh, sw, 3), np.uint8, seed=19)
+    H = wl.keystone_H(sw, sh, dw, dh)
+    Ms = np.stack([wl.jitter_H(H, 1), wl.jitter_H(H, 2)])
+    src, out = PX.strided(host, (40, 5)), PX.strided(np.full((2, dh, dw, 3), 77, np.uint8), (20, 7))
+    assert len({src.stride(0), src.stride(1), out.stride(0), out.stride(1), sh * sw * 3, sw * 3, dh * dw * 3, dw * 3}) == 8
+    W.warp_perspective(src, Ms, (dw, dh), flags=interp, out=out, border_mode=BR.REFLECT_101)
+    torch.cuda.synchronize()
+    exp = [ref(host[i], Ms[i], (dw, dh), interp, BR.REFLECT_101) for i in range(2)]
+    np.testing.assert_array_equal(out.cpu().numpy(), np.stack(exp))
+    assert not np.array_equal(exp[0], ref(host[0], Ms[1], (dw, dh), interp, BR.REFLECT_101))  # (the two matrices give different frames)
+
+
 def test_transparent_two_camera_mosaic(W):
     """cv2's stitching idiom: warpPerspective(cam_k, H_k, dsize, dst=canvas, borderMode=BORDER_TRANSPARENT) per camera."""
     dw, dh = 200, 120

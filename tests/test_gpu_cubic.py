@@ -161,6 +161,23 @@ def test_batch(W, dtype, per_frame):
             np.testing.assert_array_equal(got[i], ref(src[i], Ms[i] if per_frame else Ms, (dw, dh), mode), err_msg="%s frame %d" % (BR.NAMES[mode], i))
 
 
+def test_two_frames_two_matrices_every_stride_padded(W):
+    """What an entry point's argument filling can get wrong -- a swapped or dropped stride or pointer -- in the smallest shape that shows
+    it: two frames with a matrix each, row and frame strides of source and destination that all differ from the tight ones and from each
+    other, a destination of two tile columns (260 > 256) and two tile rows (6 > 4)."""
+    sw, sh, dw, dh = 12, 10, 260, 6
+    host = _src((2, sh, sw, 3), np.uint8, seed=31)
+    H = wl.keystone_H(sw, sh, dw, dh)
+    Ms = np.stack([wl.jitter_H(H, 1), wl.jitter_H(H, 2)])
+    src, out = px.strided(host, (40, 5)), px.strided(np.full((2, dh, dw, 3), 77, np.uint8), (20, 7))
+    assert len({src.stride(0), src.stride(1), out.stride(0), out.stride(1), sh * sw * 3, sw * 3, dh * dw * 3, dw * 3}) == 8
+    W.warp_perspective(src, Ms, (dw, dh), flags=CUBIC, out=out, border_mode=BR.REFLECT)
+    torch.cuda.synchronize()
+    exp = [ref(host[i], Ms[i], (dw, dh), BR.REFLECT) for i in range(2)]
+    np.testing.assert_array_equal(out.cpu().numpy(), np.stack(exp))
+    assert not np.array_equal(exp[0], ref(host[0], Ms[1], (dw, dh), BR.REFLECT))  # (the two matrices give different frames)
+
+
 def _source_at_the_end_of_its_allocation(frame, row_pad, lead):
     """A CUDA view of `frame` (H, W, C) with padded rows whose last element is the last element of its allocation, based `lead`
     elements into it; every other element holds a fill value that is no pixel of the frame's."""

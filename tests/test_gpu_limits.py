@@ -20,6 +20,7 @@ import torch
 from bev_amd import _lib, warp as W
 from oracle import cpu_oracle as co
 from tests import border_ref as br
+from tests import hostplan
 from tests import cubic_ref as cr
 from tests import limits_cases as lc
 from tests import pixels as px
@@ -322,11 +323,9 @@ def test_plane_rows_beyond_4gib(plane_dtype):
 
 # ---- F: item decoding at the edge of fast_div's exactness --------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def plan_driver(tmp_path_factory):
+def plan_driver():
     """tests/host_plan_driver.cpp (bev_amd/csrc/host_plan.h from the command line), built plainly."""
-    exe = str(tmp_path_factory.mktemp("limits") / "host_plan_driver")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "bev_amd", "csrc"), "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "host_plan_driver.cpp"), "-o", exe])
+    exe = hostplan.build_driver(sanitize=False)
 
     def plan(line):
         r = subprocess.run([exe], input=line + "\n", capture_output=True, text=True, timeout=60, check=True)

@@ -181,6 +181,27 @@ def test_layouts(W, interp):
     assert not np.array_equal(R.warp_nv12(ys[1], uvs[1], Ms[1], (120, 37), interp), R.warp_nv12(ys[1], uvs[1], M, (120, 37), interp))
 
 
+@pytest.mark.parametrize("interp", [NEAREST, LINEAR], ids=["nearest", "linear"])
+def test_two_frames_two_matrices_every_stride_padded(W, interp):
+    """What an entry point's argument filling can get wrong -- a swapped or dropped stride or pointer -- in the smallest shape that shows
+    it: two frames with a matrix each, row and frame strides of every image that all differ from the tight ones and from each other, a
+    destination of two tile columns (260 > 256) and two tile rows (6 > 4)."""
+    sw, sh, dw, dh = 12, 10, 260, 6
+    frames = [R.frame("uniform", 70 + i, sh, sw) for i in range(2)]
+    ys, uvs = np.stack([f[0] for f in frames]), np.stack([f[1] for f in frames])
+    H = wl.keystone_H(sw, sh, dw, dh)
+    Ms = np.stack([wl.jitter_H(H, 1), wl.jitter_H(H, 2)])
+    ty, tuv = PX.strided(ys, (9, 5)), PX.strided(uvs, (10, 6))   # (the pairs' strides stay even)
+    out = PX.strided(np.full((2, dh, dw, 3), 33, np.uint8), (20, 7))
+    strides = [ty.stride(0), ty.stride(1), tuv.stride(0), tuv.stride(1), out.stride(0), out.stride(1)]
+    assert len(set(strides + [sh * sw, sw, sh // 2 * sw, dh * dw * 3, dw * 3])) == 11
+    assert W.warp_perspective_nv12(ty, tuv, Ms, (dw, dh), flags=interp, out=out) is out
+    torch.cuda.synchronize()
+    exp = [R.warp_nv12(ys[i], uvs[i], Ms[i], (dw, dh), interp) for i in range(2)]
+    np.testing.assert_array_equal(out.cpu().numpy(), np.stack(exp))
+    assert not np.array_equal(exp[0], R.warp_nv12(ys[0], uvs[0], Ms[1], (dw, dh), interp))  # (the two matrices give different frames)
+
+
 @pytest.mark.parametrize("align", [16, 0], ids=["wide_stores", "pixel_stores"])
 @pytest.mark.parametrize("interp", [NEAREST, LINEAR], ids=["nearest", "linear"])
 def test_destination_layouts_keep_their_canaries(W, interp, align):

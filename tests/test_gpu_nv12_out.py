@@ -230,6 +230,34 @@ def test_layouts(W, interp):
     assert not np.array_equal(R.warp_to_nv12(bgrs[1], Ms[1], (dw, dh), interp)[0], R.warp_to_nv12(bgrs[1], M, (dw, dh), interp)[0])
 
 
+@pytest.mark.parametrize("source", ["bgr", "nv12"])
+@pytest.mark.parametrize("interp", [NEAREST, LINEAR], ids=["nearest", "linear"])
+def test_two_frames_two_matrices_every_stride_padded(W, interp, source):
+    """What an entry point's argument filling can get wrong -- a swapped or dropped stride or pointer -- in the smallest shape that shows
+    it: two frames with a matrix each, row and frame strides of every image that all differ from the tight ones and from each other, a
+    destination of two tile columns (260 > 256) and two tile rows (6 > 4)."""
+    sw, sh, dw, dh = 12, 10, 260, 6
+    frames = [RI.frame("uniform", 70 + i, sh, sw) for i in range(2)]
+    ys, uvs = np.stack([f[0] for f in frames]), np.stack([f[1] for f in frames])
+    H = wl.keystone_H(sw, sh, dw, dh)
+    Ms = np.stack([wl.jitter_H(H, 1), wl.jitter_H(H, 2)])
+    ty, tuv = PX.strided(ys, (9, 5)), PX.strided(uvs, (10, 6))   # (the pairs' strides stay even)
+    bgrs = np.stack([RI.nv12_to_bgr(*f) for f in frames])
+    tb = PX.strided(bgrs, (40, 3))
+    oy, ouv = PX.strided(np.full((2, dh, dw), 33, np.uint8), (11, 7)), PX.strided(np.full((2, dh // 2, dw // 2, 2), 33, np.uint8), (4, 8))
+    strides = [t.stride(0) for t in (ty, tuv, tb, oy, ouv)] + [t.stride(1) for t in (ty, tuv, tb, oy, ouv)]
+    assert len(set(strides + [sh * sw, sw, sh // 2 * sw, sh * sw * 3, sw * 3, dh * dw, dw, dh // 2 * dw])) == 18
+    if source == "bgr":
+        W.warp_perspective_to_nv12(tb, Ms, (dw, dh), flags=interp, out=(oy, ouv))
+        ref = lambda i, k: R.warp_to_nv12(bgrs[i], Ms[k], (dw, dh), interp)  # noqa: E731
+    else:
+        W.warp_nv12_to_nv12(ty, tuv, Ms, (dw, dh), flags=interp, out=(oy, ouv))
+        ref = lambda i, k: R.warp_nv12_to_nv12(ys[i], uvs[i], Ms[k], (dw, dh), interp)  # noqa: E731
+    exp = [ref(i, i) for i in range(2)]
+    same(host(W, (oy, ouv)), tuple(np.stack(p) for p in zip(*exp)), "%s source, padded strides" % source)
+    assert not np.array_equal(exp[0][0], ref(0, 1)[0])  # (the two matrices give different frames)
+
+
 def canaried_planes(batch, dh, dw, align):
     """Both destination planes inside holders of their own whose every other byte is PX.CANARY.  align 16: both admit the 4-byte stores;
     0: the Y plane's base and row stride are odd (byte stores) and the UV plane's base is 2 mod 4 (16-bit stores: 2 is the contract)."""

@@ -203,6 +203,29 @@ def test_source_layouts(W, interp, dtype):
         check(W, ys, uvs, Ms, (120, 37), interp, scale, bias, dtype=dtype, layout=layout, exp=exp, what="batch")
 
 
+@pytest.mark.parametrize("interp", [NEAREST, LINEAR], ids=["nearest", "linear"])
+def test_two_frames_two_matrices_every_stride_padded(W, interp):
+    """What an entry point's argument filling can get wrong -- a swapped or dropped stride or pointer -- in the smallest shape that shows
+    it: two frames with a matrix each, row, plane and frame strides of every image that all differ from the tight ones and from each other, a
+    destination of two tile columns (260 > 256) and two tile rows (6 > 4)."""
+    sw, sh, dw, dh = 12, 10, 260, 6
+    frames = [R.frame("uniform", 70 + i, sh, sw) for i in range(2)]
+    ys, uvs = np.stack([f[0] for f in frames]), np.stack([f[1] for f in frames])
+    H = wl.keystone_H(sw, sh, dw, dh)
+    Ms = np.stack([wl.jitter_H(H, 1), wl.jitter_H(H, 2)])
+    ty, tuv = PX.strided(ys, (9, 5)), PX.strided(uvs, (10, 6))   # (the pairs' strides stay even)
+    out = PX.strided(np.full((2, 3, dh, dw), -7.5, np.float32), (24, 12, 4), fill=-3.0)
+    strides = [ty.stride(0), ty.stride(1), tuv.stride(0), tuv.stride(1)] + [4 * v for v in out.stride()[:3]]   # bytes
+    assert len(set(strides + [sh * sw, sw, sh // 2 * sw, 4 * 3 * dh * dw, 4 * dh * dw, 4 * dw])) == 13
+    scale, bias = IMAGENET
+    got = W.warp_nv12_to_planar(ty, tuv, Ms, (dw, dh), scale=scale, bias=bias, flags=interp, out=out, rgb=True, out_dtype=F32)
+    torch.cuda.synchronize()
+    assert got is out
+    exp = expected(ys, uvs, Ms, (dw, dh), interp, scale, bias, rgb=True)
+    same(out, exp, F32, "padded strides")
+    assert not np.array_equal(exp[0], expected(ys[0], uvs[0], Ms[1], (dw, dh), interp, scale, bias, rgb=True))  # (the two matrices give different frames)
+
+
 @pytest.mark.parametrize("rgb", [False, True], ids=["bgr", "rgb"])
 @pytest.mark.parametrize("interp", [NEAREST, LINEAR], ids=["nearest", "linear"])
 def test_edges_inside_padded_allocations(W, interp, rgb):

@@ -1,38 +1,20 @@
 """The launch planning of the C ABI (bev_amd/csrc/host_plan.h) on the CPU: tests/host_plan_driver.cpp is compiled with g++ under the
-address and undefined-behaviour sanitizers and run as a subprocess.  tests/golden/launch_plans.json pins every field of the plans
+address and undefined-behaviour sanitizers and run as a subprocess (tests/hostplan.py).  tests/golden/launch_plans.json pins every field of the plans
 (recorded from the last commit that planned inside bevwarp_api.hip; tests/golden/make_launch_plans.py)."""
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from bev_amd import _lib
+from tests.hostplan import build_driver, built_lib, run_driver
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURE = os.path.join(ROOT, "tests", "golden", "launch_plans.json")
 PLAN_FIELDS = ("tile_h", "tiles_x", "tiles_per_frame", "total_tiles", "chunk", "stagger", "tail_split", "bw0", "tpf_magic", "tx_magic", "bw0_magic")
 PERIOD_FIELDS = ("per_x", "off_x", "mag_x", "per_y", "off_y", "mag_y")
 TOO_LARGE = -3
-
-
-def build_driver(tmpdir):
-    """(-static-libasan: a process that starts with some library preloaded refuses a shared sanitizer runtime that is not the first one)"""
-    exe = os.path.join(str(tmpdir), "host_plan_driver")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-Wall", "-Werror",
-                           "-I", os.path.join(ROOT, "bev_amd", "csrc"), "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "host_plan_driver.cpp"), "-o", exe])
-    return exe
-
-
-def run_driver(exe, lines):
-    """One list of integers per case line.  Any sanitizer report ends the driver with a non-zero status and fails the caller."""
-    r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and not r.stderr, (r.returncode, r.stderr[-3000:])
-    out = [[int(v) for v in ln.split()] for ln in r.stdout.splitlines()]
-    assert len(out) == len(lines)
-    return out
 
 
 def load_fixture():
@@ -80,13 +62,13 @@ def plans_from_driver(exe, cases):
 
 
 @pytest.fixture(scope="module")
-def driver(tmp_path_factory):
-    return build_driver(tmp_path_factory.mktemp("host_plan"))
+def driver():
+    return build_driver()
 
 
 @pytest.fixture(scope="module")
 def lib():
-    return _lib.load()
+    return built_lib()
 
 
 def test_fixture_takes_every_branch_of_the_planner():

@@ -1,17 +1,16 @@
 """The NV12 warp (bevwarp_warp_nv12, warp_perspective_nv12, FramePipeline(src_format="nv12")) without a device: the conversion formula's
 known answers and its whole domain, the entry point's argument validation with pointers that are never dereferenced, the Python layer's
-argument errors, host_plan.h's check_warp_nv12 at its limits in a stand-alone driver under the address and undefined-behaviour
-sanitizers (tests/nv12_plan_driver.cpp), and the compiled kernels' register and scratch figures."""
+argument errors, host_plan.h's checks of an nv12_call at their limits in a stand-alone driver under the address and undefined-behaviour
+sanitizers (tests/host_plan_driver.cpp), and the compiled kernels' register and scratch figures."""
 import ctypes
 import os
-import subprocess
-
 import numpy as np
 import pytest
 import torch
 
 from bev_amd import _lib
 from tests import codeobj
+from tests import hostplan
 from tests import nv12_ref as R
 from tests.test_abi import declared_symbols
 
@@ -24,9 +23,7 @@ KNOWN = [((16, 128, 128), (0, 0, 0)), ((235, 128, 128), (255, 255, 255)), ((126,
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    return _lib.load()
+    return hostplan.built_lib()
 
 
 # ---- the reference conversion ---------------------------------------------------------------------------------------------------------
@@ -205,24 +202,14 @@ def test_python_argument_errors_without_a_device():
         cv2.cvtColor(np.zeros((12, 8, 3), np.uint8), cv2.COLOR_YUV2BGR_NV12)
 
 
-# ---- host_plan.h's check_warp_nv12 under the sanitizers ---------------------------------------------------------------------------------
+# ---- host_plan.h's checks of an nv12_call under the sanitizers ---------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def driver(tmp_path_factory):
-    """(-static-libasan: a process that starts with some library preloaded refuses a shared sanitizer runtime that is not the first one)"""
-    exe = os.path.join(str(tmp_path_factory.mktemp("nv12_plan")), "nv12_plan_driver")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-Wall", "-Werror",
-                           "-I", os.path.join(ROOT, "bev_amd", "csrc"), "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "nv12_plan_driver.cpp"), "-o", exe])
-    return exe
+def driver():
+    return hostplan.build_driver()
 
 
 def run_driver(exe, cases):
-    lines = ["nv12 " + " ".join(str(int(v)) for v in c) for c in cases]
-    r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and not r.stderr, (r.returncode, r.stderr[-3000:])  # (any sanitizer report ends the driver with a non-zero status)
-    out = [[int(v) for v in ln.split()] for ln in r.stdout.splitlines()]
-    assert len(out) == len(cases)
-    return out
+    return hostplan.run_driver(exe, ["nv12 " + " ".join(str(int(v)) for v in c) for c in cases])
 
 
 def model(y, uv, dst, batch, sh, sw, dh, dw, yfs, yrs, uvfs, uvrs, dfs, drs, mc, interp, rgb):

@@ -1,18 +1,17 @@
 """The warps into NV12 (bevwarp_warp_to_nv12, bevwarp_warp_nv12_to_nv12; warp_perspective_to_nv12, warp_nv12_to_nv12;
 FramePipeline(dst_format="nv12")) without a device: the conversion formula's known answers, its whole domain and its chroma siting, the
 entry points' argument validation with pointers that are never dereferenced, the Python layer's argument errors, host_plan.h's
-check_warp_to_nv12 / check_warp_nv12_to_nv12 at their limits in a stand-alone driver under the address and undefined-behaviour sanitizers
-(tests/nv12_out_plan_driver.cpp), and the compiled kernels' register and scratch figures."""
+checks of a to_nv12_call / nv12_to_nv12_call at their limits in a stand-alone driver under the address and undefined-behaviour sanitizers
+(tests/host_plan_driver.cpp), and the compiled kernels' register and scratch figures."""
 import ctypes
 import os
-import subprocess
-
 import numpy as np
 import pytest
 import torch
 
 from bev_amd import _lib
 from tests import codeobj
+from tests import hostplan
 from tests import nv12_out_ref as R
 from tests import nv12_ref
 from tests.test_abi import declared_symbols
@@ -26,9 +25,7 @@ KNOWN = [((0, 0, 0), (16, 128, 128)), ((255, 255, 255), (235, 128, 128)), ((128,
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    return _lib.load()
+    return hostplan.built_lib()
 
 
 # ---- the reference conversion ---------------------------------------------------------------------------------------------------------
@@ -264,22 +261,12 @@ def test_python_argument_errors_without_a_device():
 
 # ---- host_plan.h's checks under the sanitizers ------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def driver(tmp_path_factory):
-    """(-static-libasan: a process that starts with some library preloaded refuses a shared sanitizer runtime that is not the first one)"""
-    exe = os.path.join(str(tmp_path_factory.mktemp("nv12_out_plan")), "nv12_out_plan_driver")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-Wall", "-Werror",
-                           "-I", os.path.join(ROOT, "bev_amd", "csrc"), "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "nv12_out_plan_driver.cpp"), "-o", exe])
-    return exe
+def driver():
+    return hostplan.build_driver()
 
 
 def run_driver(exe, cases):
-    lines = [c[0] + " " + " ".join(str(int(v)) for v in c[1:]) for c in cases]
-    r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and not r.stderr, (r.returncode, r.stderr[-3000:])  # (any sanitizer report ends the driver with a non-zero status)
-    out = [[int(v) for v in ln.split()] for ln in r.stdout.splitlines()]
-    assert len(out) == len(cases)
-    return out
+    return hostplan.run_driver(exe, [c[0] + " " + " ".join(str(int(v)) for v in c[1:]) for c in cases])
 
 
 def model(sources, dsts, batch, sh, sw, dh, dw, mc, interp, rgb, nv12):
@@ -341,11 +328,11 @@ def test_checks_at_their_limits_under_the_sanitizer(driver):
         dyfs, duvfs = (tight(dh, dyrs) if dyfs is None else dyfs), (tight(dh // 2, duvrs) if duvfs is None else duvfs)
         dsts = [(dy, dh, dw, dyrs, dyfs, 1), (duv, dh // 2 if dh >= 0 else -(-dh // 2), dw, duvrs, duvfs, 2)]
         if nv12:
-            cases.append(("nv12", y, uv, dy, duv, batch, sh, sw, dh, dw, yfs, yrs, uvfs, uvrs, dyfs, dyrs, duvfs, duvrs, mc, interp))
+            cases.append(("nv12_to_nv12", y, uv, dy, duv, batch, sh, sw, dh, dw, yfs, yrs, uvfs, uvrs, dyfs, dyrs, duvfs, duvrs, mc, interp))
             sources = [((y, sh, sw, yrs, yfs, 1), sw), ((uv, sh // 2, sw, uvrs, uvfs, 2), sw // 2)]
             rgb = 0
         else:
-            cases.append(("bgr", src, dy, duv, batch, sh, sw, dh, dw, sfs, srs, dyfs, dyrs, duvfs, duvrs, mc, interp, rgb))
+            cases.append(("to_nv12", src, dy, duv, batch, sh, sw, dh, dw, sfs, srs, dyfs, dyrs, duvfs, duvrs, mc, interp, rgb))
             sources = [((src, sh, 3 * sw, srs, sfs, 1), sw)]
         expect.append((model(sources, dsts, batch, sh, sw, dh, dw, mc, interp, rgb, nv12), dsts, batch, dh, dw))
 
@@ -416,7 +403,7 @@ def test_checks_at_their_limits_under_the_sanitizer(driver):
                 assert nums[3] == -3, (case, nums)
             else:
                 assert nums[3:] == [0, tiles], (case, nums)
-    for kind in ("bgr", "nv12"):
+    for kind in ("to_nv12", "nv12_to_nv12"):
         statuses = [n[0] for c, n in zip(cases, got) if c[0] == kind]
         assert statuses.count(0) > 60 and statuses.count(-1) > 40 and statuses.count(-2) >= 10 and statuses.count(-3) >= 10 and statuses.count(-6) >= 30, \
             (kind, [statuses.count(s) for s in (0, -1, -2, -3, -6)])

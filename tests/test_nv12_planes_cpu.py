@@ -1,19 +1,18 @@
 """NV12 frames warped straight to channel planes (bevwarp_warp_nv12_planes, warp_nv12_to_planar) without a device: the symbol, the entry
 point's argument validation with pointers that are never dereferenced (one case per status, in the documented order), the Python layer's
-argument errors, host_plan.h's check_warp_nv12_planes at its limits in a stand-alone driver under the address and undefined-behaviour
-sanitizers (tests/nv12_planes_plan_driver.cpp) against an exact-integer model, and the compiled kernels' register, scratch and LDS
+argument errors, host_plan.h's checks of an nv12_planes_call at their limits in a stand-alone driver under the address and undefined-behaviour
+sanitizers (tests/host_plan_driver.cpp) against an exact-integer model, and the compiled kernels' register, scratch and LDS
 figures."""
 import ctypes
 import os
 import re
-import subprocess
-
 import numpy as np
 import pytest
 import torch
 
 from bev_amd import _lib
 from tests import codeobj
+from tests import hostplan
 from tests.test_abi import declared_symbols
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,9 +22,7 @@ ELEM = {_lib.F32: 4, _lib.F16: 2, _lib.BF16: 2}  # bytes of a plane element; any
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    return _lib.load()
+    return hostplan.built_lib()
 
 
 # ---- the ABI without a device -------------------------------------------------------------------------------------------------------
@@ -162,24 +159,14 @@ def test_python_argument_errors_without_a_device():
     assert "FramePipeline" in f.__doc__ and "M_inv_device" in f.__doc__
 
 
-# ---- host_plan.h's check_warp_nv12_planes under the sanitizers ---------------------------------------------------------------------------
+# ---- host_plan.h's checks of an nv12_planes_call under the sanitizers ---------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def driver(tmp_path_factory):
-    """(-static-libasan: a process that starts with some library preloaded refuses a shared sanitizer runtime that is not the first one)"""
-    exe = os.path.join(str(tmp_path_factory.mktemp("nv12_planes_plan")), "nv12_planes_plan_driver")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-Wall", "-Werror",
-                           "-I", os.path.join(ROOT, "bev_amd", "csrc"), "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "nv12_planes_plan_driver.cpp"), "-o", exe])
-    return exe
+def driver():
+    return hostplan.build_driver()
 
 
 def run_driver(exe, cases):
-    lines = ["nv12p " + " ".join(str(int(v)) for v in c) for c in cases]
-    r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and not r.stderr, (r.returncode, r.stderr[-3000:])  # (any sanitizer report ends the driver with a non-zero status)
-    out = [[int(v) for v in ln.split()] for ln in r.stdout.splitlines()]
-    assert len(out) == len(cases)
-    return out
+    return hostplan.run_driver(exe, ["nv12p " + " ".join(str(int(v)) for v in c) for c in cases])
 
 
 def model(y, uv, dst, batch, sh, sw, dh, dw, yfs, yrs, uvfs, uvrs, dfs, dps, drs, mc, interp, rgb, pd):

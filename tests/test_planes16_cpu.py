@@ -1,16 +1,15 @@
 """float16 / bfloat16 channel planes (bevwarp_warp_planes, warp_to_planar(out_dtype=...)) without a device: the reference conversions of
 tests/planes16_ref.py against torch's CPU conversions (two independent statements of the rounding), the new entry point's argument
 validation with pointers that are never dereferenced, warp_to_planar's argument checks, and host_plan.h's checks for 2-byte planes in a
-stand-alone driver under the address and undefined-behaviour sanitizers (tests/planes16_plan_driver.cpp)."""
+stand-alone driver under the address and undefined-behaviour sanitizers (tests/host_plan_driver.cpp)."""
 import ctypes
 import os
-import subprocess
-
 import numpy as np
 import pytest
 import torch
 
 from bev_amd import _lib
+from tests import hostplan
 from tests import planes16_ref as R
 from tests.test_abi import declared_symbols
 
@@ -20,9 +19,7 @@ DTYPES = [torch.float16, torch.bfloat16]
 
 @pytest.fixture(scope="module")
 def lib():
-    if not os.path.exists(_lib.LIB_PATH):
-        _lib.build()
-    return _lib.load()
+    return hostplan.built_lib()
 
 
 def torch_bits(a, dtype):
@@ -143,22 +140,12 @@ def test_warp_to_planar_checks_out_dtype_before_it_needs_a_device():
 
 # ---- host_plan.h for 2-byte planes, under the sanitizers ------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def driver(tmp_path_factory):
-    """(-static-libasan: a process that starts with some library preloaded refuses a shared sanitizer runtime that is not the first one)"""
-    exe = os.path.join(str(tmp_path_factory.mktemp("planes16_plan")), "planes16_plan_driver")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-Wall", "-Werror",
-                           "-I", os.path.join(ROOT, "bev_amd", "csrc"), "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "planes16_plan_driver.cpp"), "-o", exe])
-    return exe
+def driver():
+    return hostplan.build_driver()
 
 
 def run_driver(exe, cases):
-    lines = ["planes %d %d %d %d %d %d %d %d %d %d" % c for c in cases]
-    r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and not r.stderr, (r.returncode, r.stderr[-3000:])  # (any sanitizer report ends the driver with a non-zero status)
-    out = [[int(v) for v in ln.split()] for ln in r.stdout.splitlines()]
-    assert len(out) == len(cases)
-    return out
+    return hostplan.run_driver(exe, ["planes %d %d %d %d %d %d %d %d %d %d" % c for c in cases])
 
 
 def model(src, dst, batch, c, dh, dw, fs, ps, rs, elem):
