@@ -27,6 +27,9 @@ SYMBOLS = {
     "bevwarp_warp_border": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
                                        _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int,
                                        _c.c_int, _c.c_void_p, _c.c_void_p]),
+    "bevwarp_warp_lens": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
+                                     _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_double,
+                                     _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p]),
     "bevwarp_warp_classes": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
                                         _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int,
                                         _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p]),

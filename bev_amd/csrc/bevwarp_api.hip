@@ -12,6 +12,7 @@
 #include "warp_border.h"
 #include "warp_cubic.h"
 #include "warp_kernels.h"
+#include "warp_lens.h"
 #include "warp_nv12.h"
 #include "warp_nv12_out.h"
 
@@ -218,6 +219,28 @@ int bevwarp_warp_border(const void* src, void* dst, int batch, int src_h, int sr
     if (!cubic) return launched(launch_warp_border(a, dtype, channels, interp, border_mode, items, (hipStream_t)stream));
     if (border_values(border_mode == BEVWARP_BORDER_CONSTANT ? border_value : nullptr, channels, a.cv_f, a.cv_u8) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
     return launched(launch_warp_cubic(a, dtype, channels, border_mode, items, (hipStream_t)stream));
+}
+
+int bevwarp_warp_lens(const void* src, void* dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int channels, int64_t src_frame_stride,
+                      int64_t src_row_stride, int64_t dst_frame_stride, int64_t dst_row_stride, const double* M_ray, int m_count, const double* lens,
+                      double r2_max, int dtype, int interp, int border_mode, const double* border_value, void* stream) {
+    const Call c = plan::lens_call({src, src_frame_stride, src_row_stride}, {dst, dst_frame_stride, dst_row_stride}, {batch, src_h, src_w, dst_h, dst_w, m_count, M_ray},
+                                   channels, dtype, interp, border_mode);
+    LensArgs a;
+    int64_t items;
+    int st = flat_grid_args(c, a, items);
+    if (!items) return st;
+    if ((st = plan::lens_status(lens, r2_max)) != BEVWARP_OK) return st;
+    const bool transparent = border_mode == BEVWARP_BORDER_TRANSPARENT;
+    uint8_t bu[4];  // (border_value is read by the constant border only)
+    if (border_values(transparent ? nullptr : border_value, channels, a.bv_f, bu) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
+    a.bv_u8 = (uint32_t)bu[0] | ((uint32_t)bu[1] << 8) | ((uint32_t)bu[2] << 16) | ((uint32_t)bu[3] << 24);
+    a.src = (const uint8_t*)src, a.src_fs = src_frame_stride, a.src_rs = src_row_stride;
+    memcpy(a.lens, lens, sizeof(a.lens));
+    a.r2_max = r2_max;
+    a.dst_vec_ok = plan::wide_stores_ok(c.writes[0], plan::store_align(dtype, channels, false));
+    a.src_vec_ok = plan::pixel_loads_ok(c.reads[0].im, plan::pixel_load_align(dtype, channels));
+    return launched(launch_warp_lens(a, dtype, channels, interp, transparent, items, (hipStream_t)stream));
 }
 
 int bevwarp_warp_nv12(const void* y, const void* uv, void* dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int64_t y_frame_stride,

@@ -107,8 +107,8 @@ struct Nv12Images {
 };
 inline Nv12Images nv12_images(Frames y, Frames uv, int h, int w, int batch) { return {y.image(h, (uint64_t)w, batch), uv.image(h / 2, (uint64_t)w, batch)}; }
 
-// What the checks need of one entry point's arguments.  The functions of the last part of this section describe the nine entry points in
-// these terms; bevwarp_api.hip and tests/host_plan_driver.cpp both build their calls with them.
+// What the checks need of one entry point's arguments.  The functions of the last part of this section describe the ten entry points in
+// these terms; bevwarp_api.hip and the tests' drivers (tests/host_plan_driver.cpp, tests/lens_plan_driver.cpp) build their calls with them.
 struct Sizes {  // (what every entry point passes besides its images and its format)
     int batch, src_h, src_w, dst_h, dst_w, m_count;
     const double* minv;
@@ -222,6 +222,20 @@ inline Call warp_call(Frames src, Frames dst, const Sizes& z, int channels, int 
     else
         c.write(dst.image(z.dst_h, (uint64_t)z.dst_w * channels * elem, z.batch), elem);
     return c;
+}
+// bevwarp_warp_lens: bevwarp_warp's images and formats without bicubic, with the constant and the transparent border
+inline Call lens_call(Frames src, Frames dst, const Sizes& z, int channels, int dtype, int interp, int border_mode) {
+    Call c = warp_call(src, dst, z, channels, dtype, interp, false);
+    c.format_ok = c.format_ok && (border_mode == BEVWARP_BORDER_CONSTANT || border_mode == BEVWARP_BORDER_TRANSPARENT);
+    return c;
+}
+// ... and its lens (HOST: fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6) and r2_max (+inf: no limit), which check_call does not see
+inline int lens_status(const double lens[12], double r2_max) {
+    if (!lens) return BEVWARP_ERR_BAD_ARG;
+    for (int i = 0; i < 12; i++)
+        if (!isfinite(lens[i])) return BEVWARP_ERR_NOT_FINITE;
+    if (lens[0] == 0.0 || lens[1] == 0.0 || !(r2_max >= 0.0)) return BEVWARP_ERR_BAD_ARG;  // (a NaN r2_max fails the comparison)
+    return BEVWARP_OK;
 }
 // What the four NV12 entry points share: nearest or bilinear, B, G, R or R, G, B.  Each adds its images.
 inline Call nv12_family_call(const Sizes& z, int interp, int rgb_order, bool plane_ok = true) {

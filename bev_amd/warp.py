@@ -310,6 +310,141 @@ def warp_perspective(src, M, dsize, flags=INTER_LINEAR, border_value=None, out=N
     return d4
 
 
+def _intrinsics(K):
+    """(fx, fy, cx, cy) of a 3x3 or 3x4 camera matrix without skew."""
+    K = np.asarray(K, dtype=np.float64)
+    if K.shape not in ((3, 3), (3, 4)):
+        raise ValueError("K must be 3x3 or 3x4, got %s" % (K.shape,))
+    if K[0, 1] != 0.0:
+        raise ValueError("K has skew (K[0, 1] = %r): the lens warp takes fx, fy, cx, cy only" % (K[0, 1],))
+    return float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])
+
+
+def ray_matrix(M, K, inverse_given=False):
+    """The matrix bevwarp_warp_lens takes: destination pixel -> normalised undistorted camera plane, inv(K) @ inv(M) written out.
+    M (3, 3) or (..., 3, 3): the forward map from UNDISTORTED source pixels to destination pixels (inverse_given: its inverse);
+    K: 3x3 or 3x4 camera matrix, no skew (ValueError).  With rows m0, m1, m2 of the inverse:
+    R = [(m0 - cx m2) / fx, (m1 - cy m2) / fy, m2], elementwise in float64.  Returns float64 of M's shape."""
+    fx, fy, cx, cy = _intrinsics(K)
+    Minv = np.ascontiguousarray(M, dtype=np.float64) if inverse_given else invert_homography(M)
+    if Minv.shape[-2:] != (3, 3):
+        raise ValueError("M must be (..., 3, 3), got %s" % (Minv.shape,))
+    m0, m1, m2 = Minv[..., 0, :], Minv[..., 1, :], Minv[..., 2, :]
+    return np.stack([(m0 - cx * m2) / fx, (m1 - cy * m2) / fy, m2], axis=-2)
+
+
+def _dist8(dist_coeff):
+    """dist_coeff (None, or 4, 5 or 8 values in OpenCV's order) as (k1, k2, p1, p2, k3, k4, k5, k6)."""
+    out = np.zeros(8, dtype=np.float64)
+    if dist_coeff is not None:
+        d = np.asarray(dist_coeff, dtype=np.float64).ravel()
+        if d.size not in (4, 5, 8):
+            raise ValueError("dist_coeff must hold 4, 5 or 8 values (k1, k2, p1, p2[, k3[, k4, k5, k6]]), got %d" % d.size)
+        out[:d.size] = d
+    return out
+
+
+def lens_valid_r2(dist_coeff):
+    """The squared radius (normalised camera plane) up to which the radial lens model is monotonic and finite: what
+    warp_perspective_lens passes as r2_max.  With s = r^2, N = 1 + k1 s + k2 s^2 + k3 s^3 and D = 1 + k4 s + k5 s^2 + k6 s^3, the
+    distorted radius r N / D stops growing where (N + 2 s N') D - 2 s N D' = 0 and has a pole where D = 0: the smallest positive
+    real root of either, `inf` if there is none.  Beyond it the model folds back and maps far-away destination pixels INTO the
+    frame -- ghost copies of it.  Host numpy (companion-matrix roots).  The tangential terms p1, p2 are ignored: they shift the
+    fold by an amount of their own order, and the radius is a guard, not a calibration."""
+    k1, k2, _, _, k3, k4, k5, k6 = _dist8(dist_coeff)
+    P = np.polynomial.polynomial
+    N, D = np.array([1.0, k1, k2, k3]), np.array([1.0, k4, k5, k6])
+    s2 = np.array([0.0, 2.0])
+    fold = P.polysub(P.polymul(P.polyadd(N, P.polymul(s2, P.polyder(N))), D), P.polymul(P.polymul(s2, N), P.polyder(D)))
+    best = np.inf
+    for poly in (fold, D):
+        c = np.trim_zeros(poly, "b")
+        if c.size < 2:
+            continue
+        for r in P.polyroots(c):
+            if abs(r.imag) <= 1e-9 * max(1.0, abs(r.real)) and r.real > 0.0:
+                best = min(best, float(r.real))
+    return best
+
+
+def lens_from_calib(calib):
+    """(K, dist_coeff) of a Calib for warp_perspective_lens: calib.K as float64 and calib.dist_coeff (None gives five zeros).
+    A Calib without K -- `from_pts` mode pins the homography alone -- raises ValueError."""
+    if getattr(calib, "K", None) is None:
+        raise ValueError("this Calib has no K (mode %r): a lens model needs the camera matrix" % (getattr(calib, "mode", None),))
+    d = calib.dist_coeff
+    return np.asarray(calib.K, dtype=np.float64), (np.zeros(5) if d is None else np.asarray(d, dtype=np.float64).ravel())
+
+
+def warp_perspective_lens(src, M, dsize, K, dist_coeff, flags=INTER_LINEAR, border_value=None, out=None, border_mode=BORDER_CONSTANT, r2_max=None):
+    """warp_perspective of the frames a distorted camera delivers: what cv2.undistort(src, K, dist_coeff) followed by
+    cv2.warpPerspective(undistorted, M, dsize) is for, with the lens model folded into the coordinate chain -- one launch, one
+    resampling of the raw frame, no undistorted frame in memory (include/bevwarp.h, bevwarp_warp_lens; not bit-equal to the cv2 pair,
+    which resamples twice).
+
+    src, dsize, border_value, out   as warp_perspective.
+    M        forward map from UNDISTORTED source pixels to destination pixels, (3, 3) or (B, 3, 3) (host): exactly what
+             warp_perspective takes for frames that went through cv2.undistort; flags | WARP_INVERSE_MAP: the dst -> src map.
+    K        3x3 or 3x4 camera matrix of the raw frames, no skew.
+    dist_coeff   None, or 4, 5 or 8 values in OpenCV's order (k1, k2, p1, p2[, k3[, k4, k5, k6]]): the rational model; thin-prism,
+             tilt and fisheye terms are not taken.  None or all zero: the call IS warp_perspective(src, M, dsize, ...), bit for bit.
+    flags    INTER_LINEAR (default) or INTER_NEAREST, optionally | WARP_INVERSE_MAP.
+    border_mode   BORDER_CONSTANT (default) or BORDER_TRANSPARENT.
+    r2_max   destination pixels whose squared radius on the normalised camera plane exceeds it are outside the frame; None:
+             lens_valid_r2(dist_coeff), which keeps the model's fold-back from painting ghost copies; float("inf"): no limit.
+    Asynchronous on the current stream.  No verdict tables, no plan cache: the lens and r2_max travel with every call (the ray
+    matrices are uploaded through device_inverse's by-value cache, which holds matrices only)."""
+    dist = _dist8(dist_coeff)
+    if not dist.any():
+        return warp_perspective(src, M, dsize, flags=flags, border_value=border_value, out=out, border_mode=border_mode)
+    if border_mode not in (BORDER_CONSTANT, BORDER_TRANSPARENT):
+        raise ValueError("unsupported border mode %r (warp_perspective_lens: BORDER_CONSTANT, BORDER_TRANSPARENT)" % (border_mode,))
+    border_mode = int(border_mode)
+    interp = int(flags) & 7
+    if interp not in (INTER_NEAREST, INTER_LINEAR):
+        raise ValueError("unsupported interpolation flag %d (warp_perspective_lens: INTER_NEAREST, INTER_LINEAR)" % interp)
+    if not isinstance(src, torch.Tensor) or not src.is_cuda or src.dtype not in _DTYPES:
+        raise ValueError("warp_perspective_lens needs a uint8 or float32 CUDA (HIP) tensor")
+    if src.dim() == 2:
+        s4 = src[None, :, :, None]
+    elif src.dim() == 3:
+        s4 = src[None]
+    elif src.dim() == 4:
+        s4 = src
+    else:
+        raise ValueError("src must be (B,H,W,C), (H,W,C) or (H,W)")
+    B, H, W, C = s4.shape
+    if s4.stride(3) != 1 or s4.stride(2) != C:
+        s4 = s4.contiguous()
+    dw, dh = int(dsize[0]), int(dsize[1])
+    esz = s4.element_size()
+    Mh = M.detach().cpu().numpy() if isinstance(M, torch.Tensor) else M
+    R = ray_matrix(Mh, K, inverse_given=bool(int(flags) & WARP_INVERSE_MAP))
+    M_ray = device_inverse(R, s4.device, inverse_given=True)
+    n_m = _check_minv(M_ray, s4.device, B)
+    lens = np.ascontiguousarray(np.concatenate([_intrinsics(K), dist]), dtype=np.float64)
+    r2 = lens_valid_r2(dist) if r2_max is None else float(r2_max)
+    if out is None:
+        d4 = (torch.zeros if border_mode == BORDER_TRANSPARENT else torch.empty)((B, dh, dw, C), dtype=s4.dtype, device=s4.device)
+    else:
+        _check_out(out, s4.dtype, s4.device, B * dh * dw * C)
+        d4 = out.reshape(B, dh, dw, C)
+        if d4.data_ptr() != out.data_ptr() or d4.stride(3) != 1 or d4.stride(2) != C:
+            raise ValueError("out must be a contiguous-row channels-last tensor")
+    bv = _border(border_value, C) if border_mode == BORDER_CONSTANT else None
+    stream = torch.cuda.current_stream(s4.device).cuda_stream
+    with torch.cuda.device(s4.device):
+        st = _lib.load().bevwarp_warp_lens(s4.data_ptr(), d4.data_ptr(), B, H, W, dh, dw, C, s4.stride(0) * esz, s4.stride(1) * esz, d4.stride(0) * esz,
+                                           d4.stride(1) * esz, M_ray.data_ptr(), n_m, lens.ctypes.data_as(ctypes.c_void_p), r2, _DTYPES[s4.dtype], interp,
+                                           border_mode, None if bv is None else bv.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(stream))
+    _lib.check(st)
+    if out is not None:
+        return out
+    if src.dim() == 2:
+        return d4[0, :, :, 0]
+    return d4[0] if src.dim() == 3 else d4
+
+
 def _plane_format(who, flags, out_dtype, out):
     """The interpolation of a call that writes channel planes, once its flags, plane type and `out` are what the plane kernels take."""
     interp = int(flags) & 7

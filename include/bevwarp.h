@@ -9,6 +9,10 @@
  *                             vis_homo.py:89, vis_homo.py:91, bev/tool/compo.py:38,46,47
  *   bevwarp_warp_border     cv2.warpPerspective(img, H, dsize, dst, flags, borderMode): the drop-in surface's other borders
  *                             (the reference passes none; stitching cameras with BORDER_TRANSPARENT needs one)
+ *   bevwarp_warp_lens       cv2.undistort(img, K, dist_coeff) + cv2.warpPerspective(undist, H_bev_img, (u_size, v_size)) on the frames a
+ *                             camera delivers, in one resampling: Calib carries `dist_coeff` (bev/calib.py:25), Rt_from_pts_K_dist
+ *                             takes `dist_coeffs` (bev/homo.py:130-135), and the material the reference was developed on went through
+ *                             a separate undistortion pass first (KAB_SK_1_undist/..., vis_homo.py:30-31)
  *   bevwarp_warp_classes, bevwarp_tile_classes_bytes
  *                           the same call inside a camera loop (one H_bev_img, every frame of the video): vis_homo.py:85-91
  *   bevwarp_invert_homography  the cv::invert(M) step inside that call (M is the forward src->dst map)
@@ -172,6 +176,46 @@ int bevwarp_warp_border(const void *src, void *dst, int batch, int src_h, int sr
                         int64_t src_frame_stride, int64_t src_row_stride, int64_t dst_frame_stride, int64_t dst_row_stride,
                         const double *M_inv, int m_count, int dtype, int interp, int border_mode,
                         const double *border_value /*HOST*/, void *stream);
+
+/*
+ * The warp of frames as a distorted camera delivers them: the lens model is a step of the coordinate chain, and the raw frame is sampled
+ * once.  Destination pixel -> normalised undistorted camera plane (M_ray) -> distorted image point (OpenCV's rational model: k1..k6, p1,
+ * p2; no thin-prism, tilt or fisheye terms) -> the taps and the blend of bevwarp_warp_border.  This is OUR chain, the natural extension
+ * of bevwarp_warp's, not a restatement of cv2.undistort + cv2.warpPerspective (which resample twice) or of initUndistortRectifyMap
+ * (which accumulates its row terms): parity with OpenCV is unpinned.  It is bit-reproducible: every step below is one correctly rounded
+ * float64 + - * / (IEEE division, no FMA), in the order written.
+ *   M_ray         device float64, row-major 3 x 3, m_count == batch or 1: destination pixel -> normalised undistorted camera plane.  With
+ *                 M_inv the inverse homography (destination px -> undistorted source px) and K = [fx 0 cx; 0 fy cy; 0 0 1], rows
+ *                 (m0 - cx m2) / fx, (m1 - cy m2) / fy, m2 of M_inv.
+ *   lens          HOST, 12 doubles: fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6 (OpenCV's coefficient order).  One lens per call.
+ *   r2_max        HOST double: a pixel whose r2 (below) exceeds it is OUTSIDE whatever its coordinates say; +inf = no limit.  A
+ *                 polynomial lens model is not monotonic: beyond the radius where d/dr [r kr(r^2)] = 0 it folds back and paints ghost
+ *                 copies of the frame into the destination.  Callers pass that radius squared.
+ * Per destination pixel (x, y), with R = M_ray, bx the origin of its evaluation block and x1 = x - bx (blocks as in bevwarp_warp):
+ *   X0 = (R0 bx + R1 y) + R2        Y0 = (R3 bx + R4 y) + R5        W0 = (R6 bx + R7 y) + R8
+ *   Xn = X0 + R0 x1                 Yn = Y0 + R3 x1                 W  = W0 + R6 x1
+ *   Wr = (W != 0) ? 1 / W : 0       xn = Xn Wr                      yn = Yn Wr
+ *   x2 = xn xn     y2 = yn yn     r2 = x2 + y2     xy2 = 2 (xn yn)
+ *   num = 1 + ((k3 r2 + k2) r2 + k1) r2       den = 1 + ((k6 r2 + k5) r2 + k4) r2       kr = num / den
+ *   xd = (xn kr + p1 xy2) + p2 (r2 + 2 x2)    yd = (yn kr + p1 (r2 + 2 y2)) + p2 xy2
+ *   u  = fx xd + cx                           v  = fy yd + cy
+ *   nearest: X = rs(u), Y = rs(v)             bilinear: X = rs(32 u), Y = rs(32 v)      rs: clamp to int32, round half to even, NaN -> INT_MAX
+ *   valid = (r2 <= r2_max)                    (false for a NaN r2)
+ * From (X, Y) on the pixel is bevwarp_warp_border's: sx = sat16(X >> 5), fx = X & 31 (nearest: sx = sat16(X)), likewise y; the four taps,
+ * the 8-bit fixed-point and the float32 blend, and "all four taps outside -> the border value itself" are unchanged.  A pixel that is not
+ * valid is outside: BEVWARP_BORDER_CONSTANT stores the border value, BEVWARP_BORDER_TRANSPARENT neither reads nor writes it.  A pole of
+ * the rational model (den == 0) needs no special case: +-inf and NaN land on INT_MAX / INT_MIN, outside every admissible source.
+ *   dtype BEVWARP_U8 | BEVWARP_F32, channels 1..4, interp BEVWARP_NEAREST | BEVWARP_LINEAR, border_mode BEVWARP_BORDER_CONSTANT |
+ *   BEVWARP_BORDER_TRANSPARENT; anything else (BEVWARP_CUBIC, the four index-remapping borders, the 16-bit types) is
+ *   BEVWARP_ERR_UNSUPPORTED.  border_value: HOST, `channels` doubles or NULL = 0, read by BEVWARP_BORDER_CONSTANT only.
+ * Status: bevwarp_warp's checks in bevwarp_warp's order (the border mode counts as part of the format); then, for a non-empty batch,
+ * the lens: BEVWARP_ERR_BAD_ARG for a NULL lens, BEVWARP_ERR_NOT_FINITE for a lens entry that is NaN or +-inf, BEVWARP_ERR_BAD_ARG for
+ * fx == 0, fy == 0, r2_max NaN or r2_max < 0; then BEVWARP_ERR_NOT_FINITE for border_value.  batch == 0 is BEVWARP_OK and launches nothing.
+ */
+int bevwarp_warp_lens(const void *src, void *dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int channels,
+                      int64_t src_frame_stride, int64_t src_row_stride, int64_t dst_frame_stride, int64_t dst_row_stride,
+                      const double *M_ray, int m_count, const double *lens /*HOST, 12*/, double r2_max, int dtype, int interp,
+                      int border_mode, const double *border_value /*HOST*/, void *stream);
 
 /*
  * bevwarp_warp with the per-tile verdicts of an earlier launch (ABI v7).  Which way a tile is processed -- inside the frame, outside,
