@@ -7,6 +7,8 @@ import ctypes
 import os
 import subprocess
 
+import torch
+
 _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB_PATH = os.environ.get("BEVWARP_LIB") or os.path.join(_CSRC, "libbevwarp.so")  # override = A/B builds
 
@@ -107,3 +109,13 @@ def check(status):
         if status == -5:
             raise BevWarpError("%s: %s" % (msg, lib.bevwarp_last_hip_error().decode()))
         raise ValueError("libbevwarp: " + msg)
+
+
+def launch(name, device, *args):
+    """One asynchronous launch: the symbol `name` called with `args` and, appended, the current stream of `device`, with that device
+    current; a status other than 0 raises (check).  The general path of every Python entry point ends here; the validated-launch fast
+    paths (warp.warp_perspective, iou.rbox_iou, tracker_geom.tracker_geometry_step) call their bound symbol themselves."""
+    stream = torch.cuda.current_stream(device).cuda_stream
+    with torch.cuda.device(device):
+        st = getattr(load(), name)(*args, ctypes.c_void_p(stream))
+    check(st)

@@ -13,7 +13,6 @@ numpy; when any image is a tensor the result stays on the device.  Image paths a
 with cv2.imread: decoding is outside this path).
 """
 import collections
-import ctypes
 
 import numpy as np
 import torch
@@ -62,10 +61,7 @@ def composite_reg_img(bg, fg, fg_mask, bw_mode=False, device="cuda"):
     if bw_mode:
         fg = gray_bgr(fg)
     out = torch.empty_like(bg)
-    stream = torch.cuda.current_stream(bg.device).cuda_stream
-    with torch.cuda.device(bg.device):
-        _lib.check(_lib.load().bevwarp_composite(bg.data_ptr(), fg.data_ptr(), fg_mask.data_ptr(), out.data_ptr(), bg.numel(),
-                                                 ctypes.c_void_p(stream)))
+    _lib.launch("bevwarp_composite", bg.device, bg.data_ptr(), fg.data_ptr(), fg_mask.data_ptr(), out.data_ptr(), bg.numel())
     return _result(out, as_numpy)
 
 
@@ -115,11 +111,7 @@ def composite_bev_img(bg, fg, fg_mask, H_world2bev, H_img2world_fix, K, RT, x_si
     minv, H_world2img_cam = _composite_maps(H_world2bev, H_img2world_fix, K, RT, bg.device)
     C = bg.shape[2]
     out = torch.empty((int(y_size), int(x_size), C), dtype=torch.uint8, device=bg.device)
-    stream = torch.cuda.current_stream(bg.device).cuda_stream
-    with torch.cuda.device(bg.device):
-        st = _lib.load().bevwarp_warp_composite(
-            bg.data_ptr(), bg.shape[0], bg.shape[1], bg.stride(0), fg.data_ptr(), fg_mask.data_ptr(), fg.shape[0], fg.shape[1], fg.stride(0),
-            fg_mask.stride(0), out.data_ptr(), out.shape[0], out.shape[1], out.stride(0), C, minv.data_ptr(), minv.data_ptr() + 72,
-            int(bool(bw_mode)), ctypes.c_void_p(stream))
-    _lib.check(st)
+    _lib.launch("bevwarp_warp_composite", bg.device, bg.data_ptr(), bg.shape[0], bg.shape[1], bg.stride(0), fg.data_ptr(), fg_mask.data_ptr(), fg.shape[0],
+                fg.shape[1], fg.stride(0), fg_mask.stride(0), out.data_ptr(), out.shape[0], out.shape[1], out.stride(0), C, minv.data_ptr(),
+                minv.data_ptr() + 72, int(bool(bw_mode)))
     return _result(out, as_numpy), H_world2img_cam

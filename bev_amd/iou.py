@@ -1,7 +1,5 @@
 """Device rotated-box IoU: the tracker's iou_batch_rbox (reference bev/tracker/rbox_tracker.py:87-92,
 which calls d3d.box.box2d_iou(.., method="rbox")) as one HIP launch over all N x M pairs."""
-import ctypes
-
 import numpy as np
 import torch
 
@@ -47,16 +45,12 @@ def rbox_iou(a, b, out=None):
         raise ValueError("out must be a contiguous %s tensor of shape %s on %s" % (a.dtype, (a.shape[0], b.shape[0]), a.device))
     a_in, b_in = a, b
     a, b = a.contiguous(), b.contiguous()
-    stream = torch.cuda.current_stream(a.device).cuda_stream
-    fn = _lib.load().bevwarp_rbox_iou
     args = (a.data_ptr(), a.shape[0], a.shape[1], b.data_ptr(), b.shape[0], b.shape[1], out.data_ptr(), _DTYPES[a.dtype])
-    with torch.cuda.device(a.device):
-        st = fn(*args, ctypes.c_void_p(stream))
-    _lib.check(st)
+    _lib.launch("bevwarp_rbox_iou", a.device, *args)
     if key is not None and a.data_ptr() == a_in.data_ptr() and b.data_ptr() == b_in.data_ptr():  # (no copy was made on the way)
         if len(_plans) >= _PLANS_MAX:
             _plans.clear()
-        _plans[key] = (fn, args, a.device.index if a.device.index is not None else torch.cuda.current_device())
+        _plans[key] = (_lib.load().bevwarp_rbox_iou, args, a.device.index if a.device.index is not None else torch.cuda.current_device())
     return out
 
 

@@ -23,9 +23,6 @@ def project_points(pts, H, out=None):
     elif out.shape != pts.shape or out.dtype != pts.dtype or not out.is_contiguous():
         raise ValueError("out must match pts")
     Hh = np.ascontiguousarray(H.detach().cpu().numpy() if isinstance(H, torch.Tensor) else H, dtype=np.float64).reshape(3, 3)
-    stream = torch.cuda.current_stream(pts.device).cuda_stream
-    with torch.cuda.device(pts.device):
-        st = _lib.load().bevwarp_project_points(pts.data_ptr(), out.data_ptr(), pts.shape[0], pts.shape[1],
-                                                Hh.ctypes.data_as(ctypes.c_void_p), _DTYPES[pts.dtype], ctypes.c_void_p(stream))
-    _lib.check(st)
+    _lib.launch("bevwarp_project_points", pts.device, pts.data_ptr(), out.data_ptr(), pts.shape[0], pts.shape[1], Hh.ctypes.data_as(ctypes.c_void_p),
+                _DTYPES[pts.dtype])
     return out

@@ -11,12 +11,11 @@ of the "small" branch needs no resize at all (bev_amd.warp.warp_perspective_resi
 for callers that want the reference's two-step pixels.  All pixel work happens in bev_amd/csrc through the C ABI; nothing here falls
 back to the CPU.
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _lib
+from .warp import _frames, _like_src
 
 INTER_LINEAR = _lib.INTER_LINEAR
 
@@ -30,19 +29,10 @@ def resize(src, dsize, interpolation=INTER_LINEAR, out=None):
         raise ValueError("unsupported dtype %s (uint8)" % src.dtype)
     if int(interpolation) != INTER_LINEAR:
         raise ValueError("only INTER_LINEAR (cv2.resize's default, what the reference uses) is implemented")
-    if src.dim() == 2:
-        s4 = src[None, :, :, None]
-    elif src.dim() == 3:
-        s4 = src[None]
-    elif src.dim() == 4:
-        s4 = src
-    else:
-        raise ValueError("src must be (B,H,W,C), (H,W,C) or (H,W)")
+    s4, _ = _frames("resize", src, None)
     B, H, W, C = s4.shape
     if not 1 <= C <= 4:
         raise ValueError("1 to 4 channels, got %d" % C)
-    if s4.stride(3) != 1 or s4.stride(2) != C:
-        s4 = s4.contiguous()
     dw, dh = int(dsize[0]), int(dsize[1])
     if dw <= 0 or dh <= 0:
         raise ValueError("dsize must be positive, got %s" % (dsize,))
@@ -54,16 +44,9 @@ def resize(src, dsize, interpolation=INTER_LINEAR, out=None):
         d4 = out.reshape(B, dh, dw, C)
         if d4.data_ptr() != out.data_ptr() or d4.stride(3) != 1 or d4.stride(2) != C:
             raise ValueError("out must be a contiguous-row channels-last tensor")
-    stream = torch.cuda.current_stream(s4.device).cuda_stream
-    with torch.cuda.device(s4.device):
-        st = _lib.load().bevwarp_resize(s4.data_ptr(), d4.data_ptr(), B, H, W, dh, dw, C, s4.stride(0), s4.stride(1), d4.stride(0), d4.stride(1),
-                                        _lib.U8, INTER_LINEAR, ctypes.c_void_p(stream))
-    _lib.check(st)
-    if out is not None:
-        return out
-    if src.dim() == 2:
-        return d4[0, :, :, 0]
-    return d4[0] if src.dim() == 3 else d4
+    _lib.launch("bevwarp_resize", s4.device, s4.data_ptr(), d4.data_ptr(), B, H, W, dh, dw, C, s4.stride(0), s4.stride(1), d4.stride(0), d4.stride(1),
+                _lib.U8, INTER_LINEAR)
+    return _like_src(d4, src.dim(), out)
 
 
 def cv2_resize(src, dsize, dst=None, fx=0, fy=0, interpolation=INTER_LINEAR, device="cuda"):

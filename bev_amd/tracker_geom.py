@@ -40,11 +40,8 @@ def rbox_world_bev_device(rbox_src, H, src):
     b = _boxes(rbox_src, "rbox_src")
     out = torch.empty((b.shape[0], 5), dtype=b.dtype, device=b.device)
     Hh = _host9(H)
-    stream = torch.cuda.current_stream(b.device).cuda_stream
-    with torch.cuda.device(b.device):
-        st = _lib.load().bevwarp_rbox_transform(b.data_ptr(), b.shape[0], b.shape[1], Hh.ctypes.data_as(ctypes.c_void_p), int(src == "bev"),
-                                                out.data_ptr(), _DTYPES[b.dtype], ctypes.c_void_p(stream))
-    _lib.check(st)
+    _lib.launch("bevwarp_rbox_transform", b.device, b.data_ptr(), b.shape[0], b.shape[1], Hh.ctypes.data_as(ctypes.c_void_p), int(src == "bev"),
+                out.data_ptr(), _DTYPES[b.dtype])
     return out
 
 
@@ -113,16 +110,12 @@ def tracker_geometry_step(dets_bev, trks_world, H_world_bev, iou_threshold=0.3, 
             out["dets_img"] = torch.empty((n, 2), dtype=d.dtype, device=d.device)
     Hwb = _host9(H_world_bev)
     Him = None if H_img_world is None else _host9(H_img_world)
-    stream = torch.cuda.current_stream(d.device).cuda_stream
-    fn = _lib.load().bevwarp_tracker_step
     args = (d.data_ptr(), n, d.shape[1], t.data_ptr(), m, t.shape[1], Hwb.ctypes.data_as(ctypes.c_void_p),
             None if Him is None else Him.ctypes.data_as(ctypes.c_void_p), float(iou_threshold), out["dets_world"].data_ptr(),
             out["iou"].data_ptr(), out["candidates"].data_ptr(), out["dets_img"].data_ptr() if Him is not None else None, _DTYPES[d.dtype])
-    with torch.cuda.device(d.device):
-        st = fn(*args, ctypes.c_void_p(stream))
-    _lib.check(st)
+    _lib.launch("bevwarp_tracker_step", d.device, *args)
     if key is not None and d.data_ptr() == dets_bev.data_ptr() and t.data_ptr() == trks_world.data_ptr():  # (no copy was made on the way)
         if len(_plans) >= _PLANS_MAX:
             _plans.clear()
-        _plans[key] = (fn, args, d.device.index if d.device.index is not None else torch.cuda.current_device(), (Hwb, Him))  # (the host matrices stay alive)
+        _plans[key] = (_lib.load().bevwarp_tracker_step, args, d.device.index if d.device.index is not None else torch.cuda.current_device(), (Hwb, Him))  # (the host matrices stay alive)
     return out

@@ -150,6 +150,70 @@ def _border(border_value, C):
     return None if border_value is None else _per_channel(border_value, C)
 
 
+def _ptr(a):
+    """A host array (or None) as the ABI takes it."""
+    return None if a is None else a.ctypes.data_as(ctypes.c_void_p)
+
+
+# What the launching entry points below share.  An entry point is its own checks, then these calls in this order, then _lib.launch
+# (the validated-launch fast path of warp_perspective goes through none of them).
+
+
+def _interp(who, flags, cubic=False):
+    """The interpolation bits of `flags`, once they name a kernel `who` has (who: the caller as its message names it)."""
+    interp = int(flags) & 7
+    if interp not in ((INTER_NEAREST, INTER_LINEAR, INTER_CUBIC) if cubic else (INTER_NEAREST, INTER_LINEAR)):
+        raise ValueError("unsupported interpolation flag %d (%sINTER_NEAREST, INTER_LINEAR%s)" % (interp, who and who + ": ", ", INTER_CUBIC" if cubic else ""))
+    return interp
+
+
+def _frames(who, src, dtypes, channels=None):
+    """Interleaved frames as the ABI reads them: (s4, copied) -- `src` as (B, H, W, C) with channels-last rows, a contiguous copy
+    (copied) where its rows are not.  dtypes: the element types `who` takes, None when the caller has judged the tensor with a message
+    of its own; channels: the one channel count taken, and then no (H, W) frames."""
+    if dtypes is not None and (not isinstance(src, torch.Tensor) or not src.is_cuda or src.dtype not in dtypes):
+        raise ValueError("%s needs a %s CUDA (HIP) tensor" % (who, " or ".join(str(t)[6:] for t in dtypes)))
+    if channels is not None and (src.dim() not in (3, 4) or src.shape[-1] != channels):
+        raise ValueError("src must be (B, H, W, %d) or (H, W, %d)" % (channels, channels))
+    if src.dim() == 2:
+        s4 = src[None, :, :, None]
+    elif src.dim() == 3:
+        s4 = src[None]
+    elif src.dim() == 4:
+        s4 = src
+    else:
+        raise ValueError("src must be (B,H,W,C), (H,W,C) or (H,W)")
+    copied = s4.stride(3) != 1 or s4.stride(2) != s4.shape[3]
+    return (s4.contiguous() if copied else s4), copied
+
+
+def _matrices(M, flags, M_inv_device, device, B):
+    """(matrix tensor, number of matrices) of a call on B frames: the caller's `M_inv_device`, or the cached inverses of `M`."""
+    if M_inv_device is None:
+        M_inv_device = device_inverse(M, device, inverse_given=bool(int(flags) & WARP_INVERSE_MAP))
+    return M_inv_device, _check_minv(M_inv_device, device, B)
+
+
+def _pixel_dst(out, dtype, device, B, dh, dw, C, zeroed=False):
+    """The (B, dh, dw, C) destination of a call that writes interleaved pixels: a new tensor, or the caller's `out` as it is."""
+    if out is None:
+        return (torch.zeros if zeroed else torch.empty)((B, dh, dw, C), dtype=dtype, device=device)
+    _check_out(out, dtype, device, B * dh * dw * C)
+    d4 = out.reshape(B, dh, dw, C)
+    if d4.data_ptr() != out.data_ptr() or d4.stride(3) != 1 or d4.stride(2) != C:
+        raise ValueError("out must be a contiguous-row channels-last tensor")
+    return d4
+
+
+def _like_src(d4, ndim, out):
+    """What the caller gets back: `out`, or the 4-D result without the batch and channel axes a source of `ndim` dimensions did not have."""
+    if out is not None:
+        return out
+    if ndim == 2:
+        return d4[0, :, :, 0]
+    return d4[0] if ndim == 3 else d4
+
+
 _CLASSES_MAX = 64
 _class_tables = collections.OrderedDict()  # (matrix tensor address, n matrices, batch, sizes, format) -> (verdict table, the matrix tensor, its _version)
 
@@ -251,37 +315,20 @@ def warp_perspective(src, M, dsize, flags=INTER_LINEAR, border_value=None, out=N
         raise ValueError("warp_perspective needs a CUDA (HIP) tensor; use warpPerspective for numpy images")
     if src.dtype not in _DTYPES:
         raise ValueError("unsupported dtype %s (uint8 / float32)" % src.dtype)
-    interp = int(flags) & 7
-    if interp not in (INTER_NEAREST, INTER_LINEAR, INTER_CUBIC):
-        raise ValueError("unsupported interpolation flag %d (INTER_NEAREST, INTER_LINEAR, INTER_CUBIC)" % interp)
-    shape = tuple(src.shape)
-    s4 = src
-    if src.dim() == 2:
-        s4 = src[None, :, :, None]
-    elif src.dim() == 3:
-        s4 = src[None]
-    elif src.dim() != 4:
-        raise ValueError("src must be (B,H,W,C), (H,W,C) or (H,W)")
+    interp = _interp("", flags, True)
+    s4, copied = _frames("warp_perspective", src, None)
     B, H, W, C = s4.shape
-    copied = s4.stride(3) != 1 or s4.stride(2) != C
-    if copied:
-        s4 = s4.contiguous()
     dw, dh = int(dsize[0]), int(dsize[1])
     esz = s4.element_size()
-    if M_inv_device is None:
-        M_inv_device = device_inverse(M, s4.device, inverse_given=bool(int(flags) & WARP_INVERSE_MAP))
-    n_m = _check_minv(M_inv_device, s4.device, B)
-    if out is None:
+    M_inv_device, n_m = _matrices(M, flags, M_inv_device, s4.device, B)
+    if out is None:  # (_pixel_dst's first branch, spelt out: this path is timed by tools/host_overhead.py, and the call was the dearest of the helpers')
         d4 = (torch.zeros if border_mode == BORDER_TRANSPARENT else torch.empty)((B, dh, dw, C), dtype=s4.dtype, device=s4.device)
     else:
-        _check_out(out, s4.dtype, s4.device, B * dh * dw * C)
-        d4 = out.reshape(B, dh, dw, C)
-        if d4.data_ptr() != out.data_ptr() or d4.stride(3) != 1 or d4.stride(2) != C:
-            raise ValueError("out must be a contiguous-row channels-last tensor")
+        d4 = _pixel_dst(out, s4.dtype, s4.device, B, dh, dw, C)
     bv = _border(border_value, C) if border_mode == BORDER_CONSTANT else None  # (only the constant border reads it)
     stream = torch.cuda.current_stream(s4.device).cuda_stream
     args = (s4.data_ptr(), d4.data_ptr(), B, H, W, dh, dw, C, s4.stride(0) * esz, s4.stride(1) * esz, d4.stride(0) * esz, d4.stride(1) * esz,
-            M_inv_device.data_ptr(), n_m, _DTYPES[s4.dtype], interp, None if bv is None else bv.ctypes.data_as(ctypes.c_void_p))
+            M_inv_device.data_ptr(), n_m, _DTYPES[s4.dtype], interp, _ptr(bv))
     if border_mode == BORDER_CONSTANT and interp != INTER_CUBIC:
         fn = plain = _lib.load().bevwarp_warp
         table = _tile_classes(M_inv_device, n_m, args, stream)
@@ -301,13 +348,7 @@ def warp_perspective(src, M, dsize, flags=INTER_LINEAR, border_value=None, out=N
         # while the plan can be hit -- and holds the matrices' _version it was filled for, and the plain entry point for graph captures)
         _plans[key] = (fn, args, s4.device.index if s4.device.index is not None else torch.cuda.current_device(), table,
                        M_inv_device if table is not None else None, M_inv_device._version if table is not None else None, plain)
-    if out is not None:
-        return out
-    if len(shape) == 2:
-        return d4[0, :, :, 0]
-    if len(shape) == 3:
-        return d4[0]
-    return d4
+    return _like_src(d4, src.dim(), out)
 
 
 def _intrinsics(K):
@@ -400,56 +441,26 @@ def warp_perspective_lens(src, M, dsize, K, dist_coeff, flags=INTER_LINEAR, bord
     if border_mode not in (BORDER_CONSTANT, BORDER_TRANSPARENT):
         raise ValueError("unsupported border mode %r (warp_perspective_lens: BORDER_CONSTANT, BORDER_TRANSPARENT)" % (border_mode,))
     border_mode = int(border_mode)
-    interp = int(flags) & 7
-    if interp not in (INTER_NEAREST, INTER_LINEAR):
-        raise ValueError("unsupported interpolation flag %d (warp_perspective_lens: INTER_NEAREST, INTER_LINEAR)" % interp)
-    if not isinstance(src, torch.Tensor) or not src.is_cuda or src.dtype not in _DTYPES:
-        raise ValueError("warp_perspective_lens needs a uint8 or float32 CUDA (HIP) tensor")
-    if src.dim() == 2:
-        s4 = src[None, :, :, None]
-    elif src.dim() == 3:
-        s4 = src[None]
-    elif src.dim() == 4:
-        s4 = src
-    else:
-        raise ValueError("src must be (B,H,W,C), (H,W,C) or (H,W)")
+    interp = _interp("warp_perspective_lens", flags)
+    s4, _ = _frames("warp_perspective_lens", src, _DTYPES)
     B, H, W, C = s4.shape
-    if s4.stride(3) != 1 or s4.stride(2) != C:
-        s4 = s4.contiguous()
     dw, dh = int(dsize[0]), int(dsize[1])
     esz = s4.element_size()
     Mh = M.detach().cpu().numpy() if isinstance(M, torch.Tensor) else M
     R = ray_matrix(Mh, K, inverse_given=bool(int(flags) & WARP_INVERSE_MAP))
-    M_ray = device_inverse(R, s4.device, inverse_given=True)
-    n_m = _check_minv(M_ray, s4.device, B)
+    M_ray, n_m = _matrices(R, WARP_INVERSE_MAP, None, s4.device, B)
     lens = np.ascontiguousarray(np.concatenate([_intrinsics(K), dist]), dtype=np.float64)
     r2 = lens_valid_r2(dist) if r2_max is None else float(r2_max)
-    if out is None:
-        d4 = (torch.zeros if border_mode == BORDER_TRANSPARENT else torch.empty)((B, dh, dw, C), dtype=s4.dtype, device=s4.device)
-    else:
-        _check_out(out, s4.dtype, s4.device, B * dh * dw * C)
-        d4 = out.reshape(B, dh, dw, C)
-        if d4.data_ptr() != out.data_ptr() or d4.stride(3) != 1 or d4.stride(2) != C:
-            raise ValueError("out must be a contiguous-row channels-last tensor")
+    d4 = _pixel_dst(out, s4.dtype, s4.device, B, dh, dw, C, zeroed=border_mode == BORDER_TRANSPARENT)
     bv = _border(border_value, C) if border_mode == BORDER_CONSTANT else None
-    stream = torch.cuda.current_stream(s4.device).cuda_stream
-    with torch.cuda.device(s4.device):
-        st = _lib.load().bevwarp_warp_lens(s4.data_ptr(), d4.data_ptr(), B, H, W, dh, dw, C, s4.stride(0) * esz, s4.stride(1) * esz, d4.stride(0) * esz,
-                                           d4.stride(1) * esz, M_ray.data_ptr(), n_m, lens.ctypes.data_as(ctypes.c_void_p), r2, _DTYPES[s4.dtype], interp,
-                                           border_mode, None if bv is None else bv.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(stream))
-    _lib.check(st)
-    if out is not None:
-        return out
-    if src.dim() == 2:
-        return d4[0, :, :, 0]
-    return d4[0] if src.dim() == 3 else d4
+    _lib.launch("bevwarp_warp_lens", s4.device, s4.data_ptr(), d4.data_ptr(), B, H, W, dh, dw, C, s4.stride(0) * esz, s4.stride(1) * esz, d4.stride(0) * esz,
+                d4.stride(1) * esz, M_ray.data_ptr(), n_m, _ptr(lens), r2, _DTYPES[s4.dtype], interp, border_mode, _ptr(bv))
+    return _like_src(d4, src.dim(), out)
 
 
 def _plane_format(who, flags, out_dtype, out):
     """The interpolation of a call that writes channel planes, once its flags, plane type and `out` are what the plane kernels take."""
-    interp = int(flags) & 7
-    if interp not in (INTER_NEAREST, INTER_LINEAR):  # (no bicubic kernel writes planes)
-        raise ValueError("unsupported interpolation flag %d (%s: INTER_NEAREST, INTER_LINEAR)" % (interp, who))
+    interp = _interp(who, flags)  # (no bicubic kernel writes planes)
     if out_dtype not in _PLANE_DTYPES:
         raise ValueError("unsupported out_dtype %s (%s: torch.float32, torch.float16, torch.bfloat16)" % (out_dtype, who))
     if out is not None and getattr(out, "dtype", None) != out_dtype:
@@ -483,43 +494,20 @@ def warp_to_planar(src, M, dsize, scale=1.0 / 255.0, bias=0.0, flags=INTER_LINEA
                A given `out` must have this dtype.
     Returns (B, C, h, w), or (C, h, w) for a single frame.  Asynchronous on the current stream."""
     interp = _plane_format("warp_to_planar", flags, out_dtype, out)
-    if not isinstance(src, torch.Tensor) or not src.is_cuda or src.dtype not in _DTYPES:
-        raise ValueError("warp_to_planar needs a uint8 or float32 CUDA (HIP) tensor")
-    if src.dim() == 2:
-        s4 = src[None, :, :, None]
-    elif src.dim() == 3:
-        s4 = src[None]
-    elif src.dim() == 4:
-        s4 = src
-    else:
-        raise ValueError("src must be (B,H,W,C), (H,W,C) or (H,W)")
+    s4, _ = _frames("warp_to_planar", src, _DTYPES)
     B, H, W, C = s4.shape
-    if s4.stride(3) != 1 or s4.stride(2) != C:
-        s4 = s4.contiguous()
     dw, dh = int(dsize[0]), int(dsize[1])
-    if M_inv_device is None:
-        M_inv_device = device_inverse(M, s4.device, inverse_given=bool(int(flags) & WARP_INVERSE_MAP))
-    n_m = _check_minv(M_inv_device, s4.device, B)
+    M_inv_device, n_m = _matrices(M, flags, M_inv_device, s4.device, B)
     d4 = _plane_dst(out, out_dtype, s4.device, B, C, dh, dw)
     sc, bi, bv = _per_channel(scale, C), _per_channel(bias, C), _border(border_value, C)
-    stream = torch.cuda.current_stream(s4.device).cuda_stream
-    with torch.cuda.device(s4.device):
-        if out_dtype == torch.float32:
-            st = _lib.load().bevwarp_warp_planar(
-                s4.data_ptr(), d4.data_ptr(), B, H, W, dh, dw, C, s4.stride(0) * s4.element_size(), s4.stride(1) * s4.element_size(),
-                d4.stride(0) * 4, d4.stride(1) * 4, d4.stride(2) * 4, M_inv_device.data_ptr(), n_m, _DTYPES[s4.dtype], interp,
-                None if bv is None else bv.ctypes.data_as(ctypes.c_void_p), sc.ctypes.data_as(ctypes.c_void_p),
-                bi.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(stream))
-        else:  # float16 / bfloat16 planes: the kernels that convert on the way out
-            st = _lib.load().bevwarp_warp_planes(
-                s4.data_ptr(), d4.data_ptr(), B, H, W, dh, dw, C, s4.stride(0) * s4.element_size(), s4.stride(1) * s4.element_size(),
-                d4.stride(0) * 2, d4.stride(1) * 2, d4.stride(2) * 2, M_inv_device.data_ptr(), n_m, _DTYPES[s4.dtype], interp,
-                None if bv is None else bv.ctypes.data_as(ctypes.c_void_p), sc.ctypes.data_as(ctypes.c_void_p),
-                bi.ctypes.data_as(ctypes.c_void_p), _PLANE_DTYPES[out_dtype], ctypes.c_void_p(stream))
-    _lib.check(st)
-    if out is not None:
-        return out
-    return d4 if src.dim() == 4 else d4[0]
+    esz, desz = s4.element_size(), d4.element_size()
+    args = (s4.data_ptr(), d4.data_ptr(), B, H, W, dh, dw, C, s4.stride(0) * esz, s4.stride(1) * esz, d4.stride(0) * desz, d4.stride(1) * desz,
+            d4.stride(2) * desz, M_inv_device.data_ptr(), n_m, _DTYPES[s4.dtype], interp, _ptr(bv), _ptr(sc), _ptr(bi))
+    if out_dtype == torch.float32:
+        _lib.launch("bevwarp_warp_planar", s4.device, *args)
+    else:  # float16 / bfloat16 planes: the kernels that convert on the way out
+        _lib.launch("bevwarp_warp_planes", s4.device, *args, _PLANE_DTYPES[out_dtype])
+    return _like_src(d4, max(src.dim(), 3), out)  # (the planes of an (H, W) source keep their channel axis)
 
 
 def split_nv12(frame):
@@ -554,9 +542,7 @@ def _nv12_source(who, y, uv, M, flags, M_inv_device):
         raise ValueError("NV12 needs even sides and uv of shape %s; got y %s, uv %s" % ((B, H // 2, W // 2, 2), tuple(y3.shape), tuple(uv4.shape)))
     if y3.stride(2) != 1 or uv4.stride(3) != 1 or uv4.stride(2) != 2:
         raise ValueError("the last dimension of y and of uv (pairs, and the pairs of a row) must be contiguous")
-    if M_inv_device is None:
-        M_inv_device = device_inverse(M, y3.device, inverse_given=bool(int(flags) & WARP_INVERSE_MAP))
-    return y3, uv4, M_inv_device, _check_minv(M_inv_device, y3.device, B)
+    return (y3, uv4) + _matrices(M, flags, M_inv_device, y3.device, B)
 
 
 def warp_perspective_nv12(y, uv, M, dsize, flags=INTER_LINEAR, border_value=None, out=None, M_inv_device=None, rgb=False):
@@ -574,29 +560,14 @@ def warp_perspective_nv12(y, uv, M, dsize, flags=INTER_LINEAR, border_value=None
     M, dsize, out, M_inv_device   as warp_perspective; flags INTER_LINEAR (default) or INTER_NEAREST, optionally | WARP_INVERSE_MAP.
     border_value   scalar or 3 values in the RESULT's channel order (not converted); BORDER_CONSTANT is the only border.
     Returns (B, h, w, 3), or (h, w, 3) for a single frame.  Asynchronous on the current stream.  No verdict tables, no plan cache."""
-    interp = int(flags) & 7
-    if interp not in (INTER_NEAREST, INTER_LINEAR):
-        raise ValueError("unsupported interpolation flag %d (warp_perspective_nv12: INTER_NEAREST, INTER_LINEAR)" % interp)
+    interp = _interp("warp_perspective_nv12", flags)
     y3, uv4, M_inv_device, n_m = _nv12_source("warp_perspective_nv12", y, uv, M, flags, M_inv_device)
     B, H, W = y3.shape
     dw, dh = int(dsize[0]), int(dsize[1])
-    if out is None:
-        d4 = torch.empty((B, dh, dw, 3), dtype=torch.uint8, device=y3.device)
-    else:
-        _check_out(out, torch.uint8, y3.device, B * dh * dw * 3)
-        d4 = out.reshape(B, dh, dw, 3)
-        if d4.data_ptr() != out.data_ptr() or d4.stride(3) != 1 or d4.stride(2) != 3:
-            raise ValueError("out must be a contiguous-row channels-last tensor")
-    bv = _border(border_value, 3)
-    stream = torch.cuda.current_stream(y3.device).cuda_stream
-    with torch.cuda.device(y3.device):
-        st = _lib.load().bevwarp_warp_nv12(y3.data_ptr(), uv4.data_ptr(), d4.data_ptr(), B, H, W, dh, dw, y3.stride(0), y3.stride(1), uv4.stride(0),
-                                           uv4.stride(1), d4.stride(0), d4.stride(1), M_inv_device.data_ptr(), n_m, interp, 1 if rgb else 0,
-                                           None if bv is None else bv.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(stream))
-    _lib.check(st)
-    if out is not None:
-        return out
-    return d4[0] if y.dim() == 2 else d4
+    d4 = _pixel_dst(out, torch.uint8, y3.device, B, dh, dw, 3)
+    _lib.launch("bevwarp_warp_nv12", y3.device, y3.data_ptr(), uv4.data_ptr(), d4.data_ptr(), B, H, W, dh, dw, y3.stride(0), y3.stride(1), uv4.stride(0),
+                uv4.stride(1), d4.stride(0), d4.stride(1), M_inv_device.data_ptr(), n_m, interp, 1 if rgb else 0, _ptr(_border(border_value, 3)))
+    return _like_src(d4, y.dim() + 1, out)
 
 
 def warp_nv12_to_planar(y, uv, M, dsize, scale=1.0 / 255.0, bias=0.0, flags=INTER_LINEAR, border_value=None, out=None, M_inv_device=None,
@@ -624,24 +595,15 @@ def warp_nv12_to_planar(y, uv, M, dsize, scale=1.0 / 255.0, bias=0.0, flags=INTE
     d4 = _plane_dst(out, out_dtype, y3.device, B, 3, dh, dw)
     sc, bi, bv = _per_channel(scale, 3), _per_channel(bias, 3), _border(border_value, 3)
     esz = d4.element_size()
-    stream = torch.cuda.current_stream(y3.device).cuda_stream
-    with torch.cuda.device(y3.device):
-        st = _lib.load().bevwarp_warp_nv12_planes(
-            y3.data_ptr(), uv4.data_ptr(), d4.data_ptr(), B, H, W, dh, dw, y3.stride(0), y3.stride(1), uv4.stride(0), uv4.stride(1),
-            d4.stride(0) * esz, d4.stride(1) * esz, d4.stride(2) * esz, M_inv_device.data_ptr(), n_m, interp, 1 if rgb else 0,
-            None if bv is None else bv.ctypes.data_as(ctypes.c_void_p), sc.ctypes.data_as(ctypes.c_void_p),
-            bi.ctypes.data_as(ctypes.c_void_p), _PLANE_DTYPES[out_dtype], ctypes.c_void_p(stream))
-    _lib.check(st)
-    if out is not None:
-        return out
-    return d4[0] if y.dim() == 2 else d4
+    _lib.launch("bevwarp_warp_nv12_planes", y3.device, y3.data_ptr(), uv4.data_ptr(), d4.data_ptr(), B, H, W, dh, dw, y3.stride(0), y3.stride(1),
+                uv4.stride(0), uv4.stride(1), d4.stride(0) * esz, d4.stride(1) * esz, d4.stride(2) * esz, M_inv_device.data_ptr(), n_m, interp,
+                1 if rgb else 0, _ptr(bv), _ptr(sc), _ptr(bi), _PLANE_DTYPES[out_dtype])
+    return _like_src(d4, y.dim() + 1, out)
 
 
 def _nv12_out_format(who, flags, dsize):
     """What the warps into NV12 check before they look at a tensor: (interp, dw, dh)."""
-    interp = int(flags) & 7
-    if interp not in (INTER_NEAREST, INTER_LINEAR):
-        raise ValueError("unsupported interpolation flag %d (%s: INTER_NEAREST, INTER_LINEAR)" % (interp, who))
+    interp = _interp(who, flags)
     dw, dh = int(dsize[0]), int(dsize[1])
     if dw <= 0 or dh <= 0 or dw % 2 or dh % 2:
         raise ValueError("%s: an NV12 frame has even sides, got dsize %s" % (who, (dw, dh)))
@@ -694,23 +656,12 @@ def warp_perspective_to_nv12(src, M, dsize, flags=INTER_LINEAR, border_value=Non
     interp, dw, dh = _nv12_out_format("warp_perspective_to_nv12", flags, dsize)
     if not isinstance(src, torch.Tensor) or not src.is_cuda or src.dtype != torch.uint8:
         raise ValueError("warp_perspective_to_nv12 needs a uint8 CUDA (HIP) tensor; src is %s" % (getattr(src, "dtype", type(src)),))
-    if src.dim() not in (3, 4) or src.shape[-1] != 3:
-        raise ValueError("src must be (B, H, W, 3) or (H, W, 3)")
-    s4 = src[None] if src.dim() == 3 else src
-    if s4.stride(3) != 1 or s4.stride(2) != 3:
-        s4 = s4.contiguous()
+    s4, _ = _frames("warp_perspective_to_nv12", src, None, channels=3)
     B, H, W, _ = s4.shape
-    if M_inv_device is None:
-        M_inv_device = device_inverse(M, s4.device, inverse_given=bool(int(flags) & WARP_INVERSE_MAP))
-    n_m = _check_minv(M_inv_device, s4.device, B)
+    M_inv_device, n_m = _matrices(M, flags, M_inv_device, s4.device, B)
     y3, uv4, ret = _nv12_dst("warp_perspective_to_nv12", out, s4.device, B, dh, dw, src.dim() == 3)
-    bv = _border(border_value, 3)
-    stream = torch.cuda.current_stream(s4.device).cuda_stream
-    with torch.cuda.device(s4.device):
-        st = _lib.load().bevwarp_warp_to_nv12(s4.data_ptr(), y3.data_ptr(), uv4.data_ptr(), B, H, W, dh, dw, s4.stride(0), s4.stride(1), y3.stride(0),
-                                              y3.stride(1), uv4.stride(0), uv4.stride(1), M_inv_device.data_ptr(), n_m, interp, 1 if rgb else 0,
-                                              None if bv is None else bv.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(stream))
-    _lib.check(st)
+    _lib.launch("bevwarp_warp_to_nv12", s4.device, s4.data_ptr(), y3.data_ptr(), uv4.data_ptr(), B, H, W, dh, dw, s4.stride(0), s4.stride(1), y3.stride(0),
+                y3.stride(1), uv4.stride(0), uv4.stride(1), M_inv_device.data_ptr(), n_m, interp, 1 if rgb else 0, _ptr(_border(border_value, 3)))
     return ret
 
 
@@ -730,14 +681,9 @@ def warp_nv12_to_nv12(y, uv, M, dsize, flags=INTER_LINEAR, border_value=None, ou
     y3, uv4, M_inv_device, n_m = _nv12_source("warp_nv12_to_nv12", y, uv, M, flags, M_inv_device)
     B, H, W = y3.shape
     dy3, duv4, ret = _nv12_dst("warp_nv12_to_nv12", out, y3.device, B, dh, dw, y.dim() == 2)
-    bv = _border(border_value, 3)
-    stream = torch.cuda.current_stream(y3.device).cuda_stream
-    with torch.cuda.device(y3.device):
-        st = _lib.load().bevwarp_warp_nv12_to_nv12(y3.data_ptr(), uv4.data_ptr(), dy3.data_ptr(), duv4.data_ptr(), B, H, W, dh, dw, y3.stride(0), y3.stride(1),
-                                                   uv4.stride(0), uv4.stride(1), dy3.stride(0), dy3.stride(1), duv4.stride(0), duv4.stride(1),
-                                                   M_inv_device.data_ptr(), n_m, interp, None if bv is None else bv.ctypes.data_as(ctypes.c_void_p),
-                                                   ctypes.c_void_p(stream))
-    _lib.check(st)
+    _lib.launch("bevwarp_warp_nv12_to_nv12", y3.device, y3.data_ptr(), uv4.data_ptr(), dy3.data_ptr(), duv4.data_ptr(), B, H, W, dh, dw, y3.stride(0),
+                y3.stride(1), uv4.stride(0), uv4.stride(1), dy3.stride(0), dy3.stride(1), duv4.stride(0), duv4.stride(1), M_inv_device.data_ptr(), n_m,
+                interp, _ptr(_border(border_value, 3)))
     return ret
 
 
@@ -748,11 +694,7 @@ def footprint(src_hw, M, dsize, batch=None, flags=INTER_LINEAR, device="cuda"):
     minv = device_inverse(M, torch.device(device), inverse_given=bool(int(flags) & WARP_INVERSE_MAP))
     n = minv.shape[0] if batch is None else int(batch)
     touched = torch.zeros((n, H, W), dtype=torch.uint8, device=minv.device)
-    stream = torch.cuda.current_stream(minv.device).cuda_stream
-    with torch.cuda.device(minv.device):
-        st = _lib.load().bevwarp_footprint(touched.data_ptr(), n, H, W, int(dsize[1]), int(dsize[0]), minv.data_ptr(),
-                                           minv.shape[0], int(flags) & 7, ctypes.c_void_p(stream))
-    _lib.check(st)
+    _lib.launch("bevwarp_footprint", minv.device, touched.data_ptr(), n, H, W, int(dsize[1]), int(dsize[0]), minv.data_ptr(), minv.shape[0], int(flags) & 7)
     return touched.reshape(n, -1).sum(dim=1, dtype=torch.int64), touched
 
 
