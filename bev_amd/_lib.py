@@ -32,6 +32,8 @@ SYMBOLS = {
     "bevwarp_warp_lens": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
                                      _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_double,
                                      _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p]),
+    "bevwarp_warp_stitch": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int,
+                                       _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p]),
     "bevwarp_warp_classes": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
                                         _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int,
                                         _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p]),
@@ -68,6 +70,15 @@ SYMBOLS = {
     "bevwarp_tracker_step": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p,
                                         _c.c_double, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p]),
 }
+
+
+class Camera(_c.Structure):
+    """bevwarp_camera (include/bevwarp.h): one camera of bevwarp_warp_stitch.  A host array of these is the call's first argument."""
+    _fields_ = [("src", _c.c_void_p), ("M_inv", _c.c_void_p), ("frame_stride", _c.c_int64), ("row_stride", _c.c_int64), ("src_h", _c.c_int),
+                ("src_w", _c.c_int), ("m_count", _c.c_int), ("reserved", _c.c_int)]
+
+
+STITCH_OVER, STITCH_FEATHER, STITCH_MAX_CAMERAS = 0, 1, 8
 
 _lib = None
 

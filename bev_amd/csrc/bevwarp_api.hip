@@ -15,6 +15,7 @@
 #include "warp_lens.h"
 #include "warp_nv12.h"
 #include "warp_nv12_out.h"
+#include "warp_stitch.h"
 
 #pragma clang fp contract(off)
 
@@ -241,6 +242,36 @@ int bevwarp_warp_lens(const void* src, void* dst, int batch, int src_h, int src_
     a.dst_vec_ok = plan::wide_stores_ok(c.writes[0], plan::store_align(dtype, channels, false));
     a.src_vec_ok = plan::pixel_loads_ok(c.reads[0].im, plan::pixel_load_align(dtype, channels));
     return launched(launch_warp_lens(a, dtype, channels, interp, transparent, items, (hipStream_t)stream));
+}
+
+int bevwarp_warp_stitch(const bevwarp_camera* cams, int n_cams, void* dst, int batch, int dst_h, int dst_w, int channels, int64_t dst_frame_stride,
+                        int64_t dst_row_stride, int dtype, int interp, int blend, int feather, int border_mode, const double* border_value, void* stream) {
+    const Frames d = {dst, dst_frame_stride, dst_row_stride};
+    TilePlan p;
+    const int st = plan::stitch_status(cams, n_cams, d, batch, dst_h, dst_w, channels, dtype, interp, blend, feather, border_mode, border_value, kBorderTileW,
+                                       kBorderTileH, p);
+    if (st != BEVWARP_OK || batch == 0) return st;
+    StitchArgs a;
+    memset(&a, 0, sizeof(a));
+    a.dst = (uint8_t*)dst, a.dst_fs = dst_frame_stride, a.dst_rs = dst_row_stride, a.dst_h = dst_h, a.dst_w = dst_w;
+    a.bw0 = p.bw0, a.tiles_x = p.tiles_x, a.tiles_per_frame = p.tiles_per_frame;
+    a.tpf_magic = p.tpf_magic, a.tx_magic = p.tx_magic, a.bw0_magic = p.bw0_magic;
+    const int elem = dtype == BEVWARP_U8 ? 1 : 4;
+    a.dst_vec_ok = plan::wide_stores_ok(d.image(dst_h, (uint64_t)dst_w * channels * elem, batch), plan::store_align(dtype, channels, false));
+    for (int k = 0; k < n_cams; k++) {
+        const bevwarp_camera& c = cams[k];
+        StitchCamera& s = a.cams[k];
+        s.src = (const uint8_t*)c.src, s.minv = c.M_inv, s.src_fs = c.frame_stride, s.src_rs = c.row_stride;
+        s.src_h = c.src_h, s.src_w = c.src_w, s.m_stride = c.m_count == 1 ? 0 : 9;
+        s.src_vec_ok = plan::pixel_loads_ok(Frames{c.src, c.frame_stride, c.row_stride}.image(c.src_h, (uint64_t)c.src_w * channels * elem, batch),
+                                            plan::pixel_load_align(dtype, channels));
+    }
+    a.n_cams = n_cams, a.feather = feather;
+    a.fill = border_mode == BEVWARP_BORDER_CONSTANT;
+    uint8_t bu[4];  // (border_value is read by the constant border only; stitch_status has found it finite)
+    border_values(a.fill ? border_value : nullptr, channels, a.bv_f, bu);
+    a.bv_u8 = (uint32_t)bu[0] | ((uint32_t)bu[1] << 8) | ((uint32_t)bu[2] << 16) | ((uint32_t)bu[3] << 24);
+    return launched(launch_warp_stitch(a, dtype, channels, interp, blend, p.total_tiles, (hipStream_t)stream));
 }
 
 int bevwarp_warp_nv12(const void* y, const void* uv, void* dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int64_t y_frame_stride,

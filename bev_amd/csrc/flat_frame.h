@@ -1,7 +1,8 @@
-// flat_frame.h -- the frame that the border, bicubic and NV12 warps share (warp_border.hip, warp_cubic.hip, warp_nv12.hip,
-// warp_nv12_planes.hip): a flat grid, item -> frame / tile row / tile column by fast_div, one wave per destination row, 4 consecutive
-// pixels per lane, the reference's exact float64 coordinate chain pixel by pixel, wide stores for lanes that write all 4 pixels.
-// What a unit adds is its sampler, its kernel body from "for each of my 4 pixels" on, and its launcher.  See DESIGN.md section 4.9.
+// flat_frame.h -- the frame that the border, bicubic, NV12, lens and stitch warps share (warp_border.hip, warp_cubic.hip, warp_nv12.hip,
+// warp_nv12_planes.hip, warp_nv12_out.hip, warp_lens.hip, warp_stitch.hip): a flat grid, item -> frame / tile row / tile column by
+// fast_div, one wave per destination row, 4 consecutive pixels per lane, the reference's exact float64 coordinate chain pixel by pixel,
+// wide stores for lanes that write all 4 pixels.  What a unit adds is its sampler, its kernel body from "for each of my 4 pixels" on, and
+// its launcher.  See DESIGN.md section 4.9.
 #pragma once
 #include "sample.h"
 
@@ -51,6 +52,11 @@ struct RowWalk {
 
     __device__ __forceinline__ RowWalk(const FrameArgs& a, uint32_t b, int row) : y(row) {
         const double* M = a.minv + (int64_t)b * a.m_stride;
+#pragma unroll
+        for (int i = 0; i < 9; i++) Mr[i] = M[i];
+    }
+    // ... from the matrix itself: a kernel with several sources, each with matrices of its own (warp_stitch.hip)
+    __device__ __forceinline__ RowWalk(const double* __restrict__ M, int row) : y(row) {
 #pragma unroll
         for (int i = 0; i < 9; i++) Mr[i] = M[i];
     }
@@ -104,6 +110,28 @@ __device__ __forceinline__ Pixel<T, C> load_pixel(const uint8_t* __restrict__ ro
         for (int k = 0; k < C; k++) p.v[k] = q[k];
     }
     return p;
+}
+
+// The taps of one pixel (source pixels: indices already remapped, or an inlier's) and the blend of the constant-border kernel: the border
+// and the stitch kernels sample with it.
+template <typename T, int C, int INTERP>
+__device__ __forceinline__ Pixel<T, C> sample_taps(const uint8_t* __restrict__ frame, int64_t rs, int x0, int x1, int y0, int y1, int fx, int fy,
+                                                   bool vec) {
+    const uint8_t* r0 = frame + (int64_t)y0 * rs;
+    if (INTERP == kNearest) return load_pixel<T, C>(r0, x0, vec);
+    const uint8_t* r1 = frame + (int64_t)y1 * rs;
+    const Pixel<T, C> p00 = load_pixel<T, C>(r0, x0, vec), p01 = load_pixel<T, C>(r0, x1, vec);
+    const Pixel<T, C> p10 = load_pixel<T, C>(r1, x0, vec), p11 = load_pixel<T, C>(r1, x1, vec);
+    Pixel<T, C> out;
+    if constexpr (sizeof(T) == 1) {
+        out.packed = blend_u8_packed<C>(p00.packed, p01.packed, p10.packed, p11.packed, (uint32_t)fx, (uint32_t)fy);
+    } else {
+        float w00, w01, w10, w11;
+        weights_f32(fx, fy, w00, w01, w10, w11);
+#pragma unroll
+        for (int k = 0; k < C; k++) out.v[k] = blend_f32(p00.v[k], p01.v[k], p10.v[k], p11.v[k], w00, w01, w10, w11);
+    }
+    return out;
 }
 
 // A lane's kBorderPPL consecutive pixels of row y of frame b, first pixel xs: wide stores (the layout rule of bevwarp_warp's

@@ -1,6 +1,6 @@
 // host_plan.h -- what the C ABI decides before a launch, as plain C++17 (no HIP): the argument checks and the launch geometry.
-// bevwarp_api.hip is its only user in the library; tests/host_plan_driver.cpp compiles it with g++ under the address and
-// undefined-behaviour sanitizers, and tests/golden/launch_plans.json pins every field of the plans.  Not installed.
+// bevwarp_api.hip is its only user in the library; tests/host_plan_driver.cpp (and lens_plan_driver.cpp, stitch_plan_driver.cpp) compile it
+// with g++ under the address and undefined-behaviour sanitizers, and tests/golden/launch_plans.json pins every field of the plans.  Not installed.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -107,7 +107,7 @@ struct Nv12Images {
 };
 inline Nv12Images nv12_images(Frames y, Frames uv, int h, int w, int batch) { return {y.image(h, (uint64_t)w, batch), uv.image(h / 2, (uint64_t)w, batch)}; }
 
-// What the checks need of one entry point's arguments.  The functions of the last part of this section describe the ten entry points in
+// What the checks need of one entry point's arguments.  The functions of the last part of this section describe the eleven entry points in
 // these terms; bevwarp_api.hip and the tests' drivers (tests/host_plan_driver.cpp, tests/lens_plan_driver.cpp) build their calls with them.
 struct Sizes {  // (what every entry point passes besides its images and its format)
     int batch, src_h, src_w, dst_h, dst_w, m_count;
@@ -237,6 +237,14 @@ inline int lens_status(const double lens[12], double r2_max) {
     if (lens[0] == 0.0 || lens[1] == 0.0 || !(r2_max >= 0.0)) return BEVWARP_ERR_BAD_ARG;  // (a NaN r2_max fails the comparison)
     return BEVWARP_OK;
 }
+// bevwarp_warp_stitch, one camera of it: that camera's frames against the canvas -- bevwarp_warp's images and formats without bicubic, with
+// the two blend rules and the constant and the transparent border.  (stitch_status below runs the checks over all cameras.)
+inline Call stitch_call(const bevwarp_camera& k, Frames dst, int batch, int dst_h, int dst_w, int channels, int dtype, int interp, int blend, int border_mode) {
+    Call c = warp_call({k.src, k.frame_stride, k.row_stride}, dst, {batch, k.src_h, k.src_w, dst_h, dst_w, k.m_count, k.M_inv}, channels, dtype, interp, false);
+    c.format_ok = c.format_ok && (blend == BEVWARP_STITCH_OVER || blend == BEVWARP_STITCH_FEATHER) &&
+                  (border_mode == BEVWARP_BORDER_CONSTANT || border_mode == BEVWARP_BORDER_TRANSPARENT);
+    return c;
+}
 // What the four NV12 entry points share: nearest or bilinear, B, G, R or R, G, B.  Each adds its images.
 inline Call nv12_family_call(const Sizes& z, int interp, int rgb_order, bool plane_ok = true) {
     return {z, (interp == BEVWARP_NEAREST || interp == BEVWARP_LINEAR) && (rgb_order == 0 || rgb_order == 1) && plane_ok, false};
@@ -365,6 +373,26 @@ inline BorderPeriod border_period(int mode, int n) {
     b.off = (32768u + b.per - 1u) / b.per * b.per;
     b.mag = div_magic((uint64_t)b.off + 32769u, b.per);
     return b;
+}
+
+// ---- bevwarp_warp_stitch: the whole of its host side but the launch -----------------------------------------------------------------------
+// The status of a call in the order include/bevwarp.h documents, and in `p` the grid of tw x th tiles (kBorderTileW x kBorderTileH) over the
+// canvas when the call goes on to a launch (BEVWARP_OK and batch > 0).  cams is HOST; no device pointer is dereferenced.
+inline int stitch_status(const bevwarp_camera* cams, int n_cams, Frames dst, int batch, int dst_h, int dst_w, int channels, int dtype, int interp, int blend,
+                         int feather, int border_mode, const double* border_value, int tw, int th, TilePlan& p) {
+    p = {};
+    if (!cams || n_cams < 1 || n_cams > BEVWARP_STITCH_MAX_CAMERAS) return BEVWARP_ERR_BAD_ARG;
+    if (blend == BEVWARP_STITCH_FEATHER && (feather < 1 || feather > 4096)) return BEVWARP_ERR_BAD_ARG;
+    for (int k = 0; k < n_cams; k++) {  // every camera against the canvas; the sources may overlap each other
+        const int st = check_call(stitch_call(cams[k], dst, batch, dst_h, dst_w, channels, dtype, interp, blend, border_mode));
+        if (st != BEVWARP_OK) return st;
+    }
+    p = plan_border(batch, dst_h, dst_w, tw, th);
+    if (p.status != BEVWARP_OK) return p.status;
+    if (border_mode == BEVWARP_BORDER_CONSTANT && border_value)
+        for (int c = 0; c < channels; c++)
+            if (!isfinite(border_value[c])) return BEVWARP_ERR_NOT_FINITE;
+    return BEVWARP_OK;
 }
 
 }  // namespace plan

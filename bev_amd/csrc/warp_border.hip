@@ -9,7 +9,8 @@
 // classification, no guarded reads.  The coordinates are the reference's exact float64 chain, pixel by pixel.
 //
 // The frame -- item decoding, the coordinate walk, the rounding with the reference's NaN, a pixel's load and the store of a lane's 4
-// pixels -- is flat_frame.h, shared with the bicubic and NV12 kernels; this unit holds the index remap, the taps and the kernel body.
+// pixels, the taps of a pixel and their blend -- is flat_frame.h, shared with the bicubic, NV12 and stitch kernels; this unit holds the index
+// remap and the kernel body.
 #include "warp_border.h"
 
 namespace bevwarp {
@@ -27,27 +28,6 @@ __device__ __forceinline__ int border_index(int p, int n, uint32_t per, uint32_t
     if (MODE == kBorderWrap) return q;
     if (MODE == kBorderReflect) return q < n ? q : (int)per - 1 - q;
     return q < n ? q : (int)per - q;  // REFLECT_101
-}
-
-// the taps (source pixels, already remapped) and the blend of the constant-border kernel
-template <typename T, int C, int INTERP>
-__device__ __forceinline__ Pixel<T, C> sample_taps(const uint8_t* __restrict__ frame, int64_t rs, int x0, int x1, int y0, int y1, int fx, int fy,
-                                                   bool vec) {
-    const uint8_t* r0 = frame + (int64_t)y0 * rs;
-    if (INTERP == kNearest) return load_pixel<T, C>(r0, x0, vec);
-    const uint8_t* r1 = frame + (int64_t)y1 * rs;
-    const Pixel<T, C> p00 = load_pixel<T, C>(r0, x0, vec), p01 = load_pixel<T, C>(r0, x1, vec);
-    const Pixel<T, C> p10 = load_pixel<T, C>(r1, x0, vec), p11 = load_pixel<T, C>(r1, x1, vec);
-    Pixel<T, C> out;
-    if constexpr (sizeof(T) == 1) {
-        out.packed = blend_u8_packed<C>(p00.packed, p01.packed, p10.packed, p11.packed, (uint32_t)fx, (uint32_t)fy);
-    } else {
-        float w00, w01, w10, w11;
-        weights_f32(fx, fy, w00, w01, w10, w11);
-#pragma unroll
-        for (int k = 0; k < C; k++) out.v[k] = blend_f32(p00.v[k], p01.v[k], p10.v[k], p11.v[k], w00, w01, w10, w11);
-    }
-    return out;
 }
 
 template <typename T, int C, int INTERP, int MODE>

@@ -13,6 +13,10 @@
  *                             camera delivers, in one resampling: Calib carries `dist_coeff` (bev/calib.py:25), Rt_from_pts_K_dist
  *                             takes `dist_coeffs` (bev/homo.py:130-135), and the material the reference was developed on went through
  *                             a separate undistortion pass first (KAB_SK_1_undist/..., vis_homo.py:30-31)
+ *   bevwarp_warp_stitch     one cv2.warpPerspective(img_k, H_bev_img_k, (u_size, v_size)) per camera of a site into ONE BEV image:
+ *                             preset_calib("KoPER", 1 | 4) describes two cameras of one intersection in one world frame
+ *                             (bev/constructor/homo_constr.py:19-25), BrnoCompSpeed sessions have a left, a centre and a right camera
+ *                             (vis_homo.py:39-43).  All cameras in one launch, last-wins or blended where they overlap
  *   bevwarp_warp_classes, bevwarp_tile_classes_bytes
  *                           the same call inside a camera loop (one H_bev_img, every frame of the video): vis_homo.py:85-91
  *   bevwarp_invert_homography  the cv::invert(M) step inside that call (M is the forward src->dst map)
@@ -149,6 +153,7 @@ typedef enum bevwarp_border {
  *                               0 <= sx <= src_w - 2 and 0 <= sy <= src_h - 2 (remapBilinear's test: an identity warp leaves
  *                               the last source column and row unwritten).  Every other destination byte is neither read
  *                               nor written -- dst keeps what it held: warping several cameras into one canvas, one call each.
+ *                               (All of them in one launch, blended where they overlap if asked: bevwarp_warp_stitch.)
  *   border_value  HOST; read by BEVWARP_BORDER_CONSTANT only (ignored otherwise, as in OpenCV).
  *   border_mode   any other value (OpenCV's BORDER_ISOLATED bit included) returns BEVWARP_ERR_UNSUPPORTED.
  * Semantics restated from OpenCV 3.x-4.x imgwarp.cpp (remapNearest / remapBilinear); parity unpinned, like the rest of the warp.
@@ -216,6 +221,59 @@ int bevwarp_warp_lens(const void *src, void *dst, int batch, int src_h, int src_
                       int64_t src_frame_stride, int64_t src_row_stride, int64_t dst_frame_stride, int64_t dst_row_stride,
                       const double *M_ray, int m_count, const double *lens /*HOST, 12*/, double r2_max, int dtype, int interp,
                       int border_mode, const double *border_value /*HOST*/, void *stream);
+
+/*
+ * Several cameras warped into one canvas in one launch.  It replaces "warping several cameras into one canvas, one call each"
+ * (bevwarp_warp_border, BEVWARP_BORDER_TRANSPARENT): the cameras of one site -- preset_calib("KoPER", 1 | 4),
+ * bev/constructor/homo_constr.py:19-25 -- each with frames, sizes, strides and matrices of its own, and two rules for the pixels that
+ * more than one camera sees.  Both are defined to the bit.
+ *   cams          HOST, n_cams (1..BEVWARP_STITCH_MAX_CAMERAS) descriptions in list order; the array is read during the call only.
+ *                 src: device, `batch` frames of src_h x src_w pixels (`channels` values of `dtype`: the call's); M_inv: device, m_count
+ *                 (batch or 1) inverse matrices, canvas px -> THIS camera's px; strides in bytes; reserved: 0.
+ *   dst           device, `batch` canvases of dst_h x dst_w pixels.  No camera's frames may overlap it (bevwarp_warp's rule, per camera);
+ *                 the cameras' frames may overlap each other.
+ * Per camera.  For frame b, destination pixel (x, y) and camera k, (X, Y), sx, sy, fx, fy are exactly bevwarp_warp_border's with camera
+ * k's matrix of frame b: the evaluation blocks, 32 / W, round half to even, NaN -> INT_MAX, int16 saturation.  Camera k COVERS the
+ * pixel iff it passes BEVWARP_BORDER_TRANSPARENT's inlier test for `interp` against camera k's own src_w, src_h; its value p_k is then
+ * that entry's nearest copy or bilinear blend (8-bit: 15-bit fixed point; float32: the float blend).
+ *   BEVWARP_STITCH_OVER     the pixel is p_k of the covering camera with the LARGEST k: bit for bit what n_cams successive
+ *                           bevwarp_warp_border(..., BEVWARP_BORDER_TRANSPARENT) calls in list order leave on a canvas.  `feather` is ignored.
+ *   BEVWARP_STITCH_FEATHER  `feather` F in 1..4096.  Covering camera k weighs w_k = min(d_k, F), an integer, with
+ *                           d_k = min(sx + 1, src_w - sx, sy + 1, src_h - sy): the distance in whole source pixels to the nearest edge
+ *                           of its frame (>= 1 for every inlier); W = sum of w_k.
+ *                           - exactly one camera covers: the pixel is that p_k itself (outside overlaps FEATHER, OVER and the plain
+ *                             TRANSPARENT warp agree by bits);
+ *                           - 8-bit, two or more: (sum of w_k p_k + (W >> 1)) / W per channel, integers, truncating division (the sums
+ *                             stay below 2^23; the result is at most 255: no clamp is live);
+ *                           - float32, two or more: acc = 0, then in ascending k acc = acc + float(w_k) * p_k, every multiply and add
+ *                             rounded to float32 (no FMA), then acc / float(W) as one correctly rounded float32 division.  A NaN gives
+ *                             some NaN.
+ *                           F = 1 is the plain mean of the covering cameras.
+ * No camera covers: BEVWARP_BORDER_CONSTANT stores border_value, converted as bevwarp_warp converts it (HOST, `channels` doubles, NULL = 0);
+ * BEVWARP_BORDER_TRANSPARENT neither reads nor writes the pixel.  One camera with BEVWARP_BORDER_CONSTANT is NOT bevwarp_warp: a pixel is
+ * covered or it is the border value -- taps at the frame's edge are not blended with the border here.
+ *   dtype BEVWARP_U8 | BEVWARP_F32, channels 1..4, interp BEVWARP_NEAREST | BEVWARP_LINEAR, blend one of the two, border_mode
+ *   BEVWARP_BORDER_CONSTANT | BEVWARP_BORDER_TRANSPARENT; anything else (BEVWARP_CUBIC, the four index-remapping borders, the 16-bit types)
+ *   is BEVWARP_ERR_UNSUPPORTED.
+ * Status, in this order: BEVWARP_ERR_BAD_ARG for cams NULL, n_cams outside 1..8, or feather outside 1..4096 under BEVWARP_STITCH_FEATHER;
+ * then per camera in ascending k bevwarp_warp's checks in bevwarp_warp's order of that camera's frames against dst (blend and border_mode
+ * count as part of the format), the first status that is not BEVWARP_OK being returned; then BEVWARP_ERR_TOO_LARGE for a destination side
+ * > 2^20; then BEVWARP_ERR_NOT_FINITE for border_value (BEVWARP_BORDER_CONSTANT only).  batch == 0 is BEVWARP_OK and launches nothing.
+ */
+#define BEVWARP_STITCH_MAX_CAMERAS 8
+typedef struct bevwarp_camera {   /* HOST; 48 bytes */
+    const void *src;              /* device: `batch` frames of src_h x src_w pixels (channels, dtype: the call's) */
+    const double *M_inv;          /* device: m_count inverse matrices, canvas px -> THIS camera's px */
+    int64_t frame_stride, row_stride;   /* bytes */
+    int src_h, src_w;
+    int m_count;                  /* batch or 1 */
+    int reserved;                 /* 0 */
+} bevwarp_camera;
+#define BEVWARP_STITCH_OVER 0
+#define BEVWARP_STITCH_FEATHER 1
+int bevwarp_warp_stitch(const bevwarp_camera *cams /*HOST*/, int n_cams, void *dst, int batch, int dst_h, int dst_w, int channels,
+                        int64_t dst_frame_stride, int64_t dst_row_stride, int dtype, int interp, int blend, int feather,
+                        int border_mode, const double *border_value /*HOST*/, void *stream);
 
 /*
  * bevwarp_warp with the per-tile verdicts of an earlier launch (ABI v7).  Which way a tile is processed -- inside the frame, outside,
