@@ -64,6 +64,8 @@ SYMBOLS = {
     "bevwarp_footprint": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int,
                                      _c.c_int, _c.c_void_p]),
     "bevwarp_project_points": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p]),
+    "bevwarp_project_points_lens": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_double, _c.c_int, _c.c_int,
+                                               _c.c_double, _c.c_int, _c.c_void_p]),
     "bevwarp_rbox_iou": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int,
                                     _c.c_void_p]),
     "bevwarp_rbox_transform": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p]),

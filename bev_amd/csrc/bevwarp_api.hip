@@ -9,6 +9,7 @@
 #include "bevwarp.h"
 #include "host_plan.h"
 #include "cubic_tab.h"
+#include "points_lens.h"
 #include "warp_border.h"
 #include "warp_cubic.h"
 #include "warp_kernels.h"
@@ -483,6 +484,17 @@ int bevwarp_project_points(const void* in, void* out, int64_t n, int dim, const 
     const int need = dim == 2 ? 2 * esz : esz;  // 2-D points move as one 8 / 16 byte unit
     if (((uintptr_t)in % need) || ((uintptr_t)out % need)) return BEVWARP_ERR_BAD_ARG;
     return launched(launch_project_points(in, out, n, dim, H, dtype, (hipStream_t)stream));
+}
+
+int bevwarp_project_points_lens(const void* in, void* out, void* residual, int64_t n, const double* H, const double* lens, double r2_max, int direction,
+                                int iters, double tol_px, int dtype, void* stream) {
+    const int st = plan::points_lens_status(in, out, residual, n, H, lens, r2_max, direction, iters, tol_px, dtype);
+    if (st != BEVWARP_OK || n == 0) return st;
+    PointsLensArgs a;
+    memcpy(a.H, H, sizeof(a.H));
+    memcpy(a.lens, lens, sizeof(a.lens));
+    a.r2_max = r2_max, a.tol_px = tol_px, a.iters = iters;
+    return launched(launch_points_lens(in, out, residual, n, a, direction, dtype, (hipStream_t)stream));
 }
 
 // H / H[2][2] when H is a similarity of the plane in the sense of bev/rbox.py:173-219 (last row ~ (0, 0, 1), equal scale on

@@ -237,6 +237,28 @@ inline int lens_status(const double lens[12], double r2_max) {
     if (lens[0] == 0.0 || lens[1] == 0.0 || !(r2_max >= 0.0)) return BEVWARP_ERR_BAD_ARG;  // (a NaN r2_max fails the comparison)
     return BEVWARP_OK;
 }
+// bevwarp_project_points_lens: every check of the call, in the order include/bevwarp.h documents.  in, out, residual are device
+// pointers (never dereferenced), H and lens HOST.  The byte ranges are compared in 128 bits: n next to 2^62 is a range like any other.
+inline int points_lens_status(const void* in, const void* out, const void* residual, int64_t n, const double* H, const double* lens, double r2_max,
+                              int direction, int iters, double tol_px, int dtype) {
+    if (!in || !out || !H || n < 0) return BEVWARP_ERR_BAD_ARG;
+    if (direction != BEVWARP_LENS_DISTORT && direction != BEVWARP_LENS_UNDISTORT) return BEVWARP_ERR_BAD_ARG;
+    if (direction == BEVWARP_LENS_DISTORT && residual) return BEVWARP_ERR_BAD_ARG;
+    if (direction == BEVWARP_LENS_UNDISTORT && (iters < 1 || iters > 100 || !(tol_px >= 0.0))) return BEVWARP_ERR_BAD_ARG;  // (a NaN tol_px fails the comparison)
+    if (dtype != BEVWARP_F32 && dtype != BEVWARP_F64) return BEVWARP_ERR_UNSUPPORTED;
+    const unsigned esz = dtype == BEVWARP_F32 ? 4 : 8;
+    if (!finite9(H, 1)) return BEVWARP_ERR_NOT_FINITE;
+    const int st = lens_status(lens, r2_max);
+    if (st != BEVWARP_OK) return st;
+    if (residual) {
+        typedef unsigned __int128 u128;
+        const u128 r0 = (uintptr_t)residual, r1 = r0 + (u128)n * esz, pt = (u128)n * (2 * esz);
+        const u128 i0 = (uintptr_t)in, o0 = (uintptr_t)out;
+        if ((r0 < i0 + pt && i0 < r1) || (r0 < o0 + pt && o0 < r1)) return BEVWARP_ERR_OVERLAP;
+    }
+    // (last: the kernel moves a point as one 8- or 16-byte unit and a residual as one value)
+    return (((uintptr_t)in | (uintptr_t)out) % (2 * esz) || (uintptr_t)residual % esz) ? BEVWARP_ERR_BAD_ARG : BEVWARP_OK;
+}
 // bevwarp_warp_stitch, one camera of it: that camera's frames against the canvas -- bevwarp_warp's images and formats without bicubic, with
 // the two blend rules and the constant and the transparent border.  (stitch_status below runs the checks over all cameras.)
 inline Call stitch_call(const bevwarp_camera& k, Frames dst, int batch, int dst_h, int dst_w, int channels, int dtype, int interp, int blend, int border_mode) {

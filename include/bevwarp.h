@@ -44,6 +44,10 @@
  *   bevwarp_footprint       -- measurement aid (SURVEY.md 8(d) "footprint_px"), no reference twin
  *   bevwarp_project_points  pts_world_bev(pts_src, H), bev/rbox.py:136-151; rbox_world_img, :221-226;
  *                             Calib.gen_center_in_world, bev/calib.py:135-138
+ *   bevwarp_project_points_lens  the same three on the frames a distorted camera delivers -- rbox_world_img, bev/rbox.py:221-226 (world ->
+ *                             RAW pixel) and Calib.gen_center_in_world, bev/calib.py:135-138 (RAW pixel -> world) -- through the lens the
+ *                             reference carries and never applies to points: Calib.dist_coeff (bev/calib.py:25), Rt_from_pts_K_dist's
+ *                             `dist_coeffs` (bev/homo.py:130-135).  What cv2.projectPoints / cv2.undistortPoints are for
  *   bevwarp_rbox_iou        iou_batch_rbox -> d3d.box.box2d_iou(.., method="rbox"),
  *                             bev/tracker/rbox_tracker.py:87-92 (call site :393-394)
  *   bevwarp_rbox_transform  rbox_world_bev(rbox_src, H, src), bev/rbox.py:173-219 (yaw conventions :20-36)
@@ -509,6 +513,51 @@ int bevwarp_footprint(unsigned char *touched, int batch, int src_h, int src_w, i
  */
 int bevwarp_project_points(const void *in, void *out, int64_t n, int dim, const double *H /*HOST*/, int dtype,
                            void *stream);
+
+/*
+ * bevwarp_project_points through bevwarp_warp_lens's lens model, in both directions: points of the plane H maps from -> pixels of the RAW
+ * frame (BEVWARP_LENS_DISTORT), and pixels of the raw frame -> the plane H maps to (BEVWARP_LENS_UNDISTORT), which inverts the model by a
+ * fixed number of fixed-point steps and gives every point a verdict.  Like the lens warp this is OUR chain: parity with OpenCV is unpinned
+ * (cv2.projectPoints / cv2.undistortPoints).  The iteration is the classic undistortPoints step, but that function runs 5 steps (or stops on
+ * its own criteria) and reports nothing; here `iters` is the caller's (the Python entry's default is 20: 5 steps leave 0.1 px on a 640-px
+ * frame), no step is skipped, and a point whose reprojection misses by more than tol_px is NaN.  Bit-reproducible: every step below is one
+ * correctly rounded float64 + - * / (IEEE division, no FMA), in the order written.
+ *   in, out       device, n x 2, contiguous, dtype BEVWARP_F32 | BEVWARP_F64, aligned to a point (8 / 16 bytes).  in == out is allowed.
+ *                 float32 inputs widen exactly; out and residual are the float64 results rounded to nearest.
+ *   H             HOST, 9 doubles (copied at call time).
+ *   lens, r2_max  exactly bevwarp_warp_lens's: the same 12 doubles, the same meaning.
+ * "The lens steps" on (xn, yn) are bevwarp_warp_lens's lines `x2 = ...` to `v = fy yd + cy`, giving (u, v, r2).  With (x, y) a point:
+ *   plane(x, y):  X = (h1 y + h2) + h0 x      Y = (h4 y + h5) + h3 x      W = (h7 y + h8) + h6 x
+ *                 Wr = (W != 0) ? 1 / W : 0   result (X Wr, Y Wr)
+ *                 (the operand order of bevwarp_warp_lens's first evaluation block: at the integer pixels of a destination no wider than
+ *                 one block, DISTORT with M_ray reproduces that warp's u, v and r2 by bits)
+ * BEVWARP_LENS_DISTORT.  H: the points' coordinates -> normalised UNDISTORTED camera plane (bevwarp_warp_lens's M_ray of the inverse
+ * homography).  residual must be NULL; iters and tol_px are ignored.
+ *   (xn, yn) = plane(in[i])        (u, v, r2) = the lens steps on (xn, yn)
+ *   out[i] = (r2 <= r2_max) ? (u, v) : (NaN, NaN)                  (false for a NaN r2)
+ * BEVWARP_LENS_UNDISTORT.  H: normalised undistorted camera plane -> the target's coordinates (H_world_img K, say).  (u, v) = in[i]:
+ *   xd = (u - cx) / fx     yd = (v - cy) / fy     x = xd     y = yd
+ *   `iters` times (1..100, no early exit):
+ *       x2 = x x   y2 = y y   r2 = x2 + y2   xy2 = 2 (x y)          num, den as in bevwarp_warp_lens          ic = den / num
+ *       dx = p1 xy2 + p2 (r2 + 2 x2)         dy = p1 (r2 + 2 y2) + p2 xy2
+ *       x = (xd - dx) ic                     y = (yd - dy) ic
+ *   (u', v', r2) = the lens steps on (x, y)
+ *   e = max(|u' - u|, |v' - v|), NaN if either is NaN              valid = (r2 <= r2_max) and (e <= tol_px)
+ *   out[i] = valid ? plane(x, y) : (NaN, NaN)
+ *   residual[i] = e                 device, n values of dtype, or NULL; written for valid and invalid points alike
+ *   tol_px        >= 0 pixels of the raw frame; +inf accepts every e that is not NaN.
+ * A NaN that is stored is some NaN: its sign and payload are unspecified.
+ * Status, in this order: BEVWARP_ERR_BAD_ARG for in, out or H NULL, n < 0, a direction outside the two, a residual under
+ * BEVWARP_LENS_DISTORT, and under BEVWARP_LENS_UNDISTORT iters outside 1..100 or tol_px NaN or negative; BEVWARP_ERR_UNSUPPORTED for dtype;
+ * BEVWARP_ERR_NOT_FINITE for H; the lens and r2_max as in bevwarp_warp_lens (NULL: BAD_ARG; NaN, +-inf: NOT_FINITE; fx == 0, fy == 0,
+ * r2_max NaN or < 0: BAD_ARG); BEVWARP_ERR_OVERLAP when residual's n values share a byte with in's or out's n points; last,
+ * BEVWARP_ERR_BAD_ARG for in or out not aligned to a point or residual not aligned to a value.  n == 0 is BEVWARP_OK and launches nothing.
+ */
+#define BEVWARP_LENS_DISTORT 0     /* plane -> raw pixel */
+#define BEVWARP_LENS_UNDISTORT 1   /* raw pixel -> plane */
+int bevwarp_project_points_lens(const void *in, void *out, void *residual /*device, may be NULL*/, int64_t n,
+                                const double *H /*HOST, 9*/, const double *lens /*HOST, 12*/, double r2_max,
+                                int direction, int iters, double tol_px, int dtype, void *stream);
 
 /*
  * out[i][j] = IoU of rotated rectangles a[i], b[j].  Rows are [x, y, w, h, yaw, ...] with
