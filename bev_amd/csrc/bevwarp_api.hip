@@ -14,6 +14,7 @@
 #include "warp_cubic.h"
 #include "warp_kernels.h"
 #include "warp_lens.h"
+#include "warp_map.h"
 #include "warp_nv12.h"
 #include "warp_nv12_out.h"
 #include "warp_stitch.h"
@@ -243,6 +244,63 @@ int bevwarp_warp_lens(const void* src, void* dst, int batch, int src_h, int src_
     a.dst_vec_ok = plan::wide_stores_ok(c.writes[0], plan::store_align(dtype, channels, false));
     a.src_vec_ok = plan::pixel_loads_ok(c.reads[0].im, plan::pixel_load_align(dtype, channels));
     return launched(launch_warp_lens(a, dtype, channels, interp, transparent, items, (hipStream_t)stream));
+}
+
+int bevwarp_build_map(const double* M, int m_count, const double* lens, double r2_max, int interp, void* map_xy, void* map_frac, int dst_h, int dst_w,
+                      int64_t xy_frame_stride, int64_t xy_row_stride, int64_t frac_frame_stride, int64_t frac_row_stride, void* stream) {
+    const Frames xy = {map_xy, xy_frame_stride, xy_row_stride}, fr = {map_frac, frac_frame_stride, frac_row_stride};
+    TilePlan p;
+    const int st = plan::build_map_status(M, m_count, lens, r2_max, interp, xy, fr, dst_h, dst_w, kBorderTileW, kBorderTileH, p);
+    if (st != BEVWARP_OK) return st;
+    const bool linear = interp == BEVWARP_LINEAR;
+    MapBuildArgs a;
+    memset(&a, 0, sizeof(a));
+    a.dst = (uint8_t*)map_xy, a.minv = M, a.m_stride = 9;
+    a.dst_fs = m_count == 1 ? 0 : xy_frame_stride, a.dst_rs = xy_row_stride, a.dst_h = dst_h, a.dst_w = dst_w;
+    a.frac = linear ? (uint8_t*)map_frac : nullptr, a.frac_fs = m_count == 1 ? 0 : frac_frame_stride, a.frac_rs = frac_row_stride;
+    a.bw0 = p.bw0, a.tiles_x = p.tiles_x, a.tiles_per_frame = p.tiles_per_frame;
+    a.tpf_magic = p.tpf_magic, a.tx_magic = p.tx_magic, a.bw0_magic = p.bw0_magic;
+    const Image ixy = Frames{map_xy, a.dst_fs, xy_row_stride}.image(dst_h, (uint64_t)dst_w * 4, m_count);
+    const Image ifr = Frames{map_frac, a.frac_fs, frac_row_stride}.image(dst_h, (uint64_t)dst_w * 2, m_count);
+    a.dst_vec_ok = plan::map_vec_ok(ixy, linear ? &ifr : nullptr);
+    if (lens) memcpy(a.lens, lens, sizeof(a.lens)), a.r2_max = r2_max;
+    return launched(launch_build_map(a, interp, lens != nullptr, p.total_tiles, (hipStream_t)stream));
+}
+
+int bevwarp_remap(const void* src, void* dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int channels, int64_t src_frame_stride,
+                  int64_t src_row_stride, int64_t dst_frame_stride, int64_t dst_row_stride, const void* map_xy, const void* map_frac, int map_count,
+                  int64_t xy_frame_stride, int64_t xy_row_stride, int64_t frac_frame_stride, int64_t frac_row_stride, int dtype, int interp, int border_mode,
+                  const double* border_value, void* stream) {
+    const Call c = plan::remap_call({src, src_frame_stride, src_row_stride}, {dst, dst_frame_stride, dst_row_stride}, {map_xy, xy_frame_stride, xy_row_stride},
+                                    {map_frac, frac_frame_stride, frac_row_stride}, {batch, src_h, src_w, dst_h, dst_w, 0, nullptr}, map_count, channels, dtype,
+                                    interp, border_mode);
+    const int st = plan::check_call(c);
+    if (st != BEVWARP_OK || batch == 0) return st;
+    const RemapPlan p = plan::plan_remap(batch, map_count, dst_h, dst_w, kBorderTileW, kBorderTileH, kRemapMaxFramesPerItem, plan::kRemapFillItems);
+    if (p.status != BEVWARP_OK) return p.status;
+    RemapArgs a;
+    memset(&a, 0, sizeof(a));
+    const bool constant = border_mode == BEVWARP_BORDER_CONSTANT;
+    uint8_t bu[4];  // (border_value is read by the constant border only)
+    if (border_values(constant ? border_value : nullptr, channels, a.bv_f, bu) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
+    a.bv_u8 = (uint32_t)bu[0] | ((uint32_t)bu[1] << 8) | ((uint32_t)bu[2] << 16) | ((uint32_t)bu[3] << 24);
+    a.dst = (uint8_t*)dst, a.dst_fs = dst_frame_stride, a.dst_rs = dst_row_stride, a.dst_h = dst_h, a.dst_w = dst_w;
+    a.bw0 = p.bw0, a.tiles_x = p.tiles_x, a.tiles_per_frame = p.tiles_per_frame;
+    a.tpf_magic = p.tpf_magic, a.tx_magic = p.tx_magic, a.bw0_magic = p.bw0_magic;
+    a.src = (const uint8_t*)src, a.src_fs = src_frame_stride, a.src_rs = src_row_stride, a.src_h = src_h, a.src_w = src_w;
+    if (!constant && border_mode != BEVWARP_BORDER_TRANSPARENT) {
+        const plan::BorderPeriod px = plan::border_period(border_mode, src_w), py = plan::border_period(border_mode, src_h);
+        a.per_x = px.per, a.off_x = px.off, a.mag_x = px.mag;
+        a.per_y = py.per, a.off_y = py.off, a.mag_y = py.mag;
+    }
+    const Image &ixy = c.reads[1].im, *ifr = (interp == BEVWARP_LINEAR) ? &c.reads[2].im : nullptr;
+    a.xy = (const uint8_t*)map_xy, a.xy_fs = ixy.fs, a.xy_rs = ixy.rs;
+    if (ifr) a.frac = (const uint8_t*)map_frac, a.frac_fs = ifr->fs, a.frac_rs = ifr->rs;
+    a.batch = batch, a.frames_per_item = p.frames_per_item;
+    a.map_vec_ok = plan::map_vec_ok(ixy, ifr);
+    a.dst_vec_ok = plan::wide_stores_ok(c.writes[0], plan::store_align(dtype, channels, false));
+    a.src_vec_ok = plan::pixel_loads_ok(c.reads[0].im, plan::pixel_load_align(dtype, channels));
+    return launched(launch_remap(a, dtype, channels, interp, border_mode, p.total_tiles, (hipStream_t)stream));
 }
 
 int bevwarp_warp_stitch(const bevwarp_camera* cams, int n_cams, void* dst, int batch, int dst_h, int dst_w, int channels, int64_t dst_frame_stride,

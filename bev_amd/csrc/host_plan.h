@@ -1,5 +1,5 @@
 // host_plan.h -- what the C ABI decides before a launch, as plain C++17 (no HIP): the argument checks and the launch geometry.
-// bevwarp_api.hip is its only user in the library; tests/host_plan_driver.cpp (and lens_plan_driver.cpp, stitch_plan_driver.cpp) compile it
+// bevwarp_api.hip is its only user in the library; tests/host_plan_driver.cpp (and lens_plan_driver.cpp, stitch_plan_driver.cpp, remap_plan_driver.cpp) compile it
 // with g++ under the address and undefined-behaviour sanitizers, and tests/golden/launch_plans.json pins every field of the plans.  Not installed.
 #pragma once
 #include <math.h>
@@ -92,6 +92,7 @@ struct Frames {  // an image batch as the ABI passes it
 struct ReadImage {
     Image im;
     int cols, elem;  // pixels of a row, for the size limits; bytes of an element: 1, 2 (a (U, V) pair) or 4 (float32)
+    bool map;        // a map plane of bevwarp_remap: as large as the destination (no source limits); its batch is the map count
 };
 struct WrittenImage {
     Image im;  // (planar: one plane's rows)
@@ -118,10 +119,11 @@ struct Call : Sizes {
     bool format_first;  // ... which is asked before the layouts (bevwarp_warp and its kin) or after the matrix count (the NV12 entry points)
     bool even_src, even_dst;  // NV12 frames have even sides
     int n_reads, n_writes;
-    ReadImage reads[2];
+    ReadImage reads[3];
     WrittenImage writes[2];
 
-    void read(const Image& im, int cols, int elem) { reads[n_reads++] = {im, cols, elem}; }
+    void read(const Image& im, int cols, int elem) { reads[n_reads++] = {im, cols, elem, false}; }
+    void read_map(const Image& im, int elem) { reads[n_reads++] = {im, 0, elem, true}; }
     void write(const Image& im, int elem) { writes[n_writes++] = {im, elem, false, 1, 0}; }
     void write_planes(const Image& im, int elem, int planes, int64_t plane_stride) { writes[n_writes++] = {im, elem, true, planes, plane_stride}; }
     void read_nv12(Frames y, Frames uv) {
@@ -182,17 +184,19 @@ inline int matrix_count_status(const Call& c) { return (c.m_count != 1 && c.m_co
 inline int format_status(const Call& c) { return c.format_ok ? BEVWARP_OK : BEVWARP_ERR_UNSUPPORTED; }
 inline int source_sizes_status(const Call& c) {
     int st = BEVWARP_OK;
-    for (int i = 0; i < c.n_reads && st == BEVWARP_OK; i++) st = source_size_status(c.reads[i].im, c.reads[i].cols);
+    for (int i = 0; i < c.n_reads && st == BEVWARP_OK; i++)
+        if (!c.reads[i].map) st = source_size_status(c.reads[i].im, c.reads[i].cols);
     return st;
 }
 // Every written image against every read one, and the written ones against each other; read images may overlap each other.  An image of
-// planes is taken as its bounding byte range: a frame's planes need not share the rows' stride.
+// planes is taken as its bounding byte range: a frame's planes need not share the rows' stride.  So is a map plane: it may have fewer
+// frames than the destination, which regions_overlap's side-by-side rule does not foresee.
 inline int overlap_status(const Call& c) {
     for (int i = 0; i < c.n_writes; i++)
         for (int k = 0; k < c.n_reads; k++) {
             const WrittenImage& w = c.writes[i];
             const Image& r = c.reads[k].im;
-            if (w.planar ? (r.base < w.end() && w.im.base < r.end()) : regions_overlap(r, w.im)) return BEVWARP_ERR_OVERLAP;
+            if ((w.planar || c.reads[k].map) ? (r.base < w.end() && w.im.base < r.end()) : regions_overlap(r, w.im)) return BEVWARP_ERR_OVERLAP;
         }
     return (c.n_writes == 2 && written_planes_overlap(c.writes[0].im, c.writes[1].im)) ? BEVWARP_ERR_OVERLAP : BEVWARP_OK;
 }
@@ -227,6 +231,19 @@ inline Call warp_call(Frames src, Frames dst, const Sizes& z, int channels, int 
 inline Call lens_call(Frames src, Frames dst, const Sizes& z, int channels, int dtype, int interp, int border_mode) {
     Call c = warp_call(src, dst, z, channels, dtype, interp, false);
     c.format_ok = c.format_ok && (border_mode == BEVWARP_BORDER_CONSTANT || border_mode == BEVWARP_BORDER_TRANSPARENT);
+    return c;
+}
+// bevwarp_remap: bevwarp_warp's images and formats without bicubic, with all six borders, and the two map planes as read images --
+// map_count (1 or batch) frames of dst_h rows of dst_w int16 pairs, and (bilinear) of dst_w uint16.  The map count stands where the
+// other entry points have their matrix count; the frac plane is an image under BEVWARP_LINEAR only (NULL there: a NULL image).
+inline Call remap_call(Frames src, Frames dst, Frames xy, Frames frac, Sizes z, int map_count, int channels, int dtype, int interp, int border_mode) {
+    z.m_count = map_count, z.minv = (const double*)xy.base;  // (no matrices: the xy plane stands in the NULL check)
+    Call c = warp_call(src, dst, z, channels, dtype, interp, false);
+    c.format_ok = c.format_ok && border_mode >= BEVWARP_BORDER_CONSTANT && border_mode <= BEVWARP_BORDER_TRANSPARENT;
+    const int n = (map_count == z.batch && z.batch > 0) ? z.batch : 1;
+    if (n == 1) xy.fs = frac.fs = 0;  // (one map: its frame stride is not looked at)
+    c.read_map(xy.image(z.dst_h, (uint64_t)z.dst_w * 4, n), 4);
+    if (interp == BEVWARP_LINEAR) c.read_map(frac.image(z.dst_h, (uint64_t)z.dst_w * 2, n), 2);
     return c;
 }
 // ... and its lens (HOST: fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6) and r2_max (+inf: no limit), which check_call does not see
@@ -383,6 +400,53 @@ inline TilePlan plan_border(int batch, int dst_h, int dst_w, int tw, int th) {
     p.status = BEVWARP_OK;
     return p;
 }
+
+// The remap kernel (warp_map.hip): plan_border's tiles, one item per tile and GROUP of frames_per_item consecutive frames -- the item loads
+// its tile's map entries once and walks the group's frames with them in registers.  Only a shared map (map_count == 1) is frame-invariant:
+// per-frame maps take one frame per item.  A shared map takes the largest power of two up to max_fpi (the library passes 2: warp_map.h) that
+// still leaves `fill` items (a few rounds of resident workgroups: enough to fill the machine and to even out tiles of different cost);
+// the last group may be short.
+// In the plan, tiles_per_frame and its magic decode the item into (group, tile); total_tiles counts items.
+struct RemapPlan : TilePlan {
+    int frames_per_item, groups;
+};
+inline RemapPlan plan_remap(int batch, int map_count, int dst_h, int dst_w, int tw, int th, int max_fpi, int64_t fill) {
+    RemapPlan p = {};
+    p.frames_per_item = 1;
+    if (map_count == 1 && batch > 1) {
+        const TilePlan one = plan_border(1, dst_h, dst_w, tw, th);
+        if (one.status != BEVWARP_OK) {
+            static_cast<TilePlan&>(p) = one;
+            return p;
+        }
+        while (p.frames_per_item * 2 <= max_fpi && p.frames_per_item * 2 <= batch && ((int64_t)batch + p.frames_per_item * 2 - 1) / (p.frames_per_item * 2) * one.tiles_per_frame >= fill)
+            p.frames_per_item *= 2;
+    }
+    p.groups = (int)(((int64_t)batch + p.frames_per_item - 1) / p.frames_per_item);  // (in 64 bits: a batch next to 2^31)
+    static_cast<TilePlan&>(p) = plan_border(p.groups, dst_h, dst_w, tw, th);
+    return p;
+}
+constexpr int64_t kRemapFillItems = 4096;  // (four rounds of 1024 resident 4-wave workgroups)
+
+// bevwarp_build_map: every check of the call, in the order include/bevwarp.h documents, and in `p` plan_border's grid over the m_count maps.
+// M, xy, frac are device pointers (never dereferenced), lens HOST or NULL.
+inline int build_map_status(const double* M, int m_count, const double* lens, double r2_max, int interp, Frames xy, Frames frac, int dst_h, int dst_w, int tw, int th,
+                            TilePlan& p) {
+    p = {};
+    if (!M || !xy.base || m_count < 1 || dst_h <= 0 || dst_w <= 0) return BEVWARP_ERR_BAD_ARG;
+    if (interp != BEVWARP_NEAREST && interp != BEVWARP_LINEAR) return BEVWARP_ERR_UNSUPPORTED;
+    const bool with_frac = interp == BEVWARP_LINEAR;
+    if (with_frac && !frac.base) return BEVWARP_ERR_BAD_ARG;
+    if (m_count == 1) xy.fs = frac.fs = 0;
+    const Image ixy = xy.image(dst_h, (uint64_t)dst_w * 4, m_count), ifr = frac.image(dst_h, (uint64_t)dst_w * 2, m_count);
+    if (layout_status(ixy, 4) != BEVWARP_OK || (with_frac && layout_status(ifr, 2) != BEVWARP_OK)) return BEVWARP_ERR_BAD_ARG;
+    p = plan_border(m_count, dst_h, dst_w, tw, th);
+    if (p.status != BEVWARP_OK) return p.status;
+    if (with_frac && regions_overlap(ixy, ifr)) return BEVWARP_ERR_OVERLAP;  // (both are written)
+    return lens ? lens_status(lens, r2_max) : BEVWARP_OK;
+}
+// the lane-wide accesses of the two planes: 16 bytes of xy, 8 bytes of frac (no frac plane: the xy plane decides)
+inline bool map_vec_ok(const Image& xy, const Image* frac) { return wide_stores_ok(xy, 16) && (!frac || wide_stores_ok(*frac, 8)); }
 
 // The index remap of the border modes that take a remainder, for an axis of n source pixels: the period (unused by REPLICATE and
 // TRANSPARENT), an offset that is a multiple of it and makes every saturated index (>= -32768) non-negative, and the period's magic.

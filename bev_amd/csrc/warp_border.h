@@ -22,6 +22,22 @@ struct BorderArgs : FrameArgs {  // (the launch geometry, the destination and th
     int src_vec_ok;               // 8-bit, 2 / 4 channels: every source pixel is 2- / 4-byte aligned (one load per tap)
 };
 
+namespace {
+// borderInterpolate(p, n, MODE) in closed form for p in [-32768, 32768] (a saturated index, or one past it):
+//   REPLICATE clamp; WRAP p mod n; REFLECT q = p mod 2n, q < n ? q : 2n-1-q; REFLECT_101 q = p mod (2n-2), q < n ? q : 2n-2-q.
+// per = the period (n, 2n, 2n - 2; 1 for REFLECT_101 of n == 1, which maps everything to 0), off = a multiple of it that makes
+// p + off non-negative, mag = fast_div's magic of per for p + off <= off + 32768.
+template <int MODE>
+__device__ __forceinline__ int border_index(int p, int n, uint32_t per, uint32_t off, uint32_t mag) {
+    if (MODE == kBorderReplicate) return min(max(p, 0), n - 1);
+    const uint32_t u = (uint32_t)(p + (int)off);
+    const int q = (int)(u - fast_div(u, mag, per) * per);
+    if (MODE == kBorderWrap) return q;
+    if (MODE == kBorderReflect) return q < n ? q : (int)per - 1 - q;
+    return q < n ? q : (int)per - q;  // REFLECT_101
+}
+}  // namespace
+
 hipError_t launch_warp_border(const BorderArgs& a, int dtype, int channels, int interp, int mode, int64_t items, hipStream_t stream);
 
 }  // namespace bevwarp

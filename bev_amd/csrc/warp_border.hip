@@ -9,26 +9,12 @@
 // classification, no guarded reads.  The coordinates are the reference's exact float64 chain, pixel by pixel.
 //
 // The frame -- item decoding, the coordinate walk, the rounding with the reference's NaN, a pixel's load and the store of a lane's 4
-// pixels, the taps of a pixel and their blend -- is flat_frame.h, shared with the bicubic, NV12 and stitch kernels; this unit holds the index
-// remap and the kernel body.
+// pixels, the taps of a pixel and their blend -- is flat_frame.h, shared with the bicubic, NV12 and stitch kernels; the index remap is
+// warp_border.h (the remap kernel takes it too); this unit holds the kernel body.
 #include "warp_border.h"
 
 namespace bevwarp {
 namespace {
-
-// borderInterpolate(p, n, MODE) in closed form for p in [-32768, 32768] (a saturated index, or one past it):
-//   REPLICATE clamp; WRAP p mod n; REFLECT q = p mod 2n, q < n ? q : 2n-1-q; REFLECT_101 q = p mod (2n-2), q < n ? q : 2n-2-q.
-// per = the period (n, 2n, 2n - 2; 1 for REFLECT_101 of n == 1, which maps everything to 0), off = a multiple of it that makes
-// p + off non-negative, mag = fast_div's magic of per for p + off <= off + 32768.
-template <int MODE>
-__device__ __forceinline__ int border_index(int p, int n, uint32_t per, uint32_t off, uint32_t mag) {
-    if (MODE == kBorderReplicate) return min(max(p, 0), n - 1);
-    const uint32_t u = (uint32_t)(p + (int)off);
-    const int q = (int)(u - fast_div(u, mag, per) * per);
-    if (MODE == kBorderWrap) return q;
-    if (MODE == kBorderReflect) return q < n ? q : (int)per - 1 - q;
-    return q < n ? q : (int)per - q;  // REFLECT_101
-}
 
 template <typename T, int C, int INTERP, int MODE>
 __global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(kWavesPerSimd, 8))) void warp_border_kernel(const BorderArgs a) {

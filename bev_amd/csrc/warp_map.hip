@@ -1,0 +1,319 @@
+// warp_map.hip -- the warp of a fixed camera in two steps (bevwarp_build_map, bevwarp_remap).  The builder runs the
+// exact float64 coordinate chain -- the border kernel's, or with a lens the lens kernel's, operation for operation -- once per camera and
+// geometry and stores what it gives in OpenCV's fixed-point map format: int16 pairs (sx, sy) and, for bilinear, uint16 (fy << 5) | fx.
+// The remap kernel samples frames through such maps: from (sx, sy, fx, fy) on it is the lens kernel's guarded sampler (BORDER_CONSTANT)
+// and the border kernel's body (the other five modes), with no float64 at all.  A lane's 4 map entries are frame-invariant under a shared
+// map: a workgroup loads its tile's entries once, derives tap offsets and the inside masks, and walks frames_per_item frames with them in
+// registers.
+//
+// The frame -- item decoding, the row walk, the rounding, a pixel's load and the store of a lane's 4 pixels -- is flat_frame.h; the lens
+// step and the blend are lens_pixel.h; the index remap is warp_border.h.
+#include "warp_map.h"
+#include "lens_pixel.h"
+
+namespace bevwarp {
+namespace {
+
+// ---- the builder ---------------------------------------------------------------------------------------------------------------------------
+template <int INTERP, bool LENS>
+__global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(kWavesPerSimd, 8))) void build_map_kernel(const MapBuildArgs a) {
+    constexpr int PPL = kBorderPPL;
+    uint32_t b;
+    int y, xs;  // map, row, the lane's first pixel
+    if (!lane_position(a, b, y, xs)) return;
+    RowWalk walk(a, b, y);
+
+    uint32_t e[PPL], fr[PPL];
+#pragma unroll
+    for (int j = 0; j < PPL; j++) {
+        // pixels past the row's end are computed like any other and not stored
+        double Xn, Yn, W;
+        walk.pixel(a, xs + j, Xn, Yn, W);
+        int X, Y;
+        bool valid = true;
+        if constexpr (LENS)
+            valid = lens_pixel<INTERP>(a, Xn, Yn, W, X, Y);
+        else
+            map_pixel_exact_nan_max<INTERP>(Xn, Yn, W, X, Y);
+        const int sx = sat16(INTERP == kLinear ? (X >> kInterBits) : X), sy = sat16(INTERP == kLinear ? (Y >> kInterBits) : Y);
+        const uint32_t f = INTERP == kLinear ? (uint32_t)(((Y & 31) << 5) | (X & 31)) : 0u;
+        // an invalid pixel: every tap of (-32768, -32768) lies outside every admissible source (include/bevwarp.h)
+        e[j] = valid ? (((uint32_t)sx & 0xffffu) | ((uint32_t)sy << 16)) : 0x80008000u;
+        fr[j] = valid ? f : 0u;
+    }
+
+    uint8_t* xrow = dst_row(a, b, y) + (int64_t)xs * 4;
+    uint8_t* frow = a.frac + (int64_t)b * a.frac_fs + (int64_t)y * a.frac_rs + (int64_t)xs * 2;
+    if (a.dst_vec_ok && xs + PPL <= a.dst_w) {  // the lane's 4 entries: one 16-byte and one 8-byte store
+        const u32x4 o = {e[0], e[1], e[2], e[3]};
+        wide_store(reinterpret_cast<u32x4*>(xrow), o);
+        if constexpr (INTERP == kLinear) {
+            const u32x2 q = {fr[0] | (fr[1] << 16), fr[2] | (fr[3] << 16)};
+            *reinterpret_cast<u32x2*>(frow) = q;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < PPL; j++)
+            if (xs + j < a.dst_w) {
+                reinterpret_cast<uint32_t*>(xrow)[j] = e[j];
+                if constexpr (INTERP == kLinear) reinterpret_cast<uint16_t*>(frow)[j] = (uint16_t)fr[j];
+            }
+    }
+}
+
+// ---- the sampler ---------------------------------------------------------------------------------------------------------------------------
+template <typename T, int C>
+__device__ __forceinline__ Pixel<T, C> border_pixel(const RemapArgs& a) {
+    Pixel<T, C> p;
+    if constexpr (sizeof(T) == 1) {
+        p.packed = a.bv_u8;
+    } else {
+#pragma unroll
+        for (int k = 0; k < C; k++) p.v[k] = a.bv_f[k];
+    }
+    return p;
+}
+
+// What a lane keeps of one map entry for every frame it walks: the byte offsets of its four taps in a frame (all four are source pixels:
+// remapped, an inlier's, or clamped; a frame is below 2 GiB, so 32 bits hold them and a load is the frame's wave-uniform base plus one
+// register), the weights, and for the constant border which of the four taps lie inside.
+struct Taps {
+    uint32_t a00, a01, a10, a11;
+    uint32_t w;  // fx | fy << 5 | in << 10; in: bit 0 = tap (row 0, col 0), 1 = (0, 1), 2 = (1, 0), 3 = (1, 1)
+    __device__ __forceinline__ int fx() const { return (int)(w & 31u); }
+    __device__ __forceinline__ int fy() const { return (int)((w >> 5) & 31u); }
+    __device__ __forceinline__ uint32_t in() const { return w >> 10; }
+};
+
+// One source pixel at a byte offset of the frame: exactly its C * sizeof(T) bytes are read (flat_frame.h's load_pixel, by offset).
+template <typename T, int C>
+__device__ __forceinline__ Pixel<T, C> load_at(const uint8_t* __restrict__ frame, uint32_t off, bool vec) {
+    Pixel<T, C> p;
+    const uint8_t* q = frame + off;
+    if constexpr (sizeof(T) == 1) {
+        if (C == 4 && vec) {
+            p.packed = *reinterpret_cast<const uint32_t*>(q);
+        } else if (C == 2 && vec) {
+            p.packed = *reinterpret_cast<const uint16_t*>(q);
+        } else {
+            p.packed = 0;
+#pragma unroll
+            for (int k = 0; k < C; k++) p.packed |= (uint32_t)q[k] << (8 * k);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < C; k++) p.v[k] = reinterpret_cast<const float*>(q)[k];
+    }
+    return p;
+}
+
+// The two taps of a row of 8-bit 3-channel pixels whose columns are adjacent are 6 contiguous bytes: one dword and one short load
+// (unaligned, as the byte pairs the compiler forms on its own already are) instead of two shorts and two bytes, and never a byte beyond the
+// six.  The tap loads are what binds this kernel.
+__device__ __forceinline__ void load_pair_u8x3(const uint8_t* __restrict__ frame, uint32_t off, Pixel<uint8_t, 3>& p0, Pixel<uint8_t, 3>& p1) {
+    uint32_t lo;
+    uint16_t hi;
+    __builtin_memcpy(&lo, frame + off, 4);
+    __builtin_memcpy(&hi, frame + off + 4, 2);
+    p0.packed = lo & 0xffffffu;
+    p1.packed = __builtin_amdgcn_alignbit((uint32_t)hi, lo, 24);  // bytes 3, 4, 5
+}
+
+// the four taps of an entry; PAIR: both rows' taps are adjacent columns of 8-bit 3-channel pixels
+template <typename T, int C, bool PAIR>
+__device__ __forceinline__ void load_taps(const uint8_t* __restrict__ frame, const Taps& t, bool vec, Pixel<T, C>& p00, Pixel<T, C>& p01, Pixel<T, C>& p10, Pixel<T, C>& p11) {
+    if constexpr (PAIR) {
+        load_pair_u8x3(frame, t.a00, p00, p01);
+        load_pair_u8x3(frame, t.a10, p10, p11);
+    } else {
+        p00 = load_at<T, C>(frame, t.a00, vec), p01 = load_at<T, C>(frame, t.a01, vec);
+        p10 = load_at<T, C>(frame, t.a10, vec), p11 = load_at<T, C>(frame, t.a11, vec);
+    }
+}
+
+template <typename T, int C, int INTERP, int MODE, bool PAIR>
+__device__ __forceinline__ Pixel<T, C> sample_entry(const RemapArgs& a, const uint8_t* __restrict__ frame, const Taps& t, bool vec) {
+    if constexpr (MODE != 0) {  // every tap is a source pixel
+        if (INTERP == kNearest) return load_at<T, C>(frame, t.a00, vec);
+        Pixel<T, C> p00, p01, p10, p11;
+        load_taps<T, C, PAIR>(frame, t, vec, p00, p01, p10, p11);
+        return blend_taps<T, C>(p00, p01, p10, p11, t.fx(), t.fy());
+    } else {
+        // The constant border: every tap is loaded from the CLAMPED position (unconditional loads, all issued before the first wait) and
+        // replaced by the border pixel where its true position is outside; all four outside: the border value itself.
+        const Pixel<T, C> b = border_pixel<T, C>(a);
+        if (INTERP == kNearest) {
+            const Pixel<T, C> p = load_at<T, C>(frame, t.a00, vec);
+            return (t.in() & 1u) ? p : b;
+        }
+        Pixel<T, C> t00, t01, t10, t11;
+        load_taps<T, C, PAIR>(frame, t, vec, t00, t01, t10, t11);
+        const Pixel<T, C> out = blend_taps<T, C>((t.in() & 1u) ? t00 : b, (t.in() & 2u) ? t01 : b, (t.in() & 4u) ? t10 : b, (t.in() & 8u) ? t11 : b, t.fx(), t.fy());
+        // (8-bit pixels: the blend of four border pixels is the border pixel)
+        return (sizeof(T) == 4 && t.in() == 0u) ? b : out;
+    }
+}
+
+// a lane's 4 pixels of one frame
+template <typename T, int C, int INTERP, int MODE, bool PAIR>
+__device__ __forceinline__ void frame_pixels(const RemapArgs& a, const uint8_t* __restrict__ frame, const Taps (&tap)[kBorderPPL], const bool (&wr)[kBorderPPL], bool vec,
+                                             Pixel<T, C> (&px)[kBorderPPL]) {
+#pragma unroll
+    for (int j = 0; j < kBorderPPL; j++) {
+        if constexpr (MODE == kBorderTransparent) {
+            if (wr[j]) px[j] = sample_entry<T, C, INTERP, MODE, PAIR>(a, frame, tap[j], vec);
+        } else {
+            px[j] = sample_entry<T, C, INTERP, MODE, PAIR>(a, frame, tap[j], vec);
+        }
+        // float32 pixels of 3 / 4 channels, bilinear: the taps of two pixels are 24 / 32 registers -- the loads of the lane's second pair
+        // wait for the first pair's blends, or the kernel passes the 128 registers its occupancy is planned for
+        if (sizeof(T) == 4 && C >= 3 && INTERP == kLinear && j == 1) __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+template <typename T, int C, int INTERP, int MODE>
+__global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(kWavesPerSimd, 8))) void remap_kernel(const RemapArgs a) {
+    constexpr int PPL = kBorderPPL;
+    constexpr bool kTransparent = MODE == kBorderTransparent;
+    uint32_t g;
+    int y, xs;  // group of frames, row, the lane's first pixel
+    if (!lane_position(a, g, y, xs)) return;
+    const int b0 = (int)g * a.frames_per_item;
+    const int nb = min(a.frames_per_item, a.batch - b0);
+
+    // the lane's map entries: wide loads where all 4 pixels lie in the row and the planes' layout admits them; no entry past the row's end
+    // is read (such a lane's entry is 0: the source's first pixel, never stored)
+    uint32_t e[PPL], fr[PPL];
+    const bool whole = xs + PPL <= a.dst_w;
+    const uint8_t* xrow = a.xy + (int64_t)b0 * a.xy_fs + (int64_t)y * a.xy_rs + (int64_t)xs * 4;
+    if (a.map_vec_ok && whole) {
+        const u32x4 v = *reinterpret_cast<const u32x4*>(xrow);
+        e[0] = v.x, e[1] = v.y, e[2] = v.z, e[3] = v.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < PPL; j++) e[j] = (xs + j < a.dst_w) ? reinterpret_cast<const uint32_t*>(xrow)[j] : 0u;
+    }
+    if constexpr (INTERP == kLinear) {
+        const uint8_t* frow = a.frac + (int64_t)b0 * a.frac_fs + (int64_t)y * a.frac_rs + (int64_t)xs * 2;
+        if (a.map_vec_ok && whole) {
+            const u32x2 v = *reinterpret_cast<const u32x2*>(frow);
+            fr[0] = v.x & 0xffffu, fr[1] = v.x >> 16, fr[2] = v.y & 0xffffu, fr[3] = v.y >> 16;
+        } else {
+#pragma unroll
+            for (int j = 0; j < PPL; j++) fr[j] = (xs + j < a.dst_w) ? (uint32_t)reinterpret_cast<const uint16_t*>(frow)[j] : 0u;
+        }
+    }
+
+    Taps tap[PPL];
+    bool wr[PPL];
+#pragma unroll
+    for (int j = 0; j < PPL; j++) {
+        const int sx = (int)(short)(e[j] & 0xffffu), sy = (int)e[j] >> 16;
+        Taps& t = tap[j];
+        const uint32_t f = INTERP == kLinear ? (fr[j] & 1023u) : 0u;  // (higher bits are ignored)
+        int c0, c1, cy0, cy1;
+        uint32_t in = 0u;
+        if constexpr (kTransparent) {
+            // inliers only (remapBilinear's (unsigned)sx < width - 1); the others' taps are never used
+            wr[j] = xs + j < a.dst_w && (INTERP == kLinear ? ((unsigned)sx < (unsigned)(a.src_w - 1) && (unsigned)sy < (unsigned)(a.src_h - 1))
+                                                            : ((unsigned)sx < (unsigned)a.src_w && (unsigned)sy < (unsigned)a.src_h));
+            c0 = sx, c1 = sx + 1, cy0 = sy, cy1 = sy + 1;
+        } else if constexpr (MODE == 0) {
+            wr[j] = xs + j < a.dst_w;
+            const int w = a.src_w, h = a.src_h;
+            const bool xin0 = (unsigned)sx < (unsigned)w, yin0 = (unsigned)sy < (unsigned)h;
+            const bool xin1 = INTERP == kLinear && (unsigned)(sx + 1) < (unsigned)w, yin1 = INTERP == kLinear && (unsigned)(sy + 1) < (unsigned)h;
+            c0 = min(max(sx, 0), w - 1), c1 = min(max(sx + 1, 0), w - 1), cy0 = min(max(sy, 0), h - 1), cy1 = min(max(sy + 1, 0), h - 1);
+            in = (uint32_t)(xin0 && yin0) | ((uint32_t)(xin1 && yin0) << 1) | ((uint32_t)(xin0 && yin1) << 2) | ((uint32_t)(xin1 && yin1) << 3);
+        } else {
+            wr[j] = xs + j < a.dst_w;
+            c0 = border_index<MODE>(sx, a.src_w, a.per_x, a.off_x, a.mag_x);
+            cy0 = border_index<MODE>(sy, a.src_h, a.per_y, a.off_y, a.mag_y);
+            c1 = INTERP == kLinear ? border_index<MODE>(sx + 1, a.src_w, a.per_x, a.off_x, a.mag_x) : c0;
+            cy1 = INTERP == kLinear ? border_index<MODE>(sy + 1, a.src_h, a.per_y, a.off_y, a.mag_y) : cy0;
+        }
+        t.w = f | (in << 10);
+        const uint32_t o0 = (uint32_t)cy0 * (uint32_t)a.src_rs, o1 = (uint32_t)cy1 * (uint32_t)a.src_rs;
+        const uint32_t x0 = (uint32_t)c0 * (uint32_t)(C * sizeof(T)), x1 = (uint32_t)c1 * (uint32_t)(C * sizeof(T));
+        t.a00 = o0 + x0, t.a01 = o0 + x1, t.a10 = o1 + x0, t.a11 = o1 + x1;
+    }
+
+    // 8-bit 3-channel bilinear: a lane whose (loaded) pixels all have their two columns side by side -- every inlier, every interior pixel --
+    // takes the pair loads; a lane with a pixel at a clamped or remapped edge takes the loads tap by tap
+    bool pair = sizeof(T) == 1 && C == 3 && INTERP == kLinear;
+    if constexpr (sizeof(T) == 1 && C == 3 && INTERP == kLinear) {
+#pragma unroll
+        for (int j = 0; j < PPL; j++) pair = pair && ((kTransparent && !wr[j]) || tap[j].a01 == tap[j].a00 + 3u);
+    }
+
+    const bool vec = a.src_vec_ok;
+#pragma unroll 1
+    for (int f = 0; f < nb; f++) {
+        const uint32_t b = (uint32_t)(b0 + f);
+        const uint8_t* frame = a.src + (int64_t)b * a.src_fs;
+        Pixel<T, C> px[PPL];
+        if constexpr (sizeof(T) == 1 && C == 3 && INTERP == kLinear) {
+            if (pair)
+                frame_pixels<T, C, INTERP, MODE, true>(a, frame, tap, wr, vec, px);
+            else
+                frame_pixels<T, C, INTERP, MODE, false>(a, frame, tap, wr, vec, px);
+        } else {
+            frame_pixels<T, C, INTERP, MODE, false>(a, frame, tap, wr, vec, px);
+        }
+        store_lane_pixels<T, C, kTransparent>(a, b, y, xs, px, wr);
+    }
+}
+
+template <typename T, int INTERP, int MODE>
+void launch_c(const RemapArgs& a, int channels, dim3 grid, hipStream_t stream) {
+    const dim3 block(kWG);
+    switch (channels) {
+        case 1: hipLaunchKernelGGL((remap_kernel<T, 1, INTERP, MODE>), grid, block, 0, stream, a); break;
+        case 2: hipLaunchKernelGGL((remap_kernel<T, 2, INTERP, MODE>), grid, block, 0, stream, a); break;
+        case 3: hipLaunchKernelGGL((remap_kernel<T, 3, INTERP, MODE>), grid, block, 0, stream, a); break;
+        default: hipLaunchKernelGGL((remap_kernel<T, 4, INTERP, MODE>), grid, block, 0, stream, a); break;
+    }
+}
+
+template <typename T, int INTERP>
+void launch_mode(const RemapArgs& a, int channels, int mode, dim3 grid, hipStream_t stream) {
+    switch (mode) {
+        case 0: launch_c<T, INTERP, 0>(a, channels, grid, stream); break;
+        case kBorderReplicate: launch_c<T, INTERP, kBorderReplicate>(a, channels, grid, stream); break;
+        case kBorderReflect: launch_c<T, INTERP, kBorderReflect>(a, channels, grid, stream); break;
+        case kBorderWrap: launch_c<T, INTERP, kBorderWrap>(a, channels, grid, stream); break;
+        case kBorderReflect101: launch_c<T, INTERP, kBorderReflect101>(a, channels, grid, stream); break;
+        default: launch_c<T, INTERP, kBorderTransparent>(a, channels, grid, stream); break;
+    }
+}
+
+}  // namespace
+
+hipError_t launch_build_map(const MapBuildArgs& a, int interp, bool lens, int64_t items, hipStream_t stream) {
+    (void)hipGetLastError();  // a stale error left by the host framework is not this call's
+    const dim3 grid((unsigned)items), block(kWG);
+    if (interp == kNearest) {
+        if (lens)
+            hipLaunchKernelGGL((build_map_kernel<kNearest, true>), grid, block, 0, stream, a);
+        else
+            hipLaunchKernelGGL((build_map_kernel<kNearest, false>), grid, block, 0, stream, a);
+    } else {
+        if (lens)
+            hipLaunchKernelGGL((build_map_kernel<kLinear, true>), grid, block, 0, stream, a);
+        else
+            hipLaunchKernelGGL((build_map_kernel<kLinear, false>), grid, block, 0, stream, a);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_remap(const RemapArgs& a, int dtype, int channels, int interp, int mode, int64_t items, hipStream_t stream) {
+    (void)hipGetLastError();  // a stale error left by the host framework is not this call's
+    const dim3 grid((unsigned)items);
+    if (dtype == 0)
+        (interp == kNearest ? launch_mode<uint8_t, kNearest> : launch_mode<uint8_t, kLinear>)(a, channels, mode, grid, stream);
+    else
+        (interp == kNearest ? launch_mode<float, kNearest> : launch_mode<float, kLinear>)(a, channels, mode, grid, stream);
+    return hipGetLastError();
+}
+
+}  // namespace bevwarp

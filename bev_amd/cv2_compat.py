@@ -14,6 +14,8 @@ and leave /root/reference/vis_homo.py:89-91, bev/homo.py:36 and bev/tool/compo.p
 
     cv2.resize(img, (w, h)[, dst, fx, fy, interpolation])                        vis_homo.py:90 (uint8, INTER_LINEAR only)
     cv2.cvtColor(nv12, COLOR_YUV2BGR_NV12 | COLOR_YUV2RGB_NV12)                  the conversion behind video.read(), vis_homo.py:86
+    cv2.remap(img, map1, map2, interpolation[, dst, borderMode, borderValue])    the per-frame half of a fixed camera's loop (vis_homo.py:85-91
+    cv2.convertMaps(map1, map2[, dstmap1type, nninterpolation])                  with Calib.dist_coeff, bev/calib.py:25): maps once, remap per frame
 
 `cv2.resize` here is OpenCV's own bilinear algorithm (sampling at (d + 0.5) * scale - 0.5, 11-bit coefficients, replicated edge, the
 2 x 2 box-mean rule) as its own device kernel -- round 3 had none, because a resize routed through the WARP kernel (1/32-px
@@ -51,6 +53,7 @@ BORDER_TRANSPARENT = 5
 COLOR_YUV2RGB_NV12 = 90
 COLOR_YUV2BGR_NV12 = 91
 DECOMP_LU = 0
+CV_16SC2, CV_16UC1, CV_32FC1, CV_32FC2 = 11, 2, 5, 13
 RANSAC, LMEDS, RHO = 8, 4, 16
 
 
@@ -67,6 +70,27 @@ def resize(src, dsize, dst=None, fx=0, fy=0, interpolation=INTER_LINEAR):
     """uint8 images of 1-4 channels, INTER_LINEAR (cv2.resize's default; the reference passes none).  Bit-exact with
     oracle/resize_oracle.c (classic OpenCV 3.x-4.x bilinear path, restated from memory: parity unpinned)."""
     return _resize.cv2_resize(src, dsize, dst=dst, fx=fx, fy=fy, interpolation=interpolation)
+
+
+def remap(src, map1, map2, interpolation, dst=None, borderMode=BORDER_CONSTANT, borderValue=0):
+    """uint8 / float32 images of 1-4 channels through coordinate maps; INTER_NEAREST or INTER_LINEAR; all six border modes (with
+    BORDER_TRANSPARENT a given `dst` is the canvas).  Maps: the fixed-point pair -- map1 (H, W, 2) int16, map2 (H, W) uint16 (None for
+    INTER_NEAREST), what convertMaps returns -- is taken as it is; float32 maps ((H, W, 2), or an (H, W) pair) go through convertMaps
+    first, so a float32 call samples at 1/32 px exactly as cv2's own fixed-point path does.  numpy in and out; the pixels come from
+    bevwarp_remap (include/bevwarp.h), whose taps and blends are bevwarp_warp_border's.  Restated from memory of imgwarp.cpp: parity with
+    an installed cv2 is unpinned.  A camera loop keeps the map on the device: bev_amd.warp.build_warp_map + remap."""
+    return _warp.remap_numpy(src, map1, map2, interpolation, dst=dst, borderMode=borderMode, borderValue=borderValue)
+
+
+def convertMaps(map1, map2, dstmap1type=None, nninterpolation=False):
+    """float32 coordinate maps -> (map1 (H, W, 2) int16, map2 (H, W) uint16): map1 (H, W, 2) with map2 None, or the (H, W) x and y maps.
+    On the host, in numpy.  Per coordinate: times 32 in float32, round half to even, clamp to int32, then sx = sat16(X >> 5) and
+    fx = X & 31, map2 = (fy << 5) | fx; nninterpolation rounds the coordinate itself and returns an all-zero map2.  dstmap1type: None or
+    CV_16SC2 (the only target).  Restated from memory of imgwarp.cpp: parity with an installed cv2 is unpinned, like the rest of the warp."""
+    if dstmap1type not in (None, CV_16SC2):
+        raise NotImplementedError("convertMaps: only dstmap1type=CV_16SC2 (the fixed-point pair) is implemented")
+    xy, frac = _warp.convert_maps(map1, map2, nearest=bool(nninterpolation))
+    return xy, (np.zeros(xy.shape[:2], dtype=np.uint16) if frac is None else frac)
 
 
 def cvtColor(src, code):

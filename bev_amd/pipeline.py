@@ -59,7 +59,7 @@ _H2D, _D2H = 1, 2  # hipMemcpyHostToDevice / hipMemcpyDeviceToHost
 
 class FramePipeline:
     def __init__(self, src_hw, channels, M, dsize, flags=_warp.INTER_LINEAR, depth=3, dtype=torch.uint8, planar=False, scale=1.0 / 255.0, bias=0.0,
-                 download=True, device="cuda", zero_copy_out=True, plane_dtype=torch.float32, src_format="bgr", dst_format="bgr"):
+                 download=True, device="cuda", zero_copy_out=True, plane_dtype=torch.float32, src_format="bgr", dst_format="bgr", warp_map=None):
         """src_hw (H, W) of the decoded frames; M the forward homography (as for warpPerspective); dsize (u_size, v_size).
         download=False leaves the BEV frames on the device (results are device tensors valid until `depth` further frames
         have been submitted).  zero_copy_out (with download): the kernel stores the BEV frame straight into the pinned host
@@ -74,7 +74,22 @@ class FramePipeline:
         dst_format  "bgr" (default): the interleaved BEV frame (or planes, with planar).  "nv12": the device and pinned output slots are
         (dh * 3 / 2, dw) uint8 -- the BEV frame's Y plane, then dh / 2 rows of (U, V) pairs, BT.601 limited range -- from either source
         format, with download on or off and with zero_copy_out; channels must be 3, dtype uint8, dsize even, flags INTER_NEAREST or
-        INTER_LINEAR, and planar output is not available (ValueError).  The input frames are taken as B, G, R."""
+        INTER_LINEAR, and planar output is not available (ValueError).  The input frames are taken as B, G, R.
+        warp_map    a bev_amd.warp.WarpMap of one frame (build_warp_map: a fixed camera's coordinates, lens included, computed once) on
+        `device`: every slot's prepared launch is then bevwarp_remap through it (BORDER_CONSTANT, border 0), `M` may be None and `flags`
+        is not looked at (the map carries its interpolation).  Interleaved frames in and out only: with planar, src_format="nv12" or
+        dst_format="nv12" it raises ValueError.  None (default): every path above, unchanged."""
+        if warp_map is not None:
+            if not isinstance(warp_map, _warp.WarpMap) or warp_map.n != 1:
+                raise ValueError("warp_map must be a bev_amd.warp.WarpMap of one frame, got %s" % (
+                    "%d frames" % warp_map.n if isinstance(warp_map, _warp.WarpMap) else type(warp_map).__name__,))
+            if planar or src_format != "bgr" or dst_format != "bgr":
+                raise ValueError("warp_map takes interleaved frames in and out only: planar, src_format=\"nv12\" and dst_format=\"nv12\" are not available with it")
+            if warp_map.dsize != (int(dsize[0]), int(dsize[1])):
+                raise ValueError("warp_map was built for dsize %s, the pipeline's is %s" % (warp_map.dsize, (int(dsize[0]), int(dsize[1]))))
+            if warp_map.device.type != torch.device(device).type:
+                raise ValueError("warp_map is on %s, the pipeline runs on %s" % (warp_map.device, device))
+        self.warp_map = warp_map
         if src_format not in ("bgr", "nv12"):
             raise ValueError("unsupported src_format %r (\"bgr\", \"nv12\")" % (src_format,))
         self.nv12 = src_format == "nv12"
@@ -118,7 +133,7 @@ class FramePipeline:
         self.d_in = [torch.empty(in_shape, dtype=dtype, device=self.device) for _ in range(depth)]
         self.d_out = [torch.empty(out_shape, dtype=out_dtype, device=self.device) for _ in range(depth)]
         self.h_out = [torch.empty(out_shape, dtype=out_dtype, pin_memory=True) for _ in range(depth)] if download else None
-        self.minv = _warp.device_inverse(M, self.device, inverse_given=bool(int(flags) & _warp.WARP_INVERSE_MAP))
+        self.minv = None if warp_map is not None else _warp.device_inverse(M, self.device, inverse_given=bool(int(flags) & _warp.WARP_INVERSE_MAP))
         self._streams = [torch.cuda.Stream(self.device) for _ in range(3)]  # (kept alive: their raw handles are used below)
         self.s_up, self.s_run, self.s_down = (ctypes.c_void_p(st.cuda_stream) for st in self._streams)
         hip = _hip_rt()
@@ -142,7 +157,12 @@ class FramePipeline:
         self._launch = []
         for slot in range(depth):
             s, d = self.d_in[slot], (self.h_out[slot] if self.zero_copy_out else self.d_out[slot])  # (pinned host memory is device-addressable)
-            if self.nv12_out:  # (one buffer per side: the (U, V) rows follow the Y rows)
+            if warp_map is not None:
+                args = (s.data_ptr(), d.data_ptr(), 1, self.H, self.W, self.dh, self.dw, self.C, s.numel() * esz, s.stride(0) * esz, d.numel() * esz,
+                        d.stride(0) * esz) + warp_map._planes()[:2] + (1,) + warp_map._planes()[2:] + (_warp._DTYPES[s.dtype], warp_map.interp,
+                                                                                                     _warp.BORDER_CONSTANT, None, self.s_run)
+                self._launch.append((lib.bevwarp_remap, args))
+            elif self.nv12_out:  # (one buffer per side: the (U, V) rows follow the Y rows)
                 dst = (d.data_ptr(), d.data_ptr() + self.dh * self.dw)
                 tail = (self.minv.data_ptr(), 1, interp)
                 if self.nv12:
@@ -206,7 +226,9 @@ class FramePipeline:
     def _launch_py(self, slot, stream):
         """The same launch through bev_amd.warp (argument validation; used once per slot at construction)."""
         with torch.cuda.stream(stream):
-            if self.nv12_out and self.nv12:
+            if self.warp_map is not None:
+                _warp.remap(self.d_in[slot], self.warp_map, out=self.d_out[slot])
+            elif self.nv12_out and self.nv12:
                 y, uv = _warp.split_nv12(self.d_in[slot])
                 _warp.warp_nv12_to_nv12(y, uv, None, (self.dw, self.dh), flags=self.flags, out=self.d_out[slot], M_inv_device=self.minv)
             elif self.nv12_out:

@@ -458,6 +458,200 @@ def warp_perspective_lens(src, M, dsize, K, dist_coeff, flags=INTER_LINEAR, bord
     return _like_src(d4, src.dim(), out)
 
 
+class WarpMap:
+    """The coordinates of one warp, kept: OpenCV's fixed-point map pair (include/bevwarp.h, "THE MAP FORMAT") for `n` cameras or frames.
+
+    xy       (n, dh, dw, 2) torch.int16: (sx, sy) per destination pixel (CV_16SC2).
+    frac     (n, dh, dw) torch.int16 holding (fy << 5) | fx (CV_16UC1; the values are below 1024), or None for INTER_NEAREST.
+    interp   INTER_NEAREST or INTER_LINEAR: the interpolation the map was built for (sx differs by it).
+    dsize    (width, height).
+    The planes may be views (padded rows, an offset base): their strides are passed through.  build_warp_map makes one on the device;
+    a hand-made pair (cv2.convertMaps's output, say) is wrapped by calling the class."""
+
+    def __init__(self, xy, frac, interp, dsize):
+        interp = int(interp)
+        if interp not in (INTER_NEAREST, INTER_LINEAR):
+            raise ValueError("a WarpMap is built for INTER_NEAREST or INTER_LINEAR, got %r" % (interp,))
+        dw, dh = int(dsize[0]), int(dsize[1])
+        if not isinstance(xy, torch.Tensor) or xy.dtype != torch.int16 or xy.dim() != 4 or tuple(xy.shape[1:]) != (dh, dw, 2) or xy.shape[0] < 1:
+            raise ValueError("xy must be an int16 tensor (n, %d, %d, 2), got %s %s" % (dh, dw, getattr(xy, "dtype", type(xy)), tuple(getattr(xy, "shape", ()))))
+        if xy.stride(3) != 1 or xy.stride(2) != 2:
+            raise ValueError("the (sx, sy) pairs of xy and the pairs of a row must be contiguous")
+        if interp == INTER_LINEAR or frac is not None:
+            if not isinstance(frac, torch.Tensor) or frac.dtype != torch.int16 or tuple(frac.shape) != (xy.shape[0], dh, dw) or frac.device != xy.device:
+                raise ValueError("frac must be an int16 tensor %s on %s%s" % ((xy.shape[0], dh, dw), xy.device, "" if frac is not None else " (INTER_LINEAR needs one)"))
+            if frac.stride(2) != 1:
+                raise ValueError("the rows of frac must be contiguous")
+        self.xy, self.frac, self.interp, self.dsize = xy, frac, interp, (dw, dh)
+
+    @property
+    def n(self):
+        return int(self.xy.shape[0])
+
+    @property
+    def device(self):
+        return self.xy.device
+
+    def _planes(self):
+        """(xy address, frac address or None, the four strides in bytes) as the ABI takes them."""
+        f = self.frac if self.interp == INTER_LINEAR else None
+        return (self.xy.data_ptr(), None if f is None else f.data_ptr(), self.xy.stride(0) * 2, self.xy.stride(1) * 2,
+                0 if f is None else f.stride(0) * 2, 0 if f is None else f.stride(1) * 2)
+
+
+def build_warp_map(M, dsize, flags=INTER_LINEAR, K=None, dist_coeff=None, r2_max=None, device="cuda", out=None):
+    """The coordinate chain of warp_perspective / warp_perspective_lens run ONCE, on the device, and kept as a WarpMap for remap():
+    what cv2.initUndistortRectifyMap + cv2.convertMaps are for in a fixed camera's loop (include/bevwarp.h, bevwarp_build_map).
+
+    M        (3, 3) or (n, 3, 3) forward map(s) (host), as warp_perspective / warp_perspective_lens take them; flags | WARP_INVERSE_MAP:
+             the dst -> src map(s).  n matrices give a map of n frames.
+    dsize    (width, height).  flags: INTER_LINEAR (default) or INTER_NEAREST, optionally | WARP_INVERSE_MAP.
+    K, dist_coeff   the lens, as warp_perspective_lens takes it.  dist_coeff None or all zero: the pinhole chain (K is not looked at) --
+             the rule by which warp_perspective_lens hands a lens without distortion to warp_perspective.
+    r2_max   None: lens_valid_r2(dist_coeff); a pixel beyond it is stored as the entry whose taps are all outside.
+    out      a WarpMap of this n, dsize and interpolation on `device` to write into (its planes may be views).
+    remap(src, build_warp_map(...)) equals warp_perspective(src, ..., border_mode=m) for every border mode, and warp_perspective_lens
+    for BORDER_CONSTANT and BORDER_TRANSPARENT, by bits.  Asynchronous on the current stream."""
+    interp = _interp("build_warp_map", flags)
+    dw, dh = int(dsize[0]), int(dsize[1])
+    if dw <= 0 or dh <= 0:
+        raise ValueError("build_warp_map: dsize must be positive, got %s" % ((dw, dh),))
+    dist = _dist8(dist_coeff)
+    inverse = bool(int(flags) & WARP_INVERSE_MAP)
+    Mh = np.asarray(M.detach().cpu().numpy() if isinstance(M, torch.Tensor) else M, dtype=np.float64)
+    if Mh.shape[-2:] != (3, 3) or Mh.ndim not in (2, 3):
+        raise ValueError("M must be (3, 3) or (n, 3, 3), got %s" % (Mh.shape,))
+    lens = None
+    if dist.any():
+        if K is None:
+            raise ValueError("build_warp_map: a lens (dist_coeff) needs the camera matrix K")
+        lens = np.ascontiguousarray(np.concatenate([_intrinsics(K), dist]), dtype=np.float64)
+        r2 = lens_valid_r2(dist) if r2_max is None else float(r2_max)
+        Mh, inverse = ray_matrix(Mh, K, inverse_given=inverse), True
+    n = int(Mh.size // 9)
+    device = torch.device(device)
+    if out is not None:
+        if not isinstance(out, WarpMap) or out.n != n or out.dsize != (dw, dh) or out.interp != interp or out.device.type != device.type:
+            raise ValueError("out must be a WarpMap of %d frame(s), dsize %s and interpolation %d on %s" % (n, (dw, dh), interp, device))
+    if device.type != "cuda":
+        raise ValueError("build_warp_map needs a CUDA (HIP) device, got %s" % (device,))
+    minv = device_inverse(Mh, device, inverse_given=inverse)
+    if out is None:
+        xy = torch.empty((n, dh, dw, 2), dtype=torch.int16, device=minv.device)
+        out = WarpMap(xy, torch.empty((n, dh, dw), dtype=torch.int16, device=minv.device) if interp == INTER_LINEAR else None, interp, (dw, dh))
+    xy_p, fr_p, xy_fs, xy_rs, fr_fs, fr_rs = out._planes()
+    _lib.launch("bevwarp_build_map", out.device, minv.data_ptr(), n, _ptr(lens), 0.0 if lens is None else r2, interp, xy_p, fr_p, dh, dw, xy_fs, xy_rs, fr_fs, fr_rs)
+    return out
+
+
+def remap(src, warp_map, border_mode=BORDER_CONSTANT, border_value=None, out=None):
+    """cv2.remap on the GPU, batched: frames sampled through a WarpMap (include/bevwarp.h, bevwarp_remap) -- no coordinate is computed,
+    no float64 is touched.  The per-frame half of a fixed camera's loop; build_warp_map is the other.
+
+    src      (B, H, W, C), (H, W, C) or (H, W) uint8 / float32 CUDA tensor, as warp_perspective.
+    warp_map a WarpMap on src's device with n == 1 (shared by all frames) or n == B; its interpolation is the call's.
+    border_mode   any of the six BORDER_* modes; border_value (BORDER_CONSTANT only) a scalar or C values, None = 0.
+    out      as warp_perspective; BORDER_TRANSPARENT without `out` starts from zeros.
+    Returns a tensor shaped like src with (height, width) replaced by the map's, or `out`.  Asynchronous on the current stream."""
+    if not isinstance(warp_map, WarpMap):
+        raise ValueError("remap needs a WarpMap (build_warp_map, or WarpMap(xy, frac, interp, dsize)), got %s" % (type(warp_map).__name__,))
+    if border_mode not in _BORDER_MODES:
+        raise ValueError("unsupported border mode %r (BORDER_CONSTANT, _REPLICATE, _REFLECT, _WRAP, _REFLECT_101, _TRANSPARENT)" % (border_mode,))
+    border_mode = int(border_mode)
+    if not isinstance(src, torch.Tensor) or src.dtype not in _DTYPES or src.dim() not in (2, 3, 4):
+        raise ValueError("remap needs a uint8 or float32 tensor (B, H, W, C), (H, W, C) or (H, W)")
+    B = src.shape[0] if src.dim() == 4 else 1
+    C = 1 if src.dim() == 2 else src.shape[-1]
+    dw, dh = warp_map.dsize
+    if warp_map.n not in (1, B):
+        raise ValueError("the map holds %d frames for a batch of %d (1 or the batch)" % (warp_map.n, B))
+    if warp_map.device != src.device:
+        raise ValueError("the map is on %s, the frames are on %s" % (warp_map.device, src.device))
+    if isinstance(out, torch.Tensor) and out.dim() == src.dim():  # (an `out` of src's rank names a size: the map's, or the call is refused)
+        hw = tuple(out.shape[-2:]) if src.dim() == 2 else tuple(out.shape[-3:-1])
+        if hw != (dh, dw):
+            raise ValueError("the map's dsize is %s, out is %s" % ((dw, dh), tuple(out.shape)))
+    if isinstance(out, torch.Tensor) and out.numel() != B * dh * dw * C:
+        raise ValueError("the map's dsize is %s (%d frames of %d channels): out has %d elements" % ((dw, dh), B, C, out.numel()))
+    s4, _ = _frames("remap", src, _DTYPES)
+    B, H, W, C = s4.shape
+    esz = s4.element_size()
+    d4 = _pixel_dst(out, s4.dtype, s4.device, B, dh, dw, C, zeroed=border_mode == BORDER_TRANSPARENT)
+    bv = _border(border_value, C) if border_mode == BORDER_CONSTANT else None
+    xy_p, fr_p, xy_fs, xy_rs, fr_fs, fr_rs = warp_map._planes()
+    _lib.launch("bevwarp_remap", s4.device, s4.data_ptr(), d4.data_ptr(), B, H, W, dh, dw, C, s4.stride(0) * esz, s4.stride(1) * esz, d4.stride(0) * esz,
+                d4.stride(1) * esz, xy_p, fr_p, warp_map.n, xy_fs, xy_rs, fr_fs, fr_rs, _DTYPES[s4.dtype], warp_map.interp, border_mode, _ptr(bv))
+    return _like_src(d4, src.dim(), out)
+
+
+def convert_maps(map1, map2=None, nearest=False):
+    """cv2.convertMaps(map1, map2, CV_16SC2, nninterpolation=nearest) on the host, in numpy: float32 coordinate maps -> the fixed-point
+    pair (xy (H, W, 2) int16, frac (H, W) uint16; frac is None for nearest).  map1 is (H, W, 2) holding (x, y), or map1 / map2 are the
+    (H, W) x and y maps.  Per coordinate: multiplied by 32 IN FLOAT32, rounded half to even, clamped to int32 (NaN: INT_MAX, as the
+    warp's chain has it), then sx = sat16(X >> 5), fx = X & 31; nearest rounds the coordinate itself and sx = sat16(X).  Restated from
+    memory of imgwarp.cpp: parity with an installed cv2 is unpinned, like the rest of the warp."""
+    m1 = np.asarray(map1)
+    if map2 is None:
+        if m1.ndim != 3 or m1.shape[2] != 2:
+            raise ValueError("convertMaps: map1 must be (H, W, 2) when map2 is absent, got %s" % (m1.shape,))
+        x, y = m1[..., 0], m1[..., 1]
+    else:
+        x, y = m1, np.asarray(map2)
+        if x.ndim != 2 or x.shape != y.shape:
+            raise ValueError("convertMaps: map1 and map2 must be (H, W) maps of one shape, got %s and %s" % (x.shape, y.shape))
+    if x.dtype != np.float32 or y.dtype != np.float32:
+        raise ValueError("convertMaps: float32 maps are needed, got %s and %s" % (x.dtype, y.dtype))
+
+    def fixed(c):
+        with np.errstate(all="ignore"):
+            v = (c if nearest else c * np.float32(32.0)).astype(np.float64)
+            v = np.where(np.isnan(v), 2147483647.0, np.clip(np.rint(v), -2147483648.0, 2147483647.0))
+        return v.astype(np.int64)
+
+    X, Y = fixed(x), fixed(y)
+    if nearest:
+        return np.stack([np.clip(X, -32768, 32767), np.clip(Y, -32768, 32767)], axis=-1).astype(np.int16), None
+    xy = np.stack([np.clip(X >> 5, -32768, 32767), np.clip(Y >> 5, -32768, 32767)], axis=-1).astype(np.int16)
+    return xy, (((Y & 31) << 5) | (X & 31)).astype(np.uint16)
+
+
+def remap_numpy(src, map1, map2, interpolation, dst=None, borderMode=BORDER_CONSTANT, borderValue=0, device="cuda"):
+    """cv2.remap call shape for numpy images and maps: uploads, samples on the GPU, downloads (cv2_compat.remap).  Maps: (H, W, 2) int16
+    + (H, W) uint16 (None for INTER_NEAREST) are taken as they are; float32 maps -- (H, W, 2), or an (H, W) pair -- go through
+    convert_maps first.  With BORDER_TRANSPARENT a given `dst` is the canvas."""
+    interp = _interp("remap", interpolation)
+    if borderMode not in _BORDER_MODES:
+        raise ValueError("unsupported borderMode %r (BORDER_CONSTANT, _REPLICATE, _REFLECT, _WRAP, _REFLECT_101, _TRANSPARENT)" % (borderMode,))
+    img = np.asarray(src)
+    if img.dtype not in (np.uint8, np.float32) or img.ndim not in (2, 3):
+        raise ValueError("remap: a uint8 / float32 image (H, W) or (H, W, C) is needed, got %s %s" % (img.dtype, img.shape))
+    m1 = np.asarray(map1)
+    if m1.dtype == np.float32:
+        xy, frac = convert_maps(m1, map2, nearest=interp == INTER_NEAREST)
+    elif m1.dtype == np.int16 and m1.ndim == 3 and m1.shape[2] == 2:
+        xy, frac = m1, None if map2 is None else np.asarray(map2)
+        if interp == INTER_LINEAR and (frac is None or frac.dtype != np.uint16 or frac.shape != m1.shape[:2]):
+            raise ValueError("remap: INTER_LINEAR with fixed-point maps needs map2 as uint16 %s" % (m1.shape[:2],))
+    else:
+        raise ValueError("remap: map1 must be float32 or (H, W, 2) int16, got %s %s" % (m1.dtype, m1.shape))
+    dh, dw = xy.shape[:2]
+    shape = (dh, dw) + tuple(img.shape[2:])
+    canvas = None
+    if borderMode == BORDER_TRANSPARENT and dst is not None:
+        if not isinstance(dst, np.ndarray) or dst.shape != shape or dst.dtype != img.dtype:
+            raise ValueError("dst must be a %s array of shape %s (the canvas BORDER_TRANSPARENT writes into)" % (img.dtype, shape))
+        canvas = torch.from_numpy(np.ascontiguousarray(dst)).to(device)
+    txy = torch.from_numpy(np.ascontiguousarray(xy)).to(device)[None]
+    tfr = None if interp == INTER_NEAREST else torch.from_numpy(np.ascontiguousarray(frac).view(np.int16)).to(device)[None]
+    t = torch.from_numpy(np.ascontiguousarray(img)).to(device)
+    bv = scalar_border(borderValue, 1 if img.ndim == 2 else img.shape[2])
+    res = remap(t, WarpMap(txy, tfr, interp, (dw, dh)), border_mode=borderMode, border_value=bv, out=canvas).cpu().numpy()
+    if dst is not None:
+        dst[...] = res
+        return dst
+    return res
+
+
 _BLENDS = {"over": _lib.STITCH_OVER, "feather": _lib.STITCH_FEATHER}
 
 

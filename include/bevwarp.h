@@ -13,6 +13,12 @@
  *                             camera delivers, in one resampling: Calib carries `dist_coeff` (bev/calib.py:25), Rt_from_pts_K_dist
  *                             takes `dist_coeffs` (bev/homo.py:130-135), and the material the reference was developed on went through
  *                             a separate undistortion pass first (KAB_SK_1_undist/..., vis_homo.py:30-31)
+ *   bevwarp_build_map, bevwarp_remap
+ *                           cv2.initUndistortRectifyMap / cv2.convertMaps once and cv2.remap per frame, for the camera loop of a FIXED
+ *                             camera: one H_bev_img, one K, one Calib.dist_coeff (bev/calib.py:25) and then the same warp for every frame
+ *                             of a video (vis_homo.py:85-91).  The coordinate chain of bevwarp_warp_border / bevwarp_warp_lens runs once
+ *                             per camera and BEV geometry and is kept as OpenCV's fixed-point maps; every batch is then sampled through
+ *                             them with no float64 at all.  bevwarp_remap is also the generic cv2.remap(src, map1, map2, ...)
  *   bevwarp_warp_stitch     one cv2.warpPerspective(img_k, H_bev_img_k, (u_size, v_size)) per camera of a site into ONE BEV image:
  *                             preset_calib("KoPER", 1 | 4) describes two cameras of one intersection in one world frame
  *                             (bev/constructor/homo_constr.py:19-25), BrnoCompSpeed sessions have a left, a centre and a right camera
@@ -225,6 +231,66 @@ int bevwarp_warp_lens(const void *src, void *dst, int batch, int src_h, int src_
                       int64_t src_frame_stride, int64_t src_row_stride, int64_t dst_frame_stride, int64_t dst_row_stride,
                       const double *M_ray, int m_count, const double *lens /*HOST, 12*/, double r2_max, int dtype, int interp,
                       int border_mode, const double *border_value /*HOST*/, void *stream);
+
+/*
+ * Fixed-camera warp maps: the coordinates once (bevwarp_build_map), the pixels per batch (bevwarp_remap).
+ *
+ * THE MAP FORMAT is OpenCV's fixed-point pair, 6 bytes per destination pixel.  For a destination of dst_h x dst_w pixels:
+ *   map_xy     int16 pairs (sx, sy) per pixel, sx first: 4 bytes per pixel, rows xy_row_stride BYTES apart, base and strides multiples
+ *              of 4 (CV_16SC2).
+ *   map_frac   uint16 per pixel, (fy << 5) | fx with fx, fy in 0..31: rows frac_row_stride BYTES apart, base and strides multiples of 2
+ *              (CV_16UC1).  A reader uses fx = v & 31, fy = (v >> 5) & 31 and ignores the higher bits, as OpenCV masks them.  Unused for
+ *              BEVWARP_NEAREST, where it may be NULL.
+ * A map is built for ONE interpolation, and sx differs by it: with (X, Y) the integer coordinates of the chain (bevwarp_warp_border,
+ * bevwarp_warp_lens: pixels for nearest, 1/32 px for bilinear),
+ *   BEVWARP_NEAREST   sx = sat16(X), sy = sat16(Y)
+ *   BEVWARP_LINEAR    sx = sat16(X >> 5), sy = sat16(Y >> 5); fx = X & 31, fy = Y & 31 of the UNSATURATED X, Y
+ * which is exactly what the warp kernels derive from (X, Y).  Several maps (frames of a map) lie *_frame_stride bytes apart.
+ * A base and strides that are all multiples of 16 (map_xy) and of 8 (map_frac) enable a lane's wide accesses; nothing else depends on it.
+ *
+ * INVALID PIXELS.  A pixel the lens chain declares invalid (r2 > r2_max, or r2 NaN) is stored as (sx, sy) = (-32768, -32768), frac 0.
+ * Its taps are at columns -32768 and -32767 and rows -32768 and -32767: all negative, so every tap is outside every admissible source
+ * (sides 1..32767).  Therefore BEVWARP_BORDER_CONSTANT yields the border value itself -- nearest: the one tap is outside; bilinear: all four
+ * taps are outside, which is the border value itself for 8-bit and float32 pixels alike -- and BEVWARP_BORDER_TRANSPARENT does not write the
+ * pixel (sx is no inlier).  Both are what bevwarp_warp_lens does with an invalid pixel.  (A VALID pixel whose coordinates saturate to the same
+ * entry has the same four taps outside: the two cannot be told apart, and need not be.)  Under the four index-remapping borders such an
+ * entry is whatever source pixel borderInterpolate maps index -32768 / -32767 to: lens maps are meant for CONSTANT and TRANSPARENT.
+ *
+ * bevwarp_build_map writes m_count maps.
+ *   M             device float64, m_count row-major 3 x 3 matrices.  lens == NULL: M is M_inv (destination px -> source px) and the
+ *                 coordinates are bevwarp_warp_border's chain -- evaluation blocks, Xn (32 / W), round half to even, NaN -> INT_MAX.
+ *                 lens != NULL: M is M_ray and the coordinates are bevwarp_warp_lens's chain, operation for operation.
+ *   lens, r2_max  HOST, exactly bevwarp_warp_lens's; lens NULL: the pinhole chain (r2_max is not looked at).
+ *   interp        BEVWARP_NEAREST | BEVWARP_LINEAR (anything else: BEVWARP_ERR_UNSUPPORTED).
+ *   map_xy, map_frac   device, WRITTEN; map_frac may be NULL for BEVWARP_NEAREST (it is not written then).
+ * Status, in this order: BEVWARP_ERR_BAD_ARG (M or map_xy NULL, m_count < 1, a non-positive side); BEVWARP_ERR_UNSUPPORTED (interp);
+ * BEVWARP_ERR_BAD_ARG (map_frac NULL under BEVWARP_LINEAR; a plane whose base or stride is misaligned, whose row stride is below a row,
+ * or whose maps overlap their successors); BEVWARP_ERR_TOO_LARGE (a side > 2^20, or more than 2^31 - 1 tiles); BEVWARP_ERR_OVERLAP (the
+ * two planes share bytes); the lens as in bevwarp_warp_lens.  With m_count == 1 the frame strides are not looked at.
+ *
+ * bevwarp_remap samples `batch` frames through map_count maps: dst[b] = remap(src[b], map[map_count == 1 ? 0 : b]).
+ *   src, dst, batch, sizes, channels, the four strides, dtype, border_value   as bevwarp_warp_border, with the same checks.
+ *   map_xy, map_frac   device, READ; map_count == 1 (shared by all frames; frame strides not looked at) or == batch.  dst must not overlap
+ *                 either plane (bounding byte ranges).  map_frac NULL under BEVWARP_LINEAR is BEVWARP_ERR_BAD_ARG.
+ *   interp        BEVWARP_NEAREST | BEVWARP_LINEAR: the interpolation the map was built for.
+ *   border_mode   all six.  From (sx, sy, fx, fy) on the pixel is defined to the bit by the existing entries: BEVWARP_BORDER_CONSTANT is
+ *                 bevwarp_warp_lens's sampler -- each tap outside the source is replaced by the border pixel, all four taps outside -> the
+ *                 border value itself --, the other five modes are bevwarp_warp_border's.  With a map from bevwarp_build_map the result
+ *                 equals bevwarp_warp / bevwarp_warp_border (pinhole map) and bevwarp_warp_lens (lens map; CONSTANT, TRANSPARENT) by bits.
+ * Status: bevwarp_warp's checks in bevwarp_warp's order, the map count standing for the matrix count, the two planes being read images
+ * (NULL, alignment, strides: BEVWARP_ERR_BAD_ARG) without the source size limits, BEVWARP_CUBIC and the 16-bit types
+ * BEVWARP_ERR_UNSUPPORTED; BEVWARP_ERR_OVERLAP; BEVWARP_ERR_TOO_LARGE for a destination side > 2^20; BEVWARP_ERR_NOT_FINITE for border_value
+ * (BEVWARP_BORDER_CONSTANT only).  batch == 0 is BEVWARP_OK and launches nothing.
+ * Restated from memory of OpenCV's remap / convertMaps (imgwarp.cpp); parity with OpenCV is unpinned, like the rest of the warp.
+ */
+int bevwarp_build_map(const double *M, int m_count, const double *lens /*HOST, 12, or NULL*/, double r2_max, int interp,
+                      void *map_xy, void *map_frac, int dst_h, int dst_w, int64_t xy_frame_stride, int64_t xy_row_stride,
+                      int64_t frac_frame_stride, int64_t frac_row_stride, void *stream);
+int bevwarp_remap(const void *src, void *dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int channels,
+                  int64_t src_frame_stride, int64_t src_row_stride, int64_t dst_frame_stride, int64_t dst_row_stride,
+                  const void *map_xy, const void *map_frac, int map_count, int64_t xy_frame_stride, int64_t xy_row_stride,
+                  int64_t frac_frame_stride, int64_t frac_row_stride, int dtype, int interp, int border_mode,
+                  const double *border_value /*HOST*/, void *stream);
 
 /*
  * Several cameras warped into one canvas in one launch.  It replaces "warping several cameras into one canvas, one call each"
