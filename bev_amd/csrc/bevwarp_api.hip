@@ -15,6 +15,7 @@
 #include "warp_kernels.h"
 #include "warp_lens.h"
 #include "warp_map.h"
+#include "warp_map_nv12.h"
 #include "warp_nv12.h"
 #include "warp_nv12_out.h"
 #include "warp_stitch.h"
@@ -87,6 +88,50 @@ int border_bytes(const double* border_value, uint8_t* bu) {
     return border_values(border_value, 3, bf, bu);
 }
 uint32_t packed3(const uint8_t* b) { return (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16); }
+// The plane kernels of the NV12 sources sample B, G, R: sampled channel k is the destination's channel k (BGR) or 2 - k (RGB), with that
+// channel's plane, scale, bias and border value -- the channel order is nothing but this table (a: the kernel's ch_off, pscale, pbias;
+// bu: the border bytes in the destination's order, bs: in the sampled order)
+template <class Args>
+int sampled_channel_table(Args& a, int rgb_order, int64_t dst_plane_stride, const double* scale, const double* bias, const uint8_t* bu, uint8_t* bs) {
+    for (int k = 0; k < 3; k++) {
+        const int ch = rgb_order ? 2 - k : k;
+        const double sc = scale ? scale[ch] : 1.0, bi = bias ? bias[ch] : 0.0;
+        if (!isfinite(sc) || !isfinite(bi)) return BEVWARP_ERR_NOT_FINITE;
+        a.pscale[k] = (float)sc, a.pbias[k] = (float)bi;
+        a.ch_off[k] = (int64_t)ch * dst_plane_stride;
+        bs[k] = bu[ch];
+    }
+    return BEVWARP_OK;
+}
+// What the map samplers (bevwarp_remap and its NV12 kin) share: the checks, plan_remap's grid of items of frames_per_item frames, and in
+// the zeroed arguments the destination, the grid, the source's sides with the index remap of the border mode, and the map planes --
+// reads[first_map] and, bilinear, reads[first_map + 1].  items = 0: nothing to launch, the status is the call's.
+template <class Args>
+int remap_grid_args(const Call& c, Args& a, int first_map, int interp, int border_mode, int64_t& items) {
+    items = 0;
+    const int st = plan::check_call(c);
+    if (st != BEVWARP_OK || c.batch == 0) return st;
+    const RemapPlan p = plan::plan_remap(c.batch, c.m_count, c.dst_h, c.dst_w, kBorderTileW, kBorderTileH, kRemapMaxFramesPerItem, plan::kRemapFillItems);
+    if (p.status != BEVWARP_OK) return p.status;
+    memset(&a, 0, sizeof(a));
+    const Image& d = c.writes[0].im;
+    a.dst = (uint8_t*)d.base, a.dst_fs = d.fs, a.dst_rs = d.rs, a.dst_h = c.dst_h, a.dst_w = c.dst_w;
+    a.bw0 = p.bw0, a.tiles_x = p.tiles_x, a.tiles_per_frame = p.tiles_per_frame;
+    a.tpf_magic = p.tpf_magic, a.tx_magic = p.tx_magic, a.bw0_magic = p.bw0_magic;
+    a.src_h = c.src_h, a.src_w = c.src_w;
+    if (border_mode != BEVWARP_BORDER_CONSTANT && border_mode != BEVWARP_BORDER_TRANSPARENT) {
+        const plan::BorderPeriod px = plan::border_period(border_mode, c.src_w), py = plan::border_period(border_mode, c.src_h);
+        a.per_x = px.per, a.off_x = px.off, a.mag_x = px.mag;
+        a.per_y = py.per, a.off_y = py.off, a.mag_y = py.mag;
+    }
+    const Image &ixy = c.reads[first_map].im, *ifr = (interp == BEVWARP_LINEAR) ? &c.reads[first_map + 1].im : nullptr;
+    a.xy = (const uint8_t*)ixy.base, a.xy_fs = ixy.fs, a.xy_rs = ixy.rs;
+    if (ifr) a.frac = (const uint8_t*)ifr->base, a.frac_fs = ifr->fs, a.frac_rs = ifr->rs;
+    a.batch = c.batch, a.frames_per_item = p.frames_per_item;
+    a.map_vec_ok = plan::map_vec_ok(ixy, ifr);
+    items = p.total_tiles;
+    return BEVWARP_OK;
+}
 }  // namespace
 
 #ifdef BEVWARP_CLOCK
@@ -274,33 +319,59 @@ int bevwarp_remap(const void* src, void* dst, int batch, int src_h, int src_w, i
     const Call c = plan::remap_call({src, src_frame_stride, src_row_stride}, {dst, dst_frame_stride, dst_row_stride}, {map_xy, xy_frame_stride, xy_row_stride},
                                     {map_frac, frac_frame_stride, frac_row_stride}, {batch, src_h, src_w, dst_h, dst_w, 0, nullptr}, map_count, channels, dtype,
                                     interp, border_mode);
-    const int st = plan::check_call(c);
-    if (st != BEVWARP_OK || batch == 0) return st;
-    const RemapPlan p = plan::plan_remap(batch, map_count, dst_h, dst_w, kBorderTileW, kBorderTileH, kRemapMaxFramesPerItem, plan::kRemapFillItems);
-    if (p.status != BEVWARP_OK) return p.status;
     RemapArgs a;
-    memset(&a, 0, sizeof(a));
-    const bool constant = border_mode == BEVWARP_BORDER_CONSTANT;
+    int64_t items;
+    const int st = remap_grid_args(c, a, 1, interp, border_mode, items);
+    if (!items) return st;
     uint8_t bu[4];  // (border_value is read by the constant border only)
-    if (border_values(constant ? border_value : nullptr, channels, a.bv_f, bu) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
+    if (border_values(border_mode == BEVWARP_BORDER_CONSTANT ? border_value : nullptr, channels, a.bv_f, bu) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
     a.bv_u8 = (uint32_t)bu[0] | ((uint32_t)bu[1] << 8) | ((uint32_t)bu[2] << 16) | ((uint32_t)bu[3] << 24);
-    a.dst = (uint8_t*)dst, a.dst_fs = dst_frame_stride, a.dst_rs = dst_row_stride, a.dst_h = dst_h, a.dst_w = dst_w;
-    a.bw0 = p.bw0, a.tiles_x = p.tiles_x, a.tiles_per_frame = p.tiles_per_frame;
-    a.tpf_magic = p.tpf_magic, a.tx_magic = p.tx_magic, a.bw0_magic = p.bw0_magic;
-    a.src = (const uint8_t*)src, a.src_fs = src_frame_stride, a.src_rs = src_row_stride, a.src_h = src_h, a.src_w = src_w;
-    if (!constant && border_mode != BEVWARP_BORDER_TRANSPARENT) {
-        const plan::BorderPeriod px = plan::border_period(border_mode, src_w), py = plan::border_period(border_mode, src_h);
-        a.per_x = px.per, a.off_x = px.off, a.mag_x = px.mag;
-        a.per_y = py.per, a.off_y = py.off, a.mag_y = py.mag;
-    }
-    const Image &ixy = c.reads[1].im, *ifr = (interp == BEVWARP_LINEAR) ? &c.reads[2].im : nullptr;
-    a.xy = (const uint8_t*)map_xy, a.xy_fs = ixy.fs, a.xy_rs = ixy.rs;
-    if (ifr) a.frac = (const uint8_t*)map_frac, a.frac_fs = ifr->fs, a.frac_rs = ifr->rs;
-    a.batch = batch, a.frames_per_item = p.frames_per_item;
-    a.map_vec_ok = plan::map_vec_ok(ixy, ifr);
+    a.src = (const uint8_t*)src, a.src_fs = src_frame_stride, a.src_rs = src_row_stride;
     a.dst_vec_ok = plan::wide_stores_ok(c.writes[0], plan::store_align(dtype, channels, false));
     a.src_vec_ok = plan::pixel_loads_ok(c.reads[0].im, plan::pixel_load_align(dtype, channels));
-    return launched(launch_remap(a, dtype, channels, interp, border_mode, p.total_tiles, (hipStream_t)stream));
+    return launched(launch_remap(a, dtype, channels, interp, border_mode, items, (hipStream_t)stream));
+}
+
+int bevwarp_remap_nv12(const void* y, const void* uv, void* dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int64_t y_frame_stride,
+                       int64_t y_row_stride, int64_t uv_frame_stride, int64_t uv_row_stride, int64_t dst_frame_stride, int64_t dst_row_stride,
+                       const void* map_xy, const void* map_frac, int map_count, int64_t xy_frame_stride, int64_t xy_row_stride, int64_t frac_frame_stride,
+                       int64_t frac_row_stride, int interp, int border_mode, int rgb_order, const double* border_value, void* stream) {
+    const Call c = plan::remap_nv12_call({y, y_frame_stride, y_row_stride}, {uv, uv_frame_stride, uv_row_stride}, {dst, dst_frame_stride, dst_row_stride},
+                                         {map_xy, xy_frame_stride, xy_row_stride}, {map_frac, frac_frame_stride, frac_row_stride},
+                                         {batch, src_h, src_w, dst_h, dst_w, 0, nullptr}, map_count, interp, rgb_order, border_mode);
+    RemapNv12Args a;
+    int64_t items;
+    const int st = remap_grid_args(c, a, 2, interp, border_mode, items);
+    if (!items) return st;
+    uint8_t bu[4];  // (in the destination's channel order, as given: the border value is not converted; read by the constant border only)
+    if (border_bytes(border_mode == BEVWARP_BORDER_CONSTANT ? border_value : nullptr, bu) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
+    fill_nv12_source(a, c);
+    a.bv_u8 = packed3(bu);
+    a.dst_vec_ok = plan::wide_stores_ok(c.writes[0], plan::store_align(BEVWARP_U8, 3, false));
+    return launched(launch_remap_nv12(a, interp, border_mode, rgb_order, items, (hipStream_t)stream));
+}
+
+int bevwarp_remap_nv12_planes(const void* y, const void* uv, void* dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int64_t y_frame_stride,
+                              int64_t y_row_stride, int64_t uv_frame_stride, int64_t uv_row_stride, int64_t dst_frame_stride, int64_t dst_plane_stride,
+                              int64_t dst_row_stride, const void* map_xy, const void* map_frac, int map_count, int64_t xy_frame_stride, int64_t xy_row_stride,
+                              int64_t frac_frame_stride, int64_t frac_row_stride, int interp, int border_mode, int rgb_order, const double* border_value,
+                              const double* scale, const double* bias, int plane_dtype, void* stream) {
+    const Call c = plan::remap_nv12_planes_call({y, y_frame_stride, y_row_stride}, {uv, uv_frame_stride, uv_row_stride}, {dst, dst_frame_stride, dst_row_stride},
+                                                dst_plane_stride, {map_xy, xy_frame_stride, xy_row_stride}, {map_frac, frac_frame_stride, frac_row_stride},
+                                                {batch, src_h, src_w, dst_h, dst_w, 0, nullptr}, map_count, interp, rgb_order, border_mode, plane_dtype);
+    RemapNv12PlanesArgs a;
+    int64_t items;
+    const int st = remap_grid_args(c, a, 2, interp, border_mode, items);
+    if (!items) return st;
+    uint8_t bu[4];  // (in the destination's channel order, as given; read by the constant border only)
+    if (border_bytes(border_mode == BEVWARP_BORDER_CONSTANT ? border_value : nullptr, bu) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
+    a.dst_vec_ok = plan::wide_stores_ok(c.writes[0], plan::store_align(BEVWARP_U8, 3, true, c.writes[0].elem));
+    a.plane = plane_dtype == BEVWARP_F32 ? kPlaneF32 : (plane_dtype == BEVWARP_F16 ? kPlaneF16 : kPlaneBF16);
+    uint8_t bs[3];
+    if (sampled_channel_table(a, rgb_order, dst_plane_stride, scale, bias, bu, bs) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
+    fill_nv12_source(a, c);
+    a.bv_u8 = packed3(bs);
+    return launched(launch_remap_nv12_planes(a, interp, border_mode, items, (hipStream_t)stream));
 }
 
 int bevwarp_warp_stitch(const bevwarp_camera* cams, int n_cams, void* dst, int batch, int dst_h, int dst_w, int channels, int64_t dst_frame_stride,
@@ -364,17 +435,8 @@ int bevwarp_warp_nv12_planes(const void* y, const void* uv, void* dst, int batch
     if (border_bytes(border_value, bu) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
     a.dst_vec_ok = plan::wide_stores_ok(c.writes[0], plan::store_align(BEVWARP_U8, 3, true, c.writes[0].elem));
     a.plane = plane_dtype == BEVWARP_F32 ? kPlaneF32 : (plane_dtype == BEVWARP_F16 ? kPlaneF16 : kPlaneBF16);
-    // the kernel samples B, G, R: sampled channel k is the destination's channel k (BGR) or 2 - k (RGB), with that channel's plane,
-    // scale, bias and border value -- the channel order is nothing but this table
     uint8_t bs[3];
-    for (int k = 0; k < 3; k++) {
-        const int ch = rgb_order ? 2 - k : k;
-        const double sc = scale ? scale[ch] : 1.0, bi = bias ? bias[ch] : 0.0;
-        if (!isfinite(sc) || !isfinite(bi)) return BEVWARP_ERR_NOT_FINITE;
-        a.pscale[k] = (float)sc, a.pbias[k] = (float)bi;
-        a.ch_off[k] = (int64_t)ch * dst_plane_stride;
-        bs[k] = bu[ch];
-    }
+    if (sampled_channel_table(a, rgb_order, dst_plane_stride, scale, bias, bu, bs) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
     fill_nv12_source(a, c);
     a.border = packed3(bs);
     return launched(launch_warp_nv12_planes(a, interp, items, (hipStream_t)stream));

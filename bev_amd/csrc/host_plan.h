@@ -1,5 +1,5 @@
 // host_plan.h -- what the C ABI decides before a launch, as plain C++17 (no HIP): the argument checks and the launch geometry.
-// bevwarp_api.hip is its only user in the library; tests/host_plan_driver.cpp (and lens_plan_driver.cpp, stitch_plan_driver.cpp, remap_plan_driver.cpp) compile it
+// bevwarp_api.hip is its only user in the library; tests/host_plan_driver.cpp (and lens_plan_driver.cpp, stitch_plan_driver.cpp, remap_plan_driver.cpp, remap_nv12_plan_driver.cpp) compile it
 // with g++ under the address and undefined-behaviour sanitizers, and tests/golden/launch_plans.json pins every field of the plans.  Not installed.
 #pragma once
 #include <math.h>
@@ -92,7 +92,7 @@ struct Frames {  // an image batch as the ABI passes it
 struct ReadImage {
     Image im;
     int cols, elem;  // pixels of a row, for the size limits; bytes of an element: 1, 2 (a (U, V) pair) or 4 (float32)
-    bool map;        // a map plane of bevwarp_remap: as large as the destination (no source limits); its batch is the map count
+    bool map;        // a map plane of bevwarp_remap and its NV12 kin: as large as the destination (no source limits); its batch is the map count
 };
 struct WrittenImage {
     Image im;  // (planar: one plane's rows)
@@ -108,7 +108,7 @@ struct Nv12Images {
 };
 inline Nv12Images nv12_images(Frames y, Frames uv, int h, int w, int batch) { return {y.image(h, (uint64_t)w, batch), uv.image(h / 2, (uint64_t)w, batch)}; }
 
-// What the checks need of one entry point's arguments.  The functions of the last part of this section describe the eleven entry points in
+// What the checks need of one entry point's arguments.  The functions of the last part of this section describe the entry points in
 // these terms; bevwarp_api.hip and the tests' drivers (tests/host_plan_driver.cpp, tests/lens_plan_driver.cpp) build their calls with them.
 struct Sizes {  // (what every entry point passes besides its images and its format)
     int batch, src_h, src_w, dst_h, dst_w, m_count;
@@ -119,7 +119,7 @@ struct Call : Sizes {
     bool format_first;  // ... which is asked before the layouts (bevwarp_warp and its kin) or after the matrix count (the NV12 entry points)
     bool even_src, even_dst;  // NV12 frames have even sides
     int n_reads, n_writes;
-    ReadImage reads[3];
+    ReadImage reads[4];
     WrittenImage writes[2];
 
     void read(const Image& im, int cols, int elem) { reads[n_reads++] = {im, cols, elem, false}; }
@@ -233,17 +233,25 @@ inline Call lens_call(Frames src, Frames dst, const Sizes& z, int channels, int 
     c.format_ok = c.format_ok && (border_mode == BEVWARP_BORDER_CONSTANT || border_mode == BEVWARP_BORDER_TRANSPARENT);
     return c;
 }
-// bevwarp_remap: bevwarp_warp's images and formats without bicubic, with all six borders, and the two map planes as read images --
-// map_count (1 or batch) frames of dst_h rows of dst_w int16 pairs, and (bilinear) of dst_w uint16.  The map count stands where the
-// other entry points have their matrix count; the frac plane is an image under BEVWARP_LINEAR only (NULL there: a NULL image).
-inline Call remap_call(Frames src, Frames dst, Frames xy, Frames frac, Sizes z, int map_count, int channels, int dtype, int interp, int border_mode) {
-    z.m_count = map_count, z.minv = (const double*)xy.base;  // (no matrices: the xy plane stands in the NULL check)
-    Call c = warp_call(src, dst, z, channels, dtype, interp, false);
-    c.format_ok = c.format_ok && border_mode >= BEVWARP_BORDER_CONSTANT && border_mode <= BEVWARP_BORDER_TRANSPARENT;
-    const int n = (map_count == z.batch && z.batch > 0) ? z.batch : 1;
+// What bevwarp_remap and its NV12 kin share: the map count stands where the other entry points have their matrix count, and the xy plane
+// stands in the NULL check (no matrices) ...
+inline Sizes map_sizes(Sizes z, Frames xy, int map_count) {
+    z.m_count = map_count, z.minv = (const double*)xy.base;
+    return z;
+}
+// ... and the two map planes are read images: map_count (1 or batch) frames of dst_h rows of dst_w int16 pairs, and (bilinear) of dst_w
+// uint16.  The frac plane is an image under BEVWARP_LINEAR only (NULL there: a NULL image).  c: a call made with map_sizes.
+inline void read_map_planes(Call& c, Frames xy, Frames frac, int interp) {
+    const int n = (c.m_count == c.batch && c.batch > 0) ? c.batch : 1;
     if (n == 1) xy.fs = frac.fs = 0;  // (one map: its frame stride is not looked at)
-    c.read_map(xy.image(z.dst_h, (uint64_t)z.dst_w * 4, n), 4);
-    if (interp == BEVWARP_LINEAR) c.read_map(frac.image(z.dst_h, (uint64_t)z.dst_w * 2, n), 2);
+    c.read_map(xy.image(c.dst_h, (uint64_t)c.dst_w * 4, n), 4);
+    if (interp == BEVWARP_LINEAR) c.read_map(frac.image(c.dst_h, (uint64_t)c.dst_w * 2, n), 2);
+}
+// bevwarp_remap: bevwarp_warp's images and formats without bicubic, with all six borders, and the two map planes.
+inline Call remap_call(Frames src, Frames dst, Frames xy, Frames frac, const Sizes& z, int map_count, int channels, int dtype, int interp, int border_mode) {
+    Call c = warp_call(src, dst, map_sizes(z, xy, map_count), channels, dtype, interp, false);
+    c.format_ok = c.format_ok && border_mode >= BEVWARP_BORDER_CONSTANT && border_mode <= BEVWARP_BORDER_TRANSPARENT;
+    read_map_planes(c, xy, frac, interp);
     return c;
 }
 // ... and its lens (HOST: fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6) and r2_max (+inf: no limit), which check_call does not see
@@ -284,7 +292,7 @@ inline Call stitch_call(const bevwarp_camera& k, Frames dst, int batch, int dst_
                   (border_mode == BEVWARP_BORDER_CONSTANT || border_mode == BEVWARP_BORDER_TRANSPARENT);
     return c;
 }
-// What the four NV12 entry points share: nearest or bilinear, B, G, R or R, G, B.  Each adds its images.
+// What the NV12 entry points share: nearest or bilinear, B, G, R or R, G, B.  Each adds its images.
 inline Call nv12_family_call(const Sizes& z, int interp, int rgb_order, bool plane_ok = true) {
     return {z, (interp == BEVWARP_NEAREST || interp == BEVWARP_LINEAR) && (rgb_order == 0 || rgb_order == 1) && plane_ok, false};
 }
@@ -302,6 +310,22 @@ inline Call nv12_planes_call(Frames y, Frames uv, Frames dst, int64_t dst_ps, co
     Call c = nv12_family_call(z, interp, rgb_order, elem != 1);  // (1: none of the three)
     c.read_nv12(y, uv);
     c.write_planes(dst.image(z.dst_h, (uint64_t)z.dst_w * elem, z.batch), elem, 3, dst_ps);
+    return c;
+}
+// bevwarp_remap_nv12: bevwarp_warp_nv12's images, formats and order of checks, with all six borders (a border mode outside them is an
+// unsupported format) and bevwarp_remap's map planes; reads[2], reads[3]: the xy and the frac plane
+inline Call remap_nv12_call(Frames y, Frames uv, Frames dst, Frames xy, Frames frac, const Sizes& z, int map_count, int interp, int rgb_order, int border_mode) {
+    Call c = nv12_call(y, uv, dst, map_sizes(z, xy, map_count), interp, rgb_order);
+    c.format_ok = c.format_ok && border_mode >= BEVWARP_BORDER_CONSTANT && border_mode <= BEVWARP_BORDER_TRANSPARENT;
+    read_map_planes(c, xy, frac, interp);
+    return c;
+}
+// bevwarp_remap_nv12_planes: bevwarp_warp_nv12_planes' likewise, with the five borders that write every pixel
+inline Call remap_nv12_planes_call(Frames y, Frames uv, Frames dst, int64_t dst_ps, Frames xy, Frames frac, const Sizes& z, int map_count, int interp, int rgb_order,
+                                   int border_mode, int plane_dtype) {
+    Call c = nv12_planes_call(y, uv, dst, dst_ps, map_sizes(z, xy, map_count), interp, rgb_order, plane_dtype);
+    c.format_ok = c.format_ok && border_mode >= BEVWARP_BORDER_CONSTANT && border_mode < BEVWARP_BORDER_TRANSPARENT;
+    read_map_planes(c, xy, frac, interp);
     return c;
 }
 // bevwarp_warp_to_nv12: from 8-bit pixels of 3 channels

@@ -25,13 +25,21 @@ __device__ __forceinline__ Chroma chroma_terms(uint32_t pair) {  // byte 0 = U, 
     c.b = 524288 + 2116026 * u;
     return c;
 }
+// the three channels of one converted pixel
+__device__ __forceinline__ void convert_channels(uint32_t Y, const Chroma& c, uint32_t& r, uint32_t& g, uint32_t& b) {
+    const int yy = max(0, (int)Y - 16) * 1220542;
+    r = (uint32_t)min(max((yy + c.r) >> 20, 0), 255);  // (min(max()): v_med3_i32)
+    g = (uint32_t)min(max((yy + c.g) >> 20, 0), 255);
+    b = (uint32_t)min(max((yy + c.b) >> 20, 0), 255);
+}
 // one converted pixel, packed in the destination's channel order (RGB = 0: B, G, R in bytes 0, 1, 2; 1: R, G, B)
+// (The compiler may fuse two channels' >> 20 and clamp with this packing into v_ashr_pk_u8_i32; the one kernel in which it did gave wrong
+// pixels on the MI355X -- warp_map_nv12.hip's convert_packed, DESIGN.md section 4.19.  A kernel that uses convert and fails its bit-exact
+// test: look for that instruction in its code first.)
 template <int RGB>
 __device__ __forceinline__ uint32_t convert(uint32_t Y, const Chroma& c) {
-    const int yy = max(0, (int)Y - 16) * 1220542;
-    const uint32_t r = (uint32_t)min(max((yy + c.r) >> 20, 0), 255);  // (min(max()): v_med3_i32)
-    const uint32_t g = (uint32_t)min(max((yy + c.g) >> 20, 0), 255);
-    const uint32_t b = (uint32_t)min(max((yy + c.b) >> 20, 0), 255);
+    uint32_t r, g, b;
+    convert_channels(Y, c, r, g, b);
     return RGB ? (r | (g << 8) | (b << 16)) : (b | (g << 8) | (r << 16));
 }
 

@@ -7,9 +7,11 @@
 // registers.
 //
 // The frame -- item decoding, the row walk, the rounding, a pixel's load and the store of a lane's 4 pixels -- is flat_frame.h; the lens
-// step and the blend are lens_pixel.h; the index remap is warp_border.h.
+// step and the blend are lens_pixel.h; the index remap is warp_border.h; the sampler's map loads and index stage are map_entry.h, shared
+// with the NV12 sampler (warp_map_nv12.hip).
 #include "warp_map.h"
 #include "lens_pixel.h"
+#include "map_entry.h"
 
 namespace bevwarp {
 namespace {
@@ -181,57 +183,16 @@ __global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(kWavesPerSi
     const int b0 = (int)g * a.frames_per_item;
     const int nb = min(a.frames_per_item, a.batch - b0);
 
-    // the lane's map entries: wide loads where all 4 pixels lie in the row and the planes' layout admits them; no entry past the row's end
-    // is read (such a lane's entry is 0: the source's first pixel, never stored)
+    // the lane's map entries (map_entry.h) and, per entry, the taps' indices under the border mode (map_entry_taps.inc)
     uint32_t e[PPL], fr[PPL];
-    const bool whole = xs + PPL <= a.dst_w;
-    const uint8_t* xrow = a.xy + (int64_t)b0 * a.xy_fs + (int64_t)y * a.xy_rs + (int64_t)xs * 4;
-    if (a.map_vec_ok && whole) {
-        const u32x4 v = *reinterpret_cast<const u32x4*>(xrow);
-        e[0] = v.x, e[1] = v.y, e[2] = v.z, e[3] = v.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < PPL; j++) e[j] = (xs + j < a.dst_w) ? reinterpret_cast<const uint32_t*>(xrow)[j] : 0u;
-    }
-    if constexpr (INTERP == kLinear) {
-        const uint8_t* frow = a.frac + (int64_t)b0 * a.frac_fs + (int64_t)y * a.frac_rs + (int64_t)xs * 2;
-        if (a.map_vec_ok && whole) {
-            const u32x2 v = *reinterpret_cast<const u32x2*>(frow);
-            fr[0] = v.x & 0xffffu, fr[1] = v.x >> 16, fr[2] = v.y & 0xffffu, fr[3] = v.y >> 16;
-        } else {
-#pragma unroll
-            for (int j = 0; j < PPL; j++) fr[j] = (xs + j < a.dst_w) ? (uint32_t)reinterpret_cast<const uint16_t*>(frow)[j] : 0u;
-        }
-    }
+    load_entries<INTERP>(a, b0, y, xs, e, fr);
 
     Taps tap[PPL];
     bool wr[PPL];
 #pragma unroll
     for (int j = 0; j < PPL; j++) {
-        const int sx = (int)(short)(e[j] & 0xffffu), sy = (int)e[j] >> 16;
         Taps& t = tap[j];
-        const uint32_t f = INTERP == kLinear ? (fr[j] & 1023u) : 0u;  // (higher bits are ignored)
-        int c0, c1, cy0, cy1;
-        uint32_t in = 0u;
-        if constexpr (kTransparent) {
-            // inliers only (remapBilinear's (unsigned)sx < width - 1); the others' taps are never used
-            wr[j] = xs + j < a.dst_w && (INTERP == kLinear ? ((unsigned)sx < (unsigned)(a.src_w - 1) && (unsigned)sy < (unsigned)(a.src_h - 1))
-                                                            : ((unsigned)sx < (unsigned)a.src_w && (unsigned)sy < (unsigned)a.src_h));
-            c0 = sx, c1 = sx + 1, cy0 = sy, cy1 = sy + 1;
-        } else if constexpr (MODE == 0) {
-            wr[j] = xs + j < a.dst_w;
-            const int w = a.src_w, h = a.src_h;
-            const bool xin0 = (unsigned)sx < (unsigned)w, yin0 = (unsigned)sy < (unsigned)h;
-            const bool xin1 = INTERP == kLinear && (unsigned)(sx + 1) < (unsigned)w, yin1 = INTERP == kLinear && (unsigned)(sy + 1) < (unsigned)h;
-            c0 = min(max(sx, 0), w - 1), c1 = min(max(sx + 1, 0), w - 1), cy0 = min(max(sy, 0), h - 1), cy1 = min(max(sy + 1, 0), h - 1);
-            in = (uint32_t)(xin0 && yin0) | ((uint32_t)(xin1 && yin0) << 1) | ((uint32_t)(xin0 && yin1) << 2) | ((uint32_t)(xin1 && yin1) << 3);
-        } else {
-            wr[j] = xs + j < a.dst_w;
-            c0 = border_index<MODE>(sx, a.src_w, a.per_x, a.off_x, a.mag_x);
-            cy0 = border_index<MODE>(sy, a.src_h, a.per_y, a.off_y, a.mag_y);
-            c1 = INTERP == kLinear ? border_index<MODE>(sx + 1, a.src_w, a.per_x, a.off_x, a.mag_x) : c0;
-            cy1 = INTERP == kLinear ? border_index<MODE>(sy + 1, a.src_h, a.per_y, a.off_y, a.mag_y) : cy0;
-        }
+#include "map_entry_taps.inc"
         t.w = f | (in << 10);
         const uint32_t o0 = (uint32_t)cy0 * (uint32_t)a.src_rs, o1 = (uint32_t)cy1 * (uint32_t)a.src_rs;
         const uint32_t x0 = (uint32_t)c0 * (uint32_t)(C * sizeof(T)), x1 = (uint32_t)c1 * (uint32_t)(C * sizeof(T));

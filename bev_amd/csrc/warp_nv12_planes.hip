@@ -5,7 +5,7 @@
 // The frame is flat_frame.h's and the sampler warp_nv12_kernel's (nv12_sample.h); the store stage, which has no twin in the frame, is
 // the plane stage of the row kernel's 8-bit sources (rows_store.inc): per channel the lane converts its 4 values and writes them with
 // one 16-byte (float32) or 8-byte (16-bit) store into that channel's plane row, so a wave writes 1024 / 512 contiguous bytes per
-// instruction.  The kernel samples B, G, R and never learns the destination's channel order: the host hands it a plane offset, scale,
+// instruction (plane_store.inc, text shared with warp_map_nv12.hip).  The kernel samples B, G, R and never learns the destination's channel order: the host hands it a plane offset, scale,
 // bias and border byte per SAMPLED channel.
 #include "nv12_sample.h"
 #include "warp_kernels.h"
@@ -36,50 +36,7 @@ __global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(kWavesPerSi
         p[j] = sample_nv12<INTERP, 0>(yf, uvf, a.y_rs, a.uv_rs, a.src_w, a.src_h, a.border, X, Y);
     }
 
-    // the plane stores: per sampled channel the 8-bit value as float32, times scale, plus bias (each rounded), converted; 4 elements of
-    // a plane row in one store for a lane whose 4 pixels lie in the row, element stores otherwise
-    constexpr int ELEM = WIDE16 ? 2 : 4;
-    uint8_t* d = dst_row(a, b, y) + (int64_t)xs * ELEM;
-    const int lane_px = min(PPL, a.dst_w - xs);
-    const bool lane_vec = a.dst_vec_ok && lane_px == PPL;
-    if constexpr (WIDE16) {
-        auto planes = [&](auto as) __attribute__((always_inline)) {
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                const float sc = a.pscale[k], bi = a.pbias[k];
-                const uint32_t h[4] = {as((float)((p[0] >> (8 * k)) & 0xffu) * sc + bi), as((float)((p[1] >> (8 * k)) & 0xffu) * sc + bi),
-                                       as((float)((p[2] >> (8 * k)) & 0xffu) * sc + bi), as((float)((p[3] >> (8 * k)) & 0xffu) * sc + bi)};
-                uint16_t* dk = reinterpret_cast<uint16_t*>(d + a.ch_off[k]);
-                if (__builtin_expect(lane_vec, 1)) {
-                    u32x2 o = {h[0] | (h[1] << 16), h[2] | (h[3] << 16)};
-                    wide_store(reinterpret_cast<u32x2*>(dk), o);
-                } else {
-#pragma unroll
-                    for (int i = 0; i < PPL; i++)
-                        if (i < lane_px) dk[i] = (uint16_t)h[i];
-                }
-            }
-        };
-        if (a.plane == kPlaneBF16)  // (wave-uniform)
-            planes(BitsBF16{});
-        else
-            planes(BitsF16{});
-    } else {
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const float sc = a.pscale[k], bi = a.pbias[k];
-            f32x4 o = {(float)((p[0] >> (8 * k)) & 0xffu) * sc + bi, (float)((p[1] >> (8 * k)) & 0xffu) * sc + bi,
-                       (float)((p[2] >> (8 * k)) & 0xffu) * sc + bi, (float)((p[3] >> (8 * k)) & 0xffu) * sc + bi};
-            float* dk = reinterpret_cast<float*>(d + a.ch_off[k]);
-            if (__builtin_expect(lane_vec, 1)) {
-                wide_store(reinterpret_cast<f32x4*>(dk), o);
-            } else {
-#pragma unroll
-                for (int i = 0; i < PPL; i++)
-                    if (i < lane_px) dk[i] = o[i];
-            }
-        }
-    }
+#include "plane_store.inc"
 }
 
 template <int INTERP>

@@ -544,6 +544,23 @@ def build_warp_map(M, dsize, flags=INTER_LINEAR, K=None, dist_coeff=None, r2_max
     return out
 
 
+def _map_call(who, warp_map, border_mode):
+    """What the entries that sample through a map check before they look at a tensor: the border mode as an int."""
+    if not isinstance(warp_map, WarpMap):
+        raise ValueError("%s needs a WarpMap (build_warp_map, or WarpMap(xy, frac, interp, dsize)), got %s" % (who, type(warp_map).__name__))
+    if border_mode not in _BORDER_MODES:
+        raise ValueError("unsupported border mode %r (BORDER_CONSTANT, _REPLICATE, _REFLECT, _WRAP, _REFLECT_101, _TRANSPARENT)" % (border_mode,))
+    return int(border_mode)
+
+
+def _map_fits(warp_map, B, device):
+    """A map serves a batch of B frames on `device`: one frame shared by all or one per frame, on the frames' device."""
+    if warp_map.n not in (1, B):
+        raise ValueError("the map holds %d frames for a batch of %d (1 or the batch)" % (warp_map.n, B))
+    if warp_map.device != device:
+        raise ValueError("the map is on %s, the frames are on %s" % (warp_map.device, device))
+
+
 def remap(src, warp_map, border_mode=BORDER_CONSTANT, border_value=None, out=None):
     """cv2.remap on the GPU, batched: frames sampled through a WarpMap (include/bevwarp.h, bevwarp_remap) -- no coordinate is computed,
     no float64 is touched.  The per-frame half of a fixed camera's loop; build_warp_map is the other.
@@ -553,20 +570,13 @@ def remap(src, warp_map, border_mode=BORDER_CONSTANT, border_value=None, out=Non
     border_mode   any of the six BORDER_* modes; border_value (BORDER_CONSTANT only) a scalar or C values, None = 0.
     out      as warp_perspective; BORDER_TRANSPARENT without `out` starts from zeros.
     Returns a tensor shaped like src with (height, width) replaced by the map's, or `out`.  Asynchronous on the current stream."""
-    if not isinstance(warp_map, WarpMap):
-        raise ValueError("remap needs a WarpMap (build_warp_map, or WarpMap(xy, frac, interp, dsize)), got %s" % (type(warp_map).__name__,))
-    if border_mode not in _BORDER_MODES:
-        raise ValueError("unsupported border mode %r (BORDER_CONSTANT, _REPLICATE, _REFLECT, _WRAP, _REFLECT_101, _TRANSPARENT)" % (border_mode,))
-    border_mode = int(border_mode)
+    border_mode = _map_call("remap", warp_map, border_mode)
     if not isinstance(src, torch.Tensor) or src.dtype not in _DTYPES or src.dim() not in (2, 3, 4):
         raise ValueError("remap needs a uint8 or float32 tensor (B, H, W, C), (H, W, C) or (H, W)")
     B = src.shape[0] if src.dim() == 4 else 1
     C = 1 if src.dim() == 2 else src.shape[-1]
     dw, dh = warp_map.dsize
-    if warp_map.n not in (1, B):
-        raise ValueError("the map holds %d frames for a batch of %d (1 or the batch)" % (warp_map.n, B))
-    if warp_map.device != src.device:
-        raise ValueError("the map is on %s, the frames are on %s" % (warp_map.device, src.device))
+    _map_fits(warp_map, B, src.device)
     if isinstance(out, torch.Tensor) and out.dim() == src.dim():  # (an `out` of src's rank names a size: the map's, or the call is refused)
         hw = tuple(out.shape[-2:]) if src.dim() == 2 else tuple(out.shape[-3:-1])
         if hw != (dh, dw):
@@ -782,9 +792,8 @@ def split_nv12(frame):
     return y, uv
 
 
-def _nv12_source(who, y, uv, M, flags, M_inv_device):
-    """The planes of an NV12 call as the ABI reads them -- (B, H, W) and (B, H / 2, W / 2, 2) views, strides passed through -- and its
-    matrices: (y3, uv4, M_inv_device, number of matrices)."""
+def _nv12_planes(who, y, uv):
+    """The planes of an NV12 call as the ABI reads them: (y3, uv4), (B, H, W) and (B, H / 2, W / 2, 2) views, strides passed through."""
     for name, t in (("y", y), ("uv", uv)):
         if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8:
             raise ValueError("%s needs uint8 CUDA (HIP) tensors; %s is %s" % (who, name, getattr(t, "dtype", type(t))))
@@ -796,7 +805,13 @@ def _nv12_source(who, y, uv, M, flags, M_inv_device):
         raise ValueError("NV12 needs even sides and uv of shape %s; got y %s, uv %s" % ((B, H // 2, W // 2, 2), tuple(y3.shape), tuple(uv4.shape)))
     if y3.stride(2) != 1 or uv4.stride(3) != 1 or uv4.stride(2) != 2:
         raise ValueError("the last dimension of y and of uv (pairs, and the pairs of a row) must be contiguous")
-    return (y3, uv4) + _matrices(M, flags, M_inv_device, y3.device, B)
+    return y3, uv4
+
+
+def _nv12_source(who, y, uv, M, flags, M_inv_device):
+    """_nv12_planes and the call's matrices: (y3, uv4, M_inv_device, number of matrices)."""
+    y3, uv4 = _nv12_planes(who, y, uv)
+    return (y3, uv4) + _matrices(M, flags, M_inv_device, y3.device, y3.shape[0])
 
 
 def warp_perspective_nv12(y, uv, M, dsize, flags=INTER_LINEAR, border_value=None, out=None, M_inv_device=None, rgb=False):
@@ -852,6 +867,77 @@ def warp_nv12_to_planar(y, uv, M, dsize, scale=1.0 / 255.0, bias=0.0, flags=INTE
     _lib.launch("bevwarp_warp_nv12_planes", y3.device, y3.data_ptr(), uv4.data_ptr(), d4.data_ptr(), B, H, W, dh, dw, y3.stride(0), y3.stride(1),
                 uv4.stride(0), uv4.stride(1), d4.stride(0) * esz, d4.stride(1) * esz, d4.stride(2) * esz, M_inv_device.data_ptr(), n_m, interp,
                 1 if rgb else 0, _ptr(bv), _ptr(sc), _ptr(bi), _PLANE_DTYPES[out_dtype])
+    return _like_src(d4, y.dim() + 1, out)
+
+
+def remap_nv12(y, uv, warp_map, border_mode=BORDER_CONSTANT, border_value=None, out=None, rgb=False):
+    """remap of a video decoder's NV12 frames, converted on the way: bit for bit
+
+        remap(cvtColor(nv12, COLOR_YUV2BGR_NV12), warp_map, border_mode, border_value)       (rgb=True: COLOR_YUV2RGB_NV12)
+
+    in one pass, without the converted frame (include/bevwarp.h, bevwarp_remap_nv12).  The per-frame half of a fixed camera's loop for
+    frames that come from a decoder: the map carries the lens (build_warp_map), no coordinate is computed, no float64 is touched.
+
+    y, uv    as warp_perspective_nv12: (H, W) / (B, H, W) and (H / 2, W / 2, 2) / (B, H / 2, W / 2, 2) uint8 CUDA tensors, H and W even;
+             split_nv12's views and row-padded planes are taken as they are (strides passed through; uv base and strides even).
+    warp_map a WarpMap on the frames' device with n == 1 (shared by all frames) or n == B; its interpolation is the call's.
+    border_mode   any of the six BORDER_* modes; the index remap applies to the pixel index (luma and chroma follow it together).
+    border_value  (BORDER_CONSTANT only) a scalar or 3 values in the RESULT's channel order, not converted; None = 0.
+    out      as remap: BORDER_TRANSPARENT without `out` starts from zeros.
+    Returns (B, h, w, 3), or (h, w, 3) for a single frame, or `out`.  Asynchronous on the current stream.  FramePipeline(warp_map=...,
+    src_format="nv12") keeps refusing: a streaming caller calls this function with `out=` on a stream of its own."""
+    border_mode = _map_call("remap_nv12", warp_map, border_mode)
+    y3, uv4 = _nv12_planes("remap_nv12", y, uv)
+    B, H, W = y3.shape
+    dw, dh = warp_map.dsize
+    _map_fits(warp_map, B, y3.device)
+    if isinstance(out, torch.Tensor) and out.dim() == y.dim() + 1 and tuple(out.shape[-3:-1]) != (dh, dw):  # (remap's rule: an `out` of the result's rank names a size)
+        raise ValueError("the map's dsize is %s, out is %s" % ((dw, dh), tuple(out.shape)))
+    if isinstance(out, torch.Tensor) and out.numel() != B * dh * dw * 3:
+        raise ValueError("the map's dsize is %s (%d frames of 3 channels): out has %d elements" % ((dw, dh), B, out.numel()))
+    d4 = _pixel_dst(out, torch.uint8, y3.device, B, dh, dw, 3, zeroed=border_mode == BORDER_TRANSPARENT)
+    bv = _border(border_value, 3) if border_mode == BORDER_CONSTANT else None
+    xy_p, fr_p, xy_fs, xy_rs, fr_fs, fr_rs = warp_map._planes()
+    _lib.launch("bevwarp_remap_nv12", y3.device, y3.data_ptr(), uv4.data_ptr(), d4.data_ptr(), B, H, W, dh, dw, y3.stride(0), y3.stride(1), uv4.stride(0),
+                uv4.stride(1), d4.stride(0), d4.stride(1), xy_p, fr_p, warp_map.n, xy_fs, xy_rs, fr_fs, fr_rs, warp_map.interp, border_mode, 1 if rgb else 0,
+                _ptr(bv))
+    return _like_src(d4, y.dim() + 1, out)
+
+
+def remap_nv12_to_planar(y, uv, warp_map, scale=1.0 / 255.0, bias=0.0, border_mode=BORDER_CONSTANT, border_value=None, out=None, rgb=False,
+                         out_dtype=torch.float32):
+    """A decoder's NV12 frames sampled through a fixed camera's map straight into the normalised channel planes a detector takes, in one
+    launch (include/bevwarp.h, bevwarp_remap_nv12_planes): bit for bit
+
+        out[b, c] = convert(float32(remap_nv12(y, uv, warp_map, border_mode, border_value, rgb=rgb)[b, :, :, c]) * scale[c] + bias[c])
+
+    (float32 mul, then add, then out_dtype) -- warp_nv12_to_planar's plane stage -- without the 8-bit BEV frame in between.
+
+    y, uv, warp_map, rgb   as remap_nv12.
+    border_mode   BORDER_CONSTANT, _REPLICATE, _REFLECT, _WRAP or _REFLECT_101; BORDER_TRANSPARENT is refused (planes hold no canvas).
+    scale, bias, border_value   scalars or 3 values in the RESULT's channel order (B, G, R; rgb=True: R, G, B).
+    out_dtype, out   as warp_nv12_to_planar: torch.float32 (default), torch.float16 or torch.bfloat16; a given `out` has this dtype and
+                     contiguous rows, and is returned as it is.
+    Returns (B, 3, h, w), or (3, h, w) for a single frame.  Asynchronous on the current stream.  FramePipeline(warp_map=...,
+    src_format="nv12") keeps refusing: a streaming caller calls this function with `out=` on a stream of its own."""
+    border_mode = _map_call("remap_nv12_to_planar", warp_map, border_mode)
+    if border_mode == BORDER_TRANSPARENT:
+        raise ValueError("remap_nv12_to_planar: BORDER_TRANSPARENT writes no planes (remap_nv12 into a canvas, then warp_to_planar)")
+    _plane_format("remap_nv12_to_planar", warp_map.interp, out_dtype, out)
+    y3, uv4 = _nv12_planes("remap_nv12_to_planar", y, uv)
+    B, H, W = y3.shape
+    dw, dh = warp_map.dsize
+    _map_fits(warp_map, B, y3.device)
+    if isinstance(out, torch.Tensor) and out.dim() == y.dim() + 1 and tuple(out.shape[-2:]) != (dh, dw):
+        raise ValueError("the map's dsize is %s, out is %s" % ((dw, dh), tuple(out.shape)))
+    d4 = _plane_dst(out, out_dtype, y3.device, B, 3, dh, dw)
+    sc, bi = _per_channel(scale, 3), _per_channel(bias, 3)
+    bv = _border(border_value, 3) if border_mode == BORDER_CONSTANT else None
+    esz = d4.element_size()
+    xy_p, fr_p, xy_fs, xy_rs, fr_fs, fr_rs = warp_map._planes()
+    _lib.launch("bevwarp_remap_nv12_planes", y3.device, y3.data_ptr(), uv4.data_ptr(), d4.data_ptr(), B, H, W, dh, dw, y3.stride(0), y3.stride(1),
+                uv4.stride(0), uv4.stride(1), d4.stride(0) * esz, d4.stride(1) * esz, d4.stride(2) * esz, xy_p, fr_p, warp_map.n, xy_fs, xy_rs, fr_fs, fr_rs,
+                warp_map.interp, border_mode, 1 if rgb else 0, _ptr(bv), _ptr(sc), _ptr(bi), _PLANE_DTYPES[out_dtype])
     return _like_src(d4, y.dim() + 1, out)
 
 

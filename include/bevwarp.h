@@ -38,6 +38,11 @@
  *   bevwarp_warp_nv12_planes  the same decoder frames, vis_homo.py:86-89, written straight as the detector-input planes of
  *                             bevwarp_warp_planes (float32, float16 or bfloat16): decoder -> BEV -> detector input in one launch,
  *                             with neither the converted frame nor the 8-bit BEV frame in memory
+ *   bevwarp_remap_nv12, bevwarp_remap_nv12_planes
+ *                           the two above for the camera loop of a FIXED, possibly distorted camera, vis_homo.py:85-91 with
+ *                             Calib.dist_coeff (bev/calib.py:25): the decoder's NV12 frames sampled through the maps that
+ *                             bevwarp_build_map made once -- cv2.remap(cv2.cvtColor(nv12, COLOR_YUV2BGR_NV12), map1, map2, ...) per
+ *                             frame, with the lens in the map, no float64, and no converted frame in memory
  *   bevwarp_warp_to_nv12    cv2.warpPerspective(img, H_bev_img, (u_size, v_size)) + `writer.write(bev)`, vis_homo.py:109-111 and
  *                             bev/io/utils.py:89-99, without the BGR -> YUV 4:2:0 pass a video writer hides inside write(): the warp
  *                             stores the BEV frame as NV12, what an encoder takes (the tracker tools read the encoded bev.avi)
@@ -469,6 +474,66 @@ int bevwarp_warp_nv12_planes(const void *y, const void *uv, void *dst, int batch
                              const double *M_inv, int m_count, int interp, int rgb_order,
                              const double *border_value /*HOST, 3 or NULL*/, const double *scale /*HOST, 3 or NULL = 1*/,
                              const double *bias /*HOST, 3 or NULL = 0*/, int plane_dtype, void *stream);
+
+/*
+ * A video decoder's NV12 frames sampled through a fixed camera's warp maps: bevwarp_remap's pixels from bevwarp_warp_nv12's sources, in
+ * one pass.  The map carries the lens (bevwarp_build_map: pinhole, or the rational model with the r2_max guard), so neither entry has a
+ * lens or a matrix, and neither touches float64.  Both are defined by composing existing entries, bit for bit; the frame is 8-bit, 3 channels.
+ *
+ * bevwarp_remap_nv12:
+ *   dst = bevwarp_remap(cvtColor(nv12, rgb_order ? COLOR_YUV2RGB_NV12 : COLOR_YUV2BGR_NV12), dst, ..., map_xy, map_frac, ..., BEVWARP_U8,
+ *                       interp, border_mode, border_value)
+ * with the converted frame never in memory: every tap is converted (bevwarp_warp_nv12's conversion) before the blend.
+ *   y, uv, src_h, src_w, the four source strides, rgb_order   bevwarp_warp_nv12's: even sides, an even uv base and even uv strides, the
+ *                 size limits of either plane.
+ *   map_xy, map_frac, map_count, the four map strides, interp   bevwarp_remap's: map_count 1 (shared; frame strides not looked at) or
+ *                 batch; the planes are read images without source limits; map_frac may be NULL for BEVWARP_NEAREST only; interp is
+ *                 the interpolation the map was built for.
+ *   border_mode   all six.  The index remap applies to the PIXEL index: a tap at remapped pixel (c, r) reads Y = y[r][c] and the chroma
+ *                 pair uv[r >> 1][2 (c >> 1)], uv[r >> 1][2 (c >> 1) + 1] and is converted before the blend.  Under BEVWARP_BORDER_CONSTANT a
+ *                 tap outside the frame is border_value in the DESTINATION's channel order, not converted (HOST, 3 doubles, NULL = 0;
+ *                 not looked at under the other modes); BEVWARP_BORDER_TRANSPARENT writes the inliers only.  An invalid map entry
+ *                 (-32768, -32768) behaves exactly as in bevwarp_remap.
+ *   dst           device, dst_h x dst_w x 3 bytes; the wide-store rule is bevwarp_warp's.  It must not overlap y, uv or either map plane.
+ * With a map from bevwarp_build_map (lens NULL) and BEVWARP_BORDER_CONSTANT the result also equals bevwarp_warp_nv12's for the same
+ * matrix.
+ * Status, in bevwarp_warp_nv12's order with the map count standing where the matrix count stood and the two map planes among the images
+ * that are checked: BEVWARP_ERR_BAD_ARG (a null pointer -- map_frac under BEVWARP_LINEAR included --, a non-positive size, odd src_w or
+ * src_h, a row stride below a row for any of the five images, frames or maps that overlap their successors, an odd uv base or stride, a
+ * map_xy base or stride that is no multiple of 4 or a map_frac one that is no multiple of 2, map_count not 1 or batch);
+ * BEVWARP_ERR_UNSUPPORTED (interp other than nearest / linear, rgb_order outside {0, 1}, border_mode outside the six);
+ * BEVWARP_ERR_TOO_LARGE (either source plane, as bevwarp_warp_nv12); BEVWARP_ERR_OVERLAP (dst shares bytes with the y or the uv image, by
+ * bevwarp_warp's rule, or with the bounding byte range of either map plane); BEVWARP_ERR_TOO_LARGE again for a destination side > 2^20;
+ * BEVWARP_ERR_NOT_FINITE (border_value, BEVWARP_BORDER_CONSTANT only).  batch == 0 is BEVWARP_OK and launches nothing.
+ *
+ * bevwarp_remap_nv12_planes: for P = plane_dtype (BEVWARP_F32 | BEVWARP_F16 | BEVWARP_BF16) and channel c in the DESTINATION's order,
+ *   p               = bevwarp_remap_nv12(y, uv, ..., interp, border_mode, rgb_order, border_value)[b][y][x][c]      (an 8-bit value)
+ *   v               = float32(p) * float32(scale[c]) + float32(bias[c])                              (multiply, then add, each rounded; no FMA)
+ *   dst[b][c][y][x] = convert_P(v)
+ * -- bevwarp_warp_nv12_planes' plane stage, unchanged (convert_P, the three destination strides in bytes, the wide-store rule, scale and
+ * bias HOST, 3 doubles each in the destination's order, NULL = 1 and 0).  Neither the converted frame nor the 8-bit BEV frame is in memory.
+ *   border_mode   the five modes that write every pixel; BEVWARP_BORDER_TRANSPARENT is BEVWARP_ERR_UNSUPPORTED (a canvas is kept as
+ *                 8-bit pixels: bevwarp_remap_nv12 over it, then bevwarp_warp_planes).
+ * Status, in bevwarp_warp_nv12_planes' order with the same two substitutions: BEVWARP_ERR_BAD_ARG (everything bevwarp_remap_nv12 lists;
+ * the destination as bevwarp_warp_nv12_planes lists it); BEVWARP_ERR_UNSUPPORTED (interp, rgb_order, plane_dtype outside {F32, F16, BF16},
+ * border_mode outside the five); BEVWARP_ERR_TOO_LARGE (either source plane); BEVWARP_ERR_OVERLAP (the bounding byte range of all
+ * destination planes meets the y image's, the uv image's or either map plane's); BEVWARP_ERR_TOO_LARGE again for a destination side
+ * > 2^20; BEVWARP_ERR_NOT_FINITE (border_value under BEVWARP_BORDER_CONSTANT only; scale, bias).  batch == 0 is BEVWARP_OK and launches nothing.
+ */
+int bevwarp_remap_nv12(const void *y, const void *uv, void *dst, int batch, int src_h, int src_w, int dst_h, int dst_w,
+                       int64_t y_frame_stride, int64_t y_row_stride, int64_t uv_frame_stride, int64_t uv_row_stride,
+                       int64_t dst_frame_stride, int64_t dst_row_stride, const void *map_xy, const void *map_frac, int map_count,
+                       int64_t xy_frame_stride, int64_t xy_row_stride, int64_t frac_frame_stride, int64_t frac_row_stride,
+                       int interp, int border_mode, int rgb_order, const double *border_value /*HOST, 3 doubles or NULL*/,
+                       void *stream);
+int bevwarp_remap_nv12_planes(const void *y, const void *uv, void *dst, int batch, int src_h, int src_w, int dst_h, int dst_w,
+                              int64_t y_frame_stride, int64_t y_row_stride, int64_t uv_frame_stride, int64_t uv_row_stride,
+                              int64_t dst_frame_stride, int64_t dst_plane_stride, int64_t dst_row_stride,
+                              const void *map_xy, const void *map_frac, int map_count, int64_t xy_frame_stride,
+                              int64_t xy_row_stride, int64_t frac_frame_stride, int64_t frac_row_stride, int interp,
+                              int border_mode, int rgb_order, const double *border_value /*HOST, 3 or NULL*/,
+                              const double *scale /*HOST, 3 or NULL = 1*/, const double *bias /*HOST, 3 or NULL = 0*/,
+                              int plane_dtype, void *stream);
 
 /*
  * The warp written as NV12 for a video encoder, in one pass: stands in for cv2.warpPerspective(img, H_bev_img, (u_size, v_size)) followed by
