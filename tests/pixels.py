@@ -2,6 +2,7 @@
 
 float_frame            float32 frames over the whole format: both signs, every binade, subnormals, signed zeros, +-Inf, quiet and
                        signalling NaNs, +-FLT_MAX (the frames of tests/workloads.py lie in [0, 1))
+zero_block_frame       a "tiny" frame under squares of -0.0 and of +0.0: sums that are -0.0 only if nothing in them started from +0
 same_float             the comparison that goes with them: by bit pattern, so -0.0 != +0.0 and a NaN equals only a NaN
 padded_source          frames inside one larger allocation whose every other byte holds a fill value that is not the border value
 strided                an array in an allocation of its own in which every outer stride is padded by an amount of the caller's choice
@@ -46,6 +47,25 @@ def float_frame(kind, seed, h, w, c):
     else:
         pick = rng.random(shape) < 0.01
         out[pick] = np.where(rng.random(int(pick.sum())) < 0.5, -FLT_MAX, FLT_MAX)
+    return out
+
+
+def zero_block_frame(seed, h, w, c, block=8):
+    """(h, w, c) float32: float_frame("tiny", seed, h, w, c) -- a call of its own, the streams of the three kinds are untouched -- with
+    block x block squares of signed zeros laid over it, one per cell of a lattice of pitch block + block // 2 that starts at the frame's
+    corner (squares are cut at the far edges); three squares of every four are -0.0, the one whose lattice row and column are both odd
+    is +0.0.  A bilinear blend whose four taps lie in one square is a sum of signed zeros: -0.0 only if every term is, in any order --
+    so a result that starts from +0 (an accumulator, a masked-out tap, a flushed product) shows as +0.0 under same_float, and under
+    nothing that compares values."""
+    assert block >= 8
+    out = float_frame("tiny", seed, h, w, c)
+    pitch = block + block // 2
+    yy, xx = np.indices((h, w))
+    inside = (yy % pitch < block) & (xx % pitch < block)
+    plus = ((yy // pitch) % 2 == 1) & ((xx // pitch) % 2 == 1)
+    b = out.view(np.uint32)
+    b[inside & ~plus] = 0x80000000
+    b[inside & plus] = 0
     return out
 
 
