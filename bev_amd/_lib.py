@@ -39,6 +39,10 @@ SYMBOLS = {
                                  _c.c_void_p]),
     "bevwarp_warp_stitch": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int,
                                        _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p]),
+    "bevwarp_stitch_maps": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int,
+                                       _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p]),
+    "bevwarp_stitch_maps_nv12": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int, _c.c_int,
+                                            _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p]),
     "bevwarp_warp_classes": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int,
                                         _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int,
                                         _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p]),
@@ -90,6 +94,15 @@ class Camera(_c.Structure):
     """bevwarp_camera (include/bevwarp.h): one camera of bevwarp_warp_stitch.  A host array of these is the call's first argument."""
     _fields_ = [("src", _c.c_void_p), ("M_inv", _c.c_void_p), ("frame_stride", _c.c_int64), ("row_stride", _c.c_int64), ("src_h", _c.c_int),
                 ("src_w", _c.c_int), ("m_count", _c.c_int), ("reserved", _c.c_int)]
+
+
+class MapCamera(_c.Structure):
+    """bevwarp_map_camera (include/bevwarp.h): one camera of bevwarp_stitch_maps / bevwarp_stitch_maps_nv12.  A host array of these is the
+    call's first argument."""
+    _fields_ = [("src", _c.c_void_p), ("uv", _c.c_void_p), ("frame_stride", _c.c_int64), ("row_stride", _c.c_int64), ("uv_frame_stride", _c.c_int64),
+                ("uv_row_stride", _c.c_int64), ("map_xy", _c.c_void_p), ("map_frac", _c.c_void_p), ("xy_frame_stride", _c.c_int64), ("xy_row_stride", _c.c_int64),
+                ("frac_frame_stride", _c.c_int64), ("frac_row_stride", _c.c_int64), ("src_h", _c.c_int), ("src_w", _c.c_int), ("map_count", _c.c_int),
+                ("reserved", _c.c_int)]
 
 
 STITCH_OVER, STITCH_FEATHER, STITCH_MAX_CAMERAS = 0, 1, 8

@@ -19,6 +19,7 @@
 #include "warp_nv12.h"
 #include "warp_nv12_out.h"
 #include "warp_stitch.h"
+#include "warp_stitch_maps.h"
 
 #pragma clang fp contract(off)
 
@@ -402,6 +403,73 @@ int bevwarp_warp_stitch(const bevwarp_camera* cams, int n_cams, void* dst, int b
     border_values(a.fill ? border_value : nullptr, channels, a.bv_f, bu);
     a.bv_u8 = (uint32_t)bu[0] | ((uint32_t)bu[1] << 8) | ((uint32_t)bu[2] << 16) | ((uint32_t)bu[3] << 24);
     return launched(launch_warp_stitch(a, dtype, channels, interp, blend, p.total_tiles, (hipStream_t)stream));
+}
+
+}  // extern "C"
+
+namespace {
+// What the two stitches through maps share once their checks have passed: the canvas, the grid, the feather width and the border pixel in the
+// zeroed arguments, and per camera what its call (stitch_maps_call / stitch_maps_nv12_call: reads[first_map] is the xy plane) reads.
+template <class MakeCall>
+void stitch_maps_args(StitchMapsArgs& a, const TilePlan& p, const bevwarp_map_camera* cams, int n_cams, const Frames& d, int batch, int dst_h, int dst_w, int channels,
+                      int dtype, int interp, int feather, int border_mode, const double* border_value, int first_map, MakeCall make_call) {
+    memset(&a, 0, sizeof(a));
+    a.dst = (uint8_t*)d.base, a.dst_fs = d.fs, a.dst_rs = d.rs, a.dst_h = dst_h, a.dst_w = dst_w;
+    a.bw0 = p.bw0, a.tiles_x = p.tiles_x, a.tiles_per_frame = p.tiles_per_frame;
+    a.tpf_magic = p.tpf_magic, a.tx_magic = p.tx_magic, a.bw0_magic = p.bw0_magic;
+    const int elem = dtype == BEVWARP_U8 ? 1 : 4;
+    a.dst_vec_ok = plan::wide_stores_ok(d.image(dst_h, (uint64_t)dst_w * channels * elem, batch), plan::store_align(dtype, channels, false));
+    for (int k = 0; k < n_cams; k++) {
+        const Call c = make_call(cams[k]);
+        StitchMapCamera& s = a.cams[k];
+        const Image &src = c.reads[0].im, &ixy = c.reads[first_map].im, *ifr = (interp == BEVWARP_LINEAR) ? &c.reads[first_map + 1].im : nullptr;
+        s.src = (const uint8_t*)src.base, s.src_fs = src.fs, s.src_rs = src.rs;
+        if (first_map == 2) {
+            const Image& uv = c.reads[1].im;
+            s.uv = (const uint8_t*)uv.base, s.uv_fs = uv.fs, s.uv_rs = uv.rs;
+        }
+        s.xy = (const uint8_t*)ixy.base, s.xy_fs = ixy.fs, s.xy_rs = ixy.rs;  // (a shared map: read_map_planes has zeroed its frame strides)
+        if (ifr) s.frac = (const uint8_t*)ifr->base, s.frac_fs = ifr->fs, s.frac_rs = ifr->rs;
+        s.src_h = c.src_h, s.src_w = c.src_w;
+        s.src_vec_ok = plan::pixel_loads_ok(src, plan::pixel_load_align(dtype, channels));
+        s.map_vec_ok = plan::map_vec_ok(ixy, ifr);
+    }
+    a.n_cams = n_cams, a.feather = feather;
+    a.fill = border_mode == BEVWARP_BORDER_CONSTANT;
+    uint8_t bu[4];  // (border_value is read by the constant border only; the status has found it finite)
+    border_values(a.fill ? border_value : nullptr, channels, a.bv_f, bu);
+    a.bv_u8 = (uint32_t)bu[0] | ((uint32_t)bu[1] << 8) | ((uint32_t)bu[2] << 16) | ((uint32_t)bu[3] << 24);
+}
+}  // namespace
+
+extern "C" {
+
+int bevwarp_stitch_maps(const bevwarp_map_camera* cams, int n_cams, void* dst, int batch, int dst_h, int dst_w, int channels, int64_t dst_frame_stride,
+                        int64_t dst_row_stride, int dtype, int interp, int blend, int feather, int border_mode, const double* border_value, void* stream) {
+    const Frames d = {dst, dst_frame_stride, dst_row_stride};
+    TilePlan p;
+    const int st = plan::stitch_maps_status(cams, n_cams, d, batch, dst_h, dst_w, channels, dtype, interp, blend, feather, border_mode, border_value, kBorderTileW,
+                                            kBorderTileH, p);
+    if (st != BEVWARP_OK || batch == 0) return st;
+    StitchMapsArgs a;
+    stitch_maps_args(a, p, cams, n_cams, d, batch, dst_h, dst_w, channels, dtype, interp, feather, border_mode, border_value, 1, [&](const bevwarp_map_camera& k) {
+        return plan::stitch_maps_call(k, d, batch, dst_h, dst_w, channels, dtype, interp, blend, border_mode);
+    });
+    return launched(launch_stitch_maps(a, dtype, channels, interp, blend, p.total_tiles, (hipStream_t)stream));
+}
+
+int bevwarp_stitch_maps_nv12(const bevwarp_map_camera* cams, int n_cams, void* dst, int batch, int dst_h, int dst_w, int64_t dst_frame_stride, int64_t dst_row_stride,
+                             int interp, int blend, int feather, int rgb_order, int border_mode, const double* border_value, void* stream) {
+    const Frames d = {dst, dst_frame_stride, dst_row_stride};
+    TilePlan p;
+    const int st = plan::stitch_maps_nv12_status(cams, n_cams, d, batch, dst_h, dst_w, interp, blend, feather, rgb_order, border_mode, border_value, kBorderTileW,
+                                                 kBorderTileH, p);
+    if (st != BEVWARP_OK || batch == 0) return st;
+    StitchMapsArgs a;  // (the border value is in the destination's channel order, as given: it is not converted)
+    stitch_maps_args(a, p, cams, n_cams, d, batch, dst_h, dst_w, 3, BEVWARP_U8, interp, feather, border_mode, border_value, 2, [&](const bevwarp_map_camera& k) {
+        return plan::stitch_maps_nv12_call(k, d, batch, dst_h, dst_w, interp, blend, rgb_order, border_mode);
+    });
+    return launched(launch_stitch_maps_nv12(a, interp, blend, rgb_order, p.total_tiles, (hipStream_t)stream));
 }
 
 int bevwarp_warp_nv12(const void* y, const void* uv, void* dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int64_t y_frame_stride,

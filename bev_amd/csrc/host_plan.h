@@ -1,5 +1,5 @@
 // host_plan.h -- what the C ABI decides before a launch, as plain C++17 (no HIP): the argument checks and the launch geometry.
-// bevwarp_api.hip is its only user in the library; tests/host_plan_driver.cpp (and lens_plan_driver.cpp, stitch_plan_driver.cpp, remap_plan_driver.cpp, remap_nv12_plan_driver.cpp) compile it
+// bevwarp_api.hip is its only user in the library; tests/host_plan_driver.cpp (and lens_plan_driver.cpp, stitch_plan_driver.cpp, remap_plan_driver.cpp, remap_nv12_plan_driver.cpp, stitch_maps_plan_driver.cpp) compile it
 // with g++ under the address and undefined-behaviour sanitizers, and tests/golden/launch_plans.json pins every field of the plans.  Not installed.
 #pragma once
 #include <math.h>
@@ -503,6 +503,54 @@ inline int stitch_status(const bevwarp_camera* cams, int n_cams, Frames dst, int
         for (int c = 0; c < channels; c++)
             if (!isfinite(border_value[c])) return BEVWARP_ERR_NOT_FINITE;
     return BEVWARP_OK;
+}
+
+// ---- bevwarp_stitch_maps, bevwarp_stitch_maps_nv12: the whole of their host side but the launch ---------------------------------------------
+// One camera of either: that camera's frames and map planes against the canvas -- bevwarp_remap's (bevwarp_remap_nv12's) call, its format
+// narrowed to the two blend rules and to the constant and the transparent border.  reads[]: the frames (NV12: Y, then the pairs), the xy
+// plane and, bilinear, the frac plane.
+inline bool stitch_format_ok(int blend, int border_mode) {
+    return (blend == BEVWARP_STITCH_OVER || blend == BEVWARP_STITCH_FEATHER) && (border_mode == BEVWARP_BORDER_CONSTANT || border_mode == BEVWARP_BORDER_TRANSPARENT);
+}
+inline Call stitch_maps_call(const bevwarp_map_camera& k, Frames dst, int batch, int dst_h, int dst_w, int channels, int dtype, int interp, int blend, int border_mode) {
+    Call c = remap_call({k.src, k.frame_stride, k.row_stride}, dst, {k.map_xy, k.xy_frame_stride, k.xy_row_stride}, {k.map_frac, k.frac_frame_stride, k.frac_row_stride},
+                        {batch, k.src_h, k.src_w, dst_h, dst_w, 0, nullptr}, k.map_count, channels, dtype, interp, border_mode);
+    c.format_ok = c.format_ok && stitch_format_ok(blend, border_mode);
+    return c;
+}
+inline Call stitch_maps_nv12_call(const bevwarp_map_camera& k, Frames dst, int batch, int dst_h, int dst_w, int interp, int blend, int rgb_order, int border_mode) {
+    Call c = remap_nv12_call({k.src, k.frame_stride, k.row_stride}, {k.uv, k.uv_frame_stride, k.uv_row_stride}, dst, {k.map_xy, k.xy_frame_stride, k.xy_row_stride},
+                             {k.map_frac, k.frac_frame_stride, k.frac_row_stride}, {batch, k.src_h, k.src_w, dst_h, dst_w, 0, nullptr}, k.map_count, interp, rgb_order,
+                             border_mode);
+    c.format_ok = c.format_ok && stitch_format_ok(blend, border_mode);
+    return c;
+}
+// The status of a call in the order include/bevwarp.h documents, and in `p` the grid of tw x th tiles over the canvas when the call goes
+// on to a launch (BEVWARP_OK and batch > 0).  cams is HOST; no device pointer is dereferenced.  nv12: channels and dtype are not looked at.
+inline int stitch_maps_any_status(bool nv12, const bevwarp_map_camera* cams, int n_cams, Frames dst, int batch, int dst_h, int dst_w, int channels, int dtype, int interp,
+                                  int blend, int feather, int rgb_order, int border_mode, const double* border_value, int tw, int th, TilePlan& p) {
+    p = {};
+    if (!cams || n_cams < 1 || n_cams > BEVWARP_STITCH_MAX_CAMERAS) return BEVWARP_ERR_BAD_ARG;
+    if (blend == BEVWARP_STITCH_FEATHER && (feather < 1 || feather > 4096)) return BEVWARP_ERR_BAD_ARG;
+    for (int k = 0; k < n_cams; k++) {  // every camera against the canvas; what the cameras read may overlap
+        const int st = check_call(nv12 ? stitch_maps_nv12_call(cams[k], dst, batch, dst_h, dst_w, interp, blend, rgb_order, border_mode)
+                                       : stitch_maps_call(cams[k], dst, batch, dst_h, dst_w, channels, dtype, interp, blend, border_mode));
+        if (st != BEVWARP_OK) return st;
+    }
+    p = plan_border(batch, dst_h, dst_w, tw, th);
+    if (p.status != BEVWARP_OK) return p.status;
+    if (border_mode == BEVWARP_BORDER_CONSTANT && border_value)
+        for (int c = 0; c < (nv12 ? 3 : channels); c++)
+            if (!isfinite(border_value[c])) return BEVWARP_ERR_NOT_FINITE;
+    return BEVWARP_OK;
+}
+inline int stitch_maps_status(const bevwarp_map_camera* cams, int n_cams, Frames dst, int batch, int dst_h, int dst_w, int channels, int dtype, int interp, int blend,
+                              int feather, int border_mode, const double* border_value, int tw, int th, TilePlan& p) {
+    return stitch_maps_any_status(false, cams, n_cams, dst, batch, dst_h, dst_w, channels, dtype, interp, blend, feather, 0, border_mode, border_value, tw, th, p);
+}
+inline int stitch_maps_nv12_status(const bevwarp_map_camera* cams, int n_cams, Frames dst, int batch, int dst_h, int dst_w, int interp, int blend, int feather,
+                                   int rgb_order, int border_mode, const double* border_value, int tw, int th, TilePlan& p) {
+    return stitch_maps_any_status(true, cams, n_cams, dst, batch, dst_h, dst_w, 3, BEVWARP_U8, interp, blend, feather, rgb_order, border_mode, border_value, tw, th, p);
 }
 
 }  // namespace plan

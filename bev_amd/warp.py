@@ -722,6 +722,125 @@ def warp_stitch(srcs, Ms, dsize, flags=INTER_LINEAR, blend="over", feather=64, b
     return _like_src(d4, srcs[0].dim(), out)
 
 
+def _stitch_maps_call(who, n_cams, warp_maps, blend, feather, border_mode):
+    """What the stitches through maps check before they look at a tensor: the camera count, one WarpMap per camera of one dsize and
+    interpolation, the blend and the border mode.  Returns (interpolation, (dw, dh), border mode as an int)."""
+    if not 1 <= n_cams <= _lib.STITCH_MAX_CAMERAS:
+        raise ValueError("%s takes 1..%d cameras, got %d" % (who, _lib.STITCH_MAX_CAMERAS, n_cams))
+    if len(warp_maps) != n_cams:
+        raise ValueError("got %d warp maps for %d cameras" % (len(warp_maps), n_cams))
+    if blend not in _BLENDS:
+        raise ValueError("unsupported blend %r (%s: \"over\", \"feather\")" % (blend, who))
+    if blend == "feather" and not 1 <= int(feather) <= 4096:
+        raise ValueError("feather must lie in 1..4096, got %r" % (feather,))
+    if border_mode not in (BORDER_CONSTANT, BORDER_TRANSPARENT):
+        raise ValueError("unsupported border mode %r (%s: BORDER_CONSTANT, BORDER_TRANSPARENT)" % (border_mode, who))
+    for k, m in enumerate(warp_maps):
+        if not isinstance(m, WarpMap):
+            raise ValueError("%s needs a WarpMap per camera (build_warp_map, or WarpMap(xy, frac, interp, dsize)); camera %d has %s" % (who, k, type(m).__name__))
+        if m.dsize != warp_maps[0].dsize or m.interp != warp_maps[0].interp:
+            raise ValueError("the map of camera %d has dsize %s and interpolation %d; camera 0's has dsize %s and interpolation %d (%s: one canvas, one interpolation)"
+                             % (k, m.dsize, m.interp, warp_maps[0].dsize, warp_maps[0].interp, who))
+    return warp_maps[0].interp, warp_maps[0].dsize, int(border_mode)
+
+
+def _stitch_maps_dst(out, ndim, B, dh, dw, C):
+    """remap's rules for a caller's `out` against the maps' dsize; ndim: the rank of the result of a single camera."""
+    if isinstance(out, torch.Tensor) and out.dim() == ndim and ndim >= 2:
+        hw = tuple(out.shape[-2:]) if ndim == 2 else tuple(out.shape[-3:-1])
+        if hw != (dh, dw):
+            raise ValueError("the maps' dsize is %s, out is %s" % ((dw, dh), tuple(out.shape)))
+    if isinstance(out, torch.Tensor) and out.numel() != B * dh * dw * C:
+        raise ValueError("the maps' dsize is %s (%d frames of %d channels): out has %d elements" % ((dw, dh), B, C, out.numel()))
+
+
+def _fill_map_camera(cam, warp_map):
+    xy_p, fr_p, cam.xy_frame_stride, cam.xy_row_stride, cam.frac_frame_stride, cam.frac_row_stride = warp_map._planes()
+    cam.map_xy, cam.map_frac, cam.map_count, cam.reserved = xy_p, fr_p, warp_map.n, 0
+
+
+def remap_stitch(srcs, warp_maps, blend="over", feather=64, border_value=None, out=None, border_mode=BORDER_CONSTANT):
+    """The FIXED cameras of one site sampled through their warp maps into ONE canvas in one launch (include/bevwarp.h,
+    bevwarp_stitch_maps): warp_stitch's cover test and blends over remap's map entries.  What a canvas fill plus one
+    remap(..., border_mode=BORDER_TRANSPARENT, out=canvas) per camera is for, without a pass over the canvas per camera, with a blend
+    where cameras overlap, with the lens in the maps, and with no coordinate computed and no float64 touched.
+
+    srcs       a sequence of 1..8 CUDA tensors as warp_stitch takes them: one dtype (uint8 / float32), one C, one B and one device; sizes
+               and strides may differ from camera to camera.
+    warp_maps  as many WarpMaps (build_warp_map: pinhole or lens) on the frames' device, all of one dsize and interpolation, each with
+               n == 1 (shared by the batch) or n == B.  Two cameras may share one map.  A camera covers a canvas pixel where its map
+               entry is an inlier of its frame; a lens map's pixels beyond r2_max cover nothing.
+    blend, feather, border_mode, border_value, out   as warp_stitch.
+    With pinhole maps the result is warp_stitch's for the same matrices, by bits; "over" is what the successive remap calls leave.
+    Returns a tensor shaped like srcs[0] with (height, width) replaced by the maps', or `out`.  Asynchronous on the current stream."""
+    srcs, warp_maps = list(srcs), list(warp_maps)
+    interp, (dw, dh), border_mode = _stitch_maps_call("remap_stitch", len(srcs), warp_maps, blend, feather, border_mode)
+    for k, src in enumerate(srcs):
+        if not isinstance(src, torch.Tensor) or src.dtype not in _DTYPES or src.dim() not in (2, 3, 4):
+            raise ValueError("remap_stitch needs uint8 or float32 tensors (B, H, W, C), (H, W, C) or (H, W); camera %d is %s" % (k, getattr(src, "dtype", type(src))))
+    kinds = [(src.dtype, 1 if src.dim() == 2 else src.shape[-1], src.shape[0] if src.dim() == 4 else 1, src.device) for src in srcs]
+    for k, kind in enumerate(kinds):  # (before anything asks for a device)
+        if kind != kinds[0]:
+            raise ValueError("camera %d has dtype %s, %d channels, batch %d on %s; camera 0 has dtype %s, %d channels, batch %d on %s "
+                             "(remap_stitch: one dtype, channel count, batch and device)" % ((k,) + kind + kinds[0]))
+    _, C, B, device = kinds[0]
+    for m in warp_maps:
+        _map_fits(m, B, device)
+    _stitch_maps_dst(out, srcs[0].dim(), B, dh, dw, C)
+    frames = [_frames("remap_stitch", src, _DTYPES)[0] for src in srcs]  # (a copy made here lives until the launch is enqueued)
+    s0 = frames[0]
+    esz = s0.element_size()
+    cams = (_lib.MapCamera * len(frames))()
+    for cam, s4, m in zip(cams, frames, warp_maps):
+        cam.src, cam.uv, cam.frame_stride, cam.row_stride = s4.data_ptr(), None, s4.stride(0) * esz, s4.stride(1) * esz
+        cam.src_h, cam.src_w = s4.shape[1], s4.shape[2]
+        _fill_map_camera(cam, m)
+    d4 = _pixel_dst(out, s0.dtype, s0.device, B, dh, dw, C, zeroed=border_mode == BORDER_TRANSPARENT)
+    bv = _border(border_value, C) if border_mode == BORDER_CONSTANT else None
+    _lib.launch("bevwarp_stitch_maps", s0.device, ctypes.addressof(cams), len(frames), d4.data_ptr(), B, dh, dw, C, d4.stride(0) * esz, d4.stride(1) * esz,
+                _DTYPES[s0.dtype], interp, _BLENDS[blend], int(feather) if blend == "feather" else 0, border_mode, _ptr(bv))  # ("over" ignores feather)
+    return _like_src(d4, srcs[0].dim(), out)
+
+
+def remap_stitch_nv12(ys, uvs, warp_maps, blend="over", feather=64, border_value=None, out=None, border_mode=BORDER_CONSTANT, rgb=False):
+    """remap_stitch of the decoders' NV12 frames, converted on the way: bit for bit
+
+        remap_stitch([cvtColor(nv12_k, COLOR_YUV2BGR_NV12) ...], warp_maps, blend, feather, border_value, ...)   (rgb=True: COLOR_YUV2RGB_NV12)
+
+    in one launch, without the converted frames (include/bevwarp.h, bevwarp_stitch_maps_nv12); every tap is converted before the blend.
+
+    ys, uvs    sequences of 1..8 planes each, per camera as remap_nv12 takes them: (H_k, W_k) / (B, H_k, W_k) and (H_k / 2, W_k / 2, 2) /
+               (B, H_k / 2, W_k / 2, 2) uint8 CUDA tensors, even sides; split_nv12's views and row-padded planes are taken as they are.
+               One B and one device.
+    warp_maps, blend, feather, border_mode, out   as remap_stitch.
+    border_value   (BORDER_CONSTANT only) a scalar or 3 values in the RESULT's channel order, not converted; None = 0.
+    Returns (B, h, w, 3), or (h, w, 3) for single frames, or `out`.  Asynchronous on the current stream."""
+    ys, uvs, warp_maps = list(ys), list(uvs), list(warp_maps)
+    interp, (dw, dh), border_mode = _stitch_maps_call("remap_stitch_nv12", len(ys), warp_maps, blend, feather, border_mode)
+    if len(uvs) != len(ys):
+        raise ValueError("got %d uv planes for %d cameras" % (len(uvs), len(ys)))
+    planes = [_nv12_planes("remap_stitch_nv12", y, uv) for y, uv in zip(ys, uvs)]
+    B, device = planes[0][0].shape[0], planes[0][0].device
+    for k, (y, (y3, _)) in enumerate(zip(ys, planes)):
+        if y3.shape[0] != B or y3.device != device or y.dim() != ys[0].dim():
+            raise ValueError("camera %d has %d frames (y of rank %d) on %s; camera 0 has %d (rank %d) on %s (remap_stitch_nv12: one batch and device)"
+                             % (k, y3.shape[0], y.dim(), y3.device, B, ys[0].dim(), device))
+    for m in warp_maps:
+        _map_fits(m, B, device)
+    _stitch_maps_dst(out, ys[0].dim() + 1, B, dh, dw, 3)
+    cams = (_lib.MapCamera * len(planes))()
+    for cam, (y3, uv4), m in zip(cams, planes, warp_maps):
+        cam.src, cam.uv, cam.frame_stride, cam.row_stride = y3.data_ptr(), uv4.data_ptr(), y3.stride(0), y3.stride(1)
+        cam.uv_frame_stride, cam.uv_row_stride = uv4.stride(0), uv4.stride(1)
+        cam.src_h, cam.src_w = y3.shape[1], y3.shape[2]
+        _fill_map_camera(cam, m)
+    d4 = _pixel_dst(out, torch.uint8, device, B, dh, dw, 3, zeroed=border_mode == BORDER_TRANSPARENT)
+    bv = _border(border_value, 3) if border_mode == BORDER_CONSTANT else None
+    _lib.launch("bevwarp_stitch_maps_nv12", device, ctypes.addressof(cams), len(planes), d4.data_ptr(), B, dh, dw, d4.stride(0), d4.stride(1), interp,
+                _BLENDS[blend], int(feather) if blend == "feather" else 0, 1 if rgb else 0, border_mode, _ptr(bv))
+    return _like_src(d4, ys[0].dim() + 1, out)
+
+
 def _plane_format(who, flags, out_dtype, out):
     """The interpolation of a call that writes channel planes, once its flags, plane type and `out` are what the plane kernels take."""
     interp = _interp(who, flags)  # (no bicubic kernel writes planes)

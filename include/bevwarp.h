@@ -23,6 +23,11 @@
  *                             preset_calib("KoPER", 1 | 4) describes two cameras of one intersection in one world frame
  *                             (bev/constructor/homo_constr.py:19-25), BrnoCompSpeed sessions have a left, a centre and a right camera
  *                             (vis_homo.py:39-43).  All cameras in one launch, last-wins or blended where they overlap
+ *   bevwarp_stitch_maps, bevwarp_stitch_maps_nv12
+ *                           the same site with FIXED, possibly distorted cameras (Calib.dist_coeff, bev/calib.py:25), from BGR frames or
+ *                             from the decoders' NV12 frames: one cv2.remap(img_k, map1_k, map2_k, ..., BORDER_TRANSPARENT) per camera
+ *                             into ONE BEV image, through the maps bevwarp_build_map made once per camera -- all cameras in one launch,
+ *                             last-wins or blended, no float64
  *   bevwarp_warp_classes, bevwarp_tile_classes_bytes
  *                           the same call inside a camera loop (one H_bev_img, every frame of the video): vis_homo.py:85-91
  *   bevwarp_invert_homography  the cv::invert(M) step inside that call (M is the forward src->dst map)
@@ -349,6 +354,62 @@ typedef struct bevwarp_camera {   /* HOST; 48 bytes */
 int bevwarp_warp_stitch(const bevwarp_camera *cams /*HOST*/, int n_cams, void *dst, int batch, int dst_h, int dst_w, int channels,
                         int64_t dst_frame_stride, int64_t dst_row_stride, int dtype, int interp, int blend, int feather,
                         int border_mode, const double *border_value /*HOST*/, void *stream);
+
+/*
+ * Several FIXED cameras sampled through their warp maps into one canvas in one launch: bevwarp_warp_stitch's cover test and blend rules
+ * over bevwarp_remap's (bevwarp_remap_nv12's) map entries.  Each camera brings frames, sizes, strides and maps (THE MAP FORMAT above,
+ * from bevwarp_build_map: pinhole or lens) of its own; no coordinate is computed and no float64 is touched.  It replaces a canvas fill
+ * plus one bevwarp_remap(..., BEVWARP_BORDER_TRANSPARENT) per camera -- one pass over the canvas per camera, and no blend -- and gives
+ * a site whose cameras are distorted the one-launch route that bevwarp_warp_stitch (pinhole only) cannot.  Defined to the bit.
+ * For frame b, canvas pixel (x, y) and camera k:
+ *   entry    (sx, sy, fx, fy) is the entry of camera k's map for frame (map_count == 1 ? 0 : b), read as bevwarp_remap reads it
+ *            (fx = v & 31, fy = (v >> 5) & 31, higher bits ignored).
+ *   cover    camera k COVERS the pixel iff the entry passes BEVWARP_BORDER_TRANSPARENT's inlier test for `interp` against camera k's own
+ *            src_w, src_h (nearest: 0 <= sx < src_w, 0 <= sy < src_h; bilinear: 0 <= sx < src_w - 1, 0 <= sy < src_h - 1).  The
+ *            invalid-pixel entry (-32768, -32768) never covers: a lens map's pixels beyond r2_max are not that camera's.
+ *   value    p_k is what bevwarp_remap(..., BEVWARP_BORDER_TRANSPARENT) writes for that entry: the nearest copy, or the bilinear blend
+ *            (8-bit: 15-bit fixed point; float32: the float blend).  bevwarp_stitch_maps_nv12: what bevwarp_remap_nv12(..., rgb_order,
+ *            BEVWARP_BORDER_TRANSPARENT) writes -- every tap converted before the blend, 3 channels of 8 bits.
+ *   blend    BEVWARP_STITCH_OVER and BEVWARP_STITCH_FEATHER are word for word bevwarp_warp_stitch's rules, with
+ *            d_k = min(sx + 1, src_w - sx, sy + 1, src_h - sy) of the map entry and w_k = min(d_k, F): the single-cover rule, the integer
+ *            mean for 8-bit pixels, the float32 sum in ascending k with one correctly rounded division.  Pixels no camera covers are
+ *            border_value under BEVWARP_BORDER_CONSTANT (NV12: in the destination's channel order, not converted) and are neither read
+ *            nor written under BEVWARP_BORDER_TRANSPARENT.
+ * Hence (i) with pinhole maps from bevwarp_build_map the result is bevwarp_warp_stitch's for the same matrices, by bits; (ii) OVER is
+ * what n_cams successive bevwarp_remap (bevwarp_remap_nv12) calls with BEVWARP_BORDER_TRANSPARENT leave on the canvas; (iii) the NV12
+ * entry equals bevwarp_stitch_maps on the converted frames.
+ *   cams     HOST, n_cams (1..BEVWARP_STITCH_MAX_CAMERAS) descriptions in list order; the array is read during the call only.  All
+ *            pointers in it are device pointers; strides in bytes.  Two cameras may share one map, and what the cameras read may overlap.
+ *   dst      device, `batch` canvases of dst_h x dst_w pixels; it must not overlap any image the call reads (frames, uv, xy or frac of
+ *            any camera).
+ *   bevwarp_stitch_maps       dtype BEVWARP_U8 | BEVWARP_F32, channels 1..4, interp BEVWARP_NEAREST | BEVWARP_LINEAR (the interpolation
+ *                             every map was built for), blend one of the two, border_mode BEVWARP_BORDER_CONSTANT |
+ *                             BEVWARP_BORDER_TRANSPARENT.
+ *   bevwarp_stitch_maps_nv12  the same without dtype and channels (8 bits, 3 channels); even source sides; rgb_order 0 (B, G, R) | 1.
+ *   Everything else is BEVWARP_ERR_UNSUPPORTED.
+ * Status, in this order: BEVWARP_ERR_BAD_ARG for cams NULL, n_cams outside 1..8, or feather outside 1..4096 under BEVWARP_STITCH_FEATHER;
+ * then per camera in ascending k bevwarp_remap's (bevwarp_remap_nv12's) checks in that entry's own order against dst (blend and
+ * border_mode count as part of the format), the first status that is not BEVWARP_OK being returned; then BEVWARP_ERR_TOO_LARGE for a
+ * destination side > 2^20; then BEVWARP_ERR_NOT_FINITE for border_value (BEVWARP_BORDER_CONSTANT only).  batch == 0 is BEVWARP_OK and
+ * launches nothing.
+ */
+typedef struct bevwarp_map_camera {      /* HOST; 112 bytes */
+    const void *src;                     /* interleaved frames; for the NV12 entry the Y plane */
+    const void *uv;                      /* NV12 entry: the plane of (U, V) pairs; otherwise NULL, not looked at */
+    int64_t frame_stride, row_stride;    /* of src / Y, bytes */
+    int64_t uv_frame_stride, uv_row_stride;
+    const void *map_xy, *map_frac;       /* THE MAP FORMAT; map_frac may be NULL for BEVWARP_NEAREST */
+    int64_t xy_frame_stride, xy_row_stride, frac_frame_stride, frac_row_stride;
+    int src_h, src_w;
+    int map_count;                       /* 1 (shared by the batch) or batch */
+    int reserved;                        /* 0 */
+} bevwarp_map_camera;
+int bevwarp_stitch_maps(const bevwarp_map_camera *cams /*HOST*/, int n_cams, void *dst, int batch, int dst_h, int dst_w, int channels,
+                        int64_t dst_frame_stride, int64_t dst_row_stride, int dtype, int interp, int blend, int feather,
+                        int border_mode, const double *border_value /*HOST*/, void *stream);
+int bevwarp_stitch_maps_nv12(const bevwarp_map_camera *cams /*HOST*/, int n_cams, void *dst, int batch, int dst_h, int dst_w,
+                             int64_t dst_frame_stride, int64_t dst_row_stride, int interp, int blend, int feather, int rgb_order,
+                             int border_mode, const double *border_value /*HOST*/, void *stream);
 
 /*
  * bevwarp_warp with the per-tile verdicts of an earlier launch (ABI v7).  Which way a tile is processed -- inside the frame, outside,
