@@ -16,10 +16,12 @@
 #include "warp_lens.h"
 #include "warp_map.h"
 #include "warp_map_nv12.h"
+#include "warp_map_nv12_out.h"
 #include "warp_nv12.h"
 #include "warp_nv12_out.h"
 #include "warp_stitch.h"
 #include "warp_stitch_maps.h"
+#include "warp_stitch_maps_nv12_out.h"
 
 #pragma clang fp contract(off)
 
@@ -552,6 +554,87 @@ int bevwarp_warp_nv12_to_nv12(const void* y, const void* uv, void* dst_y, void* 
     return warp_nv12_out_impl(plan::nv12_to_nv12_call({y, y_frame_stride, y_row_stride}, {uv, uv_frame_stride, uv_row_stride}, {dst_y, dst_y_frame_stride, dst_y_row_stride},
                                                       {dst_uv, dst_uv_frame_stride, dst_uv_row_stride}, {batch, src_h, src_w, dst_h, dst_w, m_count, M_inv}, interp),
                               interp, 0, border_value, stream);
+}
+
+}  // extern "C"
+
+namespace {
+// bevwarp_remap_to_nv12 and bevwarp_remap_nv12_to_nv12 (the call reads two planes of frames): the checks, plan_remap's grid, the border pixel,
+// one launch
+int remap_nv12_out_impl(const Call& c, int interp, int border_mode, int rgb_order, const double* border_value, void* stream) {
+    const bool nv12_src = c.even_src;
+    RemapNv12OutArgs a;
+    int64_t items;
+    const int st = remap_grid_args(c, a, nv12_src ? 2 : 1, interp, border_mode, items);
+    if (!items) return st;
+    uint8_t bu[4];  // (in the sampled pixel's channel order: a pixel value, converted by the kernel like any other; read by the constant border only)
+    if (border_bytes(border_mode == BEVWARP_BORDER_CONSTANT ? border_value : nullptr, bu) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
+    const Image& duv = c.writes[1].im;
+    a.dst_uv = (uint8_t*)duv.base, a.duv_fs = duv.fs, a.duv_rs = duv.rs;
+    a.dst_vec_ok = plan::wide_stores_ok(c.writes[0], 4);  // per plane: a lane's 4 Y bytes, and its two pairs, go out as one dword each
+    a.uv_vec_ok = plan::wide_stores_ok(c.writes[1], 4);
+    if (nv12_src)
+        fill_nv12_source(a, c);
+    else
+        a.src = (const uint8_t*)c.reads[0].im.base, a.src_fs = c.reads[0].im.fs, a.src_rs = c.reads[0].im.rs;
+    a.bv_u8 = packed3(bu);
+    return launched(launch_remap_nv12_out(a, nv12_src, interp, border_mode, rgb_order, items, (hipStream_t)stream));
+}
+// bevwarp_stitch_maps_to_nv12 and bevwarp_stitch_maps_nv12_to_nv12
+int stitch_maps_nv12_out_impl(bool nv12_src, const bevwarp_map_camera* cams, int n_cams, const Frames& dy, const Frames& duv, int batch, int dst_h, int dst_w, int interp,
+                              int blend, int feather, int rgb_order, const double* border_value, void* stream) {
+    TilePlan p;
+    const int st = plan::stitch_maps_nv12_out_status(nv12_src, cams, n_cams, dy, duv, batch, dst_h, dst_w, interp, blend, feather, rgb_order, border_value, kBorderTileW,
+                                                     kBorderTileH, p);
+    if (st != BEVWARP_OK || batch == 0) return st;
+    StitchMapsNv12OutArgs a;  // (the border value is a pixel in the sampled pixel's channel order: the kernel converts it like any other)
+    stitch_maps_args(a, p, cams, n_cams, dy, batch, dst_h, dst_w, 3, BEVWARP_U8, interp, feather, BEVWARP_BORDER_CONSTANT, border_value, nv12_src ? 2 : 1,
+                     [&](const bevwarp_map_camera& k) { return plan::stitch_maps_nv12_out_call(nv12_src, k, dy, duv, batch, dst_h, dst_w, interp, blend, rgb_order); });
+    const Nv12Images d = plan::nv12_images(dy, duv, dst_h, dst_w, batch);
+    a.dst_uv = (uint8_t*)d.uv.base, a.duv_fs = d.uv.fs, a.duv_rs = d.uv.rs;
+    a.dst_vec_ok = plan::wide_stores_ok(d.y, 4);  // per plane, as bevwarp_warp_to_nv12
+    a.uv_vec_ok = plan::wide_stores_ok(d.uv, 4);
+    return launched(launch_stitch_maps_nv12_out(a, nv12_src, interp, blend, rgb_order, p.total_tiles, (hipStream_t)stream));
+}
+}  // namespace
+
+extern "C" {
+
+int bevwarp_remap_to_nv12(const void* src, void* dst_y, void* dst_uv, int batch, int src_h, int src_w, int dst_h, int dst_w, int64_t src_frame_stride,
+                          int64_t src_row_stride, int64_t y_frame_stride, int64_t y_row_stride, int64_t uv_frame_stride, int64_t uv_row_stride, const void* map_xy,
+                          const void* map_frac, int map_count, int64_t xy_frame_stride, int64_t xy_row_stride, int64_t frac_frame_stride, int64_t frac_row_stride,
+                          int interp, int border_mode, int rgb_order, const double* border_value, void* stream) {
+    return remap_nv12_out_impl(plan::remap_to_nv12_call({src, src_frame_stride, src_row_stride}, {dst_y, y_frame_stride, y_row_stride},
+                                                        {dst_uv, uv_frame_stride, uv_row_stride}, {map_xy, xy_frame_stride, xy_row_stride},
+                                                        {map_frac, frac_frame_stride, frac_row_stride}, {batch, src_h, src_w, dst_h, dst_w, 0, nullptr}, map_count, interp,
+                                                        rgb_order, border_mode),
+                               interp, border_mode, rgb_order, border_value, stream);
+}
+
+int bevwarp_remap_nv12_to_nv12(const void* y, const void* uv, void* dst_y, void* dst_uv, int batch, int src_h, int src_w, int dst_h, int dst_w, int64_t y_frame_stride,
+                               int64_t y_row_stride, int64_t uv_frame_stride, int64_t uv_row_stride, int64_t dst_y_frame_stride, int64_t dst_y_row_stride,
+                               int64_t dst_uv_frame_stride, int64_t dst_uv_row_stride, const void* map_xy, const void* map_frac, int map_count, int64_t xy_frame_stride,
+                               int64_t xy_row_stride, int64_t frac_frame_stride, int64_t frac_row_stride, int interp, int border_mode, const double* border_value,
+                               void* stream) {
+    return remap_nv12_out_impl(plan::remap_nv12_to_nv12_call({y, y_frame_stride, y_row_stride}, {uv, uv_frame_stride, uv_row_stride},
+                                                             {dst_y, dst_y_frame_stride, dst_y_row_stride}, {dst_uv, dst_uv_frame_stride, dst_uv_row_stride},
+                                                             {map_xy, xy_frame_stride, xy_row_stride}, {map_frac, frac_frame_stride, frac_row_stride},
+                                                             {batch, src_h, src_w, dst_h, dst_w, 0, nullptr}, map_count, interp, border_mode),
+                               interp, border_mode, 0, border_value, stream);
+}
+
+int bevwarp_stitch_maps_to_nv12(const bevwarp_map_camera* cams, int n_cams, void* dst_y, void* dst_uv, int batch, int dst_h, int dst_w, int64_t y_frame_stride,
+                                int64_t y_row_stride, int64_t uv_frame_stride, int64_t uv_row_stride, int interp, int blend, int feather, int rgb_order,
+                                const double* border_value, void* stream) {
+    return stitch_maps_nv12_out_impl(false, cams, n_cams, {dst_y, y_frame_stride, y_row_stride}, {dst_uv, uv_frame_stride, uv_row_stride}, batch, dst_h, dst_w, interp,
+                                     blend, feather, rgb_order, border_value, stream);
+}
+
+int bevwarp_stitch_maps_nv12_to_nv12(const bevwarp_map_camera* cams, int n_cams, void* dst_y, void* dst_uv, int batch, int dst_h, int dst_w, int64_t y_frame_stride,
+                                     int64_t y_row_stride, int64_t uv_frame_stride, int64_t uv_row_stride, int interp, int blend, int feather,
+                                     const double* border_value, void* stream) {
+    return stitch_maps_nv12_out_impl(true, cams, n_cams, {dst_y, y_frame_stride, y_row_stride}, {dst_uv, uv_frame_stride, uv_row_stride}, batch, dst_h, dst_w, interp,
+                                     blend, feather, 0, border_value, stream);
 }
 
 int bevwarp_warp_classes(const void* src, void* dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int channels, int64_t src_frame_stride,

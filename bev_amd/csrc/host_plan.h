@@ -1,5 +1,5 @@
 // host_plan.h -- what the C ABI decides before a launch, as plain C++17 (no HIP): the argument checks and the launch geometry.
-// bevwarp_api.hip is its only user in the library; tests/host_plan_driver.cpp (and lens_plan_driver.cpp, stitch_plan_driver.cpp, remap_plan_driver.cpp, remap_nv12_plan_driver.cpp, stitch_maps_plan_driver.cpp) compile it
+// bevwarp_api.hip is its only user in the library; tests/host_plan_driver.cpp (and lens_plan_driver.cpp, stitch_plan_driver.cpp, remap_plan_driver.cpp, remap_nv12_plan_driver.cpp, stitch_maps_plan_driver.cpp, remap_nv12_out_plan_driver.cpp) compile it
 // with g++ under the address and undefined-behaviour sanitizers, and tests/golden/launch_plans.json pins every field of the plans.  Not installed.
 #pragma once
 #include <math.h>
@@ -342,6 +342,25 @@ inline Call nv12_to_nv12_call(Frames y, Frames uv, Frames dst_y, Frames dst_uv, 
     c.write_nv12(dst_y, dst_uv);
     return c;
 }
+// bevwarp_remap_to_nv12: bevwarp_remap's order of checks (the format before the layouts) over 8-bit frames of 3 channels, with
+// bevwarp_warp_to_nv12's destination where the interleaved one stood, the five borders that write every pixel, and the two map planes;
+// reads[1], reads[2]: the xy and the frac plane
+inline Call remap_to_nv12_call(Frames src, Frames dst_y, Frames dst_uv, Frames xy, Frames frac, const Sizes& z, int map_count, int interp, int rgb_order, int border_mode) {
+    Call c = nv12_family_call(map_sizes(z, xy, map_count), interp, rgb_order, border_mode >= BEVWARP_BORDER_CONSTANT && border_mode < BEVWARP_BORDER_TRANSPARENT);
+    c.format_first = true;
+    c.read(src.image(z.src_h, (uint64_t)z.src_w * 3, z.batch), z.src_w, 1);
+    c.write_nv12(dst_y, dst_uv);
+    read_map_planes(c, xy, frac, interp);
+    return c;
+}
+// bevwarp_remap_nv12_to_nv12: bevwarp_remap_nv12's order of checks (the layouts before the format) likewise (the source is sampled as
+// B, G, R); reads[2], reads[3]: the xy and the frac plane
+inline Call remap_nv12_to_nv12_call(Frames y, Frames uv, Frames dst_y, Frames dst_uv, Frames xy, Frames frac, const Sizes& z, int map_count, int interp, int border_mode) {
+    Call c = nv12_to_nv12_call(y, uv, dst_y, dst_uv, map_sizes(z, xy, map_count), interp);
+    c.format_ok = c.format_ok && border_mode >= BEVWARP_BORDER_CONSTANT && border_mode < BEVWARP_BORDER_TRANSPARENT;
+    read_map_planes(c, xy, frac, interp);
+    return c;
+}
 
 // ---- launch geometry ---------------------------------------------------------------------------------------------------------
 struct TilePlan {
@@ -551,6 +570,37 @@ inline int stitch_maps_status(const bevwarp_map_camera* cams, int n_cams, Frames
 inline int stitch_maps_nv12_status(const bevwarp_map_camera* cams, int n_cams, Frames dst, int batch, int dst_h, int dst_w, int interp, int blend, int feather,
                                    int rgb_order, int border_mode, const double* border_value, int tw, int th, TilePlan& p) {
     return stitch_maps_any_status(true, cams, n_cams, dst, batch, dst_h, dst_w, 3, BEVWARP_U8, interp, blend, feather, rgb_order, border_mode, border_value, tw, th, p);
+}
+
+// ---- bevwarp_stitch_maps_to_nv12, bevwarp_stitch_maps_nv12_to_nv12: the same for the stitches that write NV12 --------------------------------
+// One camera of either: bevwarp_remap_to_nv12's (bevwarp_remap_nv12_to_nv12's) call under BEVWARP_BORDER_CONSTANT -- there is no border mode:
+// what no camera covers is the border pixel -- its format narrowed to the two blend rules.
+inline Call stitch_maps_nv12_out_call(bool nv12, const bevwarp_map_camera& k, Frames dst_y, Frames dst_uv, int batch, int dst_h, int dst_w, int interp, int blend,
+                                      int rgb_order) {
+    const Frames src = {k.src, k.frame_stride, k.row_stride}, uv = {k.uv, k.uv_frame_stride, k.uv_row_stride};
+    const Frames xy = {k.map_xy, k.xy_frame_stride, k.xy_row_stride}, frac = {k.map_frac, k.frac_frame_stride, k.frac_row_stride};
+    const Sizes z = {batch, k.src_h, k.src_w, dst_h, dst_w, 0, nullptr};
+    Call c = nv12 ? remap_nv12_to_nv12_call(src, uv, dst_y, dst_uv, xy, frac, z, k.map_count, interp, BEVWARP_BORDER_CONSTANT)
+                  : remap_to_nv12_call(src, dst_y, dst_uv, xy, frac, z, k.map_count, interp, rgb_order, BEVWARP_BORDER_CONSTANT);
+    c.format_ok = c.format_ok && stitch_format_ok(blend, BEVWARP_BORDER_CONSTANT);
+    return c;
+}
+// stitch_maps_any_status' rules and order.  nv12: the cameras' frames are NV12 (rgb_order is not looked at).
+inline int stitch_maps_nv12_out_status(bool nv12, const bevwarp_map_camera* cams, int n_cams, Frames dst_y, Frames dst_uv, int batch, int dst_h, int dst_w, int interp,
+                                       int blend, int feather, int rgb_order, const double* border_value, int tw, int th, TilePlan& p) {
+    p = {};
+    if (!cams || n_cams < 1 || n_cams > BEVWARP_STITCH_MAX_CAMERAS) return BEVWARP_ERR_BAD_ARG;
+    if (blend == BEVWARP_STITCH_FEATHER && (feather < 1 || feather > 4096)) return BEVWARP_ERR_BAD_ARG;
+    for (int k = 0; k < n_cams; k++) {  // every camera against both planes of the canvas; what the cameras read may overlap
+        const int st = check_call(stitch_maps_nv12_out_call(nv12, cams[k], dst_y, dst_uv, batch, dst_h, dst_w, interp, blend, nv12 ? 0 : rgb_order));
+        if (st != BEVWARP_OK) return st;
+    }
+    p = plan_border(batch, dst_h, dst_w, tw, th);
+    if (p.status != BEVWARP_OK) return p.status;
+    if (border_value)
+        for (int c = 0; c < 3; c++)
+            if (!isfinite(border_value[c])) return BEVWARP_ERR_NOT_FINITE;
+    return BEVWARP_OK;
 }
 
 }  // namespace plan

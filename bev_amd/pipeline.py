@@ -19,6 +19,9 @@ pairs -- which halves the upload, and the warp converts each tap to BGR (bev_amd
 `dst_format="nv12"`: the output slots are what a video encoder takes -- (dh * 3 / 2, dw) bytes, the BEV frame's Y plane followed by its rows of
 (U, V) pairs -- which halves the download and removes the writer's colour conversion; the warp converts each pixel as it stores it
 (bev_amd.warp.warp_perspective_to_nv12, warp_nv12_to_nv12; bevwarp_warp_to_nv12, bevwarp_warp_nv12_to_nv12).
+
+`warp_map=`: a fixed camera's coordinates, lens included, computed once (bev_amd.warp.build_warp_map); every frame is then sampled through
+the map, from and into either slot format (bev_amd.warp.remap, remap_nv12, remap_to_nv12, remap_nv12_to_nv12).
 """
 import collections
 import ctypes
@@ -76,15 +79,16 @@ class FramePipeline:
         format, with download on or off and with zero_copy_out; channels must be 3, dtype uint8, dsize even, flags INTER_NEAREST or
         INTER_LINEAR, and planar output is not available (ValueError).  The input frames are taken as B, G, R.
         warp_map    a bev_amd.warp.WarpMap of one frame (build_warp_map: a fixed camera's coordinates, lens included, computed once) on
-        `device`: every slot's prepared launch is then bevwarp_remap through it (BORDER_CONSTANT, border 0), `M` may be None and `flags`
-        is not looked at (the map carries its interpolation).  Interleaved frames in and out only: with planar, src_format="nv12" or
-        dst_format="nv12" it raises ValueError.  None (default): every path above, unchanged."""
+        `device`: every slot's prepared launch then samples through it (BORDER_CONSTANT, border 0), `M` may be None and `flags` is not
+        looked at (the map carries its interpolation).  The launch follows the slots' formats: bevwarp_remap (bgr in, bgr out),
+        bevwarp_remap_nv12 (nv12 in, bgr out), bevwarp_remap_to_nv12 (bgr in, nv12 out) or bevwarp_remap_nv12_to_nv12 (nv12 in and out);
+        NV12 slots keep their rules above.  With planar it raises ValueError.  None (default): every path above, unchanged."""
         if warp_map is not None:
             if not isinstance(warp_map, _warp.WarpMap) or warp_map.n != 1:
                 raise ValueError("warp_map must be a bev_amd.warp.WarpMap of one frame, got %s" % (
                     "%d frames" % warp_map.n if isinstance(warp_map, _warp.WarpMap) else type(warp_map).__name__,))
-            if planar or src_format != "bgr" or dst_format != "bgr":
-                raise ValueError("warp_map takes interleaved frames in and out only: planar, src_format=\"nv12\" and dst_format=\"nv12\" are not available with it")
+            if planar:
+                raise ValueError("warp_map writes interleaved or NV12 frames only: planar=True is not available with it")
             if warp_map.dsize != (int(dsize[0]), int(dsize[1])):
                 raise ValueError("warp_map was built for dsize %s, the pipeline's is %s" % (warp_map.dsize, (int(dsize[0]), int(dsize[1]))))
             if warp_map.device.type != torch.device(device).type:
@@ -100,7 +104,7 @@ class FramePipeline:
                 raise ValueError("src_format=\"nv12\" needs channels=3 and dtype=torch.uint8")
             if int(src_hw[0]) % 2 or int(src_hw[1]) % 2 or int(src_hw[0]) <= 0 or int(src_hw[1]) <= 0:
                 raise ValueError("src_format=\"nv12\" needs even frame sides, got %s" % (tuple(src_hw),))
-            if (int(flags) & 7) not in (_warp.INTER_NEAREST, _warp.INTER_LINEAR):
+            if warp_map is None and (int(flags) & 7) not in (_warp.INTER_NEAREST, _warp.INTER_LINEAR):
                 raise ValueError("src_format=\"nv12\": INTER_NEAREST or INTER_LINEAR")
         if dst_format not in ("bgr", "nv12"):
             raise ValueError("unsupported dst_format %r (\"bgr\", \"nv12\")" % (dst_format,))
@@ -112,7 +116,7 @@ class FramePipeline:
                 raise ValueError("dst_format=\"nv12\" needs channels=3 and dtype=torch.uint8")
             if int(dsize[0]) % 2 or int(dsize[1]) % 2 or int(dsize[0]) <= 0 or int(dsize[1]) <= 0:
                 raise ValueError("dst_format=\"nv12\" needs an even dsize, got %s" % (tuple(dsize),))
-            if (int(flags) & 7) not in (_warp.INTER_NEAREST, _warp.INTER_LINEAR):
+            if warp_map is None and (int(flags) & 7) not in (_warp.INTER_NEAREST, _warp.INTER_LINEAR):
                 raise ValueError("dst_format=\"nv12\": INTER_NEAREST or INTER_LINEAR")
         if planar and plane_dtype not in _warp._PLANE_DTYPES:
             raise ValueError("unsupported plane_dtype %s (torch.float32, torch.float16, torch.bfloat16)" % (plane_dtype,))
@@ -157,7 +161,18 @@ class FramePipeline:
         self._launch = []
         for slot in range(depth):
             s, d = self.d_in[slot], (self.h_out[slot] if self.zero_copy_out else self.d_out[slot])  # (pinned host memory is device-addressable)
-            if warp_map is not None:
+            if warp_map is not None and (self.nv12 or self.nv12_out):  # (one buffer per NV12 side: the (U, V) rows follow the Y rows)
+                src = (s.data_ptr(), s.data_ptr() + self.H * self.W) if self.nv12 else (s.data_ptr(),)
+                dst = (d.data_ptr(), d.data_ptr() + self.dh * self.dw) if self.nv12_out else (d.data_ptr(),)
+                src_strides = (0, self.W, 0, self.W) if self.nv12 else (s.numel(), s.stride(0))
+                dst_strides = (0, self.dw, 0, self.dw) if self.nv12_out else (d.numel(), d.stride(0))
+                maps = warp_map._planes()[:2] + (1,) + warp_map._planes()[2:] + (warp_map.interp, _warp.BORDER_CONSTANT)
+                args = src + dst + (1, self.H, self.W, self.dh, self.dw) + src_strides + dst_strides + maps
+                if self.nv12 and self.nv12_out:
+                    self._launch.append((lib.bevwarp_remap_nv12_to_nv12, args + (None, self.s_run)))
+                else:  # (rgb_order 0: the frames on the interleaved side are B, G, R)
+                    self._launch.append((lib.bevwarp_remap_nv12 if self.nv12 else lib.bevwarp_remap_to_nv12, args + (0, None, self.s_run)))
+            elif warp_map is not None:
                 args = (s.data_ptr(), d.data_ptr(), 1, self.H, self.W, self.dh, self.dw, self.C, s.numel() * esz, s.stride(0) * esz, d.numel() * esz,
                         d.stride(0) * esz) + warp_map._planes()[:2] + (1,) + warp_map._planes()[2:] + (_warp._DTYPES[s.dtype], warp_map.interp,
                                                                                                      _warp.BORDER_CONSTANT, None, self.s_run)
@@ -226,8 +241,11 @@ class FramePipeline:
     def _launch_py(self, slot, stream):
         """The same launch through bev_amd.warp (argument validation; used once per slot at construction)."""
         with torch.cuda.stream(stream):
-            if self.warp_map is not None:
-                _warp.remap(self.d_in[slot], self.warp_map, out=self.d_out[slot])
+            if self.warp_map is not None and self.nv12:
+                y, uv = _warp.split_nv12(self.d_in[slot])
+                (_warp.remap_nv12_to_nv12 if self.nv12_out else _warp.remap_nv12)(y, uv, self.warp_map, out=self.d_out[slot])
+            elif self.warp_map is not None:
+                (_warp.remap_to_nv12 if self.nv12_out else _warp.remap)(self.d_in[slot], self.warp_map, out=self.d_out[slot])
             elif self.nv12_out and self.nv12:
                 y, uv = _warp.split_nv12(self.d_in[slot])
                 _warp.warp_nv12_to_nv12(y, uv, None, (self.dw, self.dh), flags=self.flags, out=self.d_out[slot], M_inv_device=self.minv)

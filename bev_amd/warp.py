@@ -1004,7 +1004,8 @@ def remap_nv12(y, uv, warp_map, border_mode=BORDER_CONSTANT, border_value=None, 
     border_value  (BORDER_CONSTANT only) a scalar or 3 values in the RESULT's channel order, not converted; None = 0.
     out      as remap: BORDER_TRANSPARENT without `out` starts from zeros.
     Returns (B, h, w, 3), or (h, w, 3) for a single frame, or `out`.  Asynchronous on the current stream.  FramePipeline(warp_map=...,
-    src_format="nv12") keeps refusing: a streaming caller calls this function with `out=` on a stream of its own."""
+    src_format="nv12") prepares this launch for every slot; a caller with a loop of its own calls this function with `out=` on a
+    stream of its own."""
     border_mode = _map_call("remap_nv12", warp_map, border_mode)
     y3, uv4 = _nv12_planes("remap_nv12", y, uv)
     B, H, W = y3.shape
@@ -1038,7 +1039,7 @@ def remap_nv12_to_planar(y, uv, warp_map, scale=1.0 / 255.0, bias=0.0, border_mo
     out_dtype, out   as warp_nv12_to_planar: torch.float32 (default), torch.float16 or torch.bfloat16; a given `out` has this dtype and
                      contiguous rows, and is returned as it is.
     Returns (B, 3, h, w), or (3, h, w) for a single frame.  Asynchronous on the current stream.  FramePipeline(warp_map=...,
-    src_format="nv12") keeps refusing: a streaming caller calls this function with `out=` on a stream of its own."""
+    planar=True) keeps refusing: a streaming caller calls this function with `out=` on a stream of its own."""
     border_mode = _map_call("remap_nv12_to_planar", warp_map, border_mode)
     if border_mode == BORDER_TRANSPARENT:
         raise ValueError("remap_nv12_to_planar: BORDER_TRANSPARENT writes no planes (remap_nv12 into a canvas, then warp_to_planar)")
@@ -1143,6 +1144,155 @@ def warp_nv12_to_nv12(y, uv, M, dsize, flags=INTER_LINEAR, border_value=None, ou
     _lib.launch("bevwarp_warp_nv12_to_nv12", y3.device, y3.data_ptr(), uv4.data_ptr(), dy3.data_ptr(), duv4.data_ptr(), B, H, W, dh, dw, y3.stride(0),
                 y3.stride(1), uv4.stride(0), uv4.stride(1), dy3.stride(0), dy3.stride(1), duv4.stride(0), duv4.stride(1), M_inv_device.data_ptr(), n_m,
                 interp, _ptr(_border(border_value, 3)))
+    return ret
+
+
+def _map_nv12_out_call(who, warp_map, border_mode):
+    """What the map samplers into NV12 check before they look at a tensor: _map_call's, a border mode that writes every pixel, and a
+    map whose dsize is an NV12 frame's.  Returns the border mode as an int."""
+    border_mode = _map_call(who, warp_map, border_mode)
+    if border_mode == BORDER_TRANSPARENT:
+        raise ValueError("%s: BORDER_TRANSPARENT writes no NV12 frame (a canvas is kept as 8-bit pixels: remap into it, then warp_perspective_to_nv12)" % who)
+    if warp_map.dsize[0] % 2 or warp_map.dsize[1] % 2:
+        raise ValueError("%s: an NV12 frame has even sides, the map's dsize is %s" % (who, warp_map.dsize))
+    return border_mode
+
+
+def _bgr_frames(who, src):
+    """8-bit frames of 3 channels as the entries into NV12 take them: _frames' 4-D view."""
+    if not isinstance(src, torch.Tensor) or not src.is_cuda or src.dtype != torch.uint8:
+        raise ValueError("%s needs a uint8 CUDA (HIP) tensor; src is %s" % (who, getattr(src, "dtype", type(src))))
+    return _frames(who, src, None, channels=3)[0]
+
+
+def remap_to_nv12(src, warp_map, border_mode=BORDER_CONSTANT, border_value=None, out=None, rgb=False):
+    """remap of 8-bit BGR frames, written as the NV12 frame a video encoder takes: bit for bit
+
+        BGR->NV12(remap(src, warp_map, border_mode, border_value))               (rgb=True: the frames are R, G, B)
+
+    in one pass, without the BEV frame in BGR (include/bevwarp.h, bevwarp_remap_to_nv12; the conversion is warp_perspective_to_nv12's).
+    The per-frame half of a fixed camera's loop whose BEV goes to an encoder: the map carries the lens (build_warp_map).
+
+    src      (B, H, W, 3) or (H, W, 3) uint8 CUDA tensor, channels-last, rows contiguous.
+    warp_map a WarpMap on src's device with n == 1 (shared by all frames) or n == B and an even dsize; its interpolation is the call's.
+    border_mode   BORDER_CONSTANT, _REPLICATE, _REFLECT, _WRAP or _REFLECT_101; BORDER_TRANSPARENT is refused (NV12 holds no canvas).
+    border_value  (BORDER_CONSTANT only) a scalar or 3 values in the SOURCE's channel order: a pixel, converted like any other.
+    out      as warp_perspective_to_nv12: a joined (dh * 3 / 2, dw) / (B, dh * 3 / 2, dw) buffer or a (y, uv) pair, strides passed through.
+    Returns `out` if given, otherwise a new joined buffer.  Asynchronous on the current stream."""
+    border_mode = _map_nv12_out_call("remap_to_nv12", warp_map, border_mode)
+    s4 = _bgr_frames("remap_to_nv12", src)
+    B, H, W, _ = s4.shape
+    dw, dh = warp_map.dsize
+    _map_fits(warp_map, B, s4.device)
+    y3, uv4, ret = _nv12_dst("remap_to_nv12", out, s4.device, B, dh, dw, src.dim() == 3)
+    bv = _border(border_value, 3) if border_mode == BORDER_CONSTANT else None
+    xy_p, fr_p, xy_fs, xy_rs, fr_fs, fr_rs = warp_map._planes()
+    _lib.launch("bevwarp_remap_to_nv12", s4.device, s4.data_ptr(), y3.data_ptr(), uv4.data_ptr(), B, H, W, dh, dw, s4.stride(0), s4.stride(1), y3.stride(0),
+                y3.stride(1), uv4.stride(0), uv4.stride(1), xy_p, fr_p, warp_map.n, xy_fs, xy_rs, fr_fs, fr_rs, warp_map.interp, border_mode, 1 if rgb else 0,
+                _ptr(bv))
+    return ret
+
+
+def remap_nv12_to_nv12(y, uv, warp_map, border_mode=BORDER_CONSTANT, border_value=None, out=None):
+    """A video decoder's NV12 frames sampled through a fixed camera's map straight to the NV12 frames a video encoder takes, in one
+    launch: bit for bit
+
+        BGR->NV12(remap_nv12(y, uv, warp_map, border_mode, border_value))
+
+    with no BGR frame in memory on either side (include/bevwarp.h, bevwarp_remap_nv12_to_nv12).  Every tap is converted to BGR, blended
+    there, and the blended pixel converted back.
+
+    y, uv, warp_map   as remap_nv12; the map's dsize is even.
+    border_mode, out  as remap_to_nv12.  border_value: a scalar or 3 values in B, G, R order, a pixel, converted like any other.
+    Returns `out` if given, otherwise a new joined buffer.  Asynchronous on the current stream."""
+    border_mode = _map_nv12_out_call("remap_nv12_to_nv12", warp_map, border_mode)
+    y3, uv4 = _nv12_planes("remap_nv12_to_nv12", y, uv)
+    B, H, W = y3.shape
+    dw, dh = warp_map.dsize
+    _map_fits(warp_map, B, y3.device)
+    dy3, duv4, ret = _nv12_dst("remap_nv12_to_nv12", out, y3.device, B, dh, dw, y.dim() == 2)
+    bv = _border(border_value, 3) if border_mode == BORDER_CONSTANT else None
+    xy_p, fr_p, xy_fs, xy_rs, fr_fs, fr_rs = warp_map._planes()
+    _lib.launch("bevwarp_remap_nv12_to_nv12", y3.device, y3.data_ptr(), uv4.data_ptr(), dy3.data_ptr(), duv4.data_ptr(), B, H, W, dh, dw, y3.stride(0), y3.stride(1),
+                uv4.stride(0), uv4.stride(1), dy3.stride(0), dy3.stride(1), duv4.stride(0), duv4.stride(1), xy_p, fr_p, warp_map.n, xy_fs, xy_rs, fr_fs, fr_rs,
+                warp_map.interp, border_mode, _ptr(bv))
+    return ret
+
+
+def _stitch_maps_nv12_out_call(who, n_cams, warp_maps, blend, feather):
+    """_stitch_maps_call for the stitches into NV12 (no border mode: what no camera covers is the border pixel) with an even canvas.
+    Returns (interpolation, (dw, dh))."""
+    interp, (dw, dh), _ = _stitch_maps_call(who, n_cams, warp_maps, blend, feather, BORDER_CONSTANT)
+    if dw % 2 or dh % 2:
+        raise ValueError("%s: an NV12 frame has even sides, the maps' dsize is %s" % (who, (dw, dh)))
+    return interp, (dw, dh)
+
+
+def remap_stitch_to_nv12(srcs, warp_maps, blend="over", feather=64, border_value=None, out=None, rgb=False):
+    """remap_stitch of 8-bit BGR cameras, written as the NV12 frame a video encoder takes: bit for bit
+
+        BGR->NV12(remap_stitch(srcs, warp_maps, blend, feather, border_value))               (rgb=True: the frames are R, G, B)
+
+    in one launch, without the canvas in BGR (include/bevwarp.h, bevwarp_stitch_maps_to_nv12).
+
+    srcs       a sequence of 1..8 uint8 CUDA tensors, each (B, H_k, W_k, 3) or (H_k, W_k, 3): one B and one device.
+    warp_maps, blend, feather   as remap_stitch; the maps' dsize is even.
+    border_value   a scalar or 3 values in the SOURCES' channel order: the pixel that no camera covers, converted like any other.
+    out        as warp_perspective_to_nv12: a joined buffer or a (y, uv) pair.
+    Returns `out` if given, otherwise a new joined buffer.  Asynchronous on the current stream."""
+    srcs, warp_maps = list(srcs), list(warp_maps)
+    interp, (dw, dh) = _stitch_maps_nv12_out_call("remap_stitch_to_nv12", len(srcs), warp_maps, blend, feather)
+    frames = [_bgr_frames("remap_stitch_to_nv12", src) for src in srcs]  # (a copy made here lives until the launch is enqueued)
+    B, device = frames[0].shape[0], frames[0].device
+    for k, (src, s4) in enumerate(zip(srcs, frames)):
+        if s4.shape[0] != B or s4.device != device or src.dim() != srcs[0].dim():
+            raise ValueError("camera %d has %d frames (rank %d) on %s; camera 0 has %d (rank %d) on %s (remap_stitch_to_nv12: one batch and device)"
+                             % (k, s4.shape[0], src.dim(), s4.device, B, srcs[0].dim(), device))
+    for m in warp_maps:
+        _map_fits(m, B, device)
+    y3, uv4, ret = _nv12_dst("remap_stitch_to_nv12", out, device, B, dh, dw, srcs[0].dim() == 3)
+    cams = (_lib.MapCamera * len(frames))()
+    for cam, s4, m in zip(cams, frames, warp_maps):
+        cam.src, cam.uv, cam.frame_stride, cam.row_stride = s4.data_ptr(), None, s4.stride(0), s4.stride(1)
+        cam.src_h, cam.src_w = s4.shape[1], s4.shape[2]
+        _fill_map_camera(cam, m)
+    _lib.launch("bevwarp_stitch_maps_to_nv12", device, ctypes.addressof(cams), len(frames), y3.data_ptr(), uv4.data_ptr(), B, dh, dw, y3.stride(0), y3.stride(1),
+                uv4.stride(0), uv4.stride(1), interp, _BLENDS[blend], int(feather) if blend == "feather" else 0, 1 if rgb else 0, _ptr(_border(border_value, 3)))
+    return ret
+
+
+def remap_stitch_nv12_to_nv12(ys, uvs, warp_maps, blend="over", feather=64, border_value=None, out=None):
+    """remap_stitch_nv12 of the decoders' NV12 frames, written as the NV12 frame a video encoder takes: bit for bit
+
+        BGR->NV12(remap_stitch_nv12(ys, uvs, warp_maps, blend, feather, border_value))
+
+    in one launch, with no BGR frame in memory on either side (include/bevwarp.h, bevwarp_stitch_maps_nv12_to_nv12).
+
+    ys, uvs, warp_maps, blend, feather   as remap_stitch_nv12; the maps' dsize is even.
+    border_value   a scalar or 3 values in B, G, R order: the pixel that no camera covers, converted like any other.
+    out        as warp_perspective_to_nv12: a joined buffer or a (y, uv) pair.
+    Returns `out` if given, otherwise a new joined buffer.  Asynchronous on the current stream."""
+    ys, uvs, warp_maps = list(ys), list(uvs), list(warp_maps)
+    interp, (dw, dh) = _stitch_maps_nv12_out_call("remap_stitch_nv12_to_nv12", len(ys), warp_maps, blend, feather)
+    if len(uvs) != len(ys):
+        raise ValueError("got %d uv planes for %d cameras" % (len(uvs), len(ys)))
+    planes = [_nv12_planes("remap_stitch_nv12_to_nv12", y, uv) for y, uv in zip(ys, uvs)]
+    B, device = planes[0][0].shape[0], planes[0][0].device
+    for k, (y, (y3, _)) in enumerate(zip(ys, planes)):
+        if y3.shape[0] != B or y3.device != device or y.dim() != ys[0].dim():
+            raise ValueError("camera %d has %d frames (y of rank %d) on %s; camera 0 has %d (rank %d) on %s (remap_stitch_nv12_to_nv12: one batch and device)"
+                             % (k, y3.shape[0], y.dim(), y3.device, B, ys[0].dim(), device))
+    for m in warp_maps:
+        _map_fits(m, B, device)
+    dy3, duv4, ret = _nv12_dst("remap_stitch_nv12_to_nv12", out, device, B, dh, dw, ys[0].dim() == 2)
+    cams = (_lib.MapCamera * len(planes))()
+    for cam, (y3, uv4), m in zip(cams, planes, warp_maps):
+        cam.src, cam.uv, cam.frame_stride, cam.row_stride = y3.data_ptr(), uv4.data_ptr(), y3.stride(0), y3.stride(1)
+        cam.uv_frame_stride, cam.uv_row_stride = uv4.stride(0), uv4.stride(1)
+        cam.src_h, cam.src_w = y3.shape[1], y3.shape[2]
+        _fill_map_camera(cam, m)
+    _lib.launch("bevwarp_stitch_maps_nv12_to_nv12", device, ctypes.addressof(cams), len(planes), dy3.data_ptr(), duv4.data_ptr(), B, dh, dw, dy3.stride(0),
+                dy3.stride(1), duv4.stride(0), duv4.stride(1), interp, _BLENDS[blend], int(feather) if blend == "feather" else 0, _ptr(_border(border_value, 3)))
     return ret
 
 

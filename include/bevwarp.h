@@ -53,6 +53,11 @@
  *                             stores the BEV frame as NV12, what an encoder takes (the tracker tools read the encoded bev.avi)
  *   bevwarp_warp_nv12_to_nv12  the same egress from a decoder's NV12 frames, vis_homo.py:85-111 and bev/io/utils.py:89-99:
  *                             decoder -> BEV -> encoder in one launch, with no BGR frame in memory on either side
+ *   bevwarp_remap_to_nv12, bevwarp_remap_nv12_to_nv12, bevwarp_stitch_maps_to_nv12, bevwarp_stitch_maps_nv12_to_nv12
+ *                           the same two egresses for FIXED, possibly distorted cameras, vis_homo.py:85-111 and bev/io/utils.py:89-99 with
+ *                             Calib.dist_coeff (bev/calib.py:25): one camera or a site's cameras, BGR or decoder frames, sampled through
+ *                             the maps bevwarp_build_map made once and stored as the NV12 frame an encoder takes -- one launch, no
+ *                             float64, no BGR BEV frame in memory
  *   bevwarp_composite       composite_reg_img(bg, fg, fg_mask), bev/tool/compo.py:5-24 (the blend after the three warps
  *                             of composite_bev_img, :26-49)
  *   bevwarp_warp_composite  composite_bev_img(bg, fg, fg_mask, ...), bev/tool/compo.py:26-49: the three warps and the blend
@@ -654,6 +659,75 @@ int bevwarp_warp_nv12_to_nv12(const void *y, const void *uv, void *dst_y, void *
                               int64_t uv_row_stride, int64_t dst_y_frame_stride, int64_t dst_y_row_stride,
                               int64_t dst_uv_frame_stride, int64_t dst_uv_row_stride, const double *M_inv, int m_count,
                               int interp, const double *border_value /*HOST, 3 (B, G, R) or NULL*/, void *stream);
+
+/*
+ * The same egress through a fixed camera's warp maps: the map samplers (bevwarp_remap, bevwarp_remap_nv12, bevwarp_stitch_maps,
+ * bevwarp_stitch_maps_nv12) with bevwarp_warp_to_nv12's store stage behind them, one launch each, no BGR BEV frame in memory and no float64.
+ * It is the ending of the reference's loop -- warp, then `writer.write(bev)`, vis_homo.py:85-111 and bev/io/utils.py:89-99 -- for a site whose
+ * cameras are fixed and distorted (the map carries the lens: bevwarp_build_map).  Each entry is defined by composing existing entries, bit
+ * for bit:
+ *   bevwarp_remap_to_nv12            BGR->NV12( bevwarp_remap(src, ..., 3 channels, BEVWARP_U8, interp, border_mode, border_value) )
+ *   bevwarp_remap_nv12_to_nv12       BGR->NV12( bevwarp_remap_nv12(y, uv, ..., interp, border_mode, rgb_order = 0, border_value) )
+ *   bevwarp_stitch_maps_to_nv12      BGR->NV12( bevwarp_stitch_maps(cams, ..., 3 channels, BEVWARP_U8, interp, blend, feather,
+ *                                               BEVWARP_BORDER_CONSTANT, border_value) )
+ *   bevwarp_stitch_maps_nv12_to_nv12 BGR->NV12( bevwarp_stitch_maps_nv12(cams, ..., interp, blend, feather, rgb_order = 0,
+ *                                               BEVWARP_BORDER_CONSTANT, border_value) )
+ *   BGR->NV12       bevwarp_warp_to_nv12's conversion, word for word: the 20-bit BT.601 limited-range sums above, Y for every pixel, the
+ *                   (U, V) pair of pixel (x, y) for even x and even y only -- no averaging over the 2 x 2 block.
+ *   rgb_order       names the SOURCE pixels' channel order (0: B, G, R; 1: R, G, B), as in bevwarp_warp_to_nv12.  The NV12 sources are
+ *                   sampled as B, G, R; the intermediate order changes nothing else.
+ *   border_value    HOST, 3 doubles in that order, or NULL = 0: a pixel, converted with the pixel -- (0, 0, 0) gives (16, 128, 128).  Remap
+ *                   entries: the border pixel of bevwarp_remap's BEVWARP_BORDER_CONSTANT sampler (a tap outside the source is replaced
+ *                   before the blend; an invalid map entry (-32768, -32768) yields the border pixel itself), not looked at under the other
+ *                   modes.  Stitch entries: the pixel that no camera covers.
+ *   border_mode     remap entries: the five modes that write every pixel, as bevwarp_remap_nv12_planes has them;
+ *                   BEVWARP_BORDER_TRANSPARENT is BEVWARP_ERR_UNSUPPORTED (a canvas that is only partly updated is kept as 8-bit pixels).
+ *                   The stitch entries have none: uncovered pixels are always the border value.
+ *   dst_y, dst_uv   bevwarp_warp_to_nv12's destination with that entry's rules: even dst_h and dst_w, an even uv base and even uv strides,
+ *                   the joined single-buffer layout accepted, 4-byte stores per plane where that plane's base and strides are multiples of 4.
+ *                   Neither plane may overlap any image the call reads (frames, uv, xy or frac, of any camera), nor the other plane.
+ *   maps, sources   as the entry each one composes: map_count 1 or batch, map_frac NULL for BEVWARP_NEAREST only, even source sides for
+ *                   NV12 sources, bevwarp_map_camera as bevwarp_stitch_maps (bevwarp_stitch_maps_nv12) reads it.
+ * Status.  bevwarp_remap_to_nv12, in bevwarp_remap's order with bevwarp_warp_to_nv12's destination checks standing where the interleaved
+ * destination's stood: BEVWARP_ERR_BAD_ARG (a null pointer -- map_frac under BEVWARP_LINEAR included --, a non-positive size, odd dst_w or
+ * dst_h); BEVWARP_ERR_UNSUPPORTED (interp other than nearest / linear, rgb_order outside {0, 1}, border_mode outside the five);
+ * BEVWARP_ERR_BAD_ARG (map_count not 1 or batch; a row stride below a row for any of the five images, frames or maps that overlap their
+ * successors, an odd uv base or stride, a map_xy base or stride that is no multiple of 4 or a map_frac one that is no multiple of 2);
+ * BEVWARP_ERR_TOO_LARGE (the source limits of bevwarp_warp); BEVWARP_ERR_OVERLAP (either destination plane shares bytes with the source, by
+ * bevwarp_warp's rule, or with the bounding byte range of either map plane, or the two destination planes with each other; the
+ * single-buffer layout is adjacent, not overlapping); BEVWARP_ERR_TOO_LARGE again for a destination side > 2^20; BEVWARP_ERR_NOT_FINITE
+ * (border_value, BEVWARP_BORDER_CONSTANT only).
+ * bevwarp_remap_nv12_to_nv12, in bevwarp_remap_nv12's order likewise: BEVWARP_ERR_BAD_ARG (a null pointer, a non-positive size, an odd side
+ * of the source or the destination, the layouts of all six images as above -- an odd uv base or stride on either side --, map_count not 1
+ * or batch); BEVWARP_ERR_UNSUPPORTED (interp, border_mode outside the five); BEVWARP_ERR_TOO_LARGE (either source plane);
+ * BEVWARP_ERR_OVERLAP (either destination plane with either source plane, with either map plane, or with the other destination plane);
+ * BEVWARP_ERR_TOO_LARGE again; BEVWARP_ERR_NOT_FINITE (border_value, BEVWARP_BORDER_CONSTANT only).
+ * The stitch entries, in bevwarp_stitch_maps' order: BEVWARP_ERR_BAD_ARG for cams NULL, n_cams outside 1..8, or feather outside 1..4096 under
+ * BEVWARP_STITCH_FEATHER; then per camera in ascending k bevwarp_remap_to_nv12's (bevwarp_remap_nv12_to_nv12's) checks in that entry's own
+ * order against both destination planes (blend counts as part of the format), the first status that is not BEVWARP_OK being returned;
+ * then BEVWARP_ERR_TOO_LARGE for a destination side > 2^20; then BEVWARP_ERR_NOT_FINITE for border_value.
+ * batch == 0 is BEVWARP_OK and launches nothing, for all four.
+ */
+int bevwarp_remap_to_nv12(const void *src, void *dst_y, void *dst_uv, int batch, int src_h, int src_w, int dst_h, int dst_w,
+                          int64_t src_frame_stride, int64_t src_row_stride, int64_t y_frame_stride, int64_t y_row_stride,
+                          int64_t uv_frame_stride, int64_t uv_row_stride, const void *map_xy, const void *map_frac, int map_count,
+                          int64_t xy_frame_stride, int64_t xy_row_stride, int64_t frac_frame_stride, int64_t frac_row_stride,
+                          int interp, int border_mode, int rgb_order, const double *border_value /*HOST, 3 or NULL*/, void *stream);
+int bevwarp_remap_nv12_to_nv12(const void *y, const void *uv, void *dst_y, void *dst_uv, int batch, int src_h, int src_w,
+                               int dst_h, int dst_w, int64_t y_frame_stride, int64_t y_row_stride, int64_t uv_frame_stride,
+                               int64_t uv_row_stride, int64_t dst_y_frame_stride, int64_t dst_y_row_stride,
+                               int64_t dst_uv_frame_stride, int64_t dst_uv_row_stride, const void *map_xy, const void *map_frac,
+                               int map_count, int64_t xy_frame_stride, int64_t xy_row_stride, int64_t frac_frame_stride,
+                               int64_t frac_row_stride, int interp, int border_mode,
+                               const double *border_value /*HOST, 3 (B, G, R) or NULL*/, void *stream);
+int bevwarp_stitch_maps_to_nv12(const bevwarp_map_camera *cams /*HOST*/, int n_cams, void *dst_y, void *dst_uv, int batch, int dst_h,
+                                int dst_w, int64_t y_frame_stride, int64_t y_row_stride, int64_t uv_frame_stride,
+                                int64_t uv_row_stride, int interp, int blend, int feather, int rgb_order,
+                                const double *border_value /*HOST, 3 or NULL*/, void *stream);
+int bevwarp_stitch_maps_nv12_to_nv12(const bevwarp_map_camera *cams /*HOST*/, int n_cams, void *dst_y, void *dst_uv, int batch,
+                                     int dst_h, int dst_w, int64_t y_frame_stride, int64_t y_row_stride, int64_t uv_frame_stride,
+                                     int64_t uv_row_stride, int interp, int blend, int feather,
+                                     const double *border_value /*HOST, 3 (B, G, R) or NULL*/, void *stream);
 
 /*
  * out[i] = uint8(min(round_half_even(fg[i] * (mask[i] / 255) + bg[i] * (1 - mask[i] / 255)), 255)) for i in [0, n), computed in
