@@ -17,11 +17,13 @@
 #include "warp_map.h"
 #include "warp_map_nv12.h"
 #include "warp_map_nv12_out.h"
+#include "warp_map_planes.h"
 #include "warp_nv12.h"
 #include "warp_nv12_out.h"
 #include "warp_stitch.h"
 #include "warp_stitch_maps.h"
 #include "warp_stitch_maps_nv12_out.h"
+#include "warp_stitch_maps_planes.h"
 
 #pragma clang fp contract(off)
 
@@ -596,6 +598,26 @@ int stitch_maps_nv12_out_impl(bool nv12_src, const bevwarp_map_camera* cams, int
     a.uv_vec_ok = plan::wide_stores_ok(d.uv, 4);
     return launched(launch_stitch_maps_nv12_out(a, nv12_src, interp, blend, rgb_order, p.total_tiles, (hipStream_t)stream));
 }
+// bevwarp_stitch_maps_planes and bevwarp_stitch_maps_nv12_planes
+int stitch_maps_planes_impl(bool nv12_src, const bevwarp_map_camera* cams, int n_cams, const Frames& d, int64_t dst_plane_stride, int batch, int dst_h, int dst_w,
+                            int interp, int blend, int feather, int rgb_order, const double* border_value, const double* scale, const double* bias, int plane_dtype,
+                            void* stream) {
+    TilePlan p;
+    const int st = plan::stitch_maps_planes_status(nv12_src, cams, n_cams, d, dst_plane_stride, batch, dst_h, dst_w, interp, blend, feather, rgb_order, border_value,
+                                                   scale, bias, plane_dtype, kBorderTileW, kBorderTileH, p);
+    if (st != BEVWARP_OK || batch == 0) return st;
+    StitchMapsPlanesArgs a;  // (border value, scale and bias are in the planes' channel order: the kernel converts NV12 taps to that order)
+    auto make_call = [&](const bevwarp_map_camera& k) {
+        return plan::stitch_maps_planes_call(nv12_src, k, d, dst_plane_stride, batch, dst_h, dst_w, interp, blend, nv12_src ? rgb_order : 0, plane_dtype);
+    };
+    stitch_maps_args(a, p, cams, n_cams, d, batch, dst_h, dst_w, 3, BEVWARP_U8, interp, feather, BEVWARP_BORDER_CONSTANT, border_value, nv12_src ? 2 : 1, make_call);
+    const WrittenImage w = make_call(cams[0]).writes[0];
+    a.dst_vec_ok = plan::wide_stores_ok(w, plan::store_align(BEVWARP_U8, 3, true, w.elem));
+    a.plane = plane_dtype == BEVWARP_F32 ? kPlaneF32 : (plane_dtype == BEVWARP_F16 ? kPlaneF16 : kPlaneBF16);
+    uint8_t bu[4] = {(uint8_t)a.bv_u8, (uint8_t)(a.bv_u8 >> 8), (uint8_t)(a.bv_u8 >> 16), 0}, bs[3];
+    sampled_channel_table(a, 0, dst_plane_stride, scale, bias, bu, bs);  // (the identity; the status has found scale and bias finite)
+    return launched(launch_stitch_maps_planes(a, nv12_src, interp, blend, rgb_order, p.total_tiles, (hipStream_t)stream));
+}
 }  // namespace
 
 extern "C" {
@@ -635,6 +657,42 @@ int bevwarp_stitch_maps_nv12_to_nv12(const bevwarp_map_camera* cams, int n_cams,
                                      const double* border_value, void* stream) {
     return stitch_maps_nv12_out_impl(true, cams, n_cams, {dst_y, y_frame_stride, y_row_stride}, {dst_uv, uv_frame_stride, uv_row_stride}, batch, dst_h, dst_w, interp,
                                      blend, feather, 0, border_value, stream);
+}
+
+int bevwarp_remap_planes(const void* src, void* dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int64_t src_frame_stride, int64_t src_row_stride,
+                         int64_t dst_frame_stride, int64_t dst_plane_stride, int64_t dst_row_stride, const void* map_xy, const void* map_frac, int map_count,
+                         int64_t xy_frame_stride, int64_t xy_row_stride, int64_t frac_frame_stride, int64_t frac_row_stride, int interp, int border_mode,
+                         const double* border_value, const double* scale, const double* bias, int plane_dtype, void* stream) {
+    const Call c = plan::remap_planes_call({src, src_frame_stride, src_row_stride}, {dst, dst_frame_stride, dst_row_stride}, dst_plane_stride,
+                                           {map_xy, xy_frame_stride, xy_row_stride}, {map_frac, frac_frame_stride, frac_row_stride},
+                                           {batch, src_h, src_w, dst_h, dst_w, 0, nullptr}, map_count, interp, border_mode, plane_dtype);
+    RemapPlanesArgs a;
+    int64_t items;
+    const int st = remap_grid_args(c, a, 1, interp, border_mode, items);
+    if (!items) return st;
+    uint8_t bu[4];  // (the 8-bit border pixel in the frames' channel order; read by the constant border only)
+    if (border_bytes(border_mode == BEVWARP_BORDER_CONSTANT ? border_value : nullptr, bu) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
+    a.dst_vec_ok = plan::wide_stores_ok(c.writes[0], plan::store_align(BEVWARP_U8, 3, true, c.writes[0].elem));
+    a.plane = plane_dtype == BEVWARP_F32 ? kPlaneF32 : (plane_dtype == BEVWARP_F16 ? kPlaneF16 : kPlaneBF16);
+    uint8_t bs[3];  // (plane k is channel k: the table is the identity)
+    if (sampled_channel_table(a, 0, dst_plane_stride, scale, bias, bu, bs) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
+    a.src = (const uint8_t*)src, a.src_fs = src_frame_stride, a.src_rs = src_row_stride;
+    a.bv_u8 = packed3(bs);
+    return launched(launch_remap_planes(a, interp, border_mode, items, (hipStream_t)stream));
+}
+
+int bevwarp_stitch_maps_planes(const bevwarp_map_camera* cams, int n_cams, void* dst, int batch, int dst_h, int dst_w, int64_t dst_frame_stride,
+                               int64_t dst_plane_stride, int64_t dst_row_stride, int interp, int blend, int feather, const double* border_value,
+                               const double* scale, const double* bias, int plane_dtype, void* stream) {
+    return stitch_maps_planes_impl(false, cams, n_cams, {dst, dst_frame_stride, dst_row_stride}, dst_plane_stride, batch, dst_h, dst_w, interp, blend, feather, 0,
+                                   border_value, scale, bias, plane_dtype, stream);
+}
+
+int bevwarp_stitch_maps_nv12_planes(const bevwarp_map_camera* cams, int n_cams, void* dst, int batch, int dst_h, int dst_w, int64_t dst_frame_stride,
+                                    int64_t dst_plane_stride, int64_t dst_row_stride, int interp, int blend, int feather, int rgb_order,
+                                    const double* border_value, const double* scale, const double* bias, int plane_dtype, void* stream) {
+    return stitch_maps_planes_impl(true, cams, n_cams, {dst, dst_frame_stride, dst_row_stride}, dst_plane_stride, batch, dst_h, dst_w, interp, blend, feather,
+                                   rgb_order, border_value, scale, bias, plane_dtype, stream);
 }
 
 int bevwarp_warp_classes(const void* src, void* dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int channels, int64_t src_frame_stride,

@@ -1,5 +1,5 @@
 // host_plan.h -- what the C ABI decides before a launch, as plain C++17 (no HIP): the argument checks and the launch geometry.
-// bevwarp_api.hip is its only user in the library; tests/host_plan_driver.cpp (and lens_plan_driver.cpp, stitch_plan_driver.cpp, remap_plan_driver.cpp, remap_nv12_plan_driver.cpp, stitch_maps_plan_driver.cpp, remap_nv12_out_plan_driver.cpp) compile it
+// bevwarp_api.hip is its only user in the library; tests/host_plan_driver.cpp (and lens_plan_driver.cpp, stitch_plan_driver.cpp, remap_plan_driver.cpp, remap_nv12_plan_driver.cpp, stitch_maps_plan_driver.cpp, remap_nv12_out_plan_driver.cpp, map_planes_plan_driver.cpp) compile it
 // with g++ under the address and undefined-behaviour sanitizers, and tests/golden/launch_plans.json pins every field of the plans.  Not installed.
 #pragma once
 #include <math.h>
@@ -362,6 +362,21 @@ inline Call remap_nv12_to_nv12_call(Frames y, Frames uv, Frames dst_y, Frames ds
     return c;
 }
 
+// bevwarp_remap_planes: bevwarp_remap's order of checks (the format before the layouts) over 8-bit frames of 3 channels, with
+// bevwarp_warp_nv12_planes' destination where the interleaved one stood (three planes of `plane_dtype`, dst_ps apart; a plane type the
+// entry point does not take has 1-byte elements here and is part of the format), the five borders that write every pixel, and the two
+// map planes; reads[1], reads[2]: the xy and the frac plane
+inline Call remap_planes_call(Frames src, Frames dst, int64_t dst_ps, Frames xy, Frames frac, const Sizes& z, int map_count, int interp, int border_mode,
+                              int plane_dtype) {
+    const int elem = plane_dtype == BEVWARP_F32 ? 4 : ((plane_dtype == BEVWARP_F16 || plane_dtype == BEVWARP_BF16) ? 2 : 1);
+    Call c = nv12_family_call(map_sizes(z, xy, map_count), interp, 0, elem != 1 && border_mode >= BEVWARP_BORDER_CONSTANT && border_mode < BEVWARP_BORDER_TRANSPARENT);
+    c.format_first = true;
+    c.read(src.image(z.src_h, (uint64_t)z.src_w * 3, z.batch), z.src_w, 1);
+    c.write_planes(dst.image(z.dst_h, (uint64_t)z.dst_w * elem, z.batch), elem, 3, dst_ps);
+    read_map_planes(c, xy, frac, interp);
+    return c;
+}
+
 // ---- launch geometry ---------------------------------------------------------------------------------------------------------
 struct TilePlan {
     int status;                  // BEVWARP_OK or BEVWARP_ERR_TOO_LARGE (the other fields are then meaningless)
@@ -600,6 +615,41 @@ inline int stitch_maps_nv12_out_status(bool nv12, const bevwarp_map_camera* cams
     if (border_value)
         for (int c = 0; c < 3; c++)
             if (!isfinite(border_value[c])) return BEVWARP_ERR_NOT_FINITE;
+    return BEVWARP_OK;
+}
+
+// ---- bevwarp_stitch_maps_planes, bevwarp_stitch_maps_nv12_planes: the same for the stitches that write channel planes --------------------------
+// One camera of either: bevwarp_remap_planes' (bevwarp_remap_nv12_planes') call under BEVWARP_BORDER_CONSTANT -- there is no border mode:
+// what no camera covers is the border pixel -- its format narrowed to the two blend rules.
+inline Call stitch_maps_planes_call(bool nv12, const bevwarp_map_camera& k, Frames dst, int64_t dst_ps, int batch, int dst_h, int dst_w, int interp, int blend,
+                                    int rgb_order, int plane_dtype) {
+    const Frames src = {k.src, k.frame_stride, k.row_stride}, uv = {k.uv, k.uv_frame_stride, k.uv_row_stride};
+    const Frames xy = {k.map_xy, k.xy_frame_stride, k.xy_row_stride}, frac = {k.map_frac, k.frac_frame_stride, k.frac_row_stride};
+    const Sizes z = {batch, k.src_h, k.src_w, dst_h, dst_w, 0, nullptr};
+    Call c = nv12 ? remap_nv12_planes_call(src, uv, dst, dst_ps, xy, frac, z, k.map_count, interp, rgb_order, BEVWARP_BORDER_CONSTANT, plane_dtype)
+                  : remap_planes_call(src, dst, dst_ps, xy, frac, z, k.map_count, interp, BEVWARP_BORDER_CONSTANT, plane_dtype);
+    c.format_ok = c.format_ok && stitch_format_ok(blend, BEVWARP_BORDER_CONSTANT);
+    return c;
+}
+// stitch_maps_any_status' rules and order, with scale and bias (HOST, 3 doubles each or NULL) after border_value.  nv12: the cameras' frames
+// are NV12 (otherwise rgb_order is not looked at).
+inline int stitch_maps_planes_status(bool nv12, const bevwarp_map_camera* cams, int n_cams, Frames dst, int64_t dst_ps, int batch, int dst_h, int dst_w, int interp,
+                                     int blend, int feather, int rgb_order, const double* border_value, const double* scale, const double* bias, int plane_dtype,
+                                     int tw, int th, TilePlan& p) {
+    p = {};
+    if (!cams || n_cams < 1 || n_cams > BEVWARP_STITCH_MAX_CAMERAS) return BEVWARP_ERR_BAD_ARG;
+    if (blend == BEVWARP_STITCH_FEATHER && (feather < 1 || feather > 4096)) return BEVWARP_ERR_BAD_ARG;
+    for (int k = 0; k < n_cams; k++) {  // every camera against the planes of the canvas; what the cameras read may overlap
+        const int st = check_call(stitch_maps_planes_call(nv12, cams[k], dst, dst_ps, batch, dst_h, dst_w, interp, blend, nv12 ? rgb_order : 0, plane_dtype));
+        if (st != BEVWARP_OK) return st;
+    }
+    p = plan_border(batch, dst_h, dst_w, tw, th);
+    if (p.status != BEVWARP_OK) return p.status;
+    const double* const values[3] = {border_value, scale, bias};
+    for (const double* v : values)
+        if (v)
+            for (int c = 0; c < 3; c++)
+                if (!isfinite(v[c])) return BEVWARP_ERR_NOT_FINITE;
     return BEVWARP_OK;
 }
 

@@ -22,6 +22,9 @@ pairs -- which halves the upload, and the warp converts each tap to BGR (bev_amd
 
 `warp_map=`: a fixed camera's coordinates, lens included, computed once (bev_amd.warp.build_warp_map); every frame is then sampled through
 the map, from and into either slot format (bev_amd.warp.remap, remap_nv12, remap_to_nv12, remap_nv12_to_nv12).
+
+SitePipeline is the same ring for a SITE: N fixed cameras in, each through its own warp map, one stitched canvas out -- interleaved, NV12
+or normalised channel planes -- with one stitch launch per committed set of frames (bev_amd.warp.remap_stitch and its kin).
 """
 import collections
 import ctypes
@@ -315,5 +318,237 @@ class FramePipeline:
             if len(self.pending) >= self.depth - 1:
                 yield self.result()
             self.submit(f)
+        while self.pending:
+            yield self.result()
+
+
+class SitePipeline:
+    """FramePipeline's ingest / egress ring for a site of fixed cameras: every committed SET of frames -- one per camera -- is uploaded,
+    stitched through the cameras' warp maps into one canvas by ONE launch, and downloaded, on three private streams with `depth` slots
+    per stage.  Results are the resident call's (bev_amd.warp.remap_stitch*), bit for bit: the same kernel runs on the same bytes."""
+
+    def __init__(self, src_hws, warp_maps, dsize, blend="over", feather=64, border_value=None, depth=3, src_format="bgr", dst_format="bgr", scale=1.0 / 255.0,
+                 bias=0.0, plane_dtype=torch.float32, rgb=False, download=True, device="cuda"):
+        """src_hws     (H_k, W_k) of each camera's decoded frames, 1..8 cameras.
+        warp_maps   one bev_amd.warp.WarpMap of one frame per camera (build_warp_map: the camera's coordinates, lens included, computed
+                    once), all built for `dsize` (u_size, v_size), of one interpolation, on `device`.
+        blend, feather, border_value   as bev_amd.warp.remap_stitch: what no camera covers is the border pixel.
+        src_format  "bgr": the input slots are (H_k, W_k, 3) uint8 frames.  "nv12": (H_k * 3 / 2, W_k) uint8, the Y plane followed by the
+                    rows of (U, V) pairs, as a video decoder delivers them; every H_k and W_k is even.
+        dst_format  "bgr": the interleaved (dh, dw, 3) canvas.  "nv12": (dh * 3 / 2, dw) uint8 for a video encoder; dsize is even.
+                    "planes": (3, dh, dw) normalised channel planes of plane_dtype (torch.float32, torch.float16 or torch.bfloat16) with
+                    scale and bias as bev_amd.warp.remap_stitch_to_planar takes them.
+        rgb         NV12 frames into "bgr" or "planes": the result is R, G, B; "bgr" frames into "nv12": the frames are R, G, B.
+        download=False leaves the results on the device (valid until `depth` further sets have been committed).
+        The launch follows the formats: bevwarp_stitch_maps, bevwarp_stitch_maps_nv12, bevwarp_stitch_maps_to_nv12,
+        bevwarp_stitch_maps_nv12_to_nv12, bevwarp_stitch_maps_planes or bevwarp_stitch_maps_nv12_planes."""
+        src_hws, warp_maps = [(int(h), int(w)) for h, w in src_hws], list(warp_maps)
+        dw, dh = int(dsize[0]), int(dsize[1])
+        if len(src_hws) != len(warp_maps):
+            raise ValueError("got %d warp maps for %d cameras" % (len(warp_maps), len(src_hws)))
+        if not 1 <= len(src_hws) <= _lib.STITCH_MAX_CAMERAS:
+            raise ValueError("SitePipeline takes 1..%d cameras, got %d" % (_lib.STITCH_MAX_CAMERAS, len(src_hws)))
+        for k, m in enumerate(warp_maps):
+            if not isinstance(m, _warp.WarpMap) or m.n != 1:
+                raise ValueError("the warp map of camera %d must be a bev_amd.warp.WarpMap of one frame, got %s" % (
+                    k, "%d frames" % m.n if isinstance(m, _warp.WarpMap) else type(m).__name__))
+            if m.dsize != (dw, dh):
+                raise ValueError("the warp map of camera %d was built for dsize %s, the pipeline's is %s" % (k, m.dsize, (dw, dh)))
+            if m.device.type != torch.device(device).type:
+                raise ValueError("the warp map of camera %d is on %s, the pipeline runs on %s" % (k, m.device, device))
+            if m.interp != warp_maps[0].interp:
+                raise ValueError("the warp map of camera %d has interpolation %d, camera 0's has %d (one interpolation per site)" % (k, m.interp, warp_maps[0].interp))
+        if src_format not in ("bgr", "nv12"):
+            raise ValueError("unsupported src_format %r (\"bgr\", \"nv12\")" % (src_format,))
+        if dst_format not in ("bgr", "nv12", "planes"):
+            raise ValueError("unsupported dst_format %r (\"bgr\", \"nv12\", \"planes\")" % (dst_format,))
+        if dst_format == "planes" and plane_dtype not in _warp._PLANE_DTYPES:
+            raise ValueError("unsupported plane_dtype %s (torch.float32, torch.float16, torch.bfloat16)" % (plane_dtype,))
+        for k, (h, w) in enumerate(src_hws):
+            if src_format == "nv12" and (h % 2 or w % 2):
+                raise ValueError("src_format=\"nv12\" needs even frame sides, camera %d has %s" % (k, (h, w)))
+        if dst_format == "nv12" and (dw % 2 or dh % 2):
+            raise ValueError("dst_format=\"nv12\" needs an even dsize, got %s" % ((dw, dh),))
+        if depth < 2:
+            raise ValueError("depth must be >= 2 (one slot in flight per stage boundary)")
+        _warp._stitch_maps_call("SitePipeline", len(src_hws), warp_maps, blend, feather, _warp.BORDER_CONSTANT)  # (the blend and the feather width)
+        host = {}  # border_value, scale and bias as the prepared launches take them: 3 finite doubles each (border_value: or None)
+        for name, v in (("border_value", border_value), ("scale", scale), ("bias", bias)):
+            host[name] = None if v is None and name == "border_value" else np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (3,)))
+            if host[name] is not None and not np.isfinite(host[name]).all():
+                raise ValueError("%s must be finite, got %r" % (name, v))
+        self.device = torch.device(device)
+        self.src_hws, self.warp_maps, self.dw, self.dh, self.n_cams = src_hws, warp_maps, dw, dh, len(src_hws)
+        self.blend, self.feather, self.border_value, self.depth, self.download = blend, int(feather), border_value, depth, download
+        self.nv12, self.dst_format, self.scale, self.bias, self.plane_dtype, self.rgb = src_format == "nv12", dst_format, scale, bias, plane_dtype, bool(rgb)
+        in_shapes = [(h * 3 // 2, w) if self.nv12 else (h, w, 3) for h, w in src_hws]
+        out_shape = {"bgr": (dh, dw, 3), "nv12": (dh * 3 // 2, dw), "planes": (3, dh, dw)}[dst_format]
+        out_dtype = plane_dtype if dst_format == "planes" else torch.uint8
+        self.h_in = [[torch.empty(shape, dtype=torch.uint8, pin_memory=True) for shape in in_shapes] for _ in range(depth)]  # [slot][camera]
+        self.d_in = [[torch.empty(shape, dtype=torch.uint8, device=self.device) for shape in in_shapes] for _ in range(depth)]
+        self.d_out = [torch.empty(out_shape, dtype=out_dtype, device=self.device) for _ in range(depth)]
+        self.h_out = [torch.empty(out_shape, dtype=out_dtype, pin_memory=True) for _ in range(depth)] if download else None
+        self._streams = [torch.cuda.Stream(self.device) for _ in range(3)]  # (kept alive: their raw handles are used below)
+        self.s_up, self.s_run, self.s_down = (ctypes.c_void_p(st.cuda_stream) for st in self._streams)
+        hip = _hip_rt()
+        self.ev_up, self.ev_run, self.ev_down = [], [], []
+        self._closed = False  # (from here on close() has events to release, also when the rest of the construction raises)
+        for evs in (self.ev_up, self.ev_run, self.ev_down):
+            for _ in range(depth):
+                e = ctypes.c_void_p()
+                _ok(hip.hipEventCreateWithFlags(ctypes.byref(e), 2))  # hipEventDisableTiming
+                evs.append(e)
+        # one prepared launch per slot: the C ABI call with its arguments bound (validated once, here, through the Python layer)
+        for slot in range(depth):
+            self._launch_py(slot, torch.cuda.current_stream(self.device))
+        torch.cuda.synchronize(self.device)
+        lib = _lib.load()
+        bv, sc, bi = host["border_value"], host["scale"], host["bias"]
+        self._keep = [bv, sc, bi]  # (host arrays and camera tables the prepared launches point into)
+        ptr = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+        interp, blend_id, f = warp_maps[0].interp, _warp._BLENDS[blend], (int(feather) if blend == "feather" else 0)
+        self._launch = []
+        for slot in range(depth):
+            cams = (_lib.MapCamera * self.n_cams)()
+            for cam, s, (h, w), m in zip(cams, self.d_in[slot], src_hws, warp_maps):
+                if self.nv12:  # (one buffer: the (U, V) rows follow the Y rows)
+                    cam.src, cam.uv, cam.frame_stride, cam.row_stride, cam.uv_frame_stride, cam.uv_row_stride = s.data_ptr(), s.data_ptr() + h * w, 0, w, 0, w
+                else:
+                    cam.src, cam.uv, cam.frame_stride, cam.row_stride = s.data_ptr(), None, s.numel(), s.stride(0)
+                cam.src_h, cam.src_w = h, w
+                _warp._fill_map_camera(cam, m)
+            self._keep.append(cams)
+            d = self.d_out[slot]
+            head = (ctypes.addressof(cams), self.n_cams)
+            if dst_format == "nv12":  # (one buffer: the (U, V) rows follow the Y rows)
+                args = head + (d.data_ptr(), d.data_ptr() + dh * dw, 1, dh, dw, 0, dw, 0, dw, interp, blend_id, f)
+                if self.nv12:
+                    self._launch.append((lib.bevwarp_stitch_maps_nv12_to_nv12, args + (ptr(bv), self.s_run)))
+                else:
+                    self._launch.append((lib.bevwarp_stitch_maps_to_nv12, args + (1 if rgb else 0, ptr(bv), self.s_run)))
+            elif dst_format == "planes":
+                psz = d.element_size()
+                args = head + (d.data_ptr(), 1, dh, dw, d.numel() * psz, d.stride(0) * psz, d.stride(1) * psz, interp, blend_id, f)
+                tail = (ptr(bv), ptr(sc), ptr(bi), _warp._PLANE_DTYPES[plane_dtype], self.s_run)
+                if self.nv12:
+                    self._launch.append((lib.bevwarp_stitch_maps_nv12_planes, args + (1 if rgb else 0,) + tail))
+                else:
+                    self._launch.append((lib.bevwarp_stitch_maps_planes, args + tail))
+            elif self.nv12:
+                args = head + (d.data_ptr(), 1, dh, dw, d.numel(), d.stride(0), interp, blend_id, f, 1 if rgb else 0, _warp.BORDER_CONSTANT, ptr(bv), self.s_run)
+                self._launch.append((lib.bevwarp_stitch_maps_nv12, args))
+            else:
+                args = head + (d.data_ptr(), 1, dh, dw, 3, d.numel(), d.stride(0), _lib.U8, interp, blend_id, f, _warp.BORDER_CONSTANT, ptr(bv), self.s_run)
+                self._launch.append((lib.bevwarp_stitch_maps, args))
+        self._in_bytes = [t.numel() for t in self.h_in[0]]
+        self._out_bytes = self.d_out[0].numel() * self.d_out[0].element_size()
+        self.n_in = 0
+        self.pending = collections.deque()  # slots whose results have not been handed out yet
+
+    def close(self):
+        """Drain the three private streams, then release the events.  The device / pinned buffers were only ever handed to those
+        streams as raw addresses (torch does not know they are in use there), so they must not be freed before this."""
+        if getattr(self, "_closed", True):
+            return
+        self._closed = True
+        try:
+            for st in self._streams:
+                st.synchronize()
+            hip = _hip_rt()
+            for e in self.ev_up + self.ev_run + self.ev_down:
+                hip.hipEventDestroy(e)
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+    def _launch_py(self, slot, stream):
+        """The same launch through bev_amd.warp (argument validation; used once per slot at construction)."""
+        kw = dict(blend=self.blend, feather=self.feather, border_value=self.border_value, out=self.d_out[slot])
+        with torch.cuda.stream(stream):
+            if self.nv12:
+                ys, uvs = zip(*[_warp.split_nv12(t) for t in self.d_in[slot]])
+                if self.dst_format == "nv12":
+                    _warp.remap_stitch_nv12_to_nv12(ys, uvs, self.warp_maps, **kw)
+                elif self.dst_format == "planes":
+                    _warp.remap_stitch_nv12_to_planar(ys, uvs, self.warp_maps, scale=self.scale, bias=self.bias, rgb=self.rgb, out_dtype=self.plane_dtype, **kw)
+                else:
+                    _warp.remap_stitch_nv12(ys, uvs, self.warp_maps, rgb=self.rgb, **kw)
+            elif self.dst_format == "nv12":
+                _warp.remap_stitch_to_nv12(self.d_in[slot], self.warp_maps, rgb=self.rgb, **kw)
+            elif self.dst_format == "planes":
+                _warp.remap_stitch_to_planar(self.d_in[slot], self.warp_maps, scale=self.scale, bias=self.bias, out_dtype=self.plane_dtype, **kw)
+            else:
+                _warp.remap_stitch(self.d_in[slot], self.warp_maps, **kw)
+
+    # -- input side
+    def next_inputs(self):
+        """The pinned host buffers (numpy views, one per camera: (H_k, W_k, 3), or (H_k * 3 / 2, W_k) for NV12) the NEXT set of frames
+        should be decoded into; call commit() when they are filled.  Blocks only if that slot's previous set has not left the device yet."""
+        slot = self.n_in % self.depth
+        if self.n_in >= self.depth:
+            _ok(_hip_rt().hipEventSynchronize((self.ev_down if self.download else self.ev_run)[slot]))  # its previous occupant is through
+        return [t.numpy() for t in self.h_in[slot]]
+
+    def commit(self):
+        """Upload, stitch and (download=True) download the set in the next pinned slots.  Safe without a next_inputs() call before it: a
+        slot is reused only after its result has been taken (the check below), and result() has then waited for the slot's last launch
+        or copy -- the event next_inputs() waits for as well."""
+        if len(self.pending) >= self.depth:  # the slot about to be reused still holds a result nobody has taken
+            raise RuntimeError("SitePipeline: %d sets of frames are in flight and none has been taken with result(); a ring of depth %d "
+                               "holds at most %d undelivered results" % (len(self.pending), self.depth, self.depth))
+        hip = _hip_rt()
+        slot = self.n_in % self.depth
+        self.n_in += 1
+        for d, h, n in zip(self.d_in[slot], self.h_in[slot], self._in_bytes):
+            _ok(hip.hipMemcpyAsync(d.data_ptr(), h.data_ptr(), n, _H2D, self.s_up))
+        _ok(hip.hipEventRecord(self.ev_up[slot], self.s_up))
+        _ok(hip.hipStreamWaitEvent(self.s_run, self.ev_up[slot], 0))
+        fn, args = self._launch[slot]
+        _lib.check(fn(*args))
+        _ok(hip.hipEventRecord(self.ev_run[slot], self.s_run))
+        if self.download:
+            _ok(hip.hipStreamWaitEvent(self.s_down, self.ev_run[slot], 0))
+            _ok(hip.hipMemcpyAsync(self.h_out[slot].data_ptr(), self.d_out[slot].data_ptr(), self._out_bytes, _D2H, self.s_down))
+            _ok(hip.hipEventRecord(self.ev_down[slot], self.s_down))
+        self.pending.append(slot)
+
+    def submit(self, frames):
+        """One decoded frame per camera from pageable memory (numpy): copied into the next pinned slots, then committed."""
+        bufs = self.next_inputs()
+        if len(frames) != len(bufs):
+            raise ValueError("got %d frames for %d cameras" % (len(frames), len(bufs)))
+        for buf, frame in zip(bufs, frames):
+            np.copyto(buf, np.asarray(frame).reshape(buf.shape))
+        self.commit()
+
+    # -- output side
+    def ready(self):
+        return len(self.pending)
+
+    def result(self):
+        """The oldest set's canvas: a numpy view of a pinned slot (download=True; valid until `depth` further sets have been committed;
+        bfloat16 planes: the pinned tensor itself) or the device tensor.  Blocks until that set is through."""
+        slot = self.pending.popleft()
+        if self.download:
+            _ok(_hip_rt().hipEventSynchronize(self.ev_down[slot]))
+            h = self.h_out[slot]
+            return h if h.dtype == torch.bfloat16 else h.numpy()  # (numpy has no bfloat16)
+        _ok(_hip_rt().hipEventSynchronize(self.ev_run[slot]))
+        return self.d_out[slot]
+
+    def run(self, frame_sets):
+        """Generator over an iterable of N-tuples of decoded frames: yields their canvases in order, keeping depth - 1 sets in flight."""
+        for frames in frame_sets:
+            if len(self.pending) >= self.depth - 1:
+                yield self.result()
+            self.submit(frames)
         while self.pending:
             yield self.result()

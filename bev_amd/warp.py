@@ -1296,6 +1296,130 @@ def remap_stitch_nv12_to_nv12(ys, uvs, warp_maps, blend="over", feather=64, bord
     return ret
 
 
+def _planes_out_fits(out, ndim, dw, dh, what="map's"):
+    """remap_nv12_to_planar's rule for a caller's `out` of the result's rank `ndim`: its plane size is the map's."""
+    if isinstance(out, torch.Tensor) and out.dim() == ndim and tuple(out.shape[-2:]) != (dh, dw):
+        raise ValueError("the %s dsize is %s, out is %s" % (what, (dw, dh), tuple(out.shape)))
+
+
+def remap_to_planar(src, warp_map, scale=1.0 / 255.0, bias=0.0, border_mode=BORDER_CONSTANT, border_value=None, out=None, out_dtype=torch.float32):
+    """8-bit BGR frames sampled through a fixed camera's map straight into the normalised channel planes a detector takes, in one launch
+    (include/bevwarp.h, bevwarp_remap_planes): bit for bit
+
+        out[b, c] = convert(float32(remap(src, warp_map, border_mode, border_value)[b, :, :, c]) * scale[c] + bias[c])
+
+    (float32 mul, then add, then out_dtype) -- warp_nv12_to_planar's plane stage -- without the 8-bit BEV frame in between and without the
+    second launch of remap followed by an identity warp_to_planar.
+
+    src      (B, H, W, 3) or (H, W, 3) uint8 CUDA tensor, channels-last, rows contiguous.  Plane c is channel c: there is no channel swap.
+    warp_map a WarpMap on src's device with n == 1 (shared by all frames) or n == B; its interpolation is the call's.
+    border_mode   BORDER_CONSTANT, _REPLICATE, _REFLECT, _WRAP or _REFLECT_101; BORDER_TRANSPARENT is refused (planes hold no canvas).
+    scale, bias, border_value   scalars or 3 values in the frames' channel order; border_value (BORDER_CONSTANT only) is an 8-bit pixel
+                                that passes through the plane stage like any other.
+    out_dtype, out   as warp_nv12_to_planar: torch.float32 (default), torch.float16 or torch.bfloat16; a given `out` has this dtype and
+                     contiguous rows, and is returned as it is.
+    Returns (B, 3, h, w), or (3, h, w) for a single frame.  Asynchronous on the current stream."""
+    border_mode = _map_call("remap_to_planar", warp_map, border_mode)
+    if border_mode == BORDER_TRANSPARENT:
+        raise ValueError("remap_to_planar: BORDER_TRANSPARENT writes no planes (remap into a canvas, then warp_to_planar)")
+    _plane_format("remap_to_planar", warp_map.interp, out_dtype, out)
+    s4 = _bgr_frames("remap_to_planar", src)
+    B, H, W, _ = s4.shape
+    dw, dh = warp_map.dsize
+    _map_fits(warp_map, B, s4.device)
+    _planes_out_fits(out, src.dim(), dw, dh)
+    d4 = _plane_dst(out, out_dtype, s4.device, B, 3, dh, dw)
+    sc, bi = _per_channel(scale, 3), _per_channel(bias, 3)
+    bv = _border(border_value, 3) if border_mode == BORDER_CONSTANT else None
+    esz = d4.element_size()
+    xy_p, fr_p, xy_fs, xy_rs, fr_fs, fr_rs = warp_map._planes()
+    _lib.launch("bevwarp_remap_planes", s4.device, s4.data_ptr(), d4.data_ptr(), B, H, W, dh, dw, s4.stride(0), s4.stride(1), d4.stride(0) * esz, d4.stride(1) * esz,
+                d4.stride(2) * esz, xy_p, fr_p, warp_map.n, xy_fs, xy_rs, fr_fs, fr_rs, warp_map.interp, border_mode, _ptr(bv), _ptr(sc), _ptr(bi),
+                _PLANE_DTYPES[out_dtype])
+    return _like_src(d4, src.dim(), out)
+
+
+def remap_stitch_to_planar(srcs, warp_maps, scale=1.0 / 255.0, bias=0.0, blend="over", feather=64, border_value=None, out=None, out_dtype=torch.float32):
+    """remap_stitch of 8-bit BGR cameras, written as the normalised channel planes a detector takes: bit for bit
+
+        out[b, c] = convert(float32(remap_stitch(srcs, warp_maps, blend, feather, border_value)[b, :, :, c]) * scale[c] + bias[c])
+
+    in one launch, without the 8-bit canvas (include/bevwarp.h, bevwarp_stitch_maps_planes).
+
+    srcs       a sequence of 1..8 uint8 CUDA tensors, each (B, H_k, W_k, 3) or (H_k, W_k, 3): one B and one device.  Plane c is channel c.
+    warp_maps, blend, feather   as remap_stitch.
+    scale, bias, border_value   scalars or 3 values in the frames' channel order; border_value is the 8-bit pixel that no camera covers,
+                                put through the plane stage like any other.  "feather" is the 8-bit integer mean, then the plane stage.
+    out_dtype, out   as remap_to_planar.
+    Returns (B, 3, h, w), or (3, h, w) for single frames.  Asynchronous on the current stream."""
+    srcs, warp_maps = list(srcs), list(warp_maps)
+    interp, (dw, dh), _ = _stitch_maps_call("remap_stitch_to_planar", len(srcs), warp_maps, blend, feather, BORDER_CONSTANT)
+    _plane_format("remap_stitch_to_planar", interp, out_dtype, out)
+    frames = [_bgr_frames("remap_stitch_to_planar", src) for src in srcs]  # (a copy made here lives until the launch is enqueued)
+    B, device = frames[0].shape[0], frames[0].device
+    for k, (src, s4) in enumerate(zip(srcs, frames)):
+        if s4.shape[0] != B or s4.device != device or src.dim() != srcs[0].dim():
+            raise ValueError("camera %d has %d frames (rank %d) on %s; camera 0 has %d (rank %d) on %s (remap_stitch_to_planar: one batch and device)"
+                             % (k, s4.shape[0], src.dim(), s4.device, B, srcs[0].dim(), device))
+    for m in warp_maps:
+        _map_fits(m, B, device)
+    _planes_out_fits(out, srcs[0].dim(), dw, dh, "maps'")
+    d4 = _plane_dst(out, out_dtype, device, B, 3, dh, dw)
+    sc, bi = _per_channel(scale, 3), _per_channel(bias, 3)
+    esz = d4.element_size()
+    cams = (_lib.MapCamera * len(frames))()
+    for cam, s4, m in zip(cams, frames, warp_maps):
+        cam.src, cam.uv, cam.frame_stride, cam.row_stride = s4.data_ptr(), None, s4.stride(0), s4.stride(1)
+        cam.src_h, cam.src_w = s4.shape[1], s4.shape[2]
+        _fill_map_camera(cam, m)
+    _lib.launch("bevwarp_stitch_maps_planes", device, ctypes.addressof(cams), len(frames), d4.data_ptr(), B, dh, dw, d4.stride(0) * esz, d4.stride(1) * esz,
+                d4.stride(2) * esz, interp, _BLENDS[blend], int(feather) if blend == "feather" else 0, _ptr(_border(border_value, 3)), _ptr(sc), _ptr(bi),
+                _PLANE_DTYPES[out_dtype])
+    return _like_src(d4, srcs[0].dim(), out)
+
+
+def remap_stitch_nv12_to_planar(ys, uvs, warp_maps, scale=1.0 / 255.0, bias=0.0, blend="over", feather=64, border_value=None, out=None, rgb=False,
+                                out_dtype=torch.float32):
+    """remap_stitch_nv12 of the decoders' NV12 frames, written as the normalised channel planes a detector takes: bit for bit
+
+        out[b, c] = convert(float32(remap_stitch_nv12(ys, uvs, warp_maps, blend, feather, border_value, rgb=rgb)[b, :, :, c]) * scale[c] + bias[c])
+
+    in one launch, with neither the converted frames nor the 8-bit canvas in memory (include/bevwarp.h, bevwarp_stitch_maps_nv12_planes).
+
+    ys, uvs, warp_maps, blend, feather, rgb   as remap_stitch_nv12.
+    scale, bias, border_value   scalars or 3 values in the RESULT's channel order (B, G, R; rgb=True: R, G, B); border_value is the 8-bit
+                                pixel that no camera covers, not converted, put through the plane stage like any other.
+    out_dtype, out   as remap_to_planar.
+    Returns (B, 3, h, w), or (3, h, w) for single frames.  Asynchronous on the current stream."""
+    ys, uvs, warp_maps = list(ys), list(uvs), list(warp_maps)
+    interp, (dw, dh), _ = _stitch_maps_call("remap_stitch_nv12_to_planar", len(ys), warp_maps, blend, feather, BORDER_CONSTANT)
+    _plane_format("remap_stitch_nv12_to_planar", interp, out_dtype, out)
+    if len(uvs) != len(ys):
+        raise ValueError("got %d uv planes for %d cameras" % (len(uvs), len(ys)))
+    planes = [_nv12_planes("remap_stitch_nv12_to_planar", y, uv) for y, uv in zip(ys, uvs)]
+    B, device = planes[0][0].shape[0], planes[0][0].device
+    for k, (y, (y3, _)) in enumerate(zip(ys, planes)):
+        if y3.shape[0] != B or y3.device != device or y.dim() != ys[0].dim():
+            raise ValueError("camera %d has %d frames (y of rank %d) on %s; camera 0 has %d (rank %d) on %s (remap_stitch_nv12_to_planar: one batch and device)"
+                             % (k, y3.shape[0], y.dim(), y3.device, B, ys[0].dim(), device))
+    for m in warp_maps:
+        _map_fits(m, B, device)
+    _planes_out_fits(out, ys[0].dim() + 1, dw, dh, "maps'")
+    d4 = _plane_dst(out, out_dtype, device, B, 3, dh, dw)
+    sc, bi = _per_channel(scale, 3), _per_channel(bias, 3)
+    esz = d4.element_size()
+    cams = (_lib.MapCamera * len(planes))()
+    for cam, (y3, uv4), m in zip(cams, planes, warp_maps):
+        cam.src, cam.uv, cam.frame_stride, cam.row_stride = y3.data_ptr(), uv4.data_ptr(), y3.stride(0), y3.stride(1)
+        cam.uv_frame_stride, cam.uv_row_stride = uv4.stride(0), uv4.stride(1)
+        cam.src_h, cam.src_w = y3.shape[1], y3.shape[2]
+        _fill_map_camera(cam, m)
+    _lib.launch("bevwarp_stitch_maps_nv12_planes", device, ctypes.addressof(cams), len(planes), d4.data_ptr(), B, dh, dw, d4.stride(0) * esz, d4.stride(1) * esz,
+                d4.stride(2) * esz, interp, _BLENDS[blend], int(feather) if blend == "feather" else 0, 1 if rgb else 0, _ptr(_border(border_value, 3)), _ptr(sc),
+                _ptr(bi), _PLANE_DTYPES[out_dtype])
+    return _like_src(d4, ys[0].dim() + 1, out)
+
+
 def footprint(src_hw, M, dsize, batch=None, flags=INTER_LINEAR, device="cuda"):
     """Exact count of distinct in-bounds source pixels the warp reads, per frame.
     Returns (counts int64 tensor [n], touched uint8 tensor [n, H, W])."""

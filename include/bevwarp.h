@@ -58,6 +58,11 @@
  *                             Calib.dist_coeff (bev/calib.py:25): one camera or a site's cameras, BGR or decoder frames, sampled through
  *                             the maps bevwarp_build_map made once and stored as the NV12 frame an encoder takes -- one launch, no
  *                             float64, no BGR BEV frame in memory
+ *   bevwarp_remap_planes, bevwarp_stitch_maps_planes, bevwarp_stitch_maps_nv12_planes
+ *                           the detector-input planes of bevwarp_warp_planes for the same FIXED, possibly distorted cameras,
+ *                             vis_homo.py:85-91 with Calib.dist_coeff (bev/calib.py:25): one camera's BGR frames or a site's cameras, BGR or
+ *                             decoder frames, sampled through the maps bevwarp_build_map made once and written as normalised float32,
+ *                             float16 or bfloat16 channel planes -- one launch, no float64, no 8-bit BEV frame or canvas in memory
  *   bevwarp_composite       composite_reg_img(bg, fg, fg_mask), bev/tool/compo.py:5-24 (the blend after the three warps
  *                             of composite_bev_img, :26-49)
  *   bevwarp_warp_composite  composite_bev_img(bg, fg, fg_mask, ...), bev/tool/compo.py:26-49: the three warps and the blend
@@ -728,6 +733,67 @@ int bevwarp_stitch_maps_nv12_to_nv12(const bevwarp_map_camera *cams /*HOST*/, in
                                      int dst_h, int dst_w, int64_t y_frame_stride, int64_t y_row_stride, int64_t uv_frame_stride,
                                      int64_t uv_row_stride, int interp, int blend, int feather,
                                      const double *border_value /*HOST, 3 (B, G, R) or NULL*/, void *stream);
+
+/*
+ * The map samplers straight to the normalised channel planes a detector takes: bevwarp_remap from 8-bit frames of 3 channels, and the two
+ * stitches through maps, with bevwarp_warp_nv12_planes' plane stage behind them, one launch each, no 8-bit BEV frame or canvas in memory and
+ * no float64.  (NV12 frames through one camera's map have bevwarp_remap_nv12_planes.)  Each entry is defined by composing existing entries,
+ * bit for bit:
+ *   bevwarp_remap_planes            planes( bevwarp_remap(src, ..., 3 channels, BEVWARP_U8, interp, border_mode, border_value) )
+ *   bevwarp_stitch_maps_planes      planes( bevwarp_stitch_maps(cams, ..., 3 channels, BEVWARP_U8, interp, blend, feather,
+ *                                           BEVWARP_BORDER_CONSTANT, border_value) )
+ *   bevwarp_stitch_maps_nv12_planes planes( bevwarp_stitch_maps_nv12(cams, ..., interp, blend, feather, rgb_order,
+ *                                           BEVWARP_BORDER_CONSTANT, border_value) )
+ *   planes          bevwarp_warp_nv12_planes' plane stage, word for word: for P = plane_dtype (BEVWARP_F32 | BEVWARP_F16 | BEVWARP_BF16), p
+ *                   the 8-bit pixel of the composed entry and c its channel,
+ *                       v               = float32(p[c]) * float32(scale[c]) + float32(bias[c])      (multiply, then add, each rounded; no FMA)
+ *                       dst[b][c][y][x] = convert_P(v)
+ *                   with that entry's convert_P, its three destination strides in bytes, its alignment rule (base and strides multiples
+ *                   of the element size) and its wide-store rule (4 elements per store where base and strides admit them).
+ *   channels        plane c is channel c of the sampled pixel: interleaved frames are not swapped (B, G, R frames give B, G, R planes);
+ *                   for bevwarp_stitch_maps_nv12_planes that is the destination's order as rgb_order names it (0: B, G, R; 1: R, G, B).
+ *   scale, bias     HOST, 3 doubles each in the planes' order, NULL = 1 and 0.
+ *   border_value    HOST, 3 doubles in the planes' order, or NULL = 0: an 8-bit pixel (saturate_cast<uchar>) that then passes through the
+ *                   plane stage like any other.  bevwarp_remap_planes: the border pixel of bevwarp_remap's BEVWARP_BORDER_CONSTANT sampler
+ *                   (a tap outside the source is replaced before the blend; an invalid map entry (-32768, -32768) yields the border pixel
+ *                   itself), not looked at under the other modes.  Stitch entries: the pixel that no camera covers; BEVWARP_STITCH_FEATHER
+ *                   is the 8-bit integer mean, then the plane stage.
+ *   border_mode     bevwarp_remap_planes: the five modes that write every pixel; BEVWARP_BORDER_TRANSPARENT is BEVWARP_ERR_UNSUPPORTED, as
+ *                   for bevwarp_remap_nv12_planes.  The stitch entries have none: uncovered pixels are always the border pixel.
+ *   dst             device, batch x 3 planes of dst_h x dst_w elements.  The bounding byte range of all planes must not meet any image the
+ *                   call reads (frames, uv, xy or frac, of any camera).
+ *   maps, sources   as the entry each one composes: map_count 1 or batch, map_frac NULL for BEVWARP_NEAREST only, even source sides for
+ *                   NV12 sources, bevwarp_map_camera as bevwarp_stitch_maps (bevwarp_stitch_maps_nv12) reads it.
+ * Status.  bevwarp_remap_planes, in bevwarp_remap's order with bevwarp_warp_nv12_planes' destination checks standing where the interleaved
+ * destination's stood: BEVWARP_ERR_BAD_ARG (a null pointer -- map_frac under BEVWARP_LINEAR included --, a non-positive size);
+ * BEVWARP_ERR_UNSUPPORTED (interp other than nearest / linear, plane_dtype outside {F32, F16, BF16}, border_mode outside the five);
+ * BEVWARP_ERR_BAD_ARG (map_count not 1 or batch; a row stride below a row for the source, either map plane or a destination plane, frames,
+ * maps or planes that overlap their successors, a map_xy base or stride that is no multiple of 4 or a map_frac one that is no multiple of
+ * 2, a destination base or stride that is no multiple of the element size); BEVWARP_ERR_TOO_LARGE (the source limits of bevwarp_warp);
+ * BEVWARP_ERR_OVERLAP (the bounding byte range of all destination planes meets the source's or either map plane's); BEVWARP_ERR_TOO_LARGE
+ * again for a destination side > 2^20; BEVWARP_ERR_NOT_FINITE (border_value under BEVWARP_BORDER_CONSTANT only; scale, bias).
+ * The stitch entries, in bevwarp_stitch_maps' order: BEVWARP_ERR_BAD_ARG for cams NULL, n_cams outside 1..8, or feather outside 1..4096 under
+ * BEVWARP_STITCH_FEATHER; then per camera in ascending k bevwarp_remap_planes' (bevwarp_remap_nv12_planes') checks in that entry's own order
+ * against the destination planes (blend counts as part of the format), the first status that is not BEVWARP_OK being returned; then
+ * BEVWARP_ERR_TOO_LARGE for a destination side > 2^20; then BEVWARP_ERR_NOT_FINITE for border_value, scale, bias, in that order.
+ * batch == 0 is BEVWARP_OK and launches nothing, for all three.
+ */
+int bevwarp_remap_planes(const void *src, void *dst, int batch, int src_h, int src_w, int dst_h, int dst_w,
+                         int64_t src_frame_stride, int64_t src_row_stride, int64_t dst_frame_stride, int64_t dst_plane_stride,
+                         int64_t dst_row_stride, const void *map_xy, const void *map_frac, int map_count, int64_t xy_frame_stride,
+                         int64_t xy_row_stride, int64_t frac_frame_stride, int64_t frac_row_stride, int interp, int border_mode,
+                         const double *border_value /*HOST, 3 or NULL*/, const double *scale /*HOST, 3 or NULL = 1*/,
+                         const double *bias /*HOST, 3 or NULL = 0*/, int plane_dtype, void *stream);
+int bevwarp_stitch_maps_planes(const bevwarp_map_camera *cams /*HOST*/, int n_cams, void *dst, int batch, int dst_h, int dst_w,
+                               int64_t dst_frame_stride, int64_t dst_plane_stride, int64_t dst_row_stride, int interp, int blend,
+                               int feather, const double *border_value /*HOST, 3 or NULL*/,
+                               const double *scale /*HOST, 3 or NULL = 1*/, const double *bias /*HOST, 3 or NULL = 0*/,
+                               int plane_dtype, void *stream);
+int bevwarp_stitch_maps_nv12_planes(const bevwarp_map_camera *cams /*HOST*/, int n_cams, void *dst, int batch, int dst_h, int dst_w,
+                                    int64_t dst_frame_stride, int64_t dst_plane_stride, int64_t dst_row_stride, int interp,
+                                    int blend, int feather, int rgb_order, const double *border_value /*HOST, 3 or NULL*/,
+                                    const double *scale /*HOST, 3 or NULL = 1*/, const double *bias /*HOST, 3 or NULL = 0*/,
+                                    int plane_dtype, void *stream);
 
 /*
  * out[i] = uint8(min(round_half_even(fg[i] * (mask[i] / 255) + bg[i] * (1 - mask[i] / 255)), 255)) for i in [0, n), computed in
