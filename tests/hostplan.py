@@ -14,15 +14,16 @@ SANITIZE = ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "
 
 
 @functools.lru_cache(maxsize=None)
-def build_driver(sanitize=True):
-    """The driver's path.  sanitize: g++ under the address and undefined-behaviour sanitizers; a GPU test builds it plainly.
+def build_driver(sanitize=True, source="host_plan_driver.cpp"):
+    """The driver's path (source: another driver of tests/ built the same way).  sanitize: g++ under the address and undefined-behaviour
+    sanitizers; a GPU test builds it plainly.
     (-static-libasan: a process that starts with some library preloaded refuses a shared sanitizer runtime that is not the first one)"""
     tmp = tempfile.mkdtemp(prefix="host_plan_driver_")
     atexit.register(shutil.rmtree, tmp, ignore_errors=True)
-    exe = os.path.join(tmp, "host_plan_driver")
+    exe = os.path.join(tmp, os.path.splitext(source)[0])
     subprocess.check_call(["g++", "-std=c++17", "-O1"] + (SANITIZE if sanitize else []) +
                           ["-I", os.path.join(ROOT, "bev_amd", "csrc"), "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "host_plan_driver.cpp"), "-o", exe])
+                           os.path.join(ROOT, "tests", source), "-o", exe])
     return exe
 
 

@@ -40,11 +40,59 @@ TALL_DSIZE = (40, 600)
 # destination's, so only then does a tile lie inside the frame -- and only tiles inside the frame form the 24-bit tap addresses.
 TALL_MAPS = {"right_end": affine(0.1, 4.3, 1.0, 32290.3), "minify64": affine(0.1, 4.3, 64.0, 61.25)}
 
+# The same two cases for the entries tests/test_gpu_limits_entries.py runs (lens, NV12, map and stitch kernels).  NV12 frames have even
+# sides, so theirs is 32766 px: `right_end` is unchanged (columns 32290 .. 32889 pass the last column with two valid taps, 32764, the last
+# column, 32765, and saturate at 32767), `minify64` starts a pixel earlier, so that x = 511 lands on sx = 32764 = w - 2 and x = 512 on the
+# saturated 32767.  Neither map leaves the frame on the near side of the long axis, so both sets get `left_end`: a 1:1 translation that
+# starts 20.6 px BEFORE the frame (indices -21 .. -1 on the long axis, -1 with one valid tap).
+MAX_EVEN = 32766            # NV12 sides
+WIDE_NV12_HW = (40, MAX_EVEN)
+TALL_NV12_HW = (MAX_EVEN, 40)
+WIDE_LEFT_END, TALL_LEFT_END = affine(1.0, -20.6, 1.0, -2.4), affine(0.1, 4.3, 1.0, -20.6)
+WIDE_ENTRY_MAPS = dict(WIDE_MAPS, left_end=WIDE_LEFT_END)
+TALL_ENTRY_MAPS = dict(TALL_MAPS, left_end=TALL_LEFT_END)
+WIDE_NV12_MAPS = {"right_end": WIDE_MAPS["right_end"], "minify64": affine(64.0, 60.25, 0.9, 0.8), "left_end": WIDE_LEFT_END}
+TALL_NV12_MAPS = {"right_end": TALL_MAPS["right_end"], "minify64": affine(0.1, 4.3, 64.0, 60.25), "left_end": TALL_LEFT_END}
+
+
+def entry_case(name, nv12=False):
+    """(source (H, W), destination (w, h), {map name: inverse matrix}, the long axis' index in (sx, sy)) of case A ("wide") or B ("tall")."""
+    if name == "wide":
+        return (WIDE_NV12_HW if nv12 else WIDE_HW), WIDE_DSIZE, (WIDE_NV12_MAPS if nv12 else WIDE_ENTRY_MAPS), 0
+    return (TALL_NV12_HW if nv12 else TALL_HW), TALL_DSIZE, (TALL_NV12_MAPS if nv12 else TALL_ENTRY_MAPS), 1
+
+
+LENS_R2 = {"right_end": 1.011, "left_end": 1.011, "minify64": 1.03}  # r2_max of a lens run, in units of the far corner's r2
+
+
+def mild_lens(hw, key="right_end"):
+    """(K, dist_coeff, r2_max) of a mild lens for a camera of hw = (H, W): lens_ref.camera_K of that size, and k1, p1 scaled to the squared
+    radius r2 of the frame's far corner on the normalised plane -- k1 r2 = -0.004 pulls that corner about 0.4 % (some 60 px of 32767)
+    towards the centre, p1 moves it about a pixel across.  With steps of about one source pixel per destination pixel the `right_end` and
+    `left_end` maps therefore still pass every index next to the frame's ends.  r2_max (LENS_R2[key] corner radii) lies between the radius
+    at which the map saturates and the radius of its last pixels: pixels beyond it are outside (tests/test_limits_cpu.py asserts that
+    valid saturated pixels and pixels beyond r2_max both occur)."""
+    from tests import lens_ref
+    h, w = hw
+    K = lens_ref.camera_K(w, h)
+    r2 = ((w - 1 - K[0, 2]) / K[0, 0]) ** 2 + ((h - 1 - K[1, 2]) / K[1, 1]) ** 2
+    return K, (-0.004 / r2, 0.0, 1.0 / (r2 * K[0, 0]), 0.0, 0.0), LENS_R2[key] * r2
+
+
+# The maps of the lens runs (undistorted source pixels): `right_end` as it is; `left_end` starts 66 px earlier, which the lens gives back;
+# `minify64` keeps its 64 px per destination pixel (about 63 after the lens) and starts where the lens lands a pixel on side - 2 = 32765
+# for both interpolations (the coordinate falls in [32765, 32765.5)), the next one on the saturated 32767, still within r2_max.
+WIDE_LENS_MAPS = {"right_end": WIDE_MAPS["right_end"], "left_end": affine(1.0, -86.6, 1.0, -2.4), "minify64": affine(64.0, 63.5, 0.9, 0.8)}
+TALL_LENS_MAPS = {"right_end": TALL_MAPS["right_end"], "left_end": affine(0.1, 4.3, 1.0, -86.6), "minify64": affine(0.1, 4.3, 64.0, 60.25)}
+
+
 # ---- C: the largest row stride ---------------------------------------------------------------------------------------------------------
 STRIDE_W = 640
 STRIDE_DSIZE = (600, 64)
 STRIDE_ALIGNED = ROW_LIMIT - 16   # float32, and 8-bit RGBA
 STRIDE_ODD = ROW_LIMIT - 1        # 8-bit, 1 and 3 channels: every row starts at another residue mod 4
+# NV12 at the largest strides the checks admit: (row stride, rows) of the Y plane and of the plane of (U, V) pairs, whose strides are even
+STRIDE_NV12 = {"y": (ROW_LIMIT - 1, 128), "uv": (ROW_LIMIT - 2, 64)}
 
 
 def max_rows(stride):
@@ -97,6 +145,37 @@ def dest_reach(dh, dw, c, esz, rs, batch=1, fs=0, planes=1, ps=0):
     return (batch - 1) * fs + (planes - 1) * ps + (dh - 1) * rs + dw * (c if planes == 1 else 1) * esz
 
 
+# NV12 frames in ONE holder.  Each helper returns {"y": spec, "uv": spec, "bytes": what the holder must hold}, a spec being the (shape,
+# strides in bytes, byte offset) of a uint8 view of the holder -- (B, h, w) / (h, w) for Y, (B, h / 2, w / 2, 2) / (h / 2, w / 2, 2) for the pairs.
+def _nv12_specs(y, uv):
+    return {"y": y, "uv": uv, "bytes": max(off + extent_bytes(shape, strides, 1) for shape, strides, off in (y, uv))}
+
+
+def nv12_joined(batch, h, w, fs):
+    """`batch` frames `fs` bytes apart, each the decoders' single buffer: h rows of Y, then h / 2 rows of pairs, all w bytes apart --
+    one frame stride for both planes."""
+    assert h % 2 == 0 and w % 2 == 0 and fs >= h * 3 // 2 * w
+    return _nv12_specs(((batch, h, w), (fs, w, 1), 0), ((batch, h // 2, w // 2, 2), (fs, w, 2, 1), h * w))
+
+
+def nv12_beside(h, w, rs, uv_off):
+    """One frame whose rows are `rs` bytes apart: row i of Y starts stretch i, row j of the pairs lies in stretch j too, `uv_off` bytes in
+    (beyond the Y row): two planes side by side with one row stride."""
+    assert h % 2 == 0 and w % 2 == 0 and uv_off % 2 == 0 and w <= uv_off and uv_off + w <= rs
+    return _nv12_specs(((h, w), (rs, 1), 0), ((h // 2, w // 2, 2), (rs, 2, 1), uv_off))
+
+
+def spec_rows(spec):
+    """[(first byte, one past the last byte)] of every row of a spec'd view, frame by frame."""
+    shape, strides, off = spec
+    lead = [(n, s) for n, s in zip(shape, strides) if s > 2]  # (frame and row dimensions; a row's bytes are contiguous)
+    row_bytes = extent_bytes(shape[len(lead):], strides[len(lead):], 1)
+    starts = [off]
+    for n, s in lead:
+        starts = [b + i * s for b in starts for i in range(n)]
+    return [(b, b + row_bytes) for b in starts]
+
+
 # ---- D, E: strides beyond 4 GiB ------------------------------------------------------------------------------------------------------------
 BIG_SRC_HW = (96, 700)
 BIG_DSIZE = (600, 40)
@@ -106,6 +185,18 @@ ROWS_PAST_4G5 = int(4.5 * (1 << 30)) // ROW_64M + 2  # destination rows of case 
 
 def big_map():
     return affine(1.1, 8.4, 2.3, -1.7)  # reaches above the frame and, on the right, just inside it
+
+
+# The three cameras of the stitch runs over one 600 x 40 canvas: the widest source parked on its right end (it covers x <= 476), the tallest
+# one on its lower end (sy = 32740 .. 32779: it covers y <= 26, or 25 for the 32766-row NV12 frame) and a 96 x 700 frame (it covers y >= 1,
+# x <= 530); nothing covers the lower right corner.
+STITCH_DSIZE = (600, 40)
+
+
+def stitch_cameras(nv12=False):
+    """[(source (H, W), inverse matrix)] of the three cameras; nv12: the even-sided sources."""
+    return [(WIDE_NV12_HW if nv12 else WIDE_HW, WIDE_MAPS["right_end"]), (TALL_NV12_HW if nv12 else TALL_HW, affine(0.06, 1.3, 1.0, 32740.3)),
+            (BIG_SRC_HW, affine(1.3, 8.4, 2.3, -1.7))]
 
 
 def jittered_inverse(Minv, idx, px=2.0):
@@ -124,6 +215,7 @@ DECODE_TILES = 37747
 DECODE_BATCHES = (3, 4)
 DECODE_SRC_HW = (64, 64)
 DECODE_DW = 3
+DECODE_DW_EVEN = 2  # for the entries that write NV12
 
 
 def decode_map(dh):

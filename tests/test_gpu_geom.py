@@ -46,6 +46,48 @@ def test_project_points_config3(golden, dtype, dim):
         project_points(torch.zeros((4, 2)), Hm)
 
 
+ODD_COUNTS = [(dtype, dim, n) for dtype in (np.float32, np.float64) for dim in (2, 3) for n in (1, 3, 255, 513)]
+ODD_COUNTS.append((np.float32, 2, 2048 * 256 * 2 + 1))  # one point past a full pass of the float32 kernel's 2048-workgroup grid (two points per lane)
+
+
+@pytest.mark.parametrize("dtype,dim,n", ODD_COUNTS, ids=["%s-dim%d-n%d" % (np.dtype(d).name, k, n) for d, k, n in ODD_COUNTS])
+def test_project_points_odd_counts_and_views_at_an_odd_point(golden, dtype, dim, n):
+    """project_points_kernel<float, 2> has two paths the even, freshly allocated tensors of the other tests never take: the tail for an odd
+    last point, and the one-point-per-step loop for buffers that are only 8-byte aligned (a view starting at an odd point).  Odd n in a fresh
+    allocation, the same points as the view t[1:] of a longer tensor, and in place on that view; the point in front of the view and a
+    guard point behind it keep their bits.  The other three kernels run the same cases."""
+    from bev_amd.points import project_points
+    Hm = np.array(golden["calib_from_vps"]["base"]["H_world_img"])
+    rng = np.random.default_rng(70 + dim)
+    pts = rng.uniform(0, [1920, 1080], (n + 2, 2))
+    if dim == 3:
+        pts = np.concatenate([pts, rng.uniform(0.5, 2, (n + 2, 1))], axis=1)
+    pts = pts.astype(dtype)
+    exp = co.project_points(pts[1:n + 1], Hm)
+    bits = np.uint32 if dtype == np.float32 else np.uint64
+
+    def same(got, what):
+        if dtype == np.float64:
+            np.testing.assert_allclose(got, exp, rtol=1e-13, atol=0, err_msg=what)
+        else:
+            np.testing.assert_array_equal(got.view(bits), exp.view(bits), err_msg=what)  # same f64 arithmetic, one final rounding to f32
+
+    fresh = torch.from_numpy(np.ascontiguousarray(pts[1:n + 1])).cuda()
+    assert fresh.data_ptr() % 16 == 0
+    same(project_points(fresh, Hm).cpu().numpy(), "fresh allocation")
+    holder = torch.from_numpy(pts).cuda()
+    view = holder[1:n + 1]
+    assert view.is_contiguous() and view.data_ptr() - holder.data_ptr() == dim * pts.itemsize
+    if dtype == np.float32 and dim == 2:
+        assert view.data_ptr() % 16 == 8  # only 8-byte aligned: the one-point-per-step loop
+    same(project_points(view, Hm).cpu().numpy(), "view at an odd point, fresh out")
+    assert np.array_equal(holder.cpu().numpy().view(bits), pts.view(bits))  # the source is read only
+    assert project_points(view, Hm, out=view) is view
+    after = holder.cpu().numpy()
+    same(after[1:n + 1], "in place on the view")
+    assert np.array_equal(after[0].view(bits), pts[0].view(bits)) and np.array_equal(after[n + 1].view(bits), pts[n + 1].view(bits))
+
+
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 def test_rbox_iou_config5(dtype):
     """configs[4]'s IoU half: 512 detections x 512 tracks."""

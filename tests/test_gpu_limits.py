@@ -26,6 +26,7 @@ from tests import limits_cases as lc
 from tests import pixels as px
 from tests import planes16_ref as p16
 from tests import workloads as wl
+from tests.limits_buffers import assert_only_the_view_was_written, byte_holder, nan_holder, per_frame, same, strided
 from tests.parity import check_modes, poisoned_out, report_comparisons, warp_modes  # noqa: F401  (report_comparisons: a module fixture)
 
 pytestmark = pytest.mark.gpu
@@ -34,52 +35,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INV = W.WARP_INVERSE_MAP
 TOO_LARGE = -3
 SCALE, BIAS = [1 / 255.0, 0.5, 2.0, 1.0], [0.0, -1.0, 3.5, 0.25]
-_BYTE_PATTERN = int(np.array([lc.U8_CANARY] * 4, np.uint8).view(np.int32)[0])
 
 
-# ---- buffers -------------------------------------------------------------------------------------------------------------------------------
-def byte_holder(nbytes):
-    """A device buffer of at least `nbytes` bytes, every byte the canary."""
-    return torch.full((-(-nbytes // 16) * 16,), lc.U8_CANARY, dtype=torch.uint8, device="cuda")
-
-
-def nan_holder(nbytes):
-    """The same for float32 sources: every element a NaN, so a tap read outside the rows that were copied in poisons its pixel."""
-    return torch.full((-(-nbytes // 16) * 4,), lc.F32_CANARY_BITS, dtype=torch.int32, device="cuda").view(torch.uint8)
-
-
-def strided(holder, dtype, shape, strides_bytes):
-    tdt = torch.from_numpy(np.zeros(0, dtype)).dtype if not isinstance(dtype, torch.dtype) else dtype
-    esz = torch.empty(0, dtype=tdt).element_size()
-    assert all(s % esz == 0 for s in strides_bytes) and lc.extent_bytes(shape, strides_bytes, esz) <= holder.numel()
-    return torch.as_strided(holder.view(tdt), tuple(shape), tuple(s // esz for s in strides_bytes))
-
-
-def assert_only_the_view_was_written(holder, view, what):
-    """Everything outside `view` still is the canary: the view's own bytes are set back to it, then the whole buffer is compared on the
-    device, a chunk at a time (the comparison's mask is the only temporary)."""
-    view.view(torch.uint8).fill_(lc.U8_CANARY)
-    words = holder.view(torch.int32)
-    step = 1 << 28
-    flags = torch.stack([(words[i:i + step] != _BYTE_PATTERN).any() for i in range(0, words.numel(), step)])
-    assert not bool(flags.any().item()), "%s: bytes outside the destination view were written" % what
-
-
-# ---- expected values -----------------------------------------------------------------------------------------------------------------------
-def per_frame(fn, src, Minv):
-    """fn(frame, matrix) for a single image, or stacked over a batch with one matrix per frame."""
-    if src.ndim == 3:
-        return fn(src, Minv)
-    return np.stack([fn(f, M) for f, M in zip(src, Minv)])
-
-
-def same(got, exp):
-    if exp.dtype == np.float32:
-        px.same_float(got, exp)
-    else:
-        np.testing.assert_array_equal(got, exp)
-
-
+# ---- expected values (the buffer helpers live in tests/limits_buffers.py) --------------------------------------------------------------------
 def run_both_interps(t, src, Minv, dsize, out=None):
     """bevwarp_warp, nearest and bilinear, in both launch modes, against the oracle.  Returns the bilinear expectation."""
     c = src.shape[-1]
