@@ -509,7 +509,8 @@ def build_warp_map(M, dsize, flags=INTER_LINEAR, K=None, dist_coeff=None, r2_max
     K, dist_coeff   the lens, as warp_perspective_lens takes it.  dist_coeff None or all zero: the pinhole chain (K is not looked at) --
              the rule by which warp_perspective_lens hands a lens without distortion to warp_perspective.
     r2_max   None: lens_valid_r2(dist_coeff); a pixel beyond it is stored as the entry whose taps are all outside.
-    out      a WarpMap of this n, dsize and interpolation on `device` to write into (its planes may be views).
+    out      a WarpMap of this n, dsize and interpolation on `device` to write into (its planes may be views).  A `device` without an
+             index (the default) then means the map's device, which need not be the current one.
     remap(src, build_warp_map(...)) equals warp_perspective(src, ..., border_mode=m) for every border mode, and warp_perspective_lens
     for BORDER_CONSTANT and BORDER_TRANSPARENT, by bits.  Asynchronous on the current stream."""
     interp = _interp("build_warp_map", flags)
@@ -533,6 +534,10 @@ def build_warp_map(M, dsize, flags=INTER_LINEAR, K=None, dist_coeff=None, r2_max
     if out is not None:
         if not isinstance(out, WarpMap) or out.n != n or out.dsize != (dw, dh) or out.interp != interp or out.device.type != device.type:
             raise ValueError("out must be a WarpMap of %d frame(s), dsize %s and interpolation %d on %s" % (n, (dw, dh), interp, device))
+        if device.index is None:
+            device = out.device  # (the matrices go where the map is: "cuda" alone would upload them to the current device)
+        elif out.device != device:
+            raise ValueError("out is on %s, device is %s" % (out.device, device))
     if device.type != "cuda":
         raise ValueError("build_warp_map needs a CUDA (HIP) device, got %s" % (device,))
     minv = device_inverse(Mh, device, inverse_given=inverse)
