@@ -1,4 +1,4 @@
-// map_entry_taps.inc -- the index stage of the map samplers (remap_kernel, warp_map.hip; remap_nv12_body, warp_map_nv12.hip), included
+// map_entry_taps.inc -- the index stage of the map samplers (remap_kernel, warp_map.hip; remap_taps_u8x3.inc; remap_taps_nv12.inc), included
 // inside their loop over the lane's pixels j.  In scope: a (RemapArgs: src_w, src_h, dst_w and the index remap), INTERP, MODE,
 // kTransparent, xs, j, e[j], fr[j], wr[].  Defines, for entry e[j] = (sx, sy): f (the weights: fx | fy << 5), the taps' columns c0, c1 and
 // rows cy0, cy1, `in` (BORDER_CONSTANT: bit 0 = tap (row 0, col 0) inside, 1 = (0, 1), 2 = (1, 0), 3 = (1, 1); else 0), and sets wr[j]:

@@ -1,6 +1,7 @@
 // nv12_sample.h -- the sampler of the NV12 warps (device code, gfx950): one destination pixel from a Y plane and a plane of (U, V) pairs,
 // every tap converted with OpenCV's 8-bit YUV420sp -> RGB fixed point before the blend.  Shared by warp_nv12.hip (8-bit BGR / RGB
-// destinations) and warp_nv12_planes.hip (normalised channel planes).  See DESIGN.md sections 4.12 and 4.13.  Not installed.
+// destinations) and warp_nv12_planes.hip (normalised channel planes); the conversion, by the samplers through warp maps as well
+// (remap_sample_nv12.h, stitch_sample.h).  See DESIGN.md sections 4.12, 4.13 and 4.19.  Not installed.
 #pragma once
 #include "sample.h"
 
@@ -34,12 +35,25 @@ __device__ __forceinline__ void convert_channels(uint32_t Y, const Chroma& c, ui
 }
 // one converted pixel, packed in the destination's channel order (RGB = 0: B, G, R in bytes 0, 1, 2; 1: R, G, B)
 // (The compiler may fuse two channels' >> 20 and clamp with this packing into v_ashr_pk_u8_i32; the one kernel in which it did gave wrong
-// pixels on the MI355X -- warp_map_nv12.hip's convert_packed, DESIGN.md section 4.19.  A kernel that uses convert and fails its bit-exact
-// test: look for that instruction in its code first.)
+// pixels on the MI355X -- convert_packed below, DESIGN.md section 4.19.  A kernel that uses convert and fails its bit-exact test: look for
+// that instruction in its code first.)
 template <int RGB>
 __device__ __forceinline__ uint32_t convert(uint32_t Y, const Chroma& c) {
     uint32_t r, g, b;
     convert_channels(Y, c, r, g, b);
+    return RGB ? (r | (g << 8) | (b << 16)) : (b | (g << 8) | (r << 16));
+}
+// convert<RGB> with the middle channel behind a value barrier: what every sampler through warp maps converts with (remap_sample_nv12.h,
+// stitch_sample.h).  Without the barrier the compiler fuses two channels' shift and clamp of one instance of the bilinear R, G, B kernel
+// of warp_map_nv12.hip into v_ashr_pk_u8_i32, and on the MI355X that instance -- the only one of the unit's kernels with the instruction
+// -- gave pixels up to 128 off the definition (2.6 % of a frame; every other instance was exact).  The barrier costs no instruction: each
+// channel keeps its own v_ashrrev_i32 and v_med3_i32, as in every other kernel of the library.  This is the only copy: a new sampler of
+// NV12 taps calls it and restates nothing.
+template <int RGB>
+__device__ __forceinline__ uint32_t convert_packed(uint32_t Y, const Chroma& c) {
+    uint32_t r, g, b;
+    convert_channels(Y, c, r, g, b);
+    asm("" : "+v"(g));
     return RGB ? (r | (g << 8) | (b << 16)) : (b | (g << 8) | (r << 16));
 }
 

@@ -8,10 +8,12 @@
 //
 // The frame -- item decoding, the row walk, the rounding, a pixel's load and the store of a lane's 4 pixels -- is flat_frame.h; the lens
 // step and the blend are lens_pixel.h; the index remap is warp_border.h; the sampler's map loads and index stage are map_entry.h, shared
-// with the NV12 sampler (warp_map_nv12.hip).
+// with the NV12 sampler (warp_map_nv12.hip); a tap's load by byte offset and the 6-byte pair load are tap_load.h, shared with the stitches
+// through maps.
 #include "warp_map.h"
 #include "lens_pixel.h"
 #include "map_entry.h"
+#include "tap_load.h"
 
 namespace bevwarp {
 namespace {
@@ -86,40 +88,6 @@ struct Taps {
     __device__ __forceinline__ int fy() const { return (int)((w >> 5) & 31u); }
     __device__ __forceinline__ uint32_t in() const { return w >> 10; }
 };
-
-// One source pixel at a byte offset of the frame: exactly its C * sizeof(T) bytes are read (flat_frame.h's load_pixel, by offset).
-template <typename T, int C>
-__device__ __forceinline__ Pixel<T, C> load_at(const uint8_t* __restrict__ frame, uint32_t off, bool vec) {
-    Pixel<T, C> p;
-    const uint8_t* q = frame + off;
-    if constexpr (sizeof(T) == 1) {
-        if (C == 4 && vec) {
-            p.packed = *reinterpret_cast<const uint32_t*>(q);
-        } else if (C == 2 && vec) {
-            p.packed = *reinterpret_cast<const uint16_t*>(q);
-        } else {
-            p.packed = 0;
-#pragma unroll
-            for (int k = 0; k < C; k++) p.packed |= (uint32_t)q[k] << (8 * k);
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < C; k++) p.v[k] = reinterpret_cast<const float*>(q)[k];
-    }
-    return p;
-}
-
-// The two taps of a row of 8-bit 3-channel pixels whose columns are adjacent are 6 contiguous bytes: one dword and one short load
-// (unaligned, as the byte pairs the compiler forms on its own already are) instead of two shorts and two bytes, and never a byte beyond the
-// six.  The tap loads are what binds this kernel.
-__device__ __forceinline__ void load_pair_u8x3(const uint8_t* __restrict__ frame, uint32_t off, Pixel<uint8_t, 3>& p0, Pixel<uint8_t, 3>& p1) {
-    uint32_t lo;
-    uint16_t hi;
-    __builtin_memcpy(&lo, frame + off, 4);
-    __builtin_memcpy(&hi, frame + off + 4, 2);
-    p0.packed = lo & 0xffffffu;
-    p1.packed = __builtin_amdgcn_alignbit((uint32_t)hi, lo, 24);  // bytes 3, 4, 5
-}
 
 // the four taps of an entry; PAIR: both rows' taps are adjacent columns of 8-bit 3-channel pixels
 template <typename T, int C, bool PAIR>

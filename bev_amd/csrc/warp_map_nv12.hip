@@ -5,7 +5,8 @@
 // depend on the frame -- per pixel the byte offsets of the taps in the Y plane and in the plane of (U, V) pairs, the weights, and the
 // inside mask (BORDER_CONSTANT) or the write mask (BORDER_TRANSPARENT) -- and walks frames_per_item frames with that in registers.
 //
-// The frame is flat_frame.h; the map loads (map_entry.h) and the index stage (map_entry_taps.inc) are shared with remap_kernel; conversion and blend are
+// The frame is flat_frame.h; the map loads (map_entry.h) and the index stage (map_entry_taps.inc) are shared with remap_kernel; what a
+// lane keeps of an entry and one pixel from it are remap_sample_nv12.h, shared with warp_map_nv12_out.hip; conversion and blend are
 // nv12_sample.h; the BGR store is store_lane_pixels and the plane store plane_store.inc, shared with warp_nv12_planes.hip.
 //
 // The tap gathers bind this kernel as they bind remap_kernel: tap by tap a bilinear pixel takes 8 loads per
@@ -17,72 +18,11 @@
 // the first src_w bytes of a plane row.
 #include "warp_map_nv12.h"
 #include "map_entry.h"
-#include "nv12_sample.h"
+#include "remap_sample_nv12.h"
 #include "warp_kernels.h"
 
 namespace bevwarp {
 namespace {
-
-// What a lane keeps of one map entry for every frame it walks.  All offsets are of source pixels (remapped, an inlier's, or clamped);
-// a plane is below 2 GiB, so 32 bits hold them and a load is the plane's wave-uniform base plus one register.
-struct NvTaps {
-    uint32_t y00, y01, y10, y11;  // bytes into the Y plane; a window lane loads 2 bytes at y00 and at y10
-    uint32_t u00, u01, u10, u11;  // bytes into the plane of pairs (even); a window lane loads 4 bytes at u00 and at u10 (the windows' starts)
-    uint32_t w;  // fx | fy << 5 | in << 10 | s0 << 14 | s1 << 15; in: map_entry_taps.inc's; s0, s1: window lanes, which pair of the window column c0 / c1 takes
-    __device__ __forceinline__ uint32_t fx() const { return w & 31u; }
-    __device__ __forceinline__ uint32_t fy() const { return (w >> 5) & 31u; }
-    __device__ __forceinline__ uint32_t in() const { return (w >> 10) & 15u; }
-};
-
-// a (U, V) pair at an even byte offset of a plane whose base and strides are even
-__device__ __forceinline__ uint32_t pair_at(const uint8_t* __restrict__ uvf, uint32_t off) { return *reinterpret_cast<const uint16_t*>(uvf + off); }
-
-// convert<RGB> (nv12_sample.h) with the middle channel behind a value barrier.  Without it the compiler fuses two channels' shift and
-// clamp of one instance of the bilinear R, G, B kernel into v_ashr_pk_u8_i32, and on the MI355X that instance -- the only one of the
-// unit's kernels with the instruction -- gave pixels up to 128 off the definition (2.6 % of a frame; every other instance was exact).
-// The barrier costs no instruction: each channel keeps its own v_ashrrev_i32 and v_med3_i32, as in every other kernel of the library.
-template <int RGB>
-__device__ __forceinline__ uint32_t convert_packed(uint32_t Y, const Chroma& c) {
-    uint32_t r, g, b;
-    convert_channels(Y, c, r, g, b);
-    asm("" : "+v"(g));
-    return RGB ? (r | (g << 8) | (b << 16)) : (b | (g << 8) | (r << 16));
-}
-
-// One destination pixel of one frame, packed in the order convert<RGB> gives.  WINDOW: the lane's pixels all have adjacent columns.
-template <int INTERP, int MODE, int RGB, bool WINDOW>
-__device__ __forceinline__ uint32_t sample_entry_nv12(const uint8_t* __restrict__ yf, const uint8_t* __restrict__ uvf, const NvTaps& t, uint32_t border) {
-    if constexpr (INTERP == kNearest) {
-        const uint32_t p = convert_packed<RGB>(yf[t.y00], chroma_terms(pair_at(uvf, t.u00)));
-        return (MODE != 0 || (t.in() & 1u)) ? p : border;
-    } else {
-        // every load is of a source pixel (the constant border: of the CLAMPED position) and issues before the first wait
-        uint32_t Y00, Y01, Y10, Y11, q00, q01, q10, q11;
-        if constexpr (WINDOW) {
-            uint16_t w0, w1;
-            uint32_t v0, v1;
-            __builtin_memcpy(&w0, yf + t.y00, 2);  // (unaligned, like sample_nv12's windows)
-            __builtin_memcpy(&w1, yf + t.y10, 2);
-            __builtin_memcpy(&v0, uvf + t.u00, 4);  // (2-byte aligned)
-            __builtin_memcpy(&v1, uvf + t.u10, 4);
-            const uint32_t s0 = (t.w >> 10) & 16u, s1 = (t.w >> 11) & 16u;  // 16 * (bit 14), 16 * (bit 15)
-            Y00 = w0 & 0xffu, Y01 = (uint32_t)w0 >> 8, Y10 = w1 & 0xffu, Y11 = (uint32_t)w1 >> 8;
-            q00 = (v0 >> s0) & 0xffffu, q01 = (v0 >> s1) & 0xffffu, q10 = (v1 >> s0) & 0xffffu, q11 = (v1 >> s1) & 0xffffu;
-        } else {
-            Y00 = yf[t.y00], Y01 = yf[t.y01], Y10 = yf[t.y10], Y11 = yf[t.y11];
-            q00 = pair_at(uvf, t.u00), q01 = pair_at(uvf, t.u01), q10 = pair_at(uvf, t.u10), q11 = pair_at(uvf, t.u11);
-        }
-        uint32_t p00 = convert_packed<RGB>(Y00, chroma_terms(q00)), p01 = convert_packed<RGB>(Y01, chroma_terms(q01));
-        uint32_t p10 = convert_packed<RGB>(Y10, chroma_terms(q10)), p11 = convert_packed<RGB>(Y11, chroma_terms(q11));
-        if constexpr (MODE == 0) {
-            // a tap outside is the border value, in the destination's order and not converted (all four outside: the blend of four
-            // border pixels is the border pixel)
-            const uint32_t in = t.in();
-            p00 = (in & 1u) ? p00 : border, p01 = (in & 2u) ? p01 : border, p10 = (in & 4u) ? p10 : border, p11 = (in & 8u) ? p11 : border;
-        }
-        return blend_u8_packed<3>(p00, p01, p10, p11, t.fx(), t.fy());
-    }
-}
 
 // a lane's 4 pixels of one frame
 template <int INTERP, int MODE, int RGB, bool WINDOW>
@@ -101,51 +41,7 @@ __device__ __forceinline__ void frame_pixels_nv12(const uint8_t* __restrict__ yf
 // The kernels' common body; store(b, y, xs, p, wr) writes a lane's 4 pixels of frame b.
 template <int INTERP, int MODE, int RGB, class Store>
 __device__ __forceinline__ void remap_nv12_body(const RemapNv12Args& a, Store store) {
-    constexpr int PPL = kBorderPPL;
-    constexpr bool kTransparent = MODE == kBorderTransparent;
-    constexpr bool kWindows = INTERP == kLinear && BEVWARP_REMAP_NV12_WINDOWS != 0;
-    uint32_t g;
-    int y, xs;  // group of frames, row, the lane's first pixel
-    if (!lane_position(a, g, y, xs)) return;
-    const int b0 = (int)g * a.frames_per_item;
-    const int nb = min(a.frames_per_item, a.batch - b0);
-
-    uint32_t e[PPL], fr[PPL];
-    load_entries<INTERP>(a, b0, y, xs, e, fr);
-
-    NvTaps tap[PPL];
-    bool wr[PPL];
-    // the windows: a row of pairs holds at least two of them (src_w >= 4), and every (loaded) pixel of the lane has its two columns side
-    // by side
-    bool window = kWindows && a.src_w >= 4;
-    const int last_start = (a.src_w >> 1) - 2;  // the last pair a 4-byte window may start at
-#pragma unroll
-    for (int j = 0; j < PPL; j++) {
-        NvTaps& t = tap[j];
-#include "map_entry_taps.inc"
-        // a tap at pixel (c, r) reads Y[r][c] and the pair (r >> 1, c >> 1)
-        const uint32_t yo0 = (uint32_t)cy0 * (uint32_t)a.y_rs, yo1 = (uint32_t)cy1 * (uint32_t)a.y_rs;
-        const uint32_t uo0 = (uint32_t)(cy0 >> 1) * (uint32_t)a.uv_rs, uo1 = (uint32_t)(cy1 >> 1) * (uint32_t)a.uv_rs;
-        const int p0 = c0 >> 1, p1 = c1 >> 1;
-        t.y00 = yo0 + (uint32_t)c0, t.y01 = yo0 + (uint32_t)c1, t.y10 = yo1 + (uint32_t)c0, t.y11 = yo1 + (uint32_t)c1;
-        t.u00 = uo0 + 2u * (uint32_t)p0, t.u01 = uo0 + 2u * (uint32_t)p1, t.u10 = uo1 + 2u * (uint32_t)p0, t.u11 = uo1 + 2u * (uint32_t)p1;
-        // with adjacent columns the window starting at pair min(p0, last_start) holds both taps' pairs: p1 is p0 or p0 + 1, and p0 is
-        // past last_start only for c0 = src_w - 2, whose two taps share the row's last pair
-        const int ps = min(p0, last_start);
-        t.w = f | (in << 10) | ((uint32_t)((p0 - ps) & 1) << 14) | ((uint32_t)((p1 - ps) & 1) << 15);
-        if constexpr (kWindows) window = window && ((kTransparent && !wr[j]) || c1 == c0 + 1);
-    }
-    if constexpr (kWindows) {
-        if (window) {
-#pragma unroll
-            for (int j = 0; j < PPL; j++) {
-                const uint32_t back = (tap[j].w >> 13) & 2u;  // 2 bytes where the window starts one pair before c0's
-                tap[j].u00 -= back, tap[j].u10 -= back;
-            }
-        }
-    }
-
-    const uint32_t border = a.bv_u8;
+#include "remap_taps_nv12.inc"
 #pragma unroll 1
     for (int f = 0; f < nb; f++) {
         const uint32_t b = (uint32_t)(b0 + f);

@@ -7,23 +7,15 @@
 // The frame -- item decoding, the row walk of the exact float64 chain, the rounding with the reference's NaN, the taps of a pixel and the
 // store of a lane's 4 pixels -- is flat_frame.h.  This unit adds the camera loop, the two rules and the launcher.  The cameras are kernel
 // arguments and the loop's camera number is wave-uniform: a camera's fields and its matrix of the workgroup's frame are scalar loads and
-// cost no vector register.  The lane's 4 pixels are walked inside the loop, so one matrix serves all four.
+// cost no vector register.  The lane's 4 pixels are walked inside the loop, so one matrix serves all four.  FEATHER's division of 8-bit
+// sums, div_byte_mean, is stitch_sample.h's, shared with the stitches through warp maps.
 #include "warp_stitch.h"
+#include "stitch_sample.h"
 
 #include <type_traits>
 
 namespace bevwarp {
 namespace {
-
-// floor(n / d) for 0 <= n < 2^23 and 1 <= d < 2^16 with a quotient of at most 255 (the rounded mean of bytes): n and d are floats
-// exactly, v_rcp_f32 is within one ulp and the product rounds once more, so the estimate is within 256 * 2^-22 of n / d and its
-// truncation within one of the quotient; one step either way makes it exact.
-__device__ __forceinline__ int div_byte_mean(int n, int d) {
-    int q = (int)((float)n * __builtin_amdgcn_rcpf((float)d));
-    const int r = n - q * d;
-    q += (r >= d ? 1 : 0) - (r < 0 ? 1 : 0);
-    return q;
-}
 
 template <typename T, int C, int INTERP, int BLEND>
 __global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(kWavesPerSimd, 8))) void warp_stitch_kernel(const StitchArgs a) {

@@ -459,6 +459,8 @@ def test_single_camera_kernels_code_object(tmp_path):
     flags = codeobj.makefile_flags("warp_map_planes.hip", "plane_store.inc")
     assert "-fno-fast-math" in flags and "-ffp-contract=off" in flags
     codeobj.makefile_flags("warp_map_planes.hip", "map_entry_taps.inc")
+    for header in ("remap_sample_u8x3.h", "remap_taps_u8x3.inc", "remap_frame_u8x3.inc", "tap_load.h"):  # (the sampler shared with the NV12-out unit)
+        codeobj.makefile_flags("warp_map_planes.hip", header)
 
 
 def test_stitch_kernels_code_object(tmp_path):
@@ -467,3 +469,5 @@ def test_stitch_kernels_code_object(tmp_path):
     assert len(found) == 3 * 2 * 2 * 2, len(found)    # {B, G, R frames; NV12 -> B, G, R; NV12 -> R, G, B} x interpolation x blend x {float32, 16-bit}
     codeobj.assert_lean(found)
     assert "-fno-fast-math" in codeobj.makefile_flags("warp_stitch_maps_planes.hip", "plane_store.inc")
+    for header in ("stitch_sample.h", "stitch_maps_u8x3.inc", "tap_load.h", "nv12_sample.h"):  # (the shared stitch samplers and camera loop rebuild the unit)
+        codeobj.makefile_flags("warp_stitch_maps_planes.hip", header)

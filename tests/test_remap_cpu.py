@@ -294,6 +294,8 @@ def test_map_kernels_code_object(tmp_path):
     assert len(found) == len(remap) + len(build)
     codeobj.assert_lean(found)
     codeobj.makefile_flags("warp_lens.hip", "lens_pixel.h")  # (the shared lens step rebuilds both of its users)
+    for unit in ("warp_map.hip", "warp_stitch_maps.hip"):  # (so do the shared tap loads)
+        codeobj.makefile_flags(unit, "tap_load.h")
 
 
 # ---- the ABI surface, without a device (fake pointers, never dereferenced: every call below fails validation first) ----

@@ -334,3 +334,6 @@ def test_nv12_map_kernels_code_object(tmp_path):
     codeobj.assert_lean(found)
     for header in ("map_entry.h", "map_entry_taps.inc", "plane_store.inc", "nv12_sample.h"):  # (the shared stages rebuild both of their users)
         codeobj.makefile_flags("warp_map.hip" if header.startswith("map_entry") else "warp_nv12_planes.hip", header)
+    for header in ("remap_sample_nv12.h", "remap_taps_nv12.inc", "nv12_sample.h"):  # (the NV12 map sampler, shared with the NV12-out unit)
+        for unit in ("warp_map_nv12.hip", "warp_map_nv12_out.hip"):
+            codeobj.makefile_flags(unit, header)

@@ -455,6 +455,8 @@ def test_single_camera_kernels_code_object(tmp_path):
     codeobj.assert_lean(found)
     flags = codeobj.makefile_flags("warp_map_nv12_out.hip", "nv12_store.h")
     assert "-fno-fast-math" in flags and "-ffp-contract=off" in flags
+    for header in ("remap_sample_u8x3.h", "remap_taps_u8x3.inc", "remap_frame_u8x3.inc", "remap_sample_nv12.h", "remap_taps_nv12.inc", "tap_load.h", "nv12_sample.h"):
+        codeobj.makefile_flags("warp_map_nv12_out.hip", header)  # (both shared samplers rebuild the unit)
 
 
 def test_stitch_kernels_code_object(tmp_path):
@@ -463,3 +465,5 @@ def test_stitch_kernels_code_object(tmp_path):
     assert len(found) == 3 * 2 * 2, len(found)    # {B, G, R; R, G, B; NV12} x interpolation x blend
     codeobj.assert_lean(found)
     assert "-fno-fast-math" in codeobj.makefile_flags("warp_stitch_maps_nv12_out.hip", "nv12_store.h")
+    for header in ("stitch_sample.h", "stitch_maps_u8x3.inc", "tap_load.h", "nv12_sample.h"):  # (the shared stitch samplers and camera loop rebuild the unit)
+        codeobj.makefile_flags("warp_stitch_maps_nv12_out.hip", header)

@@ -334,6 +334,52 @@ def test_stitch_maps_kernels_code_object(tmp_path):
     assert len(found) == len(frames) + len(nv12)
     codeobj.assert_lean(found)
     assert "-fno-fast-math" in codeobj.makefile_flags("warp_stitch_maps.hip", "warp_stitch_maps.h")
+    for unit in ("warp_stitch_maps.hip", "warp_stitch.hip"):  # (the shared stitch samplers rebuild every user, FEATHER's division the matrix stitch too)
+        for header in ("stitch_sample.h", "tap_load.h", "nv12_sample.h"):
+            codeobj.makefile_flags(unit, header)
+
+
+# ---- the map samplers' helpers are defined once ----
+
+def test_map_sampler_helpers_have_one_definition():
+    """The units that sample through warp maps share their helpers through headers and included text: a unit that
+    brings a copy of one back -- above all of convert_packed, whose value barrier keeps wrong pixels off the MI355X -- fails here."""
+    import glob
+    import re
+    csrc = os.path.join(ROOT, "bev_amd", "csrc")
+    code = {}
+    for path in sorted(glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")) + glob.glob(os.path.join(csrc, "*.inc"))):
+        with open(path) as f:
+            code[os.path.basename(path)] = re.sub(r"//[^\n]*", "", f.read())  # (comments may name them)
+    assert len(code) > 60
+
+    def where(pattern):
+        return sorted((name, len(re.findall(pattern, text))) for name, text in code.items() if re.search(pattern, text))
+
+    once = {r"\bint\s+div_byte_mean\s*\(": "stitch_sample.h",
+            r"\bvoid\s+load_camera_entries\s*\(": "stitch_sample.h",
+            r"\buint32_t\s+sample_inlier_nv12\s*\(": "stitch_sample.h",
+            r"\buint32_t\s+sample_entry_nv12\s*\(": "remap_sample_nv12.h",
+            r"\bstruct\s+NvTaps\b": "remap_sample_nv12.h",
+            r"\buint32_t\s+pair_at\s*\(": "remap_sample_nv12.h",
+            r"\buint32_t\s+convert_packed\s*\(": "nv12_sample.h",
+            r'\basm\s*\(\s*""\s*:\s*"\+v"\s*\(\s*g\s*\)\s*\)': "nv12_sample.h",                 # the value barrier
+            r"\bvoid\s+load_pair\s*\(": "tap_load.h",                                             # the packed 6-byte pair load
+            r"\bvoid\s+load_pair_u8x3\s*\(": "tap_load.h",
+            r"\bPixel<T, C>\s+load_at\s*\(": "tap_load.h",
+            r"\buint32_t\s+load_at\s*\(": "tap_load.h",
+            r"\buint32_t\s+sample_entry\s*\(": "remap_sample_u8x3.h",                             # the packed sampler
+            r"\bPixel<T, C>\s+sample_entry\s*\(": "warp_map.hip"}                                 # the generic one
+    for pattern, home in once.items():
+        assert where(pattern) == [(home, 1)], (pattern, where(pattern))
+    # (the bicubic unit has a sample_inlier of its own, for its 16 taps)
+    for pattern in (r"\buint32_t\s+sample_inlier\s*\(", r"\bPixel<T, C>\s+sample_inlier\s*\("):
+        assert [w for w in where(pattern) if w[0] != "warp_cubic.hip"] == [("stitch_sample.h", 1)], (pattern, where(pattern))
+    # two structs are called Taps: remap_kernel's, for every pixel type, and the packed one
+    assert where(r"\bstruct\s+Taps\b") == [("remap_sample_u8x3.h", 1), ("warp_map.hip", 1)]
+    # the 8-bit 3-channel camera loop is text that both of its kernels include, and the feather weight is written there and in the two generic loops only
+    assert where(r'#include "stitch_maps_u8x3\.inc"') == [("warp_stitch_maps_nv12_out.hip", 1), ("warp_stitch_maps_planes.hip", 1)]
+    assert where(r",\s*a\.feather\s*\)") ==[("stitch_maps_u8x3.inc", 1), ("warp_stitch.hip", 1), ("warp_stitch_maps.hip", 1)]
 
 
 # ---- the Python entries' own checks, all before a device is needed ----
