@@ -41,12 +41,24 @@ int launched(hipError_t e) { return e == hipSuccess ? BEVWARP_OK : hip_fail(e); 
 using namespace bevwarp;
 using namespace bevwarp::plan;
 
-// a plan's fields in the row kernel's arguments
-void copy_plan(WarpArgs& a, const TilePlan& p) {
+// a plan's grid in any kernel's arguments ...
+template <class Args>
+void copy_grid(Args& a, const TilePlan& p) {
     a.bw0 = p.bw0, a.tiles_x = p.tiles_x, a.tiles_per_frame = p.tiles_per_frame;
     a.tpf_magic = p.tpf_magic, a.tx_magic = p.tx_magic, a.bw0_magic = p.bw0_magic;
+}
+// ... and all its fields in the row kernel's
+void copy_plan(WarpArgs& a, const TilePlan& p) {
+    copy_grid(a, p);
     a.tile_h = p.tile_h, a.total_tiles = p.total_tiles, a.chunk = p.chunk, a.stagger = p.stagger, a.tail_split = p.tail_split;
 }
+// the frames a kernel samples (a.src and its two strides; a camera of a stitch has the same three)
+template <class Args>
+void fill_source(Args& a, const Image& s) {
+    a.src = (const uint8_t*)s.base, a.src_fs = s.fs, a.src_rs = s.rs;
+}
+// the kernels' plane format of a plane type that the checks have let through
+int plane_kind(int plane_dtype) { return plane_dtype == BEVWARP_F32 ? kPlaneF32 : (plane_dtype == BEVWARP_F16 ? kPlaneF16 : kPlaneBF16); }
 // What the flat-grid entry points (border, bicubic, NV12, NV12 planes, into NV12) share: the checks, plan_border's grid, and in the zeroed
 // arguments the shared frame's part (flat_frame.h) -- the first written image, the matrices, the grid -- and the source's sides.
 // items = 0: nothing to launch, the status is the call's.  (dst_vec_ok follows each entry point's own layout rule.)
@@ -62,8 +74,7 @@ int flat_grid_args(const Call& c, Args& a, int64_t& items) {
     a.dst = (uint8_t*)d.base, a.minv = c.minv;
     a.dst_fs = d.fs, a.dst_rs = d.rs, a.dst_h = c.dst_h, a.dst_w = c.dst_w;
     a.m_stride = c.m_count == 1 ? 0 : 9;
-    a.bw0 = p.bw0, a.tiles_x = p.tiles_x, a.tiles_per_frame = p.tiles_per_frame;
-    a.tpf_magic = p.tpf_magic, a.tx_magic = p.tx_magic, a.bw0_magic = p.bw0_magic;
+    copy_grid(a, p);
     a.src_h = c.src_h, a.src_w = c.src_w;
     items = p.total_tiles;
     return BEVWARP_OK;
@@ -92,6 +103,7 @@ int border_bytes(const double* border_value, uint8_t* bu) {
     float bf[4];
     return border_values(border_value, 3, bf, bu);
 }
+uint32_t packed4(const uint8_t* b) { return (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24); }  // (up to 4 channels likewise)
 uint32_t packed3(const uint8_t* b) { return (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16); }
 // The plane kernels of the NV12 sources sample B, G, R: sampled channel k is the destination's channel k (BGR) or 2 - k (RGB), with that
 // channel's plane, scale, bias and border value -- the channel order is nothing but this table (a: the kernel's ch_off, pscale, pbias;
@@ -121,8 +133,7 @@ int remap_grid_args(const Call& c, Args& a, int first_map, int interp, int borde
     memset(&a, 0, sizeof(a));
     const Image& d = c.writes[0].im;
     a.dst = (uint8_t*)d.base, a.dst_fs = d.fs, a.dst_rs = d.rs, a.dst_h = c.dst_h, a.dst_w = c.dst_w;
-    a.bw0 = p.bw0, a.tiles_x = p.tiles_x, a.tiles_per_frame = p.tiles_per_frame;
-    a.tpf_magic = p.tpf_magic, a.tx_magic = p.tx_magic, a.bw0_magic = p.bw0_magic;
+    copy_grid(a, p);
     a.src_h = c.src_h, a.src_w = c.src_w;
     if (border_mode != BEVWARP_BORDER_CONSTANT && border_mode != BEVWARP_BORDER_TRANSPARENT) {
         const plan::BorderPeriod px = plan::border_period(border_mode, c.src_w), py = plan::border_period(border_mode, c.src_h);
@@ -134,6 +145,53 @@ int remap_grid_args(const Call& c, Args& a, int first_map, int interp, int borde
     if (ifr) a.frac = (const uint8_t*)ifr->base, a.frac_fs = ifr->fs, a.frac_rs = ifr->rs;
     a.batch = c.batch, a.frames_per_item = p.frames_per_item;
     a.map_vec_ok = plan::map_vec_ok(ixy, ifr);
+    items = p.total_tiles;
+    return BEVWARP_OK;
+}
+// One camera of bevwarp_warp_stitch in the kernel's arguments, from its checked call (stitch_call); align: pixel_load_align of its pixels ...
+void fill_camera(StitchCamera& s, const Call& c, int align) {
+    fill_source(s, c.reads[0].im);
+    s.minv = c.minv, s.src_h = c.src_h, s.src_w = c.src_w, s.m_stride = c.m_count == 1 ? 0 : 9;
+    s.src_vec_ok = plan::pixel_loads_ok(c.reads[0].im, align);
+}
+// ... and of a stitch through maps (stitch_maps_call and its kin): what the call reads -- the frames (NV12: Y, then the pairs), the xy plane
+// and, bilinear, the frac plane -- and the two flags of its lane-wide accesses
+void fill_camera(StitchMapCamera& s, const Call& c, int align) {
+    const int first_map = c.even_src ? 2 : 1;
+    const Image &src = c.reads[0].im, &ixy = c.reads[first_map].im, *ifr = c.n_reads > first_map + 1 ? &c.reads[first_map + 1].im : nullptr;
+    fill_source(s, src);
+    if (c.even_src) {
+        const Image& uv = c.reads[1].im;
+        s.uv = (const uint8_t*)uv.base, s.uv_fs = uv.fs, s.uv_rs = uv.rs;
+    }
+    s.xy = (const uint8_t*)ixy.base, s.xy_fs = ixy.fs, s.xy_rs = ixy.rs;  // (a shared map: read_map_planes has zeroed its frame strides)
+    if (ifr) s.frac = (const uint8_t*)ifr->base, s.frac_fs = ifr->fs, s.frac_rs = ifr->rs;
+    s.src_h = c.src_h, s.src_w = c.src_w;
+    s.src_vec_ok = plan::pixel_loads_ok(src, align);
+    s.map_vec_ok = plan::map_vec_ok(ixy, ifr);
+}
+// What the seven stitches share: stitch_check over the cameras' calls (describe(cams[k]); values: the HOST arrays, the border value first --
+// a stitch with a border mode passes it under the constant border only, `fill`), and for a call that goes on to a launch, in the zeroed
+// arguments, the canvas (the image every camera's checked call writes), the grid, the feather width, the border pixel, and every camera
+// from its checked call: what was checked is what is launched.  calls: BEVWARP_STITCH_MAX_CAMERAS entries of the caller's, which reads the
+// other written images from them.  dtype, channels: of the sampled pixels.  items = 0: nothing to launch, the status is the call's.
+template <class Args, class Camera, class Describe>
+int stitch_grid_args(Args& a, Call* calls, int64_t& items, const Camera* cams, int n_cams, int blend, int feather, Describe describe,
+                     std::initializer_list<plan::HostValues> values, int batch, int dst_h, int dst_w, int dtype, int channels, bool fill) {
+    items = 0;
+    TilePlan p;
+    const int st = plan::stitch_check(cams, n_cams, blend, feather, describe, values, batch, dst_h, dst_w, kBorderTileW, kBorderTileH, p, calls);
+    if (st != BEVWARP_OK || batch == 0) return st;
+    memset(&a, 0, sizeof(a));
+    const Image& d = calls[0].writes[0].im;
+    a.dst = (uint8_t*)d.base, a.dst_fs = d.fs, a.dst_rs = d.rs, a.dst_h = dst_h, a.dst_w = dst_w;
+    copy_grid(a, p);
+    a.dst_vec_ok = plan::wide_stores_ok(d, plan::store_align(dtype, channels, false));
+    for (int k = 0; k < n_cams; k++) fill_camera(a.cams[k], calls[k], plan::pixel_load_align(dtype, channels));
+    a.n_cams = n_cams, a.feather = feather, a.fill = fill;
+    uint8_t bu[4];  // (stitch_check has found the border value finite)
+    border_values(values.begin()->v, channels, a.bv_f, bu);
+    a.bv_u8 = packed4(bu);
     items = p.total_tiles;
     return BEVWARP_OK;
 }
@@ -261,7 +319,7 @@ int bevwarp_warp_border(const void* src, void* dst, int batch, int src_h, int sr
     int64_t items;
     const int st = flat_grid_args(c, a, items);
     if (!items) return st;
-    a.src = (const uint8_t*)src, a.src_fs = src_frame_stride, a.src_rs = src_row_stride;
+    fill_source(a, c.reads[0].im);
     // the 4 taps of a bicubic window reach one index beyond a saturated one: a period plan of their own
     const plan::BorderPeriod px = cubic ? cubic::window_period(border_mode, src_w) : plan::border_period(border_mode, src_w);
     const plan::BorderPeriod py = cubic ? cubic::window_period(border_mode, src_h) : plan::border_period(border_mode, src_h);
@@ -287,8 +345,8 @@ int bevwarp_warp_lens(const void* src, void* dst, int batch, int src_h, int src_
     const bool transparent = border_mode == BEVWARP_BORDER_TRANSPARENT;
     uint8_t bu[4];  // (border_value is read by the constant border only)
     if (border_values(transparent ? nullptr : border_value, channels, a.bv_f, bu) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
-    a.bv_u8 = (uint32_t)bu[0] | ((uint32_t)bu[1] << 8) | ((uint32_t)bu[2] << 16) | ((uint32_t)bu[3] << 24);
-    a.src = (const uint8_t*)src, a.src_fs = src_frame_stride, a.src_rs = src_row_stride;
+    a.bv_u8 = packed4(bu);
+    fill_source(a, c.reads[0].im);
     memcpy(a.lens, lens, sizeof(a.lens));
     a.r2_max = r2_max;
     a.dst_vec_ok = plan::wide_stores_ok(c.writes[0], plan::store_align(dtype, channels, false));
@@ -308,8 +366,7 @@ int bevwarp_build_map(const double* M, int m_count, const double* lens, double r
     a.dst = (uint8_t*)map_xy, a.minv = M, a.m_stride = 9;
     a.dst_fs = m_count == 1 ? 0 : xy_frame_stride, a.dst_rs = xy_row_stride, a.dst_h = dst_h, a.dst_w = dst_w;
     a.frac = linear ? (uint8_t*)map_frac : nullptr, a.frac_fs = m_count == 1 ? 0 : frac_frame_stride, a.frac_rs = frac_row_stride;
-    a.bw0 = p.bw0, a.tiles_x = p.tiles_x, a.tiles_per_frame = p.tiles_per_frame;
-    a.tpf_magic = p.tpf_magic, a.tx_magic = p.tx_magic, a.bw0_magic = p.bw0_magic;
+    copy_grid(a, p);
     const Image ixy = Frames{map_xy, a.dst_fs, xy_row_stride}.image(dst_h, (uint64_t)dst_w * 4, m_count);
     const Image ifr = Frames{map_frac, a.frac_fs, frac_row_stride}.image(dst_h, (uint64_t)dst_w * 2, m_count);
     a.dst_vec_ok = plan::map_vec_ok(ixy, linear ? &ifr : nullptr);
@@ -330,8 +387,8 @@ int bevwarp_remap(const void* src, void* dst, int batch, int src_h, int src_w, i
     if (!items) return st;
     uint8_t bu[4];  // (border_value is read by the constant border only)
     if (border_values(border_mode == BEVWARP_BORDER_CONSTANT ? border_value : nullptr, channels, a.bv_f, bu) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
-    a.bv_u8 = (uint32_t)bu[0] | ((uint32_t)bu[1] << 8) | ((uint32_t)bu[2] << 16) | ((uint32_t)bu[3] << 24);
-    a.src = (const uint8_t*)src, a.src_fs = src_frame_stride, a.src_rs = src_row_stride;
+    a.bv_u8 = packed4(bu);
+    fill_source(a, c.reads[0].im);
     a.dst_vec_ok = plan::wide_stores_ok(c.writes[0], plan::store_align(dtype, channels, false));
     a.src_vec_ok = plan::pixel_loads_ok(c.reads[0].im, plan::pixel_load_align(dtype, channels));
     return launched(launch_remap(a, dtype, channels, interp, border_mode, items, (hipStream_t)stream));
@@ -371,7 +428,7 @@ int bevwarp_remap_nv12_planes(const void* y, const void* uv, void* dst, int batc
     uint8_t bu[4];  // (in the destination's channel order, as given; read by the constant border only)
     if (border_bytes(border_mode == BEVWARP_BORDER_CONSTANT ? border_value : nullptr, bu) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
     a.dst_vec_ok = plan::wide_stores_ok(c.writes[0], plan::store_align(BEVWARP_U8, 3, true, c.writes[0].elem));
-    a.plane = plane_dtype == BEVWARP_F32 ? kPlaneF32 : (plane_dtype == BEVWARP_F16 ? kPlaneF16 : kPlaneBF16);
+    a.plane = plane_kind(plane_dtype);
     uint8_t bs[3];
     if (sampled_channel_table(a, rgb_order, dst_plane_stride, scale, bias, bu, bs) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
     fill_nv12_source(a, c);
@@ -382,98 +439,45 @@ int bevwarp_remap_nv12_planes(const void* y, const void* uv, void* dst, int batc
 int bevwarp_warp_stitch(const bevwarp_camera* cams, int n_cams, void* dst, int batch, int dst_h, int dst_w, int channels, int64_t dst_frame_stride,
                         int64_t dst_row_stride, int dtype, int interp, int blend, int feather, int border_mode, const double* border_value, void* stream) {
     const Frames d = {dst, dst_frame_stride, dst_row_stride};
-    TilePlan p;
-    const int st = plan::stitch_status(cams, n_cams, d, batch, dst_h, dst_w, channels, dtype, interp, blend, feather, border_mode, border_value, kBorderTileW,
-                                       kBorderTileH, p);
-    if (st != BEVWARP_OK || batch == 0) return st;
+    const bool fill = border_mode == BEVWARP_BORDER_CONSTANT;  // (border_value is read by the constant border only)
+    Call calls[BEVWARP_STITCH_MAX_CAMERAS];
     StitchArgs a;
-    memset(&a, 0, sizeof(a));
-    a.dst = (uint8_t*)dst, a.dst_fs = dst_frame_stride, a.dst_rs = dst_row_stride, a.dst_h = dst_h, a.dst_w = dst_w;
-    a.bw0 = p.bw0, a.tiles_x = p.tiles_x, a.tiles_per_frame = p.tiles_per_frame;
-    a.tpf_magic = p.tpf_magic, a.tx_magic = p.tx_magic, a.bw0_magic = p.bw0_magic;
-    const int elem = dtype == BEVWARP_U8 ? 1 : 4;
-    a.dst_vec_ok = plan::wide_stores_ok(d.image(dst_h, (uint64_t)dst_w * channels * elem, batch), plan::store_align(dtype, channels, false));
-    for (int k = 0; k < n_cams; k++) {
-        const bevwarp_camera& c = cams[k];
-        StitchCamera& s = a.cams[k];
-        s.src = (const uint8_t*)c.src, s.minv = c.M_inv, s.src_fs = c.frame_stride, s.src_rs = c.row_stride;
-        s.src_h = c.src_h, s.src_w = c.src_w, s.m_stride = c.m_count == 1 ? 0 : 9;
-        s.src_vec_ok = plan::pixel_loads_ok(Frames{c.src, c.frame_stride, c.row_stride}.image(c.src_h, (uint64_t)c.src_w * channels * elem, batch),
-                                            plan::pixel_load_align(dtype, channels));
-    }
-    a.n_cams = n_cams, a.feather = feather;
-    a.fill = border_mode == BEVWARP_BORDER_CONSTANT;
-    uint8_t bu[4];  // (border_value is read by the constant border only; stitch_status has found it finite)
-    border_values(a.fill ? border_value : nullptr, channels, a.bv_f, bu);
-    a.bv_u8 = (uint32_t)bu[0] | ((uint32_t)bu[1] << 8) | ((uint32_t)bu[2] << 16) | ((uint32_t)bu[3] << 24);
-    return launched(launch_warp_stitch(a, dtype, channels, interp, blend, p.total_tiles, (hipStream_t)stream));
+    int64_t items;
+    const int st = stitch_grid_args(
+        a, calls, items, cams, n_cams, blend, feather, [&](const bevwarp_camera& k) { return plan::stitch_call(k, d, batch, dst_h, dst_w, channels, dtype, interp, blend, border_mode); },
+        {{fill ? border_value : nullptr, channels}}, batch, dst_h, dst_w, dtype, channels, fill);
+    if (!items) return st;
+    return launched(launch_warp_stitch(a, dtype, channels, interp, blend, items, (hipStream_t)stream));
 }
-
-}  // extern "C"
-
-namespace {
-// What the two stitches through maps share once their checks have passed: the canvas, the grid, the feather width and the border pixel in the
-// zeroed arguments, and per camera what its call (stitch_maps_call / stitch_maps_nv12_call: reads[first_map] is the xy plane) reads.
-template <class MakeCall>
-void stitch_maps_args(StitchMapsArgs& a, const TilePlan& p, const bevwarp_map_camera* cams, int n_cams, const Frames& d, int batch, int dst_h, int dst_w, int channels,
-                      int dtype, int interp, int feather, int border_mode, const double* border_value, int first_map, MakeCall make_call) {
-    memset(&a, 0, sizeof(a));
-    a.dst = (uint8_t*)d.base, a.dst_fs = d.fs, a.dst_rs = d.rs, a.dst_h = dst_h, a.dst_w = dst_w;
-    a.bw0 = p.bw0, a.tiles_x = p.tiles_x, a.tiles_per_frame = p.tiles_per_frame;
-    a.tpf_magic = p.tpf_magic, a.tx_magic = p.tx_magic, a.bw0_magic = p.bw0_magic;
-    const int elem = dtype == BEVWARP_U8 ? 1 : 4;
-    a.dst_vec_ok = plan::wide_stores_ok(d.image(dst_h, (uint64_t)dst_w * channels * elem, batch), plan::store_align(dtype, channels, false));
-    for (int k = 0; k < n_cams; k++) {
-        const Call c = make_call(cams[k]);
-        StitchMapCamera& s = a.cams[k];
-        const Image &src = c.reads[0].im, &ixy = c.reads[first_map].im, *ifr = (interp == BEVWARP_LINEAR) ? &c.reads[first_map + 1].im : nullptr;
-        s.src = (const uint8_t*)src.base, s.src_fs = src.fs, s.src_rs = src.rs;
-        if (first_map == 2) {
-            const Image& uv = c.reads[1].im;
-            s.uv = (const uint8_t*)uv.base, s.uv_fs = uv.fs, s.uv_rs = uv.rs;
-        }
-        s.xy = (const uint8_t*)ixy.base, s.xy_fs = ixy.fs, s.xy_rs = ixy.rs;  // (a shared map: read_map_planes has zeroed its frame strides)
-        if (ifr) s.frac = (const uint8_t*)ifr->base, s.frac_fs = ifr->fs, s.frac_rs = ifr->rs;
-        s.src_h = c.src_h, s.src_w = c.src_w;
-        s.src_vec_ok = plan::pixel_loads_ok(src, plan::pixel_load_align(dtype, channels));
-        s.map_vec_ok = plan::map_vec_ok(ixy, ifr);
-    }
-    a.n_cams = n_cams, a.feather = feather;
-    a.fill = border_mode == BEVWARP_BORDER_CONSTANT;
-    uint8_t bu[4];  // (border_value is read by the constant border only; the status has found it finite)
-    border_values(a.fill ? border_value : nullptr, channels, a.bv_f, bu);
-    a.bv_u8 = (uint32_t)bu[0] | ((uint32_t)bu[1] << 8) | ((uint32_t)bu[2] << 16) | ((uint32_t)bu[3] << 24);
-}
-}  // namespace
-
-extern "C" {
 
 int bevwarp_stitch_maps(const bevwarp_map_camera* cams, int n_cams, void* dst, int batch, int dst_h, int dst_w, int channels, int64_t dst_frame_stride,
                         int64_t dst_row_stride, int dtype, int interp, int blend, int feather, int border_mode, const double* border_value, void* stream) {
     const Frames d = {dst, dst_frame_stride, dst_row_stride};
-    TilePlan p;
-    const int st = plan::stitch_maps_status(cams, n_cams, d, batch, dst_h, dst_w, channels, dtype, interp, blend, feather, border_mode, border_value, kBorderTileW,
-                                            kBorderTileH, p);
-    if (st != BEVWARP_OK || batch == 0) return st;
+    const bool fill = border_mode == BEVWARP_BORDER_CONSTANT;  // (border_value is read by the constant border only)
+    Call calls[BEVWARP_STITCH_MAX_CAMERAS];
     StitchMapsArgs a;
-    stitch_maps_args(a, p, cams, n_cams, d, batch, dst_h, dst_w, channels, dtype, interp, feather, border_mode, border_value, 1, [&](const bevwarp_map_camera& k) {
-        return plan::stitch_maps_call(k, d, batch, dst_h, dst_w, channels, dtype, interp, blend, border_mode);
-    });
-    return launched(launch_stitch_maps(a, dtype, channels, interp, blend, p.total_tiles, (hipStream_t)stream));
+    int64_t items;
+    const int st = stitch_grid_args(
+        a, calls, items, cams, n_cams, blend, feather,
+        [&](const bevwarp_map_camera& k) { return plan::stitch_maps_call(k, d, batch, dst_h, dst_w, channels, dtype, interp, blend, border_mode); },
+        {{fill ? border_value : nullptr, channels}}, batch, dst_h, dst_w, dtype, channels, fill);
+    if (!items) return st;
+    return launched(launch_stitch_maps(a, dtype, channels, interp, blend, items, (hipStream_t)stream));
 }
 
 int bevwarp_stitch_maps_nv12(const bevwarp_map_camera* cams, int n_cams, void* dst, int batch, int dst_h, int dst_w, int64_t dst_frame_stride, int64_t dst_row_stride,
                              int interp, int blend, int feather, int rgb_order, int border_mode, const double* border_value, void* stream) {
     const Frames d = {dst, dst_frame_stride, dst_row_stride};
-    TilePlan p;
-    const int st = plan::stitch_maps_nv12_status(cams, n_cams, d, batch, dst_h, dst_w, interp, blend, feather, rgb_order, border_mode, border_value, kBorderTileW,
-                                                 kBorderTileH, p);
-    if (st != BEVWARP_OK || batch == 0) return st;
+    const bool fill = border_mode == BEVWARP_BORDER_CONSTANT;  // (border_value is read by the constant border only)
+    Call calls[BEVWARP_STITCH_MAX_CAMERAS];
     StitchMapsArgs a;  // (the border value is in the destination's channel order, as given: it is not converted)
-    stitch_maps_args(a, p, cams, n_cams, d, batch, dst_h, dst_w, 3, BEVWARP_U8, interp, feather, border_mode, border_value, 2, [&](const bevwarp_map_camera& k) {
-        return plan::stitch_maps_nv12_call(k, d, batch, dst_h, dst_w, interp, blend, rgb_order, border_mode);
-    });
-    return launched(launch_stitch_maps_nv12(a, interp, blend, rgb_order, p.total_tiles, (hipStream_t)stream));
+    int64_t items;
+    const int st = stitch_grid_args(
+        a, calls, items, cams, n_cams, blend, feather,
+        [&](const bevwarp_map_camera& k) { return plan::stitch_maps_nv12_call(k, d, batch, dst_h, dst_w, interp, blend, rgb_order, border_mode); },
+        {{fill ? border_value : nullptr, 3}}, batch, dst_h, dst_w, BEVWARP_U8, 3, fill);
+    if (!items) return st;
+    return launched(launch_stitch_maps_nv12(a, interp, blend, rgb_order, items, (hipStream_t)stream));
 }
 
 int bevwarp_warp_nv12(const void* y, const void* uv, void* dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int64_t y_frame_stride,
@@ -506,7 +510,7 @@ int bevwarp_warp_nv12_planes(const void* y, const void* uv, void* dst, int batch
     uint8_t bu[4];  // (in the destination's channel order, as given)
     if (border_bytes(border_value, bu) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
     a.dst_vec_ok = plan::wide_stores_ok(c.writes[0], plan::store_align(BEVWARP_U8, 3, true, c.writes[0].elem));
-    a.plane = plane_dtype == BEVWARP_F32 ? kPlaneF32 : (plane_dtype == BEVWARP_F16 ? kPlaneF16 : kPlaneBF16);
+    a.plane = plane_kind(plane_dtype);
     uint8_t bs[3];
     if (sampled_channel_table(a, rgb_order, dst_plane_stride, scale, bias, bu, bs) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
     fill_nv12_source(a, c);
@@ -533,7 +537,7 @@ int warp_nv12_out_impl(const Call& c, int interp, int rgb_order, const double* b
     if (nv12_src)
         fill_nv12_source(a, c);
     else
-        a.src = (const uint8_t*)c.reads[0].im.base, a.src_fs = c.reads[0].im.fs, a.src_rs = c.reads[0].im.rs;
+        fill_source(a, c.reads[0].im);
     a.border = packed3(bu);
     return launched(launch_warp_nv12_out(a, nv12_src, interp, rgb_order, items, (hipStream_t)stream));
 }
@@ -578,45 +582,47 @@ int remap_nv12_out_impl(const Call& c, int interp, int border_mode, int rgb_orde
     if (nv12_src)
         fill_nv12_source(a, c);
     else
-        a.src = (const uint8_t*)c.reads[0].im.base, a.src_fs = c.reads[0].im.fs, a.src_rs = c.reads[0].im.rs;
+        fill_source(a, c.reads[0].im);
     a.bv_u8 = packed3(bu);
     return launched(launch_remap_nv12_out(a, nv12_src, interp, border_mode, rgb_order, items, (hipStream_t)stream));
 }
 // bevwarp_stitch_maps_to_nv12 and bevwarp_stitch_maps_nv12_to_nv12
 int stitch_maps_nv12_out_impl(bool nv12_src, const bevwarp_map_camera* cams, int n_cams, const Frames& dy, const Frames& duv, int batch, int dst_h, int dst_w, int interp,
                               int blend, int feather, int rgb_order, const double* border_value, void* stream) {
-    TilePlan p;
-    const int st = plan::stitch_maps_nv12_out_status(nv12_src, cams, n_cams, dy, duv, batch, dst_h, dst_w, interp, blend, feather, rgb_order, border_value, kBorderTileW,
-                                                     kBorderTileH, p);
-    if (st != BEVWARP_OK || batch == 0) return st;
+    Call calls[BEVWARP_STITCH_MAX_CAMERAS];
     StitchMapsNv12OutArgs a;  // (the border value is a pixel in the sampled pixel's channel order: the kernel converts it like any other)
-    stitch_maps_args(a, p, cams, n_cams, dy, batch, dst_h, dst_w, 3, BEVWARP_U8, interp, feather, BEVWARP_BORDER_CONSTANT, border_value, nv12_src ? 2 : 1,
-                     [&](const bevwarp_map_camera& k) { return plan::stitch_maps_nv12_out_call(nv12_src, k, dy, duv, batch, dst_h, dst_w, interp, blend, rgb_order); });
-    const Nv12Images d = plan::nv12_images(dy, duv, dst_h, dst_w, batch);
-    a.dst_uv = (uint8_t*)d.uv.base, a.duv_fs = d.uv.fs, a.duv_rs = d.uv.rs;
-    a.dst_vec_ok = plan::wide_stores_ok(d.y, 4);  // per plane, as bevwarp_warp_to_nv12
-    a.uv_vec_ok = plan::wide_stores_ok(d.uv, 4);
-    return launched(launch_stitch_maps_nv12_out(a, nv12_src, interp, blend, rgb_order, p.total_tiles, (hipStream_t)stream));
+    int64_t items;
+    const int st = stitch_grid_args(
+        a, calls, items, cams, n_cams, blend, feather,
+        [&](const bevwarp_map_camera& k) { return plan::stitch_maps_nv12_out_call(nv12_src, k, dy, duv, batch, dst_h, dst_w, interp, blend, nv12_src ? 0 : rgb_order); },
+        {{border_value, 3}}, batch, dst_h, dst_w, BEVWARP_U8, 3, true);
+    if (!items) return st;
+    const Image &y = calls[0].writes[0].im, &uv = calls[0].writes[1].im;
+    a.dst_uv = (uint8_t*)uv.base, a.duv_fs = uv.fs, a.duv_rs = uv.rs;
+    a.dst_vec_ok = plan::wide_stores_ok(y, 4);  // per plane, as bevwarp_warp_to_nv12
+    a.uv_vec_ok = plan::wide_stores_ok(uv, 4);
+    return launched(launch_stitch_maps_nv12_out(a, nv12_src, interp, blend, rgb_order, items, (hipStream_t)stream));
 }
 // bevwarp_stitch_maps_planes and bevwarp_stitch_maps_nv12_planes
 int stitch_maps_planes_impl(bool nv12_src, const bevwarp_map_camera* cams, int n_cams, const Frames& d, int64_t dst_plane_stride, int batch, int dst_h, int dst_w,
                             int interp, int blend, int feather, int rgb_order, const double* border_value, const double* scale, const double* bias, int plane_dtype,
                             void* stream) {
-    TilePlan p;
-    const int st = plan::stitch_maps_planes_status(nv12_src, cams, n_cams, d, dst_plane_stride, batch, dst_h, dst_w, interp, blend, feather, rgb_order, border_value,
-                                                   scale, bias, plane_dtype, kBorderTileW, kBorderTileH, p);
-    if (st != BEVWARP_OK || batch == 0) return st;
+    Call calls[BEVWARP_STITCH_MAX_CAMERAS];
     StitchMapsPlanesArgs a;  // (border value, scale and bias are in the planes' channel order: the kernel converts NV12 taps to that order)
-    auto make_call = [&](const bevwarp_map_camera& k) {
-        return plan::stitch_maps_planes_call(nv12_src, k, d, dst_plane_stride, batch, dst_h, dst_w, interp, blend, nv12_src ? rgb_order : 0, plane_dtype);
-    };
-    stitch_maps_args(a, p, cams, n_cams, d, batch, dst_h, dst_w, 3, BEVWARP_U8, interp, feather, BEVWARP_BORDER_CONSTANT, border_value, nv12_src ? 2 : 1, make_call);
-    const WrittenImage w = make_call(cams[0]).writes[0];
+    int64_t items;
+    const int st = stitch_grid_args(
+        a, calls, items, cams, n_cams, blend, feather,
+        [&](const bevwarp_map_camera& k) {
+            return plan::stitch_maps_planes_call(nv12_src, k, d, dst_plane_stride, batch, dst_h, dst_w, interp, blend, nv12_src ? rgb_order : 0, plane_dtype);
+        },
+        {{border_value, 3}, {scale, 3}, {bias, 3}}, batch, dst_h, dst_w, BEVWARP_U8, 3, true);
+    if (!items) return st;
+    const WrittenImage& w = calls[0].writes[0];
     a.dst_vec_ok = plan::wide_stores_ok(w, plan::store_align(BEVWARP_U8, 3, true, w.elem));
-    a.plane = plane_dtype == BEVWARP_F32 ? kPlaneF32 : (plane_dtype == BEVWARP_F16 ? kPlaneF16 : kPlaneBF16);
+    a.plane = plane_kind(plane_dtype);
     uint8_t bu[4] = {(uint8_t)a.bv_u8, (uint8_t)(a.bv_u8 >> 8), (uint8_t)(a.bv_u8 >> 16), 0}, bs[3];
-    sampled_channel_table(a, 0, dst_plane_stride, scale, bias, bu, bs);  // (the identity; the status has found scale and bias finite)
-    return launched(launch_stitch_maps_planes(a, nv12_src, interp, blend, rgb_order, p.total_tiles, (hipStream_t)stream));
+    sampled_channel_table(a, 0, dst_plane_stride, scale, bias, bu, bs);  // (the identity; stitch_check has found scale and bias finite)
+    return launched(launch_stitch_maps_planes(a, nv12_src, interp, blend, rgb_order, items, (hipStream_t)stream));
 }
 }  // namespace
 
@@ -673,10 +679,10 @@ int bevwarp_remap_planes(const void* src, void* dst, int batch, int src_h, int s
     uint8_t bu[4];  // (the 8-bit border pixel in the frames' channel order; read by the constant border only)
     if (border_bytes(border_mode == BEVWARP_BORDER_CONSTANT ? border_value : nullptr, bu) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
     a.dst_vec_ok = plan::wide_stores_ok(c.writes[0], plan::store_align(BEVWARP_U8, 3, true, c.writes[0].elem));
-    a.plane = plane_dtype == BEVWARP_F32 ? kPlaneF32 : (plane_dtype == BEVWARP_F16 ? kPlaneF16 : kPlaneBF16);
+    a.plane = plane_kind(plane_dtype);
     uint8_t bs[3];  // (plane k is channel k: the table is the identity)
     if (sampled_channel_table(a, 0, dst_plane_stride, scale, bias, bu, bs) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
-    a.src = (const uint8_t*)src, a.src_fs = src_frame_stride, a.src_rs = src_row_stride;
+    fill_source(a, c.reads[0].im);
     a.bv_u8 = packed3(bs);
     return launched(launch_remap_planes(a, interp, border_mode, items, (hipStream_t)stream));
 }
@@ -729,10 +735,9 @@ int bevwarp_warp_planes(const void* src, void* dst, int batch, int src_h, int sr
                         int64_t dst_row_stride, const double* M_inv, int m_count, int dtype, int interp, const double* border_value,
                         const double* scale, const double* bias, int plane_dtype, void* stream) {
     if (plane_dtype != BEVWARP_F32 && plane_dtype != BEVWARP_F16 && plane_dtype != BEVWARP_BF16) return BEVWARP_ERR_UNSUPPORTED;
-    const int plane_elem = plane_dtype == BEVWARP_F32 ? 4 : 2;
     return warp_impl(plan::warp_call({src, src_frame_stride, src_row_stride}, {dst, dst_frame_stride, dst_row_stride}, {batch, src_h, src_w, dst_h, dst_w, m_count, M_inv},
-                                     channels, dtype, interp, false, plane_elem, dst_plane_stride),
-                     channels, dtype, interp, border_value, stream, plane_dtype == BEVWARP_F32 ? kPlaneF32 : (plane_dtype == BEVWARP_F16 ? kPlaneF16 : kPlaneBF16), scale, bias);
+                                     channels, dtype, interp, false, plan::plane_elem_size(plane_dtype), dst_plane_stride),
+                     channels, dtype, interp, border_value, stream, plane_kind(plane_dtype), scale, bias);
 }
 
 int bevwarp_composite(const void* bg, const void* fg, const void* mask, void* out, int64_t n, void* stream) {

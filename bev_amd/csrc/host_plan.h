@@ -1,9 +1,12 @@
 // host_plan.h -- what the C ABI decides before a launch, as plain C++17 (no HIP): the argument checks and the launch geometry.
-// bevwarp_api.hip is its only user in the library; tests/host_plan_driver.cpp (and lens_plan_driver.cpp, stitch_plan_driver.cpp, remap_plan_driver.cpp, remap_nv12_plan_driver.cpp, stitch_maps_plan_driver.cpp, remap_nv12_out_plan_driver.cpp, map_planes_plan_driver.cpp) compile it
-// with g++ under the address and undefined-behaviour sanitizers, and tests/golden/launch_plans.json pins every field of the plans.  Not installed.
+// bevwarp_api.hip is its only user in the library; the drivers of tests/ (every *_plan_driver.cpp, the three map-stitch ones through
+// plan_driver_io.h) compile it with g++ under the address and undefined-behaviour sanitizers, and tests/golden/launch_plans.json pins
+// every field of the plans.  Not installed.
 #pragma once
 #include <math.h>
 #include <stdint.h>
+
+#include <initializer_list>
 
 #include "bevwarp.h"
 
@@ -109,7 +112,7 @@ struct Nv12Images {
 inline Nv12Images nv12_images(Frames y, Frames uv, int h, int w, int batch) { return {y.image(h, (uint64_t)w, batch), uv.image(h / 2, (uint64_t)w, batch)}; }
 
 // What the checks need of one entry point's arguments.  The functions of the last part of this section describe the entry points in
-// these terms; bevwarp_api.hip and the tests' drivers (tests/host_plan_driver.cpp, tests/lens_plan_driver.cpp) build their calls with them.
+// these terms; bevwarp_api.hip and the tests' drivers (tests/*_plan_driver.cpp) build their calls with them.
 struct Sizes {  // (what every entry point passes besides its images and its format)
     int batch, src_h, src_w, dst_h, dst_w, m_count;
     const double* minv;
@@ -284,14 +287,8 @@ inline int points_lens_status(const void* in, const void* out, const void* resid
     // (last: the kernel moves a point as one 8- or 16-byte unit and a residual as one value)
     return (((uintptr_t)in | (uintptr_t)out) % (2 * esz) || (uintptr_t)residual % esz) ? BEVWARP_ERR_BAD_ARG : BEVWARP_OK;
 }
-// bevwarp_warp_stitch, one camera of it: that camera's frames against the canvas -- bevwarp_warp's images and formats without bicubic, with
-// the two blend rules and the constant and the transparent border.  (stitch_status below runs the checks over all cameras.)
-inline Call stitch_call(const bevwarp_camera& k, Frames dst, int batch, int dst_h, int dst_w, int channels, int dtype, int interp, int blend, int border_mode) {
-    Call c = warp_call({k.src, k.frame_stride, k.row_stride}, dst, {batch, k.src_h, k.src_w, dst_h, dst_w, k.m_count, k.M_inv}, channels, dtype, interp, false);
-    c.format_ok = c.format_ok && (blend == BEVWARP_STITCH_OVER || blend == BEVWARP_STITCH_FEATHER) &&
-                  (border_mode == BEVWARP_BORDER_CONSTANT || border_mode == BEVWARP_BORDER_TRANSPARENT);
-    return c;
-}
+// The element size of a plane type (BEVWARP_F32 | BEVWARP_F16 | BEVWARP_BF16), or 1 for none of the three
+inline int plane_elem_size(int plane_dtype) { return plane_dtype == BEVWARP_F32 ? 4 : ((plane_dtype == BEVWARP_F16 || plane_dtype == BEVWARP_BF16) ? 2 : 1); }
 // What the NV12 entry points share: nearest or bilinear, B, G, R or R, G, B.  Each adds its images.
 inline Call nv12_family_call(const Sizes& z, int interp, int rgb_order, bool plane_ok = true) {
     return {z, (interp == BEVWARP_NEAREST || interp == BEVWARP_LINEAR) && (rgb_order == 0 || rgb_order == 1) && plane_ok, false};
@@ -306,7 +303,7 @@ inline Call nv12_call(Frames y, Frames uv, Frames dst, const Sizes& z, int inter
 // bevwarp_warp_nv12_planes: to three planes of `plane_dtype` (BEVWARP_F32 | BEVWARP_F16 | BEVWARP_BF16), dst_ps apart.  A plane type the entry
 // point does not take has 1-byte elements here: it asks no alignment, because the layout is looked at first.
 inline Call nv12_planes_call(Frames y, Frames uv, Frames dst, int64_t dst_ps, const Sizes& z, int interp, int rgb_order, int plane_dtype) {
-    const int elem = plane_dtype == BEVWARP_F32 ? 4 : ((plane_dtype == BEVWARP_F16 || plane_dtype == BEVWARP_BF16) ? 2 : 1);
+    const int elem = plane_elem_size(plane_dtype);
     Call c = nv12_family_call(z, interp, rgb_order, elem != 1);  // (1: none of the three)
     c.read_nv12(y, uv);
     c.write_planes(dst.image(z.dst_h, (uint64_t)z.dst_w * elem, z.batch), elem, 3, dst_ps);
@@ -368,7 +365,7 @@ inline Call remap_nv12_to_nv12_call(Frames y, Frames uv, Frames dst_y, Frames ds
 // map planes; reads[1], reads[2]: the xy and the frac plane
 inline Call remap_planes_call(Frames src, Frames dst, int64_t dst_ps, Frames xy, Frames frac, const Sizes& z, int map_count, int interp, int border_mode,
                               int plane_dtype) {
-    const int elem = plane_dtype == BEVWARP_F32 ? 4 : ((plane_dtype == BEVWARP_F16 || plane_dtype == BEVWARP_BF16) ? 2 : 1);
+    const int elem = plane_elem_size(plane_dtype);
     Call c = nv12_family_call(map_sizes(z, xy, map_count), interp, 0, elem != 1 && border_mode >= BEVWARP_BORDER_CONSTANT && border_mode < BEVWARP_BORDER_TRANSPARENT);
     c.format_first = true;
     c.read(src.image(z.src_h, (uint64_t)z.src_w * 3, z.batch), z.src_w, 1);
@@ -519,137 +516,92 @@ inline BorderPeriod border_period(int mode, int n) {
     return b;
 }
 
-// ---- bevwarp_warp_stitch: the whole of its host side but the launch -----------------------------------------------------------------------
-// The status of a call in the order include/bevwarp.h documents, and in `p` the grid of tw x th tiles (kBorderTileW x kBorderTileH) over the
-// canvas when the call goes on to a launch (BEVWARP_OK and batch > 0).  cams is HOST; no device pointer is dereferenced.
-inline int stitch_status(const bevwarp_camera* cams, int n_cams, Frames dst, int batch, int dst_h, int dst_w, int channels, int dtype, int interp, int blend,
-                         int feather, int border_mode, const double* border_value, int tw, int th, TilePlan& p) {
-    p = {};
-    if (!cams || n_cams < 1 || n_cams > BEVWARP_STITCH_MAX_CAMERAS) return BEVWARP_ERR_BAD_ARG;
-    if (blend == BEVWARP_STITCH_FEATHER && (feather < 1 || feather > 4096)) return BEVWARP_ERR_BAD_ARG;
-    for (int k = 0; k < n_cams; k++) {  // every camera against the canvas; the sources may overlap each other
-        const int st = check_call(stitch_call(cams[k], dst, batch, dst_h, dst_w, channels, dtype, interp, blend, border_mode));
-        if (st != BEVWARP_OK) return st;
-    }
-    p = plan_border(batch, dst_h, dst_w, tw, th);
-    if (p.status != BEVWARP_OK) return p.status;
-    if (border_mode == BEVWARP_BORDER_CONSTANT && border_value)
-        for (int c = 0; c < channels; c++)
-            if (!isfinite(border_value[c])) return BEVWARP_ERR_NOT_FINITE;
-    return BEVWARP_OK;
-}
-
-// ---- bevwarp_stitch_maps, bevwarp_stitch_maps_nv12: the whole of their host side but the launch ---------------------------------------------
-// One camera of either: that camera's frames and map planes against the canvas -- bevwarp_remap's (bevwarp_remap_nv12's) call, its format
-// narrowed to the two blend rules and to the constant and the transparent border.  reads[]: the frames (NV12: Y, then the pairs), the xy
-// plane and, bilinear, the frac plane.
+// ---- the stitches: bevwarp_warp_stitch and the six through maps -- the whole of their host side but the launch ----------------------------------
+// What every stitch narrows its camera's format to: the two blend rules, and the constant and the transparent border.
 inline bool stitch_format_ok(int blend, int border_mode) {
     return (blend == BEVWARP_STITCH_OVER || blend == BEVWARP_STITCH_FEATHER) && (border_mode == BEVWARP_BORDER_CONSTANT || border_mode == BEVWARP_BORDER_TRANSPARENT);
 }
+// bevwarp_warp_stitch, one camera of it: that camera's frames against the canvas -- bevwarp_warp's images and formats without bicubic,
+// narrowed as above.  (stitch_check below runs the checks over all cameras.)
+inline Call stitch_call(const bevwarp_camera& k, Frames dst, int batch, int dst_h, int dst_w, int channels, int dtype, int interp, int blend, int border_mode) {
+    Call c = warp_call({k.src, k.frame_stride, k.row_stride}, dst, {batch, k.src_h, k.src_w, dst_h, dst_w, k.m_count, k.M_inv}, channels, dtype, interp, false);
+    c.format_ok = c.format_ok && stitch_format_ok(blend, border_mode);
+    return c;
+}
+// What a bevwarp_map_camera passes, as the remap calls take it: its frames (NV12: Y and the pairs), its two map planes, its sides.
+struct MapCamera {
+    Frames src, uv, xy, frac;
+    Sizes z;
+};
+inline MapCamera map_camera(const bevwarp_map_camera& k, int batch, int dst_h, int dst_w) {
+    return {{k.src, k.frame_stride, k.row_stride},
+            {k.uv, k.uv_frame_stride, k.uv_row_stride},
+            {k.map_xy, k.xy_frame_stride, k.xy_row_stride},
+            {k.map_frac, k.frac_frame_stride, k.frac_row_stride},
+            {batch, k.src_h, k.src_w, dst_h, dst_w, 0, nullptr}};
+}
+// bevwarp_stitch_maps, bevwarp_stitch_maps_nv12, one camera of either: that camera's frames and map planes against the canvas --
+// bevwarp_remap's (bevwarp_remap_nv12's) call, its format narrowed to the two blend rules and to the constant and the transparent border.
+// reads[]: the frames (NV12: Y, then the pairs), the xy plane and, bilinear, the frac plane.
 inline Call stitch_maps_call(const bevwarp_map_camera& k, Frames dst, int batch, int dst_h, int dst_w, int channels, int dtype, int interp, int blend, int border_mode) {
-    Call c = remap_call({k.src, k.frame_stride, k.row_stride}, dst, {k.map_xy, k.xy_frame_stride, k.xy_row_stride}, {k.map_frac, k.frac_frame_stride, k.frac_row_stride},
-                        {batch, k.src_h, k.src_w, dst_h, dst_w, 0, nullptr}, k.map_count, channels, dtype, interp, border_mode);
+    const MapCamera m = map_camera(k, batch, dst_h, dst_w);
+    Call c = remap_call(m.src, dst, m.xy, m.frac, m.z, k.map_count, channels, dtype, interp, border_mode);
     c.format_ok = c.format_ok && stitch_format_ok(blend, border_mode);
     return c;
 }
 inline Call stitch_maps_nv12_call(const bevwarp_map_camera& k, Frames dst, int batch, int dst_h, int dst_w, int interp, int blend, int rgb_order, int border_mode) {
-    Call c = remap_nv12_call({k.src, k.frame_stride, k.row_stride}, {k.uv, k.uv_frame_stride, k.uv_row_stride}, dst, {k.map_xy, k.xy_frame_stride, k.xy_row_stride},
-                             {k.map_frac, k.frac_frame_stride, k.frac_row_stride}, {batch, k.src_h, k.src_w, dst_h, dst_w, 0, nullptr}, k.map_count, interp, rgb_order,
-                             border_mode);
+    const MapCamera m = map_camera(k, batch, dst_h, dst_w);
+    Call c = remap_nv12_call(m.src, m.uv, dst, m.xy, m.frac, m.z, k.map_count, interp, rgb_order, border_mode);
     c.format_ok = c.format_ok && stitch_format_ok(blend, border_mode);
     return c;
 }
-// The status of a call in the order include/bevwarp.h documents, and in `p` the grid of tw x th tiles over the canvas when the call goes
-// on to a launch (BEVWARP_OK and batch > 0).  cams is HOST; no device pointer is dereferenced.  nv12: channels and dtype are not looked at.
-inline int stitch_maps_any_status(bool nv12, const bevwarp_map_camera* cams, int n_cams, Frames dst, int batch, int dst_h, int dst_w, int channels, int dtype, int interp,
-                                  int blend, int feather, int rgb_order, int border_mode, const double* border_value, int tw, int th, TilePlan& p) {
+// bevwarp_stitch_maps_to_nv12, bevwarp_stitch_maps_nv12_to_nv12, one camera of either: bevwarp_remap_to_nv12's (bevwarp_remap_nv12_to_nv12's)
+// call under BEVWARP_BORDER_CONSTANT -- there is no border mode: what no camera covers is the border pixel -- its format narrowed to the two
+// blend rules.  nv12: the cameras' frames are NV12 (rgb_order is not looked at).
+inline Call stitch_maps_nv12_out_call(bool nv12, const bevwarp_map_camera& k, Frames dst_y, Frames dst_uv, int batch, int dst_h, int dst_w, int interp, int blend,
+                                      int rgb_order) {
+    const MapCamera m = map_camera(k, batch, dst_h, dst_w);
+    Call c = nv12 ? remap_nv12_to_nv12_call(m.src, m.uv, dst_y, dst_uv, m.xy, m.frac, m.z, k.map_count, interp, BEVWARP_BORDER_CONSTANT)
+                  : remap_to_nv12_call(m.src, dst_y, dst_uv, m.xy, m.frac, m.z, k.map_count, interp, rgb_order, BEVWARP_BORDER_CONSTANT);
+    c.format_ok = c.format_ok && stitch_format_ok(blend, BEVWARP_BORDER_CONSTANT);
+    return c;
+}
+// bevwarp_stitch_maps_planes, bevwarp_stitch_maps_nv12_planes, one camera of either: bevwarp_remap_planes' (bevwarp_remap_nv12_planes') call
+// likewise.  nv12: the cameras' frames are NV12 (otherwise rgb_order is not looked at).
+inline Call stitch_maps_planes_call(bool nv12, const bevwarp_map_camera& k, Frames dst, int64_t dst_ps, int batch, int dst_h, int dst_w, int interp, int blend,
+                                    int rgb_order, int plane_dtype) {
+    const MapCamera m = map_camera(k, batch, dst_h, dst_w);
+    Call c = nv12 ? remap_nv12_planes_call(m.src, m.uv, dst, dst_ps, m.xy, m.frac, m.z, k.map_count, interp, rgb_order, BEVWARP_BORDER_CONSTANT, plane_dtype)
+                  : remap_planes_call(m.src, dst, dst_ps, m.xy, m.frac, m.z, k.map_count, interp, BEVWARP_BORDER_CONSTANT, plane_dtype);
+    c.format_ok = c.format_ok && stitch_format_ok(blend, BEVWARP_BORDER_CONSTANT);
+    return c;
+}
+
+// The status of a stitch in the order include/bevwarp.h documents: the camera array and count, the feather, every check of camera 0's call
+// before camera 1's (describe(cams[k]): one of the calls above), the grid of tw x th tiles (kBorderTileW x kBorderTileH) over the canvas, and
+// last the HOST values -- the border value, then scale, then bias: `n` doubles each, or NULL.  A stitch with a border mode passes its border
+// value under BEVWARP_BORDER_CONSTANT only: no other mode reads it.  cams is HOST; no device pointer is dereferenced.
+// Out: in `calls` (BEVWARP_STITCH_MAX_CAMERAS entries of the caller's) every camera's call as it was checked -- what is launched is filled
+// from these -- and in `p` the grid; both are whole when the call goes on to a launch (BEVWARP_OK and batch > 0).
+struct HostValues {
+    const double* v;
+    int n;
+};
+template <class Camera, class Describe>
+int stitch_check(const Camera* cams, int n_cams, int blend, int feather, Describe describe, std::initializer_list<HostValues> values, int batch, int dst_h, int dst_w,
+                 int tw, int th, TilePlan& p, Call* calls) {
     p = {};
     if (!cams || n_cams < 1 || n_cams > BEVWARP_STITCH_MAX_CAMERAS) return BEVWARP_ERR_BAD_ARG;
     if (blend == BEVWARP_STITCH_FEATHER && (feather < 1 || feather > 4096)) return BEVWARP_ERR_BAD_ARG;
     for (int k = 0; k < n_cams; k++) {  // every camera against the canvas; what the cameras read may overlap
-        const int st = check_call(nv12 ? stitch_maps_nv12_call(cams[k], dst, batch, dst_h, dst_w, interp, blend, rgb_order, border_mode)
-                                       : stitch_maps_call(cams[k], dst, batch, dst_h, dst_w, channels, dtype, interp, blend, border_mode));
+        const int st = check_call(calls[k] = describe(cams[k]));
         if (st != BEVWARP_OK) return st;
     }
     p = plan_border(batch, dst_h, dst_w, tw, th);
     if (p.status != BEVWARP_OK) return p.status;
-    if (border_mode == BEVWARP_BORDER_CONSTANT && border_value)
-        for (int c = 0; c < (nv12 ? 3 : channels); c++)
-            if (!isfinite(border_value[c])) return BEVWARP_ERR_NOT_FINITE;
-    return BEVWARP_OK;
-}
-inline int stitch_maps_status(const bevwarp_map_camera* cams, int n_cams, Frames dst, int batch, int dst_h, int dst_w, int channels, int dtype, int interp, int blend,
-                              int feather, int border_mode, const double* border_value, int tw, int th, TilePlan& p) {
-    return stitch_maps_any_status(false, cams, n_cams, dst, batch, dst_h, dst_w, channels, dtype, interp, blend, feather, 0, border_mode, border_value, tw, th, p);
-}
-inline int stitch_maps_nv12_status(const bevwarp_map_camera* cams, int n_cams, Frames dst, int batch, int dst_h, int dst_w, int interp, int blend, int feather,
-                                   int rgb_order, int border_mode, const double* border_value, int tw, int th, TilePlan& p) {
-    return stitch_maps_any_status(true, cams, n_cams, dst, batch, dst_h, dst_w, 3, BEVWARP_U8, interp, blend, feather, rgb_order, border_mode, border_value, tw, th, p);
-}
-
-// ---- bevwarp_stitch_maps_to_nv12, bevwarp_stitch_maps_nv12_to_nv12: the same for the stitches that write NV12 --------------------------------
-// One camera of either: bevwarp_remap_to_nv12's (bevwarp_remap_nv12_to_nv12's) call under BEVWARP_BORDER_CONSTANT -- there is no border mode:
-// what no camera covers is the border pixel -- its format narrowed to the two blend rules.
-inline Call stitch_maps_nv12_out_call(bool nv12, const bevwarp_map_camera& k, Frames dst_y, Frames dst_uv, int batch, int dst_h, int dst_w, int interp, int blend,
-                                      int rgb_order) {
-    const Frames src = {k.src, k.frame_stride, k.row_stride}, uv = {k.uv, k.uv_frame_stride, k.uv_row_stride};
-    const Frames xy = {k.map_xy, k.xy_frame_stride, k.xy_row_stride}, frac = {k.map_frac, k.frac_frame_stride, k.frac_row_stride};
-    const Sizes z = {batch, k.src_h, k.src_w, dst_h, dst_w, 0, nullptr};
-    Call c = nv12 ? remap_nv12_to_nv12_call(src, uv, dst_y, dst_uv, xy, frac, z, k.map_count, interp, BEVWARP_BORDER_CONSTANT)
-                  : remap_to_nv12_call(src, dst_y, dst_uv, xy, frac, z, k.map_count, interp, rgb_order, BEVWARP_BORDER_CONSTANT);
-    c.format_ok = c.format_ok && stitch_format_ok(blend, BEVWARP_BORDER_CONSTANT);
-    return c;
-}
-// stitch_maps_any_status' rules and order.  nv12: the cameras' frames are NV12 (rgb_order is not looked at).
-inline int stitch_maps_nv12_out_status(bool nv12, const bevwarp_map_camera* cams, int n_cams, Frames dst_y, Frames dst_uv, int batch, int dst_h, int dst_w, int interp,
-                                       int blend, int feather, int rgb_order, const double* border_value, int tw, int th, TilePlan& p) {
-    p = {};
-    if (!cams || n_cams < 1 || n_cams > BEVWARP_STITCH_MAX_CAMERAS) return BEVWARP_ERR_BAD_ARG;
-    if (blend == BEVWARP_STITCH_FEATHER && (feather < 1 || feather > 4096)) return BEVWARP_ERR_BAD_ARG;
-    for (int k = 0; k < n_cams; k++) {  // every camera against both planes of the canvas; what the cameras read may overlap
-        const int st = check_call(stitch_maps_nv12_out_call(nv12, cams[k], dst_y, dst_uv, batch, dst_h, dst_w, interp, blend, nv12 ? 0 : rgb_order));
-        if (st != BEVWARP_OK) return st;
-    }
-    p = plan_border(batch, dst_h, dst_w, tw, th);
-    if (p.status != BEVWARP_OK) return p.status;
-    if (border_value)
-        for (int c = 0; c < 3; c++)
-            if (!isfinite(border_value[c])) return BEVWARP_ERR_NOT_FINITE;
-    return BEVWARP_OK;
-}
-
-// ---- bevwarp_stitch_maps_planes, bevwarp_stitch_maps_nv12_planes: the same for the stitches that write channel planes --------------------------
-// One camera of either: bevwarp_remap_planes' (bevwarp_remap_nv12_planes') call under BEVWARP_BORDER_CONSTANT -- there is no border mode:
-// what no camera covers is the border pixel -- its format narrowed to the two blend rules.
-inline Call stitch_maps_planes_call(bool nv12, const bevwarp_map_camera& k, Frames dst, int64_t dst_ps, int batch, int dst_h, int dst_w, int interp, int blend,
-                                    int rgb_order, int plane_dtype) {
-    const Frames src = {k.src, k.frame_stride, k.row_stride}, uv = {k.uv, k.uv_frame_stride, k.uv_row_stride};
-    const Frames xy = {k.map_xy, k.xy_frame_stride, k.xy_row_stride}, frac = {k.map_frac, k.frac_frame_stride, k.frac_row_stride};
-    const Sizes z = {batch, k.src_h, k.src_w, dst_h, dst_w, 0, nullptr};
-    Call c = nv12 ? remap_nv12_planes_call(src, uv, dst, dst_ps, xy, frac, z, k.map_count, interp, rgb_order, BEVWARP_BORDER_CONSTANT, plane_dtype)
-                  : remap_planes_call(src, dst, dst_ps, xy, frac, z, k.map_count, interp, BEVWARP_BORDER_CONSTANT, plane_dtype);
-    c.format_ok = c.format_ok && stitch_format_ok(blend, BEVWARP_BORDER_CONSTANT);
-    return c;
-}
-// stitch_maps_any_status' rules and order, with scale and bias (HOST, 3 doubles each or NULL) after border_value.  nv12: the cameras' frames
-// are NV12 (otherwise rgb_order is not looked at).
-inline int stitch_maps_planes_status(bool nv12, const bevwarp_map_camera* cams, int n_cams, Frames dst, int64_t dst_ps, int batch, int dst_h, int dst_w, int interp,
-                                     int blend, int feather, int rgb_order, const double* border_value, const double* scale, const double* bias, int plane_dtype,
-                                     int tw, int th, TilePlan& p) {
-    p = {};
-    if (!cams || n_cams < 1 || n_cams > BEVWARP_STITCH_MAX_CAMERAS) return BEVWARP_ERR_BAD_ARG;
-    if (blend == BEVWARP_STITCH_FEATHER && (feather < 1 || feather > 4096)) return BEVWARP_ERR_BAD_ARG;
-    for (int k = 0; k < n_cams; k++) {  // every camera against the planes of the canvas; what the cameras read may overlap
-        const int st = check_call(stitch_maps_planes_call(nv12, cams[k], dst, dst_ps, batch, dst_h, dst_w, interp, blend, nv12 ? rgb_order : 0, plane_dtype));
-        if (st != BEVWARP_OK) return st;
-    }
-    p = plan_border(batch, dst_h, dst_w, tw, th);
-    if (p.status != BEVWARP_OK) return p.status;
-    const double* const values[3] = {border_value, scale, bias};
-    for (const double* v : values)
-        if (v)
-            for (int c = 0; c < 3; c++)
-                if (!isfinite(v[c])) return BEVWARP_ERR_NOT_FINITE;
+    for (const HostValues& h : values)
+        for (int c = 0; h.v && c < h.n; c++)
+            if (!isfinite(h.v[c])) return BEVWARP_ERR_NOT_FINITE;
     return BEVWARP_OK;
 }
 

@@ -670,6 +670,17 @@ def remap_numpy(src, map1, map2, interpolation, dst=None, borderMode=BORDER_CONS
 _BLENDS = {"over": _lib.STITCH_OVER, "feather": _lib.STITCH_FEATHER}
 
 
+def _one_kind(who, srcs):
+    """The cameras of a stitch that takes any pixel type (tensors of rank 2..4) are of one kind, which is returned: (dtype, channels, batch,
+    device).  Compared on the tensors as given, before anything asks for a device."""
+    kinds = [(src.dtype, 1 if src.dim() == 2 else src.shape[-1], src.shape[0] if src.dim() == 4 else 1, src.device) for src in srcs]
+    for k, kind in enumerate(kinds):
+        if kind != kinds[0]:
+            raise ValueError("camera %d has dtype %s, %d channels, batch %d on %s; camera 0 has dtype %s, %d channels, batch %d on %s "
+                             "(%s: one dtype, channel count, batch and device)" % ((k,) + kind + kinds[0] + (who,)))
+    return kinds[0]
+
+
 def warp_stitch(srcs, Ms, dsize, flags=INTER_LINEAR, blend="over", feather=64, border_value=None, out=None, border_mode=BORDER_CONSTANT):
     """The cameras of one site warped into ONE canvas in one launch (include/bevwarp.h, bevwarp_warp_stitch): what one
     warp_perspective(..., border_mode=BORDER_TRANSPARENT, out=canvas) per camera is for, without a pass over the canvas per camera, and
@@ -702,12 +713,8 @@ def warp_stitch(srcs, Ms, dsize, flags=INTER_LINEAR, blend="over", feather=64, b
         raise ValueError("unsupported border mode %r (warp_stitch: BORDER_CONSTANT, BORDER_TRANSPARENT)" % (border_mode,))
     border_mode = int(border_mode)
     interp = _interp("warp_stitch", flags)
-    kinds = [(src.dtype, 1 if src.dim() == 2 else src.shape[-1], src.shape[0] if src.dim() == 4 else 1, src.device)
-             for src in srcs if isinstance(src, torch.Tensor) and src.dim() in (2, 3, 4)]
-    for k, kind in enumerate(kinds):  # (before anything asks for a device)
-        if len(kinds) == len(srcs) and kind != kinds[0]:
-            raise ValueError("camera %d has dtype %s, %d channels, batch %d on %s; camera 0 has dtype %s, %d channels, batch %d on %s "
-                             "(warp_stitch: one dtype, channel count, batch and device)" % ((k,) + kind + kinds[0]))
+    if all(isinstance(src, torch.Tensor) and src.dim() in (2, 3, 4) for src in srcs):  # (_frames refuses the others, one by one)
+        _one_kind("warp_stitch", srcs)
     frames = [_frames("warp_stitch", src, _DTYPES)[0] for src in srcs]  # (a copy made here lives until the launch is enqueued)
     s0 = frames[0]
     B, C = s0.shape[0], s0.shape[3]
@@ -759,9 +766,37 @@ def _stitch_maps_dst(out, ndim, B, dh, dw, C):
         raise ValueError("the maps' dsize is %s (%d frames of %d channels): out has %d elements" % ((dw, dh), B, C, out.numel()))
 
 
-def _fill_map_camera(cam, warp_map):
+def _fill_map_camera(cam, warp_map, s=None, uv4=None):
+    """One bevwarp_map_camera: its map, and its frames s (B, H, W, C) -- NV12: the Y planes (B, H, W), with the planes of pairs uv4.
+    (s=None: the caller fills the frames itself.)"""
     xy_p, fr_p, cam.xy_frame_stride, cam.xy_row_stride, cam.frac_frame_stride, cam.frac_row_stride = warp_map._planes()
     cam.map_xy, cam.map_frac, cam.map_count, cam.reserved = xy_p, fr_p, warp_map.n, 0
+    if s is not None:
+        esz = s.element_size()
+        cam.src, cam.uv, cam.frame_stride, cam.row_stride = s.data_ptr(), None if uv4 is None else uv4.data_ptr(), s.stride(0) * esz, s.stride(1) * esz
+        cam.src_h, cam.src_w = s.shape[1], s.shape[2]
+    if uv4 is not None:
+        cam.uv_frame_stride, cam.uv_row_stride = uv4.stride(0), uv4.stride(1)
+
+
+def _nv12_map_cameras(who, ys, uvs, warp_maps):
+    """The NV12 cameras of a stitch through maps: a plane of pairs per camera, every camera's planes as _nv12_planes takes them, one batch
+    and device, a map that serves them per camera.  Returns (planes, cams, B, device): the filled bevwarp_map_camera array, and the
+    tensors it points into, which the caller keeps until the launch is enqueued."""
+    if len(uvs) != len(ys):
+        raise ValueError("got %d uv planes for %d cameras" % (len(uvs), len(ys)))
+    planes = [_nv12_planes(who, y, uv) for y, uv in zip(ys, uvs)]
+    B, device = planes[0][0].shape[0], planes[0][0].device
+    for k, (y, (y3, _)) in enumerate(zip(ys, planes)):
+        if y3.shape[0] != B or y3.device != device or y.dim() != ys[0].dim():
+            raise ValueError("camera %d has %d frames (y of rank %d) on %s; camera 0 has %d (rank %d) on %s (%s: one batch and device)"
+                             % (k, y3.shape[0], y.dim(), y3.device, B, ys[0].dim(), device, who))
+    for m in warp_maps:
+        _map_fits(m, B, device)
+    cams = (_lib.MapCamera * len(planes))()
+    for cam, (y3, uv4), m in zip(cams, planes, warp_maps):
+        _fill_map_camera(cam, m, y3, uv4)
+    return planes, cams, B, device
 
 
 def remap_stitch(srcs, warp_maps, blend="over", feather=64, border_value=None, out=None, border_mode=BORDER_CONSTANT):
@@ -783,12 +818,7 @@ def remap_stitch(srcs, warp_maps, blend="over", feather=64, border_value=None, o
     for k, src in enumerate(srcs):
         if not isinstance(src, torch.Tensor) or src.dtype not in _DTYPES or src.dim() not in (2, 3, 4):
             raise ValueError("remap_stitch needs uint8 or float32 tensors (B, H, W, C), (H, W, C) or (H, W); camera %d is %s" % (k, getattr(src, "dtype", type(src))))
-    kinds = [(src.dtype, 1 if src.dim() == 2 else src.shape[-1], src.shape[0] if src.dim() == 4 else 1, src.device) for src in srcs]
-    for k, kind in enumerate(kinds):  # (before anything asks for a device)
-        if kind != kinds[0]:
-            raise ValueError("camera %d has dtype %s, %d channels, batch %d on %s; camera 0 has dtype %s, %d channels, batch %d on %s "
-                             "(remap_stitch: one dtype, channel count, batch and device)" % ((k,) + kind + kinds[0]))
-    _, C, B, device = kinds[0]
+    _, C, B, device = _one_kind("remap_stitch", srcs)
     for m in warp_maps:
         _map_fits(m, B, device)
     _stitch_maps_dst(out, srcs[0].dim(), B, dh, dw, C)
@@ -797,9 +827,7 @@ def remap_stitch(srcs, warp_maps, blend="over", feather=64, border_value=None, o
     esz = s0.element_size()
     cams = (_lib.MapCamera * len(frames))()
     for cam, s4, m in zip(cams, frames, warp_maps):
-        cam.src, cam.uv, cam.frame_stride, cam.row_stride = s4.data_ptr(), None, s4.stride(0) * esz, s4.stride(1) * esz
-        cam.src_h, cam.src_w = s4.shape[1], s4.shape[2]
-        _fill_map_camera(cam, m)
+        _fill_map_camera(cam, m, s4)
     d4 = _pixel_dst(out, s0.dtype, s0.device, B, dh, dw, C, zeroed=border_mode == BORDER_TRANSPARENT)
     bv = _border(border_value, C) if border_mode == BORDER_CONSTANT else None
     _lib.launch("bevwarp_stitch_maps", s0.device, ctypes.addressof(cams), len(frames), d4.data_ptr(), B, dh, dw, C, d4.stride(0) * esz, d4.stride(1) * esz,
@@ -822,23 +850,8 @@ def remap_stitch_nv12(ys, uvs, warp_maps, blend="over", feather=64, border_value
     Returns (B, h, w, 3), or (h, w, 3) for single frames, or `out`.  Asynchronous on the current stream."""
     ys, uvs, warp_maps = list(ys), list(uvs), list(warp_maps)
     interp, (dw, dh), border_mode = _stitch_maps_call("remap_stitch_nv12", len(ys), warp_maps, blend, feather, border_mode)
-    if len(uvs) != len(ys):
-        raise ValueError("got %d uv planes for %d cameras" % (len(uvs), len(ys)))
-    planes = [_nv12_planes("remap_stitch_nv12", y, uv) for y, uv in zip(ys, uvs)]
-    B, device = planes[0][0].shape[0], planes[0][0].device
-    for k, (y, (y3, _)) in enumerate(zip(ys, planes)):
-        if y3.shape[0] != B or y3.device != device or y.dim() != ys[0].dim():
-            raise ValueError("camera %d has %d frames (y of rank %d) on %s; camera 0 has %d (rank %d) on %s (remap_stitch_nv12: one batch and device)"
-                             % (k, y3.shape[0], y.dim(), y3.device, B, ys[0].dim(), device))
-    for m in warp_maps:
-        _map_fits(m, B, device)
+    planes, cams, B, device = _nv12_map_cameras("remap_stitch_nv12", ys, uvs, warp_maps)
     _stitch_maps_dst(out, ys[0].dim() + 1, B, dh, dw, 3)
-    cams = (_lib.MapCamera * len(planes))()
-    for cam, (y3, uv4), m in zip(cams, planes, warp_maps):
-        cam.src, cam.uv, cam.frame_stride, cam.row_stride = y3.data_ptr(), uv4.data_ptr(), y3.stride(0), y3.stride(1)
-        cam.uv_frame_stride, cam.uv_row_stride = uv4.stride(0), uv4.stride(1)
-        cam.src_h, cam.src_w = y3.shape[1], y3.shape[2]
-        _fill_map_camera(cam, m)
     d4 = _pixel_dst(out, torch.uint8, device, B, dh, dw, 3, zeroed=border_mode == BORDER_TRANSPARENT)
     bv = _border(border_value, 3) if border_mode == BORDER_CONSTANT else None
     _lib.launch("bevwarp_stitch_maps_nv12", device, ctypes.addressof(cams), len(planes), d4.data_ptr(), B, dh, dw, d4.stride(0), d4.stride(1), interp,
@@ -1170,6 +1183,24 @@ def _bgr_frames(who, src):
     return _frames(who, src, None, channels=3)[0]
 
 
+def _bgr_map_cameras(who, srcs, warp_maps):
+    """The 8-bit cameras of 3 channels of a stitch through maps: every camera's frames as _bgr_frames takes them, one batch and device, a
+    map that serves them per camera.  Returns (frames, cams, B, device): the filled bevwarp_map_camera array, and the tensors it points
+    into -- a copy _frames made may be among them -- which the caller keeps until the launch is enqueued."""
+    frames = [_bgr_frames(who, src) for src in srcs]
+    B, device = frames[0].shape[0], frames[0].device
+    for k, (src, s4) in enumerate(zip(srcs, frames)):
+        if s4.shape[0] != B or s4.device != device or src.dim() != srcs[0].dim():
+            raise ValueError("camera %d has %d frames (rank %d) on %s; camera 0 has %d (rank %d) on %s (%s: one batch and device)"
+                             % (k, s4.shape[0], src.dim(), s4.device, B, srcs[0].dim(), device, who))
+    for m in warp_maps:
+        _map_fits(m, B, device)
+    cams = (_lib.MapCamera * len(frames))()
+    for cam, s4, m in zip(cams, frames, warp_maps):
+        _fill_map_camera(cam, m, s4)
+    return frames, cams, B, device
+
+
 def remap_to_nv12(src, warp_map, border_mode=BORDER_CONSTANT, border_value=None, out=None, rgb=False):
     """remap of 8-bit BGR frames, written as the NV12 frame a video encoder takes: bit for bit
 
@@ -1247,20 +1278,8 @@ def remap_stitch_to_nv12(srcs, warp_maps, blend="over", feather=64, border_value
     Returns `out` if given, otherwise a new joined buffer.  Asynchronous on the current stream."""
     srcs, warp_maps = list(srcs), list(warp_maps)
     interp, (dw, dh) = _stitch_maps_nv12_out_call("remap_stitch_to_nv12", len(srcs), warp_maps, blend, feather)
-    frames = [_bgr_frames("remap_stitch_to_nv12", src) for src in srcs]  # (a copy made here lives until the launch is enqueued)
-    B, device = frames[0].shape[0], frames[0].device
-    for k, (src, s4) in enumerate(zip(srcs, frames)):
-        if s4.shape[0] != B or s4.device != device or src.dim() != srcs[0].dim():
-            raise ValueError("camera %d has %d frames (rank %d) on %s; camera 0 has %d (rank %d) on %s (remap_stitch_to_nv12: one batch and device)"
-                             % (k, s4.shape[0], src.dim(), s4.device, B, srcs[0].dim(), device))
-    for m in warp_maps:
-        _map_fits(m, B, device)
+    frames, cams, B, device = _bgr_map_cameras("remap_stitch_to_nv12", srcs, warp_maps)
     y3, uv4, ret = _nv12_dst("remap_stitch_to_nv12", out, device, B, dh, dw, srcs[0].dim() == 3)
-    cams = (_lib.MapCamera * len(frames))()
-    for cam, s4, m in zip(cams, frames, warp_maps):
-        cam.src, cam.uv, cam.frame_stride, cam.row_stride = s4.data_ptr(), None, s4.stride(0), s4.stride(1)
-        cam.src_h, cam.src_w = s4.shape[1], s4.shape[2]
-        _fill_map_camera(cam, m)
     _lib.launch("bevwarp_stitch_maps_to_nv12", device, ctypes.addressof(cams), len(frames), y3.data_ptr(), uv4.data_ptr(), B, dh, dw, y3.stride(0), y3.stride(1),
                 uv4.stride(0), uv4.stride(1), interp, _BLENDS[blend], int(feather) if blend == "feather" else 0, 1 if rgb else 0, _ptr(_border(border_value, 3)))
     return ret
@@ -1279,23 +1298,8 @@ def remap_stitch_nv12_to_nv12(ys, uvs, warp_maps, blend="over", feather=64, bord
     Returns `out` if given, otherwise a new joined buffer.  Asynchronous on the current stream."""
     ys, uvs, warp_maps = list(ys), list(uvs), list(warp_maps)
     interp, (dw, dh) = _stitch_maps_nv12_out_call("remap_stitch_nv12_to_nv12", len(ys), warp_maps, blend, feather)
-    if len(uvs) != len(ys):
-        raise ValueError("got %d uv planes for %d cameras" % (len(uvs), len(ys)))
-    planes = [_nv12_planes("remap_stitch_nv12_to_nv12", y, uv) for y, uv in zip(ys, uvs)]
-    B, device = planes[0][0].shape[0], planes[0][0].device
-    for k, (y, (y3, _)) in enumerate(zip(ys, planes)):
-        if y3.shape[0] != B or y3.device != device or y.dim() != ys[0].dim():
-            raise ValueError("camera %d has %d frames (y of rank %d) on %s; camera 0 has %d (rank %d) on %s (remap_stitch_nv12_to_nv12: one batch and device)"
-                             % (k, y3.shape[0], y.dim(), y3.device, B, ys[0].dim(), device))
-    for m in warp_maps:
-        _map_fits(m, B, device)
+    planes, cams, B, device = _nv12_map_cameras("remap_stitch_nv12_to_nv12", ys, uvs, warp_maps)
     dy3, duv4, ret = _nv12_dst("remap_stitch_nv12_to_nv12", out, device, B, dh, dw, ys[0].dim() == 2)
-    cams = (_lib.MapCamera * len(planes))()
-    for cam, (y3, uv4), m in zip(cams, planes, warp_maps):
-        cam.src, cam.uv, cam.frame_stride, cam.row_stride = y3.data_ptr(), uv4.data_ptr(), y3.stride(0), y3.stride(1)
-        cam.uv_frame_stride, cam.uv_row_stride = uv4.stride(0), uv4.stride(1)
-        cam.src_h, cam.src_w = y3.shape[1], y3.shape[2]
-        _fill_map_camera(cam, m)
     _lib.launch("bevwarp_stitch_maps_nv12_to_nv12", device, ctypes.addressof(cams), len(planes), dy3.data_ptr(), duv4.data_ptr(), B, dh, dw, dy3.stride(0),
                 dy3.stride(1), duv4.stride(0), duv4.stride(1), interp, _BLENDS[blend], int(feather) if blend == "feather" else 0, _ptr(_border(border_value, 3)))
     return ret
@@ -1360,23 +1364,11 @@ def remap_stitch_to_planar(srcs, warp_maps, scale=1.0 / 255.0, bias=0.0, blend="
     srcs, warp_maps = list(srcs), list(warp_maps)
     interp, (dw, dh), _ = _stitch_maps_call("remap_stitch_to_planar", len(srcs), warp_maps, blend, feather, BORDER_CONSTANT)
     _plane_format("remap_stitch_to_planar", interp, out_dtype, out)
-    frames = [_bgr_frames("remap_stitch_to_planar", src) for src in srcs]  # (a copy made here lives until the launch is enqueued)
-    B, device = frames[0].shape[0], frames[0].device
-    for k, (src, s4) in enumerate(zip(srcs, frames)):
-        if s4.shape[0] != B or s4.device != device or src.dim() != srcs[0].dim():
-            raise ValueError("camera %d has %d frames (rank %d) on %s; camera 0 has %d (rank %d) on %s (remap_stitch_to_planar: one batch and device)"
-                             % (k, s4.shape[0], src.dim(), s4.device, B, srcs[0].dim(), device))
-    for m in warp_maps:
-        _map_fits(m, B, device)
+    frames, cams, B, device = _bgr_map_cameras("remap_stitch_to_planar", srcs, warp_maps)
     _planes_out_fits(out, srcs[0].dim(), dw, dh, "maps'")
     d4 = _plane_dst(out, out_dtype, device, B, 3, dh, dw)
     sc, bi = _per_channel(scale, 3), _per_channel(bias, 3)
     esz = d4.element_size()
-    cams = (_lib.MapCamera * len(frames))()
-    for cam, s4, m in zip(cams, frames, warp_maps):
-        cam.src, cam.uv, cam.frame_stride, cam.row_stride = s4.data_ptr(), None, s4.stride(0), s4.stride(1)
-        cam.src_h, cam.src_w = s4.shape[1], s4.shape[2]
-        _fill_map_camera(cam, m)
     _lib.launch("bevwarp_stitch_maps_planes", device, ctypes.addressof(cams), len(frames), d4.data_ptr(), B, dh, dw, d4.stride(0) * esz, d4.stride(1) * esz,
                 d4.stride(2) * esz, interp, _BLENDS[blend], int(feather) if blend == "feather" else 0, _ptr(_border(border_value, 3)), _ptr(sc), _ptr(bi),
                 _PLANE_DTYPES[out_dtype])
@@ -1399,26 +1391,11 @@ def remap_stitch_nv12_to_planar(ys, uvs, warp_maps, scale=1.0 / 255.0, bias=0.0,
     ys, uvs, warp_maps = list(ys), list(uvs), list(warp_maps)
     interp, (dw, dh), _ = _stitch_maps_call("remap_stitch_nv12_to_planar", len(ys), warp_maps, blend, feather, BORDER_CONSTANT)
     _plane_format("remap_stitch_nv12_to_planar", interp, out_dtype, out)
-    if len(uvs) != len(ys):
-        raise ValueError("got %d uv planes for %d cameras" % (len(uvs), len(ys)))
-    planes = [_nv12_planes("remap_stitch_nv12_to_planar", y, uv) for y, uv in zip(ys, uvs)]
-    B, device = planes[0][0].shape[0], planes[0][0].device
-    for k, (y, (y3, _)) in enumerate(zip(ys, planes)):
-        if y3.shape[0] != B or y3.device != device or y.dim() != ys[0].dim():
-            raise ValueError("camera %d has %d frames (y of rank %d) on %s; camera 0 has %d (rank %d) on %s (remap_stitch_nv12_to_planar: one batch and device)"
-                             % (k, y3.shape[0], y.dim(), y3.device, B, ys[0].dim(), device))
-    for m in warp_maps:
-        _map_fits(m, B, device)
+    planes, cams, B, device = _nv12_map_cameras("remap_stitch_nv12_to_planar", ys, uvs, warp_maps)
     _planes_out_fits(out, ys[0].dim() + 1, dw, dh, "maps'")
     d4 = _plane_dst(out, out_dtype, device, B, 3, dh, dw)
     sc, bi = _per_channel(scale, 3), _per_channel(bias, 3)
     esz = d4.element_size()
-    cams = (_lib.MapCamera * len(planes))()
-    for cam, (y3, uv4), m in zip(cams, planes, warp_maps):
-        cam.src, cam.uv, cam.frame_stride, cam.row_stride = y3.data_ptr(), uv4.data_ptr(), y3.stride(0), y3.stride(1)
-        cam.uv_frame_stride, cam.uv_row_stride = uv4.stride(0), uv4.stride(1)
-        cam.src_h, cam.src_w = y3.shape[1], y3.shape[2]
-        _fill_map_camera(cam, m)
     _lib.launch("bevwarp_stitch_maps_nv12_planes", device, ctypes.addressof(cams), len(planes), d4.data_ptr(), B, dh, dw, d4.stride(0) * esz, d4.stride(1) * esz,
                 d4.stride(2) * esz, interp, _BLENDS[blend], int(feather) if blend == "feather" else 0, 1 if rgb else 0, _ptr(_border(border_value, 3)), _ptr(sc),
                 _ptr(bi), _PLANE_DTYPES[out_dtype])

@@ -1,6 +1,6 @@
 // remap_nv12_out_plan_driver.cpp -- the host side of bevwarp_remap_to_nv12, bevwarp_remap_nv12_to_nv12, bevwarp_stitch_maps_to_nv12 and
-// bevwarp_stitch_maps_nv12_to_nv12 (bev_amd/csrc/host_plan.h: remap_to_nv12_call, remap_nv12_to_nv12_call, stitch_maps_nv12_out_status,
-// plan_remap) from the command line, for tests/test_remap_nv12_out_cpu.py, which builds it with g++ under the address and
+// bevwarp_stitch_maps_nv12_to_nv12 (bev_amd/csrc/host_plan.h: remap_to_nv12_call, remap_nv12_to_nv12_call, stitch_check over
+// stitch_maps_nv12_out_call, plan_remap) from the command line, for tests/test_remap_nv12_out_cpu.py, which builds it with g++ under the address and
 // undefined-behaviour sanitizers.  One case per line of stdin, one line of numbers per case on stdout.  The calls are built as
 // bevwarp_api.hip builds them (a base of 0 is a null pointer; no pointer is dereferenced but the camera array and the border value, which
 // are HOST):
@@ -13,30 +13,10 @@
 //                    src uv src_h src_w fs rs uv_fs uv_rs xy frac xy_fs xy_rs frac_fs frac_rs map_count
 //       border: 0 = NULL, 1 = finite values, 2 = a NaN in the last of the 3 channels
 //       -> the status, then the plan's status and total_tiles where the status is BEVWARP_OK, else 0 0
-#include <inttypes.h>
-#include <math.h>
-#include <stdio.h>
-
-#include <iostream>
-#include <sstream>
-#include <string>
-
-#include "host_plan.h"
-
-using namespace bevwarp::plan;
-
-static const void* ptr(uint64_t v) { return (const void*)(uintptr_t)v; }
-
-static int malformed(const std::string& line) {
-    fprintf(stderr, "malformed case: %s\n", line.c_str());
-    return 2;
-}
+#include "plan_driver_io.h"
 
 int main() {
-    std::string line, cmd;
-    while (std::getline(std::cin, line)) {
-        std::istringstream in(line);
-        if (!(in >> cmd)) continue;
+    return run_cases([](const std::string& cmd, std::istream& in, const std::string& line) {
         if (cmd == "bgr" || cmd == "nv12") {
             uint64_t src = 0, uv = 0, dy = 0, duv = 0, xy = 0, frac = 0;
             Frames fs = {}, fuv = {}, fdy = {}, fduv = {}, mx = {}, mf = {};
@@ -55,31 +35,23 @@ int main() {
             const bool ok = launches && p.status == BEVWARP_OK;
             printf("%d %d %d %" PRId64 "\n", st, p.status, ok ? p.frames_per_item : 0, ok ? p.total_tiles : 0);
         } else if (cmd == "sbgr" || cmd == "snv12") {
+            const bool nv12 = cmd == "snv12";
             bevwarp_map_camera cams[16] = {};
             uint64_t dy = 0, duv = 0;
             Frames fdy = {}, fduv = {};
             int n_cams, cams_null, batch, dst_h, dst_w, interp, blend, feather, rgb, border, listed;
             in >> n_cams >> cams_null >> dy >> duv >> batch >> dst_h >> dst_w >> fdy.fs >> fdy.rs >> fduv.fs >> fduv.rs >> interp >> blend >> feather >> rgb >> border >> listed;
-            if (!in || listed < 0 || listed > 16) return malformed(line);
             fdy.base = ptr(dy), fduv.base = ptr(duv);
-            for (int k = 0; k < listed; k++) {
-                uint64_t src = 0, uv = 0, xy = 0, frac = 0;
-                bevwarp_map_camera& c = cams[k];
-                in >> src >> uv >> c.src_h >> c.src_w >> c.frame_stride >> c.row_stride >> c.uv_frame_stride >> c.uv_row_stride >> xy >> frac >> c.xy_frame_stride >>
-                    c.xy_row_stride >> c.frac_frame_stride >> c.frac_row_stride >> c.map_count;
-                c.src = ptr(src), c.uv = ptr(uv), c.map_xy = ptr(xy), c.map_frac = ptr(frac);
-            }
-            if (!in) return malformed(line);
+            if (!read_map_cameras(in, listed, cams)) return malformed(line);
             double bv[3] = {1.0, 2.0, 3.0};
             if (border == 2) bv[2] = NAN;
             TilePlan p = {};
-            const int st = stitch_maps_nv12_out_status(cmd == "snv12", cams_null ? nullptr : cams, n_cams, fdy, fduv, batch, dst_h, dst_w, interp, blend, feather, rgb,
-                                                       border ? bv : nullptr, 256, 4, p);
-            printf("%d %d %" PRId64 "\n", st, st == BEVWARP_OK ? p.status : 0, st == BEVWARP_OK ? p.total_tiles : 0);
+            Call calls[BEVWARP_STITCH_MAX_CAMERAS];
+            const auto describe = [&](const bevwarp_map_camera& k) { return stitch_maps_nv12_out_call(nv12, k, fdy, fduv, batch, dst_h, dst_w, interp, blend, nv12 ? 0 : rgb); };
+            print_stitch(stitch_check(cams_null ? nullptr : cams, n_cams, blend, feather, describe, {{border ? bv : nullptr, 3}}, batch, dst_h, dst_w, 256, 4, p, calls), p);
         } else {
-            fprintf(stderr, "unknown case: %s\n", line.c_str());
-            return 2;
+            return -1;
         }
-    }
-    return 0;
+        return 0;
+    });
 }
