@@ -335,13 +335,14 @@ int bevwarp_warp_border(const void* src, void* dst, int batch, int src_h, int sr
 int bevwarp_warp_lens(const void* src, void* dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int channels, int64_t src_frame_stride,
                       int64_t src_row_stride, int64_t dst_frame_stride, int64_t dst_row_stride, const double* M_ray, int m_count, const double* lens,
                       double r2_max, int dtype, int interp, int border_mode, const double* border_value, void* stream) {
+    const bool fisheye = plan::take_fisheye_flag(interp);
     const Call c = plan::lens_call({src, src_frame_stride, src_row_stride}, {dst, dst_frame_stride, dst_row_stride}, {batch, src_h, src_w, dst_h, dst_w, m_count, M_ray},
                                    channels, dtype, interp, border_mode);
     LensArgs a;
     int64_t items;
     int st = flat_grid_args(c, a, items);
     if (!items) return st;
-    if ((st = plan::lens_status(lens, r2_max)) != BEVWARP_OK) return st;
+    if ((st = plan::lens_model_status(fisheye, lens, r2_max)) != BEVWARP_OK) return st;
     const bool transparent = border_mode == BEVWARP_BORDER_TRANSPARENT;
     uint8_t bu[4];  // (border_value is read by the constant border only)
     if (border_values(transparent ? nullptr : border_value, channels, a.bv_f, bu) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
@@ -351,14 +352,15 @@ int bevwarp_warp_lens(const void* src, void* dst, int batch, int src_h, int src_
     a.r2_max = r2_max;
     a.dst_vec_ok = plan::wide_stores_ok(c.writes[0], plan::store_align(dtype, channels, false));
     a.src_vec_ok = plan::pixel_loads_ok(c.reads[0].im, plan::pixel_load_align(dtype, channels));
-    return launched(launch_warp_lens(a, dtype, channels, interp, transparent, items, (hipStream_t)stream));
+    return launched((fisheye ? launch_warp_fisheye : launch_warp_lens)(a, dtype, channels, interp, transparent, items, (hipStream_t)stream));
 }
 
 int bevwarp_build_map(const double* M, int m_count, const double* lens, double r2_max, int interp, void* map_xy, void* map_frac, int dst_h, int dst_w,
                       int64_t xy_frame_stride, int64_t xy_row_stride, int64_t frac_frame_stride, int64_t frac_row_stride, void* stream) {
     const Frames xy = {map_xy, xy_frame_stride, xy_row_stride}, fr = {map_frac, frac_frame_stride, frac_row_stride};
     TilePlan p;
-    const int st = plan::build_map_status(M, m_count, lens, r2_max, interp, xy, fr, dst_h, dst_w, kBorderTileW, kBorderTileH, p);
+    const bool fisheye = plan::take_fisheye_flag(interp);
+    const int st = plan::build_map_model_status(fisheye, M, m_count, lens, r2_max, interp, xy, fr, dst_h, dst_w, kBorderTileW, kBorderTileH, p);
     if (st != BEVWARP_OK) return st;
     const bool linear = interp == BEVWARP_LINEAR;
     MapBuildArgs a;
@@ -371,6 +373,7 @@ int bevwarp_build_map(const double* M, int m_count, const double* lens, double r
     const Image ifr = Frames{map_frac, a.frac_fs, frac_row_stride}.image(dst_h, (uint64_t)dst_w * 2, m_count);
     a.dst_vec_ok = plan::map_vec_ok(ixy, linear ? &ifr : nullptr);
     if (lens) memcpy(a.lens, lens, sizeof(a.lens)), a.r2_max = r2_max;
+    if (fisheye) return launched(launch_build_map_fisheye(a, interp, p.total_tiles, (hipStream_t)stream));
     return launched(launch_build_map(a, interp, lens != nullptr, p.total_tiles, (hipStream_t)stream));
 }
 
@@ -822,13 +825,14 @@ int bevwarp_project_points(const void* in, void* out, int64_t n, int dim, const 
 
 int bevwarp_project_points_lens(const void* in, void* out, void* residual, int64_t n, const double* H, const double* lens, double r2_max, int direction,
                                 int iters, double tol_px, int dtype, void* stream) {
-    const int st = plan::points_lens_status(in, out, residual, n, H, lens, r2_max, direction, iters, tol_px, dtype);
+    const bool fisheye = plan::take_fisheye_flag(direction);
+    const int st = plan::points_model_status(fisheye, in, out, residual, n, H, lens, r2_max, direction, iters, tol_px, dtype);
     if (st != BEVWARP_OK || n == 0) return st;
     PointsLensArgs a;
     memcpy(a.H, H, sizeof(a.H));
     memcpy(a.lens, lens, sizeof(a.lens));
     a.r2_max = r2_max, a.tol_px = tol_px, a.iters = iters;
-    return launched(launch_points_lens(in, out, residual, n, a, direction, dtype, (hipStream_t)stream));
+    return launched((fisheye ? launch_points_fisheye : launch_points_lens)(in, out, residual, n, a, direction, dtype, (hipStream_t)stream));
 }
 
 // H / H[2][2] when H is a similarity of the plane in the sense of bev/rbox.py:173-219 (last row ~ (0, 0, 1), equal scale on

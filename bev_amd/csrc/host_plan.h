@@ -265,10 +265,29 @@ inline int lens_status(const double lens[12], double r2_max) {
     if (lens[0] == 0.0 || lens[1] == 0.0 || !(r2_max >= 0.0)) return BEVWARP_ERR_BAD_ARG;  // (a NaN r2_max fails the comparison)
     return BEVWARP_OK;
 }
+// BEVWARP_LENS_FISHEYE in the `interp` word (bevwarp_warp_lens, bevwarp_build_map) or the `direction` word (bevwarp_project_points_lens):
+// taken out of the word, which every check then sees as it always did.  True: the call is a fisheye one.
+inline bool take_fisheye_flag(int& word) {
+    const bool fisheye = (word & BEVWARP_LENS_FISHEYE) != 0;
+    word &= ~BEVWARP_LENS_FISHEYE;
+    return fisheye;
+}
+// ... under which the lens is HOST: fx, fy, cx, cy, k1, k2, k3, k4 and four reserved zeros, and r2_max carries theta_max (+inf: no limit):
+// lens_status's order, the reserved entries next to fx and fy
+inline int fisheye_status(const double lens[12], double theta_max) {
+    if (!lens) return BEVWARP_ERR_BAD_ARG;
+    for (int i = 0; i < 12; i++)
+        if (!isfinite(lens[i])) return BEVWARP_ERR_NOT_FINITE;
+    if (lens[0] == 0.0 || lens[1] == 0.0 || lens[8] != 0.0 || lens[9] != 0.0 || lens[10] != 0.0 || lens[11] != 0.0) return BEVWARP_ERR_BAD_ARG;
+    return (theta_max >= 0.0) ? BEVWARP_OK : BEVWARP_ERR_BAD_ARG;  // (a NaN theta_max fails the comparison)
+}
+// the lens of either model, where bevwarp_warp_lens and bevwarp_project_points_lens look at it
+inline int lens_model_status(bool fisheye, const double lens[12], double r2_max) { return fisheye ? fisheye_status(lens, r2_max) : lens_status(lens, r2_max); }
 // bevwarp_project_points_lens: every check of the call, in the order include/bevwarp.h documents.  in, out, residual are device
 // pointers (never dereferenced), H and lens HOST.  The byte ranges are compared in 128 bits: n next to 2^62 is a range like any other.
-inline int points_lens_status(const void* in, const void* out, const void* residual, int64_t n, const double* H, const double* lens, double r2_max,
-                              int direction, int iters, double tol_px, int dtype) {
+// direction: without BEVWARP_LENS_FISHEYE (take_fisheye_flag), which `fisheye` carries.
+inline int points_model_status(bool fisheye, const void* in, const void* out, const void* residual, int64_t n, const double* H, const double* lens, double r2_max,
+                               int direction, int iters, double tol_px, int dtype) {
     if (!in || !out || !H || n < 0) return BEVWARP_ERR_BAD_ARG;
     if (direction != BEVWARP_LENS_DISTORT && direction != BEVWARP_LENS_UNDISTORT) return BEVWARP_ERR_BAD_ARG;
     if (direction == BEVWARP_LENS_DISTORT && residual) return BEVWARP_ERR_BAD_ARG;
@@ -276,7 +295,7 @@ inline int points_lens_status(const void* in, const void* out, const void* resid
     if (dtype != BEVWARP_F32 && dtype != BEVWARP_F64) return BEVWARP_ERR_UNSUPPORTED;
     const unsigned esz = dtype == BEVWARP_F32 ? 4 : 8;
     if (!finite9(H, 1)) return BEVWARP_ERR_NOT_FINITE;
-    const int st = lens_status(lens, r2_max);
+    const int st = lens_model_status(fisheye, lens, r2_max);
     if (st != BEVWARP_OK) return st;
     if (residual) {
         typedef unsigned __int128 u128;
@@ -286,6 +305,11 @@ inline int points_lens_status(const void* in, const void* out, const void* resid
     }
     // (last: the kernel moves a point as one 8- or 16-byte unit and a residual as one value)
     return (((uintptr_t)in | (uintptr_t)out) % (2 * esz) || (uintptr_t)residual % esz) ? BEVWARP_ERR_BAD_ARG : BEVWARP_OK;
+}
+// ... of the rational model
+inline int points_lens_status(const void* in, const void* out, const void* residual, int64_t n, const double* H, const double* lens, double r2_max,
+                              int direction, int iters, double tol_px, int dtype) {
+    return points_model_status(false, in, out, residual, n, H, lens, r2_max, direction, iters, tol_px, dtype);
 }
 // The element size of a plane type (BEVWARP_F32 | BEVWARP_F16 | BEVWARP_BF16), or 1 for none of the three
 inline int plane_elem_size(int plane_dtype) { return plane_dtype == BEVWARP_F32 ? 4 : ((plane_dtype == BEVWARP_F16 || plane_dtype == BEVWARP_BF16) ? 2 : 1); }
@@ -484,9 +508,10 @@ inline RemapPlan plan_remap(int batch, int map_count, int dst_h, int dst_w, int 
 constexpr int64_t kRemapFillItems = 4096;  // (four rounds of 1024 resident 4-wave workgroups)
 
 // bevwarp_build_map: every check of the call, in the order include/bevwarp.h documents, and in `p` plan_border's grid over the m_count maps.
-// M, xy, frac are device pointers (never dereferenced), lens HOST or NULL.
-inline int build_map_status(const double* M, int m_count, const double* lens, double r2_max, int interp, Frames xy, Frames frac, int dst_h, int dst_w, int tw, int th,
-                            TilePlan& p) {
+// M, xy, frac are device pointers (never dereferenced), lens HOST or NULL.  interp: without BEVWARP_LENS_FISHEYE (take_fisheye_flag), which
+// `fisheye` carries; a fisheye map has no pinhole chain to fall back to, so a NULL lens is refused there.
+inline int build_map_model_status(bool fisheye, const double* M, int m_count, const double* lens, double r2_max, int interp, Frames xy, Frames frac, int dst_h, int dst_w,
+                                  int tw, int th, TilePlan& p) {
     p = {};
     if (!M || !xy.base || m_count < 1 || dst_h <= 0 || dst_w <= 0) return BEVWARP_ERR_BAD_ARG;
     if (interp != BEVWARP_NEAREST && interp != BEVWARP_LINEAR) return BEVWARP_ERR_UNSUPPORTED;
@@ -498,7 +523,12 @@ inline int build_map_status(const double* M, int m_count, const double* lens, do
     p = plan_border(m_count, dst_h, dst_w, tw, th);
     if (p.status != BEVWARP_OK) return p.status;
     if (with_frac && regions_overlap(ixy, ifr)) return BEVWARP_ERR_OVERLAP;  // (both are written)
-    return lens ? lens_status(lens, r2_max) : BEVWARP_OK;
+    return (lens || fisheye) ? lens_model_status(fisheye, lens, r2_max) : BEVWARP_OK;
+}
+// ... of the pinhole chain and the rational model
+inline int build_map_status(const double* M, int m_count, const double* lens, double r2_max, int interp, Frames xy, Frames frac, int dst_h, int dst_w, int tw, int th,
+                            TilePlan& p) {
+    return build_map_model_status(false, M, m_count, lens, r2_max, interp, xy, frac, dst_h, dst_w, tw, th, p);
 }
 // the lane-wide accesses of the two planes: 16 bytes of xy, 8 bytes of frac (no frac plane: the xy plane decides)
 inline bool map_vec_ok(const Image& xy, const Image* frac) { return wide_stores_ok(xy, 16) && (!frac || wide_stores_ok(*frac, 8)); }

@@ -21,5 +21,7 @@ struct PointsLensArgs {  // by value: wave-uniform, in scalar registers
 
 // in, out: n x 2 values of dtype (BEVWARP_F32 | BEVWARP_F64), aligned to a point; residual: n values or NULL (UNDISTORT only).
 hipError_t launch_points_lens(const void* in, void* out, void* residual, int64_t n, const PointsLensArgs& a, int direction, int dtype, hipStream_t stream);
+// ... under BEVWARP_LENS_FISHEYE (points_fisheye.hip): lens holds fx, fy, cx, cy, k1, k2, k3, k4 and four zeros, r2_max holds theta_max
+hipError_t launch_points_fisheye(const void* in, void* out, void* residual, int64_t n, const PointsLensArgs& a, int direction, int dtype, hipStream_t stream);
 
 }  // namespace bevwarp

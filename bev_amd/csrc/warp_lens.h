@@ -14,5 +14,7 @@ struct LensArgs : BorderArgs {  // (minv holds M_ray: destination pixel -> norma
 };
 
 hipError_t launch_warp_lens(const LensArgs& a, int dtype, int channels, int interp, bool transparent, int64_t items, hipStream_t stream);
+// ... under BEVWARP_LENS_FISHEYE (warp_fisheye.hip): lens holds fx, fy, cx, cy, k1, k2, k3, k4 and four zeros, r2_max holds theta_max
+hipError_t launch_warp_fisheye(const LensArgs& a, int dtype, int channels, int interp, bool transparent, int64_t items, hipStream_t stream);
 
 }  // namespace bevwarp

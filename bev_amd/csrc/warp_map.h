@@ -36,6 +36,8 @@ struct RemapArgs : BorderArgs {
 };
 
 hipError_t launch_build_map(const MapBuildArgs& a, int interp, bool lens, int64_t items, hipStream_t stream);
+// ... under BEVWARP_LENS_FISHEYE (warp_map_fisheye.hip): lens holds fx, fy, cx, cy, k1, k2, k3, k4 and four zeros, r2_max holds theta_max
+hipError_t launch_build_map_fisheye(const MapBuildArgs& a, int interp, int64_t items, hipStream_t stream);
 hipError_t launch_remap(const RemapArgs& a, int dtype, int channels, int interp, int mode, int64_t items, hipStream_t stream);
 
 }  // namespace bevwarp

@@ -7,9 +7,9 @@
 // registers.
 //
 // The frame -- item decoding, the row walk, the rounding, a pixel's load and the store of a lane's 4 pixels -- is flat_frame.h; the lens
-// step and the blend are lens_pixel.h; the index remap is warp_border.h; the sampler's map loads and index stage are map_entry.h, shared
-// with the NV12 sampler (warp_map_nv12.hip); a tap's load by byte offset and the 6-byte pair load are tap_load.h, shared with the stitches
-// through maps.
+// step and the blend are lens_pixel.h; the builder's body is map_build.inc, shared with the fisheye builder
+// (warp_map_fisheye.hip); the index remap is warp_border.h; the sampler's map loads and index stage are map_entry.h, shared with the NV12
+// sampler (warp_map_nv12.hip); a tap's load by byte offset and the 6-byte pair load are tap_load.h, shared with the stitches through maps.
 #include "warp_map.h"
 #include "lens_pixel.h"
 #include "map_entry.h"
@@ -19,51 +19,17 @@ namespace bevwarp {
 namespace {
 
 // ---- the builder ---------------------------------------------------------------------------------------------------------------------------
+#define BEVWARP_MAP_STEP                                   \
+    bool valid = true;                                     \
+    if constexpr (LENS)                                    \
+        valid = lens_pixel<INTERP>(a, Xn, Yn, W, X, Y);    \
+    else                                                   \
+        map_pixel_exact_nan_max<INTERP>(Xn, Yn, W, X, Y);
 template <int INTERP, bool LENS>
 __global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(kWavesPerSimd, 8))) void build_map_kernel(const MapBuildArgs a) {
-    constexpr int PPL = kBorderPPL;
-    uint32_t b;
-    int y, xs;  // map, row, the lane's first pixel
-    if (!lane_position(a, b, y, xs)) return;
-    RowWalk walk(a, b, y);
-
-    uint32_t e[PPL], fr[PPL];
-#pragma unroll
-    for (int j = 0; j < PPL; j++) {
-        // pixels past the row's end are computed like any other and not stored
-        double Xn, Yn, W;
-        walk.pixel(a, xs + j, Xn, Yn, W);
-        int X, Y;
-        bool valid = true;
-        if constexpr (LENS)
-            valid = lens_pixel<INTERP>(a, Xn, Yn, W, X, Y);
-        else
-            map_pixel_exact_nan_max<INTERP>(Xn, Yn, W, X, Y);
-        const int sx = sat16(INTERP == kLinear ? (X >> kInterBits) : X), sy = sat16(INTERP == kLinear ? (Y >> kInterBits) : Y);
-        const uint32_t f = INTERP == kLinear ? (uint32_t)(((Y & 31) << 5) | (X & 31)) : 0u;
-        // an invalid pixel: every tap of (-32768, -32768) lies outside every admissible source (include/bevwarp.h)
-        e[j] = valid ? (((uint32_t)sx & 0xffffu) | ((uint32_t)sy << 16)) : 0x80008000u;
-        fr[j] = valid ? f : 0u;
-    }
-
-    uint8_t* xrow = dst_row(a, b, y) + (int64_t)xs * 4;
-    uint8_t* frow = a.frac + (int64_t)b * a.frac_fs + (int64_t)y * a.frac_rs + (int64_t)xs * 2;
-    if (a.dst_vec_ok && xs + PPL <= a.dst_w) {  // the lane's 4 entries: one 16-byte and one 8-byte store
-        const u32x4 o = {e[0], e[1], e[2], e[3]};
-        wide_store(reinterpret_cast<u32x4*>(xrow), o);
-        if constexpr (INTERP == kLinear) {
-            const u32x2 q = {fr[0] | (fr[1] << 16), fr[2] | (fr[3] << 16)};
-            *reinterpret_cast<u32x2*>(frow) = q;
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < PPL; j++)
-            if (xs + j < a.dst_w) {
-                reinterpret_cast<uint32_t*>(xrow)[j] = e[j];
-                if constexpr (INTERP == kLinear) reinterpret_cast<uint16_t*>(frow)[j] = (uint16_t)fr[j];
-            }
-    }
+#include "map_build.inc"
 }
+#undef BEVWARP_MAP_STEP
 
 // ---- the sampler ---------------------------------------------------------------------------------------------------------------------------
 template <typename T, int C>

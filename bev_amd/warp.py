@@ -11,6 +11,7 @@ falls back to the CPU.
 """
 import collections
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -361,17 +362,28 @@ def _intrinsics(K):
     return float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])
 
 
-def ray_matrix(M, K, inverse_given=False):
+def ray_matrix(M, K, inverse_given=False, oriented=False):
     """The matrix bevwarp_warp_lens takes: destination pixel -> normalised undistorted camera plane, inv(K) @ inv(M) written out.
     M (3, 3) or (..., 3, 3): the forward map from UNDISTORTED source pixels to destination pixels (inverse_given: its inverse);
     K: 3x3 or 3x4 camera matrix, no skew (ValueError).  With rows m0, m1, m2 of the inverse:
-    R = [(m0 - cx m2) / fx, (m1 - cy m2) / fy, m2], elementwise in float64.  Returns float64 of M's shape."""
+    R = [(m0 - cx m2) / fx, (m1 - cy m2) / fy, m2], elementwise in float64.  Returns float64 of M's shape.
+    oriented   the rational model divides the ray by its depth and does not see the sign of R; the fisheye model does not divide, and
+               R (x, y, 1) has to point FORWARD for the pixels the camera sees.  True: R carries the sign of the third component of
+               p = M (cx, cy, 1) (inverse_given: of the solution of M p = (cx, cy, 1)), the homogeneous destination point of the
+               optical axis -- at the pixel p / p2 the ray is then (0, 0, 1 / |p2|), forward.  M and -M give the same R.  A homography
+               is orientable only where its denominator keeps one sign; for an affine M (every BEVWorldSpec) that is everywhere.
+               False (default): R as written above."""
     fx, fy, cx, cy = _intrinsics(K)
     Minv = np.ascontiguousarray(M, dtype=np.float64) if inverse_given else invert_homography(M)
     if Minv.shape[-2:] != (3, 3):
         raise ValueError("M must be (..., 3, 3), got %s" % (Minv.shape,))
     m0, m1, m2 = Minv[..., 0, :], Minv[..., 1, :], Minv[..., 2, :]
-    return np.stack([(m0 - cx * m2) / fx, (m1 - cy * m2) / fy, m2], axis=-2)
+    R = np.stack([(m0 - cx * m2) / fx, (m1 - cy * m2) / fy, m2], axis=-2)
+    if oriented:
+        c = np.array([cx, cy, 1.0])
+        p2 = np.linalg.solve(Minv, np.broadcast_to(c, Minv.shape[:-1])[..., None])[..., 2, 0] if inverse_given else (np.asarray(M, dtype=np.float64) @ c)[..., 2]
+        R = R * np.where(p2 < 0.0, -1.0, 1.0)[..., None, None]
+    return R
 
 
 def _dist8(dist_coeff):
@@ -408,6 +420,55 @@ def lens_valid_r2(dist_coeff):
     return best
 
 
+LENS_FISHEYE = 0x100  # BEVWARP_LENS_FISHEYE: ORed into the ABI's interp (direction) word
+
+
+def _lens_model(who, lens_model, r2_max=None, theta_max=None):
+    """lens_model ("rational" | "fisheye") as a bool, fisheye; each model has its own guard keyword."""
+    if lens_model not in ("rational", "fisheye"):
+        raise ValueError("%s: lens_model must be 'rational' or 'fisheye', got %r" % (who, lens_model))
+    fisheye = lens_model == "fisheye"
+    if fisheye and r2_max is not None:
+        raise ValueError("%s: the fisheye model's guard is theta_max (radians), not r2_max" % who)
+    if not fisheye and theta_max is not None:
+        raise ValueError("%s: the rational model's guard is r2_max, not theta_max" % who)
+    return fisheye
+
+
+def _fisheye4(dist_coeff):
+    """dist_coeff of the fisheye model (None, or cv2.fisheye's D: k1, k2, k3, k4) as 4 float64."""
+    if dist_coeff is None:
+        return np.zeros(4, dtype=np.float64)
+    d = np.asarray(dist_coeff, dtype=np.float64).ravel()
+    if d.size != 4:
+        raise ValueError("dist_coeff must hold 4 values (k1, k2, k3, k4) for the fisheye model, got %d" % d.size)
+    return d
+
+
+def fisheye_valid_theta(dist_coeff):
+    """The angle from the optical axis (radians) up to which the fisheye model theta (1 + k1 theta^2 + ... + k4 theta^8) is monotonic:
+    the smallest positive real root of its derivative D = 1 + 3 k1 theta^2 + 5 k2 theta^4 + 7 k3 theta^6 + 9 k4 theta^8, capped at pi
+    (no ray is further from the axis); pi when there is none.  The analogue of lens_valid_r2, and what the fisheye entries pass as
+    theta_max.  Host numpy (companion-matrix roots in theta^2)."""
+    k1, k2, k3, k4 = _fisheye4(dist_coeff)
+    c = np.trim_zeros(np.array([1.0, 3.0 * k1, 5.0 * k2, 7.0 * k3, 9.0 * k4]), "b")
+    best = math.pi
+    if c.size >= 2:
+        for r in np.polynomial.polynomial.polyroots(c):
+            if abs(r.imag) <= 1e-9 * max(1.0, abs(r.real)) and r.real > 0.0:
+                best = min(best, math.sqrt(float(r.real)))
+    return best
+
+
+def _fisheye_lens(who, K, dist_coeff, theta_max):
+    """(lens of 12 doubles: fx, fy, cx, cy, k1..k4, four zeros; theta_max) as the ABI takes them under BEVWARP_LENS_FISHEYE."""
+    if K is None:
+        raise ValueError("%s: the fisheye model needs the camera matrix K" % who)
+    d = _fisheye4(dist_coeff)
+    lens = np.ascontiguousarray(np.concatenate([_intrinsics(K), d, np.zeros(4)]), dtype=np.float64)
+    return lens, (fisheye_valid_theta(d) if theta_max is None else float(theta_max))
+
+
 def lens_from_calib(calib):
     """(K, dist_coeff) of a Calib for warp_perspective_lens: calib.K as float64 and calib.dist_coeff (None gives five zeros).
     A Calib without K -- `from_pts` mode pins the homography alone -- raises ValueError."""
@@ -417,7 +478,8 @@ def lens_from_calib(calib):
     return np.asarray(calib.K, dtype=np.float64), (np.zeros(5) if d is None else np.asarray(d, dtype=np.float64).ravel())
 
 
-def warp_perspective_lens(src, M, dsize, K, dist_coeff, flags=INTER_LINEAR, border_value=None, out=None, border_mode=BORDER_CONSTANT, r2_max=None):
+def warp_perspective_lens(src, M, dsize, K, dist_coeff, flags=INTER_LINEAR, border_value=None, out=None, border_mode=BORDER_CONSTANT, r2_max=None,
+                          lens_model="rational", theta_max=None):
     """warp_perspective of the frames a distorted camera delivers: what cv2.undistort(src, K, dist_coeff) followed by
     cv2.warpPerspective(undistorted, M, dsize) is for, with the lens model folded into the coordinate chain -- one launch, one
     resampling of the raw frame, no undistorted frame in memory (include/bevwarp.h, bevwarp_warp_lens; not bit-equal to the cv2 pair,
@@ -433,10 +495,19 @@ def warp_perspective_lens(src, M, dsize, K, dist_coeff, flags=INTER_LINEAR, bord
     border_mode   BORDER_CONSTANT (default) or BORDER_TRANSPARENT.
     r2_max   destination pixels whose squared radius on the normalised camera plane exceeds it are outside the frame; None:
              lens_valid_r2(dist_coeff), which keeps the model's fold-back from painting ghost copies; float("inf"): no limit.
+    lens_model   "rational" (default: everything above), or "fisheye": the equidistant model of cv2.fisheye (include/bevwarp.h,
+             BEVWARP_LENS_FISHEYE).  dist_coeff is then None or its 4 values (k1, k2, k3, k4); the guard is theta_max, the angle from the
+             optical axis in radians (None: fisheye_valid_theta(dist_coeff); passing r2_max raises ValueError); the ray matrix is built
+             oriented (ray_matrix), so rays at and beyond 90 degrees are pixels like any other; and a lens without distortion is still a
+             fisheye lens -- nothing is handed to warp_perspective.
     Asynchronous on the current stream.  No verdict tables, no plan cache: the lens and r2_max travel with every call (the ray
     matrices are uploaded through device_inverse's by-value cache, which holds matrices only)."""
-    dist = _dist8(dist_coeff)
-    if not dist.any():
+    fisheye = _lens_model("warp_perspective_lens", lens_model, r2_max, theta_max)
+    if fisheye:
+        lens, r2 = _fisheye_lens("warp_perspective_lens", K, dist_coeff, theta_max)
+    else:
+        dist = _dist8(dist_coeff)
+    if not fisheye and not dist.any():
         return warp_perspective(src, M, dsize, flags=flags, border_value=border_value, out=out, border_mode=border_mode)
     if border_mode not in (BORDER_CONSTANT, BORDER_TRANSPARENT):
         raise ValueError("unsupported border mode %r (warp_perspective_lens: BORDER_CONSTANT, BORDER_TRANSPARENT)" % (border_mode,))
@@ -447,14 +518,15 @@ def warp_perspective_lens(src, M, dsize, K, dist_coeff, flags=INTER_LINEAR, bord
     dw, dh = int(dsize[0]), int(dsize[1])
     esz = s4.element_size()
     Mh = M.detach().cpu().numpy() if isinstance(M, torch.Tensor) else M
-    R = ray_matrix(Mh, K, inverse_given=bool(int(flags) & WARP_INVERSE_MAP))
+    R = ray_matrix(Mh, K, inverse_given=bool(int(flags) & WARP_INVERSE_MAP), oriented=fisheye)
     M_ray, n_m = _matrices(R, WARP_INVERSE_MAP, None, s4.device, B)
-    lens = np.ascontiguousarray(np.concatenate([_intrinsics(K), dist]), dtype=np.float64)
-    r2 = lens_valid_r2(dist) if r2_max is None else float(r2_max)
+    if not fisheye:
+        lens = np.ascontiguousarray(np.concatenate([_intrinsics(K), dist]), dtype=np.float64)
+        r2 = lens_valid_r2(dist) if r2_max is None else float(r2_max)
     d4 = _pixel_dst(out, s4.dtype, s4.device, B, dh, dw, C, zeroed=border_mode == BORDER_TRANSPARENT)
     bv = _border(border_value, C) if border_mode == BORDER_CONSTANT else None
     _lib.launch("bevwarp_warp_lens", s4.device, s4.data_ptr(), d4.data_ptr(), B, H, W, dh, dw, C, s4.stride(0) * esz, s4.stride(1) * esz, d4.stride(0) * esz,
-                d4.stride(1) * esz, M_ray.data_ptr(), n_m, _ptr(lens), r2, _DTYPES[s4.dtype], interp, border_mode, _ptr(bv))
+                d4.stride(1) * esz, M_ray.data_ptr(), n_m, _ptr(lens), r2, _DTYPES[s4.dtype], interp | (LENS_FISHEYE if fisheye else 0), border_mode, _ptr(bv))
     return _like_src(d4, src.dim(), out)
 
 
@@ -499,7 +571,7 @@ class WarpMap:
                 0 if f is None else f.stride(0) * 2, 0 if f is None else f.stride(1) * 2)
 
 
-def build_warp_map(M, dsize, flags=INTER_LINEAR, K=None, dist_coeff=None, r2_max=None, device="cuda", out=None):
+def build_warp_map(M, dsize, flags=INTER_LINEAR, K=None, dist_coeff=None, r2_max=None, device="cuda", out=None, lens_model="rational", theta_max=None):
     """The coordinate chain of warp_perspective / warp_perspective_lens run ONCE, on the device, and kept as a WarpMap for remap():
     what cv2.initUndistortRectifyMap + cv2.convertMaps are for in a fixed camera's loop (include/bevwarp.h, bevwarp_build_map).
 
@@ -511,19 +583,26 @@ def build_warp_map(M, dsize, flags=INTER_LINEAR, K=None, dist_coeff=None, r2_max
     r2_max   None: lens_valid_r2(dist_coeff); a pixel beyond it is stored as the entry whose taps are all outside.
     out      a WarpMap of this n, dsize and interpolation on `device` to write into (its planes may be views).  A `device` without an
              index (the default) then means the map's device, which need not be the current one.
+    lens_model, theta_max   as warp_perspective_lens: "fisheye" builds the map of an equidistant lens (K is needed; dist_coeff None or 4
+             values; theta_max None: fisheye_valid_theta(dist_coeff)).  The map's format is the same, so remap, the stitches and the
+             pipelines serve a fisheye camera as they stand.
     remap(src, build_warp_map(...)) equals warp_perspective(src, ..., border_mode=m) for every border mode, and warp_perspective_lens
     for BORDER_CONSTANT and BORDER_TRANSPARENT, by bits.  Asynchronous on the current stream."""
+    fisheye = _lens_model("build_warp_map", lens_model, r2_max, theta_max)
     interp = _interp("build_warp_map", flags)
     dw, dh = int(dsize[0]), int(dsize[1])
     if dw <= 0 or dh <= 0:
         raise ValueError("build_warp_map: dsize must be positive, got %s" % ((dw, dh),))
-    dist = _dist8(dist_coeff)
+    dist = np.zeros(8) if fisheye else _dist8(dist_coeff)
     inverse = bool(int(flags) & WARP_INVERSE_MAP)
     Mh = np.asarray(M.detach().cpu().numpy() if isinstance(M, torch.Tensor) else M, dtype=np.float64)
     if Mh.shape[-2:] != (3, 3) or Mh.ndim not in (2, 3):
         raise ValueError("M must be (3, 3) or (n, 3, 3), got %s" % (Mh.shape,))
     lens = None
-    if dist.any():
+    if fisheye:
+        lens, r2 = _fisheye_lens("build_warp_map", K, dist_coeff, theta_max)
+        Mh, inverse = ray_matrix(Mh, K, inverse_given=inverse, oriented=True), True
+    elif dist.any():
         if K is None:
             raise ValueError("build_warp_map: a lens (dist_coeff) needs the camera matrix K")
         lens = np.ascontiguousarray(np.concatenate([_intrinsics(K), dist]), dtype=np.float64)
@@ -545,7 +624,7 @@ def build_warp_map(M, dsize, flags=INTER_LINEAR, K=None, dist_coeff=None, r2_max
         xy = torch.empty((n, dh, dw, 2), dtype=torch.int16, device=minv.device)
         out = WarpMap(xy, torch.empty((n, dh, dw), dtype=torch.int16, device=minv.device) if interp == INTER_LINEAR else None, interp, (dw, dh))
     xy_p, fr_p, xy_fs, xy_rs, fr_fs, fr_rs = out._planes()
-    _lib.launch("bevwarp_build_map", out.device, minv.data_ptr(), n, _ptr(lens), 0.0 if lens is None else r2, interp, xy_p, fr_p, dh, dw, xy_fs, xy_rs, fr_fs, fr_rs)
+    _lib.launch("bevwarp_build_map", out.device, minv.data_ptr(), n, _ptr(lens), 0.0 if lens is None else r2, interp | (LENS_FISHEYE if fisheye else 0), xy_p, fr_p, dh, dw, xy_fs, xy_rs, fr_fs, fr_rs)
     return out
 
 

@@ -215,7 +215,7 @@ int bevwarp_warp_border(const void *src, void *dst, int batch, int src_h, int sr
 /*
  * The warp of frames as a distorted camera delivers them: the lens model is a step of the coordinate chain, and the raw frame is sampled
  * once.  Destination pixel -> normalised undistorted camera plane (M_ray) -> distorted image point (OpenCV's rational model: k1..k6, p1,
- * p2; no thin-prism, tilt or fisheye terms) -> the taps and the blend of bevwarp_warp_border.  This is OUR chain, the natural extension
+ * p2; no thin-prism or tilt terms; the fisheye model is BEVWARP_LENS_FISHEYE below) -> the taps and the blend of bevwarp_warp_border.  This is OUR chain, the natural extension
  * of bevwarp_warp's, not a restatement of cv2.undistort + cv2.warpPerspective (which resample twice) or of initUndistortRectifyMap
  * (which accumulates its row terms): parity with OpenCV is unpinned.  It is bit-reproducible: every step below is one correctly rounded
  * float64 + - * / (IEEE division, no FMA), in the order written.
@@ -247,6 +247,49 @@ int bevwarp_warp_border(const void *src, void *dst, int batch, int src_h, int sr
  * the lens: BEVWARP_ERR_BAD_ARG for a NULL lens, BEVWARP_ERR_NOT_FINITE for a lens entry that is NaN or +-inf, BEVWARP_ERR_BAD_ARG for
  * fx == 0, fy == 0, r2_max NaN or r2_max < 0; then BEVWARP_ERR_NOT_FINITE for border_value.  batch == 0 is BEVWARP_OK and launches nothing.
  */
+/*
+ * BEVWARP_LENS_FISHEYE: the equidistant (fisheye) lens model of cv2.fisheye, selected by ORing the flag into `interp` (bevwarp_warp_lens,
+ * bevwarp_build_map) or into `direction` (bevwarp_project_points_lens), as OpenCV's own flags word carries WARP_INVERSE_MAP.  Without the
+ * flag every entry is what it was, bit for bit and status for status; with it, the flag is taken out of the word before any check, so what
+ * is left of the word is judged exactly as before.  The rational model divides the ray by its depth (xn = Xn / W) and cannot express a ray
+ * at 90 degrees or more from the optical axis; this one never divides by W, and such a ray is a pixel like any other.
+ *   lens          HOST, 12 doubles: fx, fy, cx, cy, k1, k2, k3, k4, 0, 0, 0, 0 -- k1..k4 are cv2.fisheye's D; no skew; the last four
+ *                 entries are reserved and must be 0.
+ *   r2_max        carries theta_max: the angle from the optical axis, in radians, beyond which a ray is OUTSIDE; +inf = no limit.  Callers
+ *                 pass the angle where theta poly(theta^2) stops growing (its derivative's first root), at most pi.
+ *   M_ray         as above, but the ray R (x, y, 1) is NOT divided, so the sign of M_ray matters for this model and for no other: -M_ray is
+ *                 the camera looking backwards.  Callers orient it so that the pixels the camera sees have W > 0.  For an affine
+ *                 BEV-to-world map -- every BEVWorldSpec -- W has one sign relation to the scene over the whole destination, and one sign
+ *                 serves all of it.
+ * Everything is float64, every line below one correctly rounded operation (IEEE + - * / and square root, no FMA), in the order written.
+ * No library arctangent is called (two libraries do not agree on the last bit); atan_pos is part of the definition:
+ *   A[i] = the double nearest to atan(i / 8), i = 0..8:  0x0.0p+0, 0x1.fd5ba9aac2f6ep-4, 0x1.f5b75f92c80ddp-3, 0x1.6f61941e4def1p-2,
+ *          0x1.dac670561bb4fp-2, 0x1.1e00babdefeb4p-1, 0x1.4978fa3269ee1p-1, 0x1.700a7c5784634p-1, 0x1.921fb54442d18p-1
+ *   PIO2_HI = 0x1.921fb54442d18p+0 (nearest to pi / 2)      PIO2_LO = 0x1.1a62633145c07p-54 (nearest to pi / 2 - PIO2_HI)
+ *   PI_HI   = 0x1.921fb54442d18p+1                          PI_LO   = 0x1.1a62633145c07p-53
+ *   c3 = 1.0 / 3.0, c5 = 1.0 / 5.0, ... c15 = 1.0 / 15.0    (each one division)
+ *   atan_pos(t), t >= 0 (+inf and NaN admitted):
+ *     big = t > 1          r = big ? 1 / t : t
+ *     i = rint(8 r)        (half to even; 8 r is exact)       c = i / 8
+ *     z = (r - c) / (1 + r c)          z2 = z z
+ *     p = c15;  p = c13 - z2 p;  p = c11 - z2 p;  p = c9 - z2 p;  p = c7 - z2 p;  p = c5 - z2 p;  p = c3 - z2 p
+ *     a = A[i] + (z - (z z2) p)        (i clamped to 0..8)
+ *     atan_pos = big ? (PIO2_HI - a) + PIO2_LO : a
+ *   atan_pos(0) = 0, atan_pos(+inf) = PIO2_HI, atan_pos(NaN) = NaN; elsewhere it is within 2 ulp of the arctangent (1.52 measured).
+ * "The fisheye steps" on a ray (Xn, Yn, W):
+ *   q = Xn Xn + Yn Yn     rho = sqrt(q)     t = rho / |W|     a = atan_pos(t)
+ *   theta = (W < 0) ? (PI_HI - a) + PI_LO : a             (W == 0, rho > 0: t = +inf, theta = PIO2_HI;  0 / 0: NaN)
+ *   th2 = theta theta     poly = 1 + (((k4 th2 + k3) th2 + k2) th2 + k1) th2     thd = theta poly
+ *   g = (rho != 0) ? thd / rho : 0
+ *   xd = Xn g     yd = Yn g     u = fx xd + cx     v = fy yd + cy
+ *   valid = (theta <= theta_max)                          (false for a NaN theta)
+ * bevwarp_warp_lens | BEVWARP_LENS_FISHEYE: (Xn, Yn, W) come from the same evaluation-block row walk (the first two lines of the chain
+ * above, R = M_ray); the fisheye steps stand where the lines `Wr = ...` to `valid = ...` stood; from (u, v) on -- the rs rounding, NaN ->
+ * INT_MAX, sat16, the taps, the blends, "a pixel that is not valid is outside" -- nothing changes.  Formats, borders and the order of the
+ * status checks are unchanged; at the place of the lens: BEVWARP_ERR_BAD_ARG for a NULL lens, BEVWARP_ERR_NOT_FINITE for an entry that is
+ * NaN or +-inf, BEVWARP_ERR_BAD_ARG for fx == 0, fy == 0, a reserved entry != 0, theta_max NaN or < 0.
+ */
+#define BEVWARP_LENS_FISHEYE 0x100
 int bevwarp_warp_lens(const void *src, void *dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int channels,
                       int64_t src_frame_stride, int64_t src_row_stride, int64_t dst_frame_stride, int64_t dst_row_stride,
                       const double *M_ray, int m_count, const double *lens /*HOST, 12*/, double r2_max, int dtype, int interp,
@@ -281,12 +324,17 @@ int bevwarp_warp_lens(const void *src, void *dst, int batch, int src_h, int src_
  *                 coordinates are bevwarp_warp_border's chain -- evaluation blocks, Xn (32 / W), round half to even, NaN -> INT_MAX.
  *                 lens != NULL: M is M_ray and the coordinates are bevwarp_warp_lens's chain, operation for operation.
  *   lens, r2_max  HOST, exactly bevwarp_warp_lens's; lens NULL: the pinhole chain (r2_max is not looked at).
- *   interp        BEVWARP_NEAREST | BEVWARP_LINEAR (anything else: BEVWARP_ERR_UNSUPPORTED).
+ *   interp        BEVWARP_NEAREST | BEVWARP_LINEAR (anything else: BEVWARP_ERR_UNSUPPORTED), optionally | BEVWARP_LENS_FISHEYE: M is M_ray,
+ *                 lens and r2_max (theta_max) are bevwarp_warp_lens's under that flag, and the coordinates are its chain with the fisheye
+ *                 steps, operation for operation.  The map format is unchanged -- an invalid pixel (theta > theta_max, or NaN) is the
+ *                 (-32768, -32768), frac 0 entry -- so bevwarp_remap, its NV12 and plane kin and every stitch through maps serve a fisheye
+ *                 camera as they stand.  A fisheye map has no pinhole chain behind it: lens NULL is BEVWARP_ERR_BAD_ARG.
  *   map_xy, map_frac   device, WRITTEN; map_frac may be NULL for BEVWARP_NEAREST (it is not written then).
  * Status, in this order: BEVWARP_ERR_BAD_ARG (M or map_xy NULL, m_count < 1, a non-positive side); BEVWARP_ERR_UNSUPPORTED (interp);
  * BEVWARP_ERR_BAD_ARG (map_frac NULL under BEVWARP_LINEAR; a plane whose base or stride is misaligned, whose row stride is below a row,
  * or whose maps overlap their successors); BEVWARP_ERR_TOO_LARGE (a side > 2^20, or more than 2^31 - 1 tiles); BEVWARP_ERR_OVERLAP (the
- * two planes share bytes); the lens as in bevwarp_warp_lens.  With m_count == 1 the frame strides are not looked at.
+ * two planes share bytes); the lens as in bevwarp_warp_lens (under BEVWARP_LENS_FISHEYE: as there under the flag, a NULL lens included).
+ * With m_count == 1 the frame strides are not looked at.
  *
  * bevwarp_remap samples `batch` frames through map_count maps: dst[b] = remap(src[b], map[map_count == 1 ? 0 : b]).
  *   src, dst, batch, sizes, channels, the four strides, dtype, border_value   as bevwarp_warp_border, with the same checks.
@@ -878,15 +926,36 @@ int bevwarp_project_points(const void *in, void *out, int64_t n, int dim, const 
  *   out[i] = valid ? plane(x, y) : (NaN, NaN)
  *   residual[i] = e                 device, n values of dtype, or NULL; written for valid and invalid points alike
  *   tol_px        >= 0 pixels of the raw frame; +inf accepts every e that is not NaN.
+ * direction | BEVWARP_LENS_FISHEYE: the same two directions through the fisheye model (bevwarp_warp_lens | BEVWARP_LENS_FISHEYE: the same lens,
+ * r2_max carrying theta_max, atan_pos and "the fisheye steps").  ray(x, y, z) is H (x, y, z) in plane()'s operand order, NOT divided:
+ *   X = (h1 y + h2 z) + h0 x      Y = (h4 y + h5 z) + h3 x      W = (h7 y + h8 z) + h6 x
+ * BEVWARP_LENS_DISTORT | BEVWARP_LENS_FISHEYE.  H: the points' coordinates -> rays in the camera's frame (the oriented M_ray).
+ *   (u, v, theta) = the fisheye steps on ray(x, y, 1)      out[i] = (theta <= theta_max) ? (u, v) : (NaN, NaN)
+ *   (at the integer pixels of one evaluation block this reproduces the fisheye warp's u, v and theta by bits, as the rational one does)
+ * BEVWARP_LENS_UNDISTORT | BEVWARP_LENS_FISHEYE.  H: rays in the camera's frame -> the target's coordinates (H_world_img K, say).  The
+ * unknown is s = tan(theta / 2), in which the ray is rational, so atan_pos is the only transcendental step.  (u, v) = in[i]:
+ *   xd = (u - cx) / fx    yd = (v - cy) / fy    thd = sqrt(xd xd + yd yd)    s = thd / 2
+ *   d1 = 3 k1    d2 = 5 k2    d3 = 7 k3    d4 = 9 k4
+ *   `iters` times (1..100, no early exit):
+ *       theta = 2 atan_pos(s)    th2, poly as in the fisheye steps    f = theta poly - thd
+ *       D = 1 + (((d4 th2 + d3) th2 + d2) th2 + d1) th2
+ *       s = s - (f (1 + s s)) / (2 D)        s = (s < 0) ? 0 : s
+ *   (rx, ry, rz) = (thd != 0) ? ((2 s) (xd / thd), (2 s) (yd / thd), 1 - s s) : (0, 0, 1)
+ *   (u', v', theta') = the fisheye steps on (rx, ry, rz)       e = max(|u' - u|, |v' - v|), NaN if either is NaN
+ *   valid = (theta' <= theta_max) and (e <= tol_px)
+ *   (X, Y, W) = ray(rx, ry, rz)    Wr = (W != 0) ? 1 / W : 0    out[i] = valid ? (X Wr, Y Wr) : (NaN, NaN)    residual[i] = e
+ *   These are Newton's steps: 5 reach 4.4e-16 rad for every theta up to 110 degrees of a lens that is monotonic there; the Python entry's
+ *   default is 10.
  * A NaN that is stored is some NaN: its sign and payload are unspecified.
  * Status, in this order: BEVWARP_ERR_BAD_ARG for in, out or H NULL, n < 0, a direction outside the two, a residual under
  * BEVWARP_LENS_DISTORT, and under BEVWARP_LENS_UNDISTORT iters outside 1..100 or tol_px NaN or negative; BEVWARP_ERR_UNSUPPORTED for dtype;
  * BEVWARP_ERR_NOT_FINITE for H; the lens and r2_max as in bevwarp_warp_lens (NULL: BAD_ARG; NaN, +-inf: NOT_FINITE; fx == 0, fy == 0,
- * r2_max NaN or < 0: BAD_ARG); BEVWARP_ERR_OVERLAP when residual's n values share a byte with in's or out's n points; last,
+ * r2_max NaN or < 0: BAD_ARG; under BEVWARP_LENS_FISHEYE also a reserved entry != 0: BAD_ARG); BEVWARP_ERR_OVERLAP when residual's n values share a byte with in's or out's n points; last,
  * BEVWARP_ERR_BAD_ARG for in or out not aligned to a point or residual not aligned to a value.  n == 0 is BEVWARP_OK and launches nothing.
  */
 #define BEVWARP_LENS_DISTORT 0     /* plane -> raw pixel */
 #define BEVWARP_LENS_UNDISTORT 1   /* raw pixel -> plane */
+/* (BEVWARP_LENS_FISHEYE, 0x100, is ORed into either) */
 int bevwarp_project_points_lens(const void *in, void *out, void *residual /*device, may be NULL*/, int64_t n,
                                 const double *H /*HOST, 9*/, const double *lens /*HOST, 12*/, double r2_max,
                                 int direction, int iters, double tol_px, int dtype, void *stream);
