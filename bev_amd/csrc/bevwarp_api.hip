@@ -175,14 +175,22 @@ void fill_camera(StitchMapCamera& s, const Call& c, int align) {
 // arguments, the canvas (the image every camera's checked call writes), the grid, the feather width, the border pixel, and every camera
 // from its checked call: what was checked is what is launched.  calls: BEVWARP_STITCH_MAX_CAMERAS entries of the caller's, which reads the
 // other written images from them.  dtype, channels: of the sampled pixels.  items = 0: nothing to launch, the status is the call's.
+// blend: without BEVWARP_STITCH_GAIN (plan::take_gain_flag).  Under the flag a is Gained<> arguments, and stitch_check looks at every
+// camera's gain word at its documented place and leaves the checked words in a.gains, taken by value like everything else of the array.
+template <class Args>
+uint32_t* gains_of(Args&) { return nullptr; }
+template <class Args>
+uint32_t* gains_of(Gained<Args>& a) { return a.gains; }
 template <class Args, class Camera, class Describe>
 int stitch_grid_args(Args& a, Call* calls, int64_t& items, const Camera* cams, int n_cams, int blend, int feather, Describe describe,
                      std::initializer_list<plan::HostValues> values, int batch, int dst_h, int dst_w, int dtype, int channels, bool fill) {
     items = 0;
     TilePlan p;
-    const int st = plan::stitch_check(cams, n_cams, blend, feather, describe, values, batch, dst_h, dst_w, kBorderTileW, kBorderTileH, p, calls);
+    uint32_t gains[BEVWARP_STITCH_MAX_CAMERAS] = {};
+    const int st = plan::stitch_check(cams, n_cams, blend, feather, describe, values, batch, dst_h, dst_w, kBorderTileW, kBorderTileH, p, calls, gains_of(a) ? gains : nullptr);
     if (st != BEVWARP_OK || batch == 0) return st;
     memset(&a, 0, sizeof(a));
+    if (uint32_t* g = gains_of(a)) memcpy(g, gains, sizeof(gains));
     const Image& d = calls[0].writes[0].im;
     a.dst = (uint8_t*)d.base, a.dst_fs = d.fs, a.dst_rs = d.rs, a.dst_h = dst_h, a.dst_w = dst_w;
     copy_grid(a, p);
@@ -457,30 +465,44 @@ int bevwarp_stitch_maps(const bevwarp_map_camera* cams, int n_cams, void* dst, i
                         int64_t dst_row_stride, int dtype, int interp, int blend, int feather, int border_mode, const double* border_value, void* stream) {
     const Frames d = {dst, dst_frame_stride, dst_row_stride};
     const bool fill = border_mode == BEVWARP_BORDER_CONSTANT;  // (border_value is read by the constant border only)
+    const bool gained = plan::take_gain_flag(blend);
     Call calls[BEVWARP_STITCH_MAX_CAMERAS];
-    StitchMapsArgs a;
     int64_t items;
-    const int st = stitch_grid_args(
-        a, calls, items, cams, n_cams, blend, feather,
-        [&](const bevwarp_map_camera& k) { return plan::stitch_maps_call(k, d, batch, dst_h, dst_w, channels, dtype, interp, blend, border_mode); },
-        {{fill ? border_value : nullptr, channels}}, batch, dst_h, dst_w, dtype, channels, fill);
-    if (!items) return st;
-    return launched(launch_stitch_maps(a, dtype, channels, interp, blend, items, (hipStream_t)stream));
+    const auto run = [&](auto& a, auto launch) {
+        const int st = stitch_grid_args(
+            a, calls, items, cams, n_cams, blend, feather,
+            [&](const bevwarp_map_camera& k) { return plan::stitch_maps_call(k, d, batch, dst_h, dst_w, channels, dtype, interp, blend, border_mode, gained); },
+            {{fill ? border_value : nullptr, channels}}, batch, dst_h, dst_w, dtype, channels, fill);
+        return items ? launched(launch(a, dtype, channels, interp, blend, items, (hipStream_t)stream)) : st;
+    };
+    if (gained) {
+        Gained<StitchMapsArgs> a;
+        return run(a, launch_stitch_gain);
+    }
+    StitchMapsArgs a;
+    return run(a, launch_stitch_maps);
 }
 
 int bevwarp_stitch_maps_nv12(const bevwarp_map_camera* cams, int n_cams, void* dst, int batch, int dst_h, int dst_w, int64_t dst_frame_stride, int64_t dst_row_stride,
                              int interp, int blend, int feather, int rgb_order, int border_mode, const double* border_value, void* stream) {
     const Frames d = {dst, dst_frame_stride, dst_row_stride};
     const bool fill = border_mode == BEVWARP_BORDER_CONSTANT;  // (border_value is read by the constant border only)
+    const bool gained = plan::take_gain_flag(blend);
     Call calls[BEVWARP_STITCH_MAX_CAMERAS];
-    StitchMapsArgs a;  // (the border value is in the destination's channel order, as given: it is not converted)
     int64_t items;
-    const int st = stitch_grid_args(
-        a, calls, items, cams, n_cams, blend, feather,
-        [&](const bevwarp_map_camera& k) { return plan::stitch_maps_nv12_call(k, d, batch, dst_h, dst_w, interp, blend, rgb_order, border_mode); },
-        {{fill ? border_value : nullptr, 3}}, batch, dst_h, dst_w, BEVWARP_U8, 3, fill);
-    if (!items) return st;
-    return launched(launch_stitch_maps_nv12(a, interp, blend, rgb_order, items, (hipStream_t)stream));
+    const auto run = [&](auto& a, auto launch) {  // (the border value is in the destination's channel order, as given: it is not converted)
+        const int st = stitch_grid_args(
+            a, calls, items, cams, n_cams, blend, feather,
+            [&](const bevwarp_map_camera& k) { return plan::stitch_maps_nv12_call(k, d, batch, dst_h, dst_w, interp, blend, rgb_order, border_mode); },
+            {{fill ? border_value : nullptr, 3}}, batch, dst_h, dst_w, BEVWARP_U8, 3, fill);
+        return items ? launched(launch(a, interp, blend, rgb_order, items, (hipStream_t)stream)) : st;
+    };
+    if (gained) {
+        Gained<StitchMapsArgs> a;
+        return run(a, launch_stitch_gain_nv12);
+    }
+    StitchMapsArgs a;
+    return run(a, launch_stitch_maps_nv12);
 }
 
 int bevwarp_warp_nv12(const void* y, const void* uv, void* dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int64_t y_frame_stride,
@@ -592,40 +614,56 @@ int remap_nv12_out_impl(const Call& c, int interp, int border_mode, int rgb_orde
 // bevwarp_stitch_maps_to_nv12 and bevwarp_stitch_maps_nv12_to_nv12
 int stitch_maps_nv12_out_impl(bool nv12_src, const bevwarp_map_camera* cams, int n_cams, const Frames& dy, const Frames& duv, int batch, int dst_h, int dst_w, int interp,
                               int blend, int feather, int rgb_order, const double* border_value, void* stream) {
+    const bool gained = plan::take_gain_flag(blend);
     Call calls[BEVWARP_STITCH_MAX_CAMERAS];
-    StitchMapsNv12OutArgs a;  // (the border value is a pixel in the sampled pixel's channel order: the kernel converts it like any other)
     int64_t items;
-    const int st = stitch_grid_args(
-        a, calls, items, cams, n_cams, blend, feather,
-        [&](const bevwarp_map_camera& k) { return plan::stitch_maps_nv12_out_call(nv12_src, k, dy, duv, batch, dst_h, dst_w, interp, blend, nv12_src ? 0 : rgb_order); },
-        {{border_value, 3}}, batch, dst_h, dst_w, BEVWARP_U8, 3, true);
-    if (!items) return st;
-    const Image &y = calls[0].writes[0].im, &uv = calls[0].writes[1].im;
-    a.dst_uv = (uint8_t*)uv.base, a.duv_fs = uv.fs, a.duv_rs = uv.rs;
-    a.dst_vec_ok = plan::wide_stores_ok(y, 4);  // per plane, as bevwarp_warp_to_nv12
-    a.uv_vec_ok = plan::wide_stores_ok(uv, 4);
-    return launched(launch_stitch_maps_nv12_out(a, nv12_src, interp, blend, rgb_order, items, (hipStream_t)stream));
+    const auto run = [&](auto& a, auto launch) {  // (the border value is a pixel in the sampled pixel's channel order: the kernel converts it like any other)
+        const int st = stitch_grid_args(
+            a, calls, items, cams, n_cams, blend, feather,
+            [&](const bevwarp_map_camera& k) { return plan::stitch_maps_nv12_out_call(nv12_src, k, dy, duv, batch, dst_h, dst_w, interp, blend, nv12_src ? 0 : rgb_order); },
+            {{border_value, 3}}, batch, dst_h, dst_w, BEVWARP_U8, 3, true);
+        if (!items) return st;
+        const Image &y = calls[0].writes[0].im, &uv = calls[0].writes[1].im;
+        a.dst_uv = (uint8_t*)uv.base, a.duv_fs = uv.fs, a.duv_rs = uv.rs;
+        a.dst_vec_ok = plan::wide_stores_ok(y, 4);  // per plane, as bevwarp_warp_to_nv12
+        a.uv_vec_ok = plan::wide_stores_ok(uv, 4);
+        return launched(launch(a, nv12_src, interp, blend, rgb_order, items, (hipStream_t)stream));
+    };
+    if (gained) {
+        Gained<StitchMapsNv12OutArgs> a;
+        return run(a, launch_stitch_gain_nv12_out);
+    }
+    StitchMapsNv12OutArgs a;
+    return run(a, launch_stitch_maps_nv12_out);
 }
 // bevwarp_stitch_maps_planes and bevwarp_stitch_maps_nv12_planes
 int stitch_maps_planes_impl(bool nv12_src, const bevwarp_map_camera* cams, int n_cams, const Frames& d, int64_t dst_plane_stride, int batch, int dst_h, int dst_w,
                             int interp, int blend, int feather, int rgb_order, const double* border_value, const double* scale, const double* bias, int plane_dtype,
                             void* stream) {
+    const bool gained = plan::take_gain_flag(blend);
     Call calls[BEVWARP_STITCH_MAX_CAMERAS];
-    StitchMapsPlanesArgs a;  // (border value, scale and bias are in the planes' channel order: the kernel converts NV12 taps to that order)
     int64_t items;
-    const int st = stitch_grid_args(
-        a, calls, items, cams, n_cams, blend, feather,
-        [&](const bevwarp_map_camera& k) {
-            return plan::stitch_maps_planes_call(nv12_src, k, d, dst_plane_stride, batch, dst_h, dst_w, interp, blend, nv12_src ? rgb_order : 0, plane_dtype);
-        },
-        {{border_value, 3}, {scale, 3}, {bias, 3}}, batch, dst_h, dst_w, BEVWARP_U8, 3, true);
-    if (!items) return st;
-    const WrittenImage& w = calls[0].writes[0];
-    a.dst_vec_ok = plan::wide_stores_ok(w, plan::store_align(BEVWARP_U8, 3, true, w.elem));
-    a.plane = plane_kind(plane_dtype);
-    uint8_t bu[4] = {(uint8_t)a.bv_u8, (uint8_t)(a.bv_u8 >> 8), (uint8_t)(a.bv_u8 >> 16), 0}, bs[3];
-    sampled_channel_table(a, 0, dst_plane_stride, scale, bias, bu, bs);  // (the identity; stitch_check has found scale and bias finite)
-    return launched(launch_stitch_maps_planes(a, nv12_src, interp, blend, rgb_order, items, (hipStream_t)stream));
+    const auto run = [&](auto& a, auto launch) {  // (border value, scale and bias are in the planes' channel order: the kernel converts NV12 taps to that order)
+        const int st = stitch_grid_args(
+            a, calls, items, cams, n_cams, blend, feather,
+            [&](const bevwarp_map_camera& k) {
+                return plan::stitch_maps_planes_call(nv12_src, k, d, dst_plane_stride, batch, dst_h, dst_w, interp, blend, nv12_src ? rgb_order : 0, plane_dtype);
+            },
+            {{border_value, 3}, {scale, 3}, {bias, 3}}, batch, dst_h, dst_w, BEVWARP_U8, 3, true);
+        if (!items) return st;
+        const WrittenImage& w = calls[0].writes[0];
+        a.dst_vec_ok = plan::wide_stores_ok(w, plan::store_align(BEVWARP_U8, 3, true, w.elem));
+        a.plane = plane_kind(plane_dtype);
+        uint8_t bu[4] = {(uint8_t)a.bv_u8, (uint8_t)(a.bv_u8 >> 8), (uint8_t)(a.bv_u8 >> 16), 0}, bs[3];
+        sampled_channel_table(a, 0, dst_plane_stride, scale, bias, bu, bs);  // (the identity; stitch_check has found scale and bias finite)
+        return launched(launch(a, nv12_src, interp, blend, rgb_order, items, (hipStream_t)stream));
+    };
+    if (gained) {
+        Gained<StitchMapsPlanesArgs> a;
+        return run(a, launch_stitch_gain_planes);
+    }
+    StitchMapsPlanesArgs a;
+    return run(a, launch_stitch_maps_planes);
 }
 }  // namespace
 

@@ -551,6 +551,17 @@ inline BorderPeriod border_period(int mode, int n) {
 inline bool stitch_format_ok(int blend, int border_mode) {
     return (blend == BEVWARP_STITCH_OVER || blend == BEVWARP_STITCH_FEATHER) && (border_mode == BEVWARP_BORDER_CONSTANT || border_mode == BEVWARP_BORDER_TRANSPARENT);
 }
+// BEVWARP_STITCH_GAIN in the `blend` word of the six stitches through maps: taken out of the word, which every check then sees as it always
+// did (take_fisheye_flag's way).  True: every camera's `reserved` is its gain word, G0 | G1 << 10 | G2 << 20 in Q8, bits 30 and 31 zero.
+inline bool take_gain_flag(int& blend) {
+    const bool gained = (blend & BEVWARP_STITCH_GAIN) != 0;
+    blend &= ~BEVWARP_STITCH_GAIN;
+    return gained;
+}
+// a camera's gain word as stitch_check reads it under the flag (bevwarp_warp_stitch has no gains: its check never asks)
+inline uint32_t gain_word(const bevwarp_map_camera& k) { return (uint32_t)k.reserved; }
+inline uint32_t gain_word(const bevwarp_camera&) { return 0u; }
+inline bool gain_word_ok(uint32_t g) { return (g >> 30) == 0u; }
 // bevwarp_warp_stitch, one camera of it: that camera's frames against the canvas -- bevwarp_warp's images and formats without bicubic,
 // narrowed as above.  (stitch_check below runs the checks over all cameras.)
 inline Call stitch_call(const bevwarp_camera& k, Frames dst, int batch, int dst_h, int dst_w, int channels, int dtype, int interp, int blend, int border_mode) {
@@ -573,10 +584,12 @@ inline MapCamera map_camera(const bevwarp_map_camera& k, int batch, int dst_h, i
 // bevwarp_stitch_maps, bevwarp_stitch_maps_nv12, one camera of either: that camera's frames and map planes against the canvas --
 // bevwarp_remap's (bevwarp_remap_nv12's) call, its format narrowed to the two blend rules and to the constant and the transparent border.
 // reads[]: the frames (NV12: Y, then the pairs), the xy plane and, bilinear, the frac plane.
-inline Call stitch_maps_call(const bevwarp_map_camera& k, Frames dst, int batch, int dst_h, int dst_w, int channels, int dtype, int interp, int blend, int border_mode) {
+// blend: without BEVWARP_STITCH_GAIN (take_gain_flag), which `gained` carries: the gain step knows 8-bit pixels of 3 channels only.
+inline Call stitch_maps_call(const bevwarp_map_camera& k, Frames dst, int batch, int dst_h, int dst_w, int channels, int dtype, int interp, int blend, int border_mode,
+                             bool gained = false) {
     const MapCamera m = map_camera(k, batch, dst_h, dst_w);
     Call c = remap_call(m.src, dst, m.xy, m.frac, m.z, k.map_count, channels, dtype, interp, border_mode);
-    c.format_ok = c.format_ok && stitch_format_ok(blend, border_mode);
+    c.format_ok = c.format_ok && stitch_format_ok(blend, border_mode) && (!gained || (dtype == BEVWARP_U8 && channels == 3));
     return c;
 }
 inline Call stitch_maps_nv12_call(const bevwarp_map_camera& k, Frames dst, int batch, int dst_h, int dst_w, int interp, int blend, int rgb_order, int border_mode) {
@@ -607,22 +620,26 @@ inline Call stitch_maps_planes_call(bool nv12, const bevwarp_map_camera& k, Fram
     return c;
 }
 
-// The status of a stitch in the order include/bevwarp.h documents: the camera array and count, the feather, every check of camera 0's call
+// The status of a stitch in the order include/bevwarp.h documents: the camera array and count, the feather, under BEVWARP_STITCH_GAIN
+// (gains != NULL; blend is the word without the flag) every camera's gain word in ascending k, every check of camera 0's call
 // before camera 1's (describe(cams[k]): one of the calls above), the grid of tw x th tiles (kBorderTileW x kBorderTileH) over the canvas, and
 // last the HOST values -- the border value, then scale, then bias: `n` doubles each, or NULL.  A stitch with a border mode passes its border
 // value under BEVWARP_BORDER_CONSTANT only: no other mode reads it.  cams is HOST; no device pointer is dereferenced.
 // Out: in `calls` (BEVWARP_STITCH_MAX_CAMERAS entries of the caller's) every camera's call as it was checked -- what is launched is filled
-// from these -- and in `p` the grid; both are whole when the call goes on to a launch (BEVWARP_OK and batch > 0).
+// from these -- in `p` the grid, and in `gains` (where given) the checked gain words; all are whole when the call goes on to a launch
+// (BEVWARP_OK and batch > 0).
 struct HostValues {
     const double* v;
     int n;
 };
 template <class Camera, class Describe>
 int stitch_check(const Camera* cams, int n_cams, int blend, int feather, Describe describe, std::initializer_list<HostValues> values, int batch, int dst_h, int dst_w,
-                 int tw, int th, TilePlan& p, Call* calls) {
+                 int tw, int th, TilePlan& p, Call* calls, uint32_t* gains = nullptr) {
     p = {};
     if (!cams || n_cams < 1 || n_cams > BEVWARP_STITCH_MAX_CAMERAS) return BEVWARP_ERR_BAD_ARG;
     if (blend == BEVWARP_STITCH_FEATHER && (feather < 1 || feather > 4096)) return BEVWARP_ERR_BAD_ARG;
+    for (int k = 0; gains && k < n_cams; k++)
+        if (!gain_word_ok(gains[k] = gain_word(cams[k]))) return BEVWARP_ERR_BAD_ARG;
     for (int k = 0; k < n_cams; k++) {  // every camera against the canvas; what the cameras read may overlap
         const int st = check_call(calls[k] = describe(cams[k]));
         if (st != BEVWARP_OK) return st;

@@ -1,6 +1,6 @@
 // stitch_maps_u8x3.inc -- the camera loop of the map stitches that keep an 8-bit pixel of 3 channels packed and store every pixel
 // (stitch_maps_nv12_out_kernel, warp_stitch_maps_nv12_out.hip; stitch_maps_planes_kernel, warp_stitch_maps_planes.hip), included in the
-// kernel's body after lane_position.  It is stitch_maps_body's loop and blends (warp_stitch_maps.hip), unchanged in meaning, with every
+// kernel's body after lane_position; the gained units (BEVWARP_STITCH_GAIN_UNIT, warp_stitch_maps.h) are these two units' text.  It is stitch_maps_body's loop and blends (warp_stitch_maps.hip), unchanged in meaning, with every
 // pixel starting as the border pixel.  Shared as text, the way map_entry_taps.inc is: as a function template the loop changed both units'
 // machine code (profiles/map_samplers_identity.txt).  In scope: a (StitchMapsArgs: dst_w, n_cams, cams, feather, bv_u8), INTERP, NV12 (the
 // cameras' frames are NV12, converted in the order RGB), kFeather, PPL, b, y, xs.  Defines px[PPL], the lane's 4 pixels of row y of frame b
@@ -24,7 +24,9 @@
     const int n = a.n_cams;
     for (int i = 0; i < n; i++) {
         if (!kFeather && !(todo[0] || todo[1] || todo[2] || todo[3])) break;
-        const StitchMapCamera& cam = a.cams[kFeather ? i : n - 1 - i];
+        const int k = kFeather ? i : n - 1 - i;
+        const StitchMapCamera& cam = a.cams[k];
+        const auto tap = camera_tap(a, k);  // (a gained launch: the camera's gain on every tap; otherwise nothing)
         uint32_t e[PPL], fr[PPL];
         load_camera_entries<INTERP>(cam, b, y, xs, a.dst_w, e, fr);
         const uint8_t* frame = cam.src + (int64_t)b * cam.src_fs;
@@ -43,9 +45,9 @@
             if (!in) continue;
             uint32_t p;
             if constexpr (NV12)
-                p = sample_inlier_nv12<INTERP, RGB>(frame, uvf, rs, uv_rs, sw, window, sx, sy, fx, fy);
+                p = sample_inlier_nv12<INTERP, RGB>(frame, uvf, rs, uv_rs, sw, window, sx, sy, fx, fy, tap);
             else
-                p = sample_inlier<INTERP>(frame, rs, sx, sy, fx, fy);
+                p = sample_inlier<INTERP>(frame, rs, sx, sy, fx, fy, tap);
             wr[j] = true;
             if constexpr (!kFeather) {
                 px[j] = p;

@@ -1,0 +1,6 @@
+// warp_stitch_gain.hip -- the gained instances of the stitch through warp maps into an interleaved canvas (bevwarp_stitch_maps and
+// bevwarp_stitch_maps_nv12 under BEVWARP_STITCH_GAIN): warp_stitch_maps.hip's text over Gained<> arguments, 8-bit
+// pixels of 3 channels, every tap put through its camera's gain before the interpolation.  A unit of its own: the plain unit's kernels
+// and machine code stay what they were (profiles/stitch_gain_identity.txt).
+#define BEVWARP_STITCH_GAIN_UNIT
+#include "warp_stitch_maps.hip"

@@ -31,7 +31,30 @@ struct StitchMapsArgs : FrameArgs {  // (the destination and the grid: flat_fram
 };
 static_assert(sizeof(StitchMapsArgs) <= 4096, "eight cameras fit the kernel-argument block");
 
+// A gained launch's arguments (BEVWARP_STITCH_GAIN): the plain launch's, and behind them every camera's gain word
+// G0 | G1 << 10 | G2 << 20 (Q8).  Only the gained kernels see them: StitchMapCamera and the plain kernels' arguments are what they were.
+template <class Args>
+struct Gained : Args {
+    uint32_t gains[kStitchMaxCameras];
+};
+static_assert(sizeof(Gained<StitchMapsArgs>) <= 4096, "eight cameras and their gains fit the kernel-argument block");
+
+// The gained units -- warp_stitch_gain.hip, warp_stitch_gain_nv12_out.hip, warp_stitch_gain_planes.hip -- are the text of the unit each
+// shadows, compiled once more with BEVWARP_STITCH_GAIN_UNIT defined: the same kernel bodies and launch ladders over Gained<> arguments,
+// under names of their own.  (8-bit pixels of 3 channels only: warp_stitch_maps.hip leaves its other formats out.)
+#ifdef BEVWARP_STITCH_GAIN_UNIT
+#define BEVWARP_STITCH_UNIT(plain, gained) gained
+template <class Args>
+using UnitArgs = Gained<Args>;
+#else
+#define BEVWARP_STITCH_UNIT(plain, gained) plain
+template <class Args>
+using UnitArgs = Args;
+#endif
+
 hipError_t launch_stitch_maps(const StitchMapsArgs& a, int dtype, int channels, int interp, int blend, int64_t items, hipStream_t stream);
+hipError_t launch_stitch_gain(const Gained<StitchMapsArgs>& a, int dtype, int channels, int interp, int blend, int64_t items, hipStream_t stream);  // (8-bit, 3 channels)
+hipError_t launch_stitch_gain_nv12(const Gained<StitchMapsArgs>& a, int interp, int blend, int rgb_order, int64_t items, hipStream_t stream);
 hipError_t launch_stitch_maps_nv12(const StitchMapsArgs& a, int interp, int blend, int rgb_order, int64_t items, hipStream_t stream);
 
 }  // namespace bevwarp

@@ -14,19 +14,29 @@
 // the 6-byte pair loads (8-bit, 3 channels) and the NV12 windows apply to every covered pixel with no per-lane decision; warp_map.hip and
 // warp_map_nv12.hip, where an edge lane falls back to loads tap by tap, describe both.  A camera's entries, the inlier samplers and
 // FEATHER's division are stitch_sample.h, shared with warp_stitch_maps_nv12_out.hip and warp_stitch_maps_planes.hip.
+//
+// warp_stitch_gain.hip is this text once more under BEVWARP_STITCH_GAIN_UNIT (warp_stitch_maps.h): the same body and launch ladders over
+// Gained<> arguments, for 8-bit pixels of 3 channels only, every tap put through its camera's gain (stitch_sample.h: TapGain).
 #include "warp_stitch_maps.h"
 #include "stitch_sample.h"
 
 #include <type_traits>
 
+#define UNIT_KERNEL BEVWARP_STITCH_UNIT(stitch_maps_kernel, stitch_gain_kernel)
+#define UNIT_KERNEL_NV12 BEVWARP_STITCH_UNIT(stitch_maps_nv12_kernel, stitch_gain_nv12_kernel)
+#define UNIT_LAUNCH BEVWARP_STITCH_UNIT(launch_stitch_maps, launch_stitch_gain)
+#define UNIT_LAUNCH_NV12 BEVWARP_STITCH_UNIT(launch_stitch_maps_nv12, launch_stitch_gain_nv12)
+
 namespace bevwarp {
 namespace {
 
+using Args = UnitArgs<StitchMapsArgs>;
+
 // The kernels' common body.  NV12: T = uint8_t, C = 3, and RGB is the destination's channel order.
 template <typename T, int C, int INTERP, int BLEND, bool NV12, int RGB>
-__device__ __forceinline__ void stitch_maps_body(const StitchMapsArgs& a) {
+__device__ __forceinline__ void stitch_maps_body(const Args& a) {
     constexpr int PPL = kBorderPPL;
-    constexpr bool kFeather = BLEND == kStitchFeather, kU8 = sizeof(T) == 1;
+    constexpr bool kFeather = BLEND == kStitchFeather, kU8 = sizeof(T) == 1, kGained = !std::is_same_v<Args, StitchMapsArgs>;
     using Acc = std::conditional_t<kU8, int, float>;
     uint32_t b;
     int y, xs;  // frame, row, the lane's first pixel
@@ -52,7 +62,9 @@ __device__ __forceinline__ void stitch_maps_body(const StitchMapsArgs& a) {
     const int n = a.n_cams;
     for (int i = 0; i < n; i++) {
         if (!kFeather && !(todo[0] || todo[1] || todo[2] || todo[3])) break;
-        const StitchMapCamera& cam = a.cams[kFeather ? i : n - 1 - i];
+        const int k = kFeather ? i : n - 1 - i;
+        const StitchMapCamera& cam = a.cams[k];
+        const auto tap = camera_tap(a, k);  // (a gained launch: the camera's gain on every tap; otherwise nothing)
         uint32_t e[PPL], fr[PPL];
         load_camera_entries<INTERP>(cam, b, y, xs, a.dst_w, e, fr);
         const uint8_t* frame = cam.src + (int64_t)b * cam.src_fs;
@@ -71,7 +83,9 @@ __device__ __forceinline__ void stitch_maps_body(const StitchMapsArgs& a) {
             if (!in) continue;
             Pixel<T, C> p;
             if constexpr (NV12)
-                p.packed = sample_inlier_nv12<INTERP, RGB>(frame, uvf, rs, uv_rs, sw, window, sx, sy, fx, fy);
+                p.packed = sample_inlier_nv12<INTERP, RGB>(frame, uvf, rs, uv_rs, sw, window, sx, sy, fx, fy, tap);
+            else if constexpr (kGained)
+                p.packed = sample_inlier<INTERP>(frame, rs, sx, sy, fx, fy, tap);  // (the packed sampler: the same pixel, by bits)
             else
                 p = sample_inlier<T, C, INTERP>(frame, rs, sx, sy, fx, fy, vec);
             wr[j] = true;
@@ -127,28 +141,32 @@ __device__ __forceinline__ void stitch_maps_body(const StitchMapsArgs& a) {
 }
 
 template <typename T, int C, int INTERP, int BLEND>
-__global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(kWavesPerSimd, 8))) void stitch_maps_kernel(const StitchMapsArgs a) {
+__global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(kWavesPerSimd, 8))) void UNIT_KERNEL(const Args a) {
     stitch_maps_body<T, C, INTERP, BLEND, false, 0>(a);
 }
 
 template <int INTERP, int BLEND, int RGB>
-__global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(kWavesPerSimd, 8))) void stitch_maps_nv12_kernel(const StitchMapsArgs a) {
+__global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(kWavesPerSimd, 8))) void UNIT_KERNEL_NV12(const Args a) {
     stitch_maps_body<uint8_t, 3, INTERP, BLEND, true, RGB>(a);
 }
 
 template <typename T, int INTERP, int BLEND>
-void launch_c(const StitchMapsArgs& a, int channels, dim3 grid, hipStream_t stream) {
+void launch_c(const Args& a, int channels, dim3 grid, hipStream_t stream) {
     const dim3 block(kWG);
+#ifdef BEVWARP_STITCH_GAIN_UNIT
+    hipLaunchKernelGGL((UNIT_KERNEL<T, 3, INTERP, BLEND>), grid, block, 0, stream, a);  // (the host checks admit no other channel count)
+#else
     switch (channels) {
-        case 1: hipLaunchKernelGGL((stitch_maps_kernel<T, 1, INTERP, BLEND>), grid, block, 0, stream, a); break;
-        case 2: hipLaunchKernelGGL((stitch_maps_kernel<T, 2, INTERP, BLEND>), grid, block, 0, stream, a); break;
-        case 3: hipLaunchKernelGGL((stitch_maps_kernel<T, 3, INTERP, BLEND>), grid, block, 0, stream, a); break;
-        default: hipLaunchKernelGGL((stitch_maps_kernel<T, 4, INTERP, BLEND>), grid, block, 0, stream, a); break;
+        case 1: hipLaunchKernelGGL((UNIT_KERNEL<T, 1, INTERP, BLEND>), grid, block, 0, stream, a); break;
+        case 2: hipLaunchKernelGGL((UNIT_KERNEL<T, 2, INTERP, BLEND>), grid, block, 0, stream, a); break;
+        case 3: hipLaunchKernelGGL((UNIT_KERNEL<T, 3, INTERP, BLEND>), grid, block, 0, stream, a); break;
+        default: hipLaunchKernelGGL((UNIT_KERNEL<T, 4, INTERP, BLEND>), grid, block, 0, stream, a); break;
     }
+#endif
 }
 
 template <typename T, int INTERP>
-void launch_blend(const StitchMapsArgs& a, int channels, int blend, dim3 grid, hipStream_t stream) {
+void launch_blend(const Args& a, int channels, int blend, dim3 grid, hipStream_t stream) {
     if (blend == kStitchFeather)
         launch_c<T, INTERP, kStitchFeather>(a, channels, grid, stream);
     else
@@ -156,16 +174,16 @@ void launch_blend(const StitchMapsArgs& a, int channels, int blend, dim3 grid, h
 }
 
 template <int INTERP, int BLEND>
-void launch_order(const StitchMapsArgs& a, int rgb_order, dim3 grid, hipStream_t stream) {
+void launch_order(const Args& a, int rgb_order, dim3 grid, hipStream_t stream) {
     const dim3 block(kWG);
     if (rgb_order)
-        hipLaunchKernelGGL((stitch_maps_nv12_kernel<INTERP, BLEND, 1>), grid, block, 0, stream, a);
+        hipLaunchKernelGGL((UNIT_KERNEL_NV12<INTERP, BLEND, 1>), grid, block, 0, stream, a);
     else
-        hipLaunchKernelGGL((stitch_maps_nv12_kernel<INTERP, BLEND, 0>), grid, block, 0, stream, a);
+        hipLaunchKernelGGL((UNIT_KERNEL_NV12<INTERP, BLEND, 0>), grid, block, 0, stream, a);
 }
 
 template <int INTERP>
-void launch_nv12_blend(const StitchMapsArgs& a, int blend, int rgb_order, dim3 grid, hipStream_t stream) {
+void launch_nv12_blend(const Args& a, int blend, int rgb_order, dim3 grid, hipStream_t stream) {
     if (blend == kStitchFeather)
         launch_order<INTERP, kStitchFeather>(a, rgb_order, grid, stream);
     else
@@ -174,17 +192,21 @@ void launch_nv12_blend(const StitchMapsArgs& a, int blend, int rgb_order, dim3 g
 
 }  // namespace
 
-hipError_t launch_stitch_maps(const StitchMapsArgs& a, int dtype, int channels, int interp, int blend, int64_t items, hipStream_t stream) {
+hipError_t UNIT_LAUNCH(const UnitArgs<StitchMapsArgs>& a, int dtype, int channels, int interp, int blend, int64_t items, hipStream_t stream) {
     (void)hipGetLastError();  // a stale error left by the host framework is not this call's
     const dim3 grid((unsigned)items);
+#ifdef BEVWARP_STITCH_GAIN_UNIT  // (the host checks admit no float32 pixels under the flag)
+    (interp == kNearest ? launch_blend<uint8_t, kNearest> : launch_blend<uint8_t, kLinear>)(a, channels, blend, grid, stream);
+#else
     if (dtype == 0)
         (interp == kNearest ? launch_blend<uint8_t, kNearest> : launch_blend<uint8_t, kLinear>)(a, channels, blend, grid, stream);
     else
         (interp == kNearest ? launch_blend<float, kNearest> : launch_blend<float, kLinear>)(a, channels, blend, grid, stream);
+#endif
     return hipGetLastError();
 }
 
-hipError_t launch_stitch_maps_nv12(const StitchMapsArgs& a, int interp, int blend, int rgb_order, int64_t items, hipStream_t stream) {
+hipError_t UNIT_LAUNCH_NV12(const UnitArgs<StitchMapsArgs>& a, int interp, int blend, int rgb_order, int64_t items, hipStream_t stream) {
     (void)hipGetLastError();  // a stale error left by the host framework is not this call's
     const dim3 grid((unsigned)items);
     (interp == kNearest ? launch_nv12_blend<kNearest> : launch_nv12_blend<kLinear>)(a, blend, rgb_order, grid, stream);

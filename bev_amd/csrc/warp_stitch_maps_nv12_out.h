@@ -15,5 +15,7 @@ static_assert(sizeof(StitchMapsNv12OutArgs) <= 4096, "eight cameras fit the kern
 
 // nv12_src: the cameras' frames are (src = y, uv), sampled as B, G, R (rgb_order is then 0); otherwise src, B, G, R (rgb_order 0) or R, G, B (1)
 hipError_t launch_stitch_maps_nv12_out(const StitchMapsNv12OutArgs& a, int nv12_src, int interp, int blend, int rgb_order, int64_t items, hipStream_t stream);
+// ... and under BEVWARP_STITCH_GAIN (warp_stitch_gain_nv12_out.hip)
+hipError_t launch_stitch_gain_nv12_out(const Gained<StitchMapsNv12OutArgs>& a, int nv12_src, int interp, int blend, int rgb_order, int64_t items, hipStream_t stream);
 
 }  // namespace bevwarp

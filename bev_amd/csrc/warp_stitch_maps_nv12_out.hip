@@ -7,15 +7,23 @@
 // One frame per item, the cameras are kernel arguments and the loop's camera number is wave-uniform, every sampled pixel is an inlier: all
 // as warp_stitch_maps.hip describes.  The samplers are stitch_sample.h's, shared with that unit; the camera loop is stitch_maps_u8x3.inc,
 // shared as text with warp_stitch_maps_planes.hip.
+//
+// warp_stitch_gain_nv12_out.hip is this text once more under BEVWARP_STITCH_GAIN_UNIT (warp_stitch_maps.h): the same kernel and launch
+// ladder over Gained<> arguments, with which the camera loop applies the camera's gain to every tap.
 #include "warp_stitch_maps_nv12_out.h"
 #include "stitch_sample.h"
+
+#define UNIT_KERNEL BEVWARP_STITCH_UNIT(stitch_maps_nv12_out_kernel, stitch_gain_nv12_out_kernel)
+#define UNIT_LAUNCH BEVWARP_STITCH_UNIT(launch_stitch_maps_nv12_out, launch_stitch_gain_nv12_out)
 
 namespace bevwarp {
 namespace {
 
+using Args = UnitArgs<StitchMapsNv12OutArgs>;
+
 // NV12: the cameras' frames are NV12, sampled as B, G, R (RGB is then 0); otherwise RGB names the frames' channel order.
 template <int INTERP, int BLEND, bool NV12, int RGB>
-__global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(kWavesPerSimd, 8))) void stitch_maps_nv12_out_kernel(const StitchMapsNv12OutArgs a) {
+__global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(kWavesPerSimd, 8))) void UNIT_KERNEL(const Args a) {
     constexpr int PPL = kBorderPPL;
     constexpr bool kFeather = BLEND == kStitchFeather;
     uint32_t b;
@@ -27,18 +35,18 @@ __global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(kWavesPerSi
 }
 
 template <int INTERP, int BLEND>
-void launch_source(const StitchMapsNv12OutArgs& a, int source, dim3 grid, hipStream_t stream) {
+void launch_source(const Args& a, int source, dim3 grid, hipStream_t stream) {
     const dim3 block(kWG);
     if (source == 2)
-        hipLaunchKernelGGL((stitch_maps_nv12_out_kernel<INTERP, BLEND, true, 0>), grid, block, 0, stream, a);
+        hipLaunchKernelGGL((UNIT_KERNEL<INTERP, BLEND, true, 0>), grid, block, 0, stream, a);
     else if (source == 1)
-        hipLaunchKernelGGL((stitch_maps_nv12_out_kernel<INTERP, BLEND, false, 1>), grid, block, 0, stream, a);
+        hipLaunchKernelGGL((UNIT_KERNEL<INTERP, BLEND, false, 1>), grid, block, 0, stream, a);
     else
-        hipLaunchKernelGGL((stitch_maps_nv12_out_kernel<INTERP, BLEND, false, 0>), grid, block, 0, stream, a);
+        hipLaunchKernelGGL((UNIT_KERNEL<INTERP, BLEND, false, 0>), grid, block, 0, stream, a);
 }
 
 template <int INTERP>
-void launch_blend(const StitchMapsNv12OutArgs& a, int blend, int source, dim3 grid, hipStream_t stream) {
+void launch_blend(const Args& a, int blend, int source, dim3 grid, hipStream_t stream) {
     if (blend == kStitchFeather)
         launch_source<INTERP, kStitchFeather>(a, source, grid, stream);
     else
@@ -47,7 +55,7 @@ void launch_blend(const StitchMapsNv12OutArgs& a, int blend, int source, dim3 gr
 
 }  // namespace
 
-hipError_t launch_stitch_maps_nv12_out(const StitchMapsNv12OutArgs& a, int nv12_src, int interp, int blend, int rgb_order, int64_t items, hipStream_t stream) {
+hipError_t UNIT_LAUNCH(const UnitArgs<StitchMapsNv12OutArgs>& a, int nv12_src, int interp, int blend, int rgb_order, int64_t items, hipStream_t stream) {
     (void)hipGetLastError();  // a stale error left by the host framework is not this call's
     const dim3 grid((unsigned)items);
     const int source = nv12_src ? 2 : (rgb_order ? 1 : 0);  // 0 = B, G, R frames, 1 = R, G, B frames, 2 = NV12 frames

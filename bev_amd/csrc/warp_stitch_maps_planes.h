@@ -19,5 +19,7 @@ static_assert(sizeof(StitchMapsPlanesArgs) <= 4096, "eight cameras fit the kerne
 
 // nv12_src: the cameras' frames are (src = y, uv), converted to B, G, R (rgb_order 0) or R, G, B (1); otherwise src, whose channel k is plane k
 hipError_t launch_stitch_maps_planes(const StitchMapsPlanesArgs& a, int nv12_src, int interp, int blend, int rgb_order, int64_t items, hipStream_t stream);
+// ... and under BEVWARP_STITCH_GAIN (warp_stitch_gain_planes.hip)
+hipError_t launch_stitch_gain_planes(const Gained<StitchMapsPlanesArgs>& a, int nv12_src, int interp, int blend, int rgb_order, int64_t items, hipStream_t stream);
 
 }  // namespace bevwarp

@@ -8,15 +8,23 @@
 // One frame per item, the cameras are kernel arguments and the loop's camera number is wave-uniform, every sampled pixel is an inlier: all
 // as warp_stitch_maps.hip describes.  The samplers are stitch_sample.h's, shared with that unit; the camera loop is stitch_maps_u8x3.inc,
 // shared as text with warp_stitch_maps_nv12_out.hip.
+//
+// warp_stitch_gain_planes.hip is this text once more under BEVWARP_STITCH_GAIN_UNIT (warp_stitch_maps.h): the same kernel and launch ladder
+// over Gained<> arguments, with which the camera loop applies the camera's gain to every tap.
 #include "warp_stitch_maps_planes.h"
 #include "stitch_sample.h"
+
+#define UNIT_KERNEL BEVWARP_STITCH_UNIT(stitch_maps_planes_kernel, stitch_gain_planes_kernel)
+#define UNIT_LAUNCH BEVWARP_STITCH_UNIT(launch_stitch_maps_planes, launch_stitch_gain_planes)
 
 namespace bevwarp {
 namespace {
 
+using Args = UnitArgs<StitchMapsPlanesArgs>;
+
 // NV12: the cameras' frames are NV12, converted to B, G, R (RGB = 0) or R, G, B (1); otherwise plane k is the frames' channel k (RGB is 0).
 template <int INTERP, int BLEND, bool NV12, int RGB, bool WIDE16>
-__global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(kWavesPerSimd, 8))) void stitch_maps_planes_kernel(const StitchMapsPlanesArgs a) {
+__global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(kWavesPerSimd, 8))) void UNIT_KERNEL(const Args a) {
     constexpr int PPL = kBorderPPL;
     constexpr bool kFeather = BLEND == kStitchFeather;
     uint32_t b;
@@ -29,16 +37,16 @@ __global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(kWavesPerSi
 }
 
 template <int INTERP, int BLEND, bool NV12, int RGB>
-void launch_format(const StitchMapsPlanesArgs& a, dim3 grid, hipStream_t stream) {
+void launch_format(const Args& a, dim3 grid, hipStream_t stream) {
     const dim3 block(kWG);
     if (a.plane == kPlaneF32)
-        hipLaunchKernelGGL((stitch_maps_planes_kernel<INTERP, BLEND, NV12, RGB, false>), grid, block, 0, stream, a);
+        hipLaunchKernelGGL((UNIT_KERNEL<INTERP, BLEND, NV12, RGB, false>), grid, block, 0, stream, a);
     else
-        hipLaunchKernelGGL((stitch_maps_planes_kernel<INTERP, BLEND, NV12, RGB, true>), grid, block, 0, stream, a);
+        hipLaunchKernelGGL((UNIT_KERNEL<INTERP, BLEND, NV12, RGB, true>), grid, block, 0, stream, a);
 }
 
 template <int INTERP, int BLEND>
-void launch_source(const StitchMapsPlanesArgs& a, int source, dim3 grid, hipStream_t stream) {
+void launch_source(const Args& a, int source, dim3 grid, hipStream_t stream) {
     if (source == 2)
         launch_format<INTERP, BLEND, true, 1>(a, grid, stream);
     else if (source == 1)
@@ -48,7 +56,7 @@ void launch_source(const StitchMapsPlanesArgs& a, int source, dim3 grid, hipStre
 }
 
 template <int INTERP>
-void launch_blend(const StitchMapsPlanesArgs& a, int blend, int source, dim3 grid, hipStream_t stream) {
+void launch_blend(const Args& a, int blend, int source, dim3 grid, hipStream_t stream) {
     if (blend == kStitchFeather)
         launch_source<INTERP, kStitchFeather>(a, source, grid, stream);
     else
@@ -57,7 +65,7 @@ void launch_blend(const StitchMapsPlanesArgs& a, int blend, int source, dim3 gri
 
 }  // namespace
 
-hipError_t launch_stitch_maps_planes(const StitchMapsPlanesArgs& a, int nv12_src, int interp, int blend, int rgb_order, int64_t items, hipStream_t stream) {
+hipError_t UNIT_LAUNCH(const UnitArgs<StitchMapsPlanesArgs>& a, int nv12_src, int interp, int blend, int rgb_order, int64_t items, hipStream_t stream) {
     (void)hipGetLastError();  // a stale error left by the host framework is not this call's
     const dim3 grid((unsigned)items);
     const int source = nv12_src ? (rgb_order ? 2 : 1) : 0;  // 0 = interleaved frames, 1 = NV12 frames as B, G, R, 2 = NV12 frames as R, G, B

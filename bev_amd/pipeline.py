@@ -328,7 +328,7 @@ class SitePipeline:
     per stage.  Results are the resident call's (bev_amd.warp.remap_stitch*), bit for bit: the same kernel runs on the same bytes."""
 
     def __init__(self, src_hws, warp_maps, dsize, blend="over", feather=64, border_value=None, depth=3, src_format="bgr", dst_format="bgr", scale=1.0 / 255.0,
-                 bias=0.0, plane_dtype=torch.float32, rgb=False, download=True, device="cuda"):
+                 bias=0.0, plane_dtype=torch.float32, rgb=False, download=True, device="cuda", gains=None):
         """src_hws     (H_k, W_k) of each camera's decoded frames, 1..8 cameras.
         warp_maps   one bev_amd.warp.WarpMap of one frame per camera (build_warp_map: the camera's coordinates, lens included, computed
                     once), all built for `dsize` (u_size, v_size), of one interpolation, on `device`.
@@ -340,6 +340,8 @@ class SitePipeline:
                     scale and bias as bev_amd.warp.remap_stitch_to_planar takes them.
         rgb         NV12 frames into "bgr" or "planes": the result is R, G, B; "bgr" frames into "nv12": the frames are R, G, B.
         download=False leaves the results on the device (valid until `depth` further sets have been committed).
+        gains       None, or per-camera exposure gains as bev_amd.warp.remap_stitch takes them ((n_cams,) or (n_cams, 3) floats in
+                    [0, 1023/256]; bev_amd.exposure.estimate_gains): the launches then carry BEVWARP_STITCH_GAIN.  set_gains() changes them.
         The launch follows the formats: bevwarp_stitch_maps, bevwarp_stitch_maps_nv12, bevwarp_stitch_maps_to_nv12,
         bevwarp_stitch_maps_nv12_to_nv12, bevwarp_stitch_maps_planes or bevwarp_stitch_maps_nv12_planes."""
         src_hws, warp_maps = [(int(h), int(w)) for h, w in src_hws], list(warp_maps)
@@ -372,6 +374,7 @@ class SitePipeline:
         if depth < 2:
             raise ValueError("depth must be >= 2 (one slot in flight per stage boundary)")
         _warp._stitch_maps_call("SitePipeline", len(src_hws), warp_maps, blend, feather, _warp.BORDER_CONSTANT)  # (the blend and the feather width)
+        gain_flag, words = _warp._stitch_gains("SitePipeline", gains, len(src_hws))
         host = {}  # border_value, scale and bias as the prepared launches take them: 3 finite doubles each (border_value: or None)
         for name, v in (("border_value", border_value), ("scale", scale), ("bias", bias)):
             host[name] = None if v is None and name == "border_value" else np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (3,)))
@@ -381,6 +384,7 @@ class SitePipeline:
         self.src_hws, self.warp_maps, self.dw, self.dh, self.n_cams = src_hws, warp_maps, dw, dh, len(src_hws)
         self.blend, self.feather, self.border_value, self.depth, self.download = blend, int(feather), border_value, depth, download
         self.nv12, self.dst_format, self.scale, self.bias, self.plane_dtype, self.rgb = src_format == "nv12", dst_format, scale, bias, plane_dtype, bool(rgb)
+        self.gains = gains
         in_shapes = [(h * 3 // 2, w) if self.nv12 else (h, w, 3) for h, w in src_hws]
         out_shape = {"bgr": (dh, dw, 3), "nv12": (dh * 3 // 2, dw), "planes": (3, dh, dw)}[dst_format]
         out_dtype = plane_dtype if dst_format == "planes" else torch.uint8
@@ -406,8 +410,8 @@ class SitePipeline:
         bv, sc, bi = host["border_value"], host["scale"], host["bias"]
         self._keep = [bv, sc, bi]  # (host arrays and camera tables the prepared launches point into)
         ptr = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
-        interp, blend_id, f = warp_maps[0].interp, _warp._BLENDS[blend], (int(feather) if blend == "feather" else 0)
-        self._launch = []
+        interp, blend_id, f = warp_maps[0].interp, _warp._BLENDS[blend] | gain_flag, (int(feather) if blend == "feather" else 0)
+        self._launch, self._cams = [], []
         for slot in range(depth):
             cams = (_lib.MapCamera * self.n_cams)()
             for cam, s, (h, w), m in zip(cams, self.d_in[slot], src_hws, warp_maps):
@@ -417,7 +421,8 @@ class SitePipeline:
                     cam.src, cam.uv, cam.frame_stride, cam.row_stride = s.data_ptr(), None, s.numel(), s.stride(0)
                 cam.src_h, cam.src_w = h, w
                 _warp._fill_map_camera(cam, m)
-            self._keep.append(cams)
+            _warp._set_gain_words(cams, words)
+            self._cams.append(cams)
             d = self.d_out[slot]
             head = (ctypes.addressof(cams), self.n_cams)
             if dst_format == "nv12":  # (one buffer: the (U, V) rows follow the Y rows)
@@ -440,6 +445,9 @@ class SitePipeline:
             else:
                 args = head + (d.data_ptr(), 1, dh, dw, 3, d.numel(), d.stride(0), _lib.U8, interp, blend_id, f, _warp.BORDER_CONSTANT, ptr(bv), self.s_run)
                 self._launch.append((lib.bevwarp_stitch_maps, args))
+        # (`blend` stands behind the interpolation in all six argument lists: set_gains rewrites it)
+        self._blend_at = {"nv12": 12, "planes": 10}.get(dst_format, 9 if self.nv12 else 11)
+        assert all(args[self._blend_at] == blend_id and args[self._blend_at - 1] == interp for _, args in self._launch)
         self._in_bytes = [t.numel() for t in self.h_in[0]]
         self._out_bytes = self.d_out[0].numel() * self.d_out[0].element_size()
         self.n_in = 0
@@ -469,9 +477,21 @@ class SitePipeline:
     def __del__(self):
         self.close()
 
+    def set_gains(self, gains):
+        """New per-camera gains (as the constructor's `gains`; None: none) for every set of frames committed from now on: the gain words
+        in every slot's host camera table and the flag in its `blend` word are rewritten.  The library reads the table during the call
+        only and takes the gains by value, so sets already committed keep the gains they were committed with, and the next commit()
+        uses the new ones.  Call it from the thread that commits."""
+        gain_flag, words = _warp._stitch_gains("SitePipeline.set_gains", gains, self.n_cams)
+        blend_id = _warp._BLENDS[self.blend] | gain_flag
+        for slot, (fn, args) in enumerate(self._launch):
+            _warp._set_gain_words(self._cams[slot], words or [0] * self.n_cams)
+            self._launch[slot] = (fn, args[:self._blend_at] + (blend_id,) + args[self._blend_at + 1:])
+        self.gains = gains
+
     def _launch_py(self, slot, stream):
         """The same launch through bev_amd.warp (argument validation; used once per slot at construction)."""
-        kw = dict(blend=self.blend, feather=self.feather, border_value=self.border_value, out=self.d_out[slot])
+        kw = dict(blend=self.blend, feather=self.feather, border_value=self.border_value, out=self.d_out[slot], gains=self.gains)
         with torch.cuda.stream(stream):
             if self.nv12:
                 ys, uvs = zip(*[_warp.split_nv12(t) for t in self.d_in[slot]])

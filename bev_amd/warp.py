@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import exposure as _exposure
 
 INTER_NEAREST = _lib.INTER_NEAREST
 INTER_LINEAR = _lib.INTER_LINEAR
@@ -835,6 +836,25 @@ def _stitch_maps_call(who, n_cams, warp_maps, blend, feather, border_mode):
     return warp_maps[0].interp, warp_maps[0].dsize, int(border_mode)
 
 
+def _stitch_gains(who, gains, n_cams, srcs=None):
+    """`gains=` of the stitches through maps (bev_amd.exposure.quantize_gains: (n_cams,) or (n_cams, 3) floats in [0, 1023/256], None: no
+    gains), checked before a tensor's device is looked at.  srcs: remap_stitch's frames, which under gains are uint8 with 3 channels.
+    Returns (the flag to OR into `blend`, the cameras' gain words): (0, ()) without gains."""
+    if gains is None:
+        return 0, ()
+    words = _exposure.gain_words(_exposure.quantize_gains(gains, n_cams))
+    for k, src in enumerate(srcs or ()):
+        if src.dtype != torch.uint8 or src.dim() < 3 or src.shape[-1] != 3:
+            raise ValueError("%s: gains apply to uint8 frames of 3 channels; camera %d is %s %s" % (who, k, src.dtype, tuple(src.shape)))
+    return _lib.STITCH_GAIN, words
+
+
+def _set_gain_words(cams, words):
+    """The gain words into the camera table (bevwarp_map_camera.reserved); the library reads them during the call only."""
+    for cam, w in zip(cams, words):
+        cam.reserved = w
+
+
 def _stitch_maps_dst(out, ndim, B, dh, dw, C):
     """remap's rules for a caller's `out` against the maps' dsize; ndim: the rank of the result of a single camera."""
     if isinstance(out, torch.Tensor) and out.dim() == ndim and ndim >= 2:
@@ -878,7 +898,7 @@ def _nv12_map_cameras(who, ys, uvs, warp_maps):
     return planes, cams, B, device
 
 
-def remap_stitch(srcs, warp_maps, blend="over", feather=64, border_value=None, out=None, border_mode=BORDER_CONSTANT):
+def remap_stitch(srcs, warp_maps, blend="over", feather=64, border_value=None, out=None, border_mode=BORDER_CONSTANT, gains=None):
     """The FIXED cameras of one site sampled through their warp maps into ONE canvas in one launch (include/bevwarp.h,
     bevwarp_stitch_maps): warp_stitch's cover test and blends over remap's map entries.  What a canvas fill plus one
     remap(..., border_mode=BORDER_TRANSPARENT, out=canvas) per camera is for, without a pass over the canvas per camera, with a blend
@@ -890,6 +910,12 @@ def remap_stitch(srcs, warp_maps, blend="over", feather=64, border_value=None, o
                n == 1 (shared by the batch) or n == B.  Two cameras may share one map.  A camera covers a canvas pixel where its map
                entry is an inlier of its frame; a lens map's pixels beyond r2_max cover nothing.
     blend, feather, border_mode, border_value, out   as warp_stitch.
+    gains      None, or per-camera exposure gains (BEVWARP_STITCH_GAIN): (n_cams,) or (n_cams, 3) floats in [0, 1023/256], quantised as
+               rint(256 g); uint8 frames of 3 channels only.  Every tap of camera k is replaced, channel by channel, by
+               min(255, (p G + 128) >> 8) before the interpolation: the result is remap_stitch's of frames put through
+               bev_amd.exposure.apply_gains, by bits, without that pass.  The border pixel is not gained.  Taken by value at the call.
+               bev_amd.exposure.estimate_gains finds gains that even out the cameras' exposure.  The other five remap_stitch* take the
+               same argument.
     With pinhole maps the result is warp_stitch's for the same matrices, by bits; "over" is what the successive remap calls leave.
     Returns a tensor shaped like srcs[0] with (height, width) replaced by the maps', or `out`.  Asynchronous on the current stream."""
     srcs, warp_maps = list(srcs), list(warp_maps)
@@ -897,6 +923,7 @@ def remap_stitch(srcs, warp_maps, blend="over", feather=64, border_value=None, o
     for k, src in enumerate(srcs):
         if not isinstance(src, torch.Tensor) or src.dtype not in _DTYPES or src.dim() not in (2, 3, 4):
             raise ValueError("remap_stitch needs uint8 or float32 tensors (B, H, W, C), (H, W, C) or (H, W); camera %d is %s" % (k, getattr(src, "dtype", type(src))))
+    gain_flag, words = _stitch_gains("remap_stitch", gains, len(srcs), srcs)
     _, C, B, device = _one_kind("remap_stitch", srcs)
     for m in warp_maps:
         _map_fits(m, B, device)
@@ -907,14 +934,15 @@ def remap_stitch(srcs, warp_maps, blend="over", feather=64, border_value=None, o
     cams = (_lib.MapCamera * len(frames))()
     for cam, s4, m in zip(cams, frames, warp_maps):
         _fill_map_camera(cam, m, s4)
+    _set_gain_words(cams, words)
     d4 = _pixel_dst(out, s0.dtype, s0.device, B, dh, dw, C, zeroed=border_mode == BORDER_TRANSPARENT)
     bv = _border(border_value, C) if border_mode == BORDER_CONSTANT else None
     _lib.launch("bevwarp_stitch_maps", s0.device, ctypes.addressof(cams), len(frames), d4.data_ptr(), B, dh, dw, C, d4.stride(0) * esz, d4.stride(1) * esz,
-                _DTYPES[s0.dtype], interp, _BLENDS[blend], int(feather) if blend == "feather" else 0, border_mode, _ptr(bv))  # ("over" ignores feather)
+                _DTYPES[s0.dtype], interp, _BLENDS[blend] | gain_flag, int(feather) if blend == "feather" else 0, border_mode, _ptr(bv))  # ("over" ignores feather)
     return _like_src(d4, srcs[0].dim(), out)
 
 
-def remap_stitch_nv12(ys, uvs, warp_maps, blend="over", feather=64, border_value=None, out=None, border_mode=BORDER_CONSTANT, rgb=False):
+def remap_stitch_nv12(ys, uvs, warp_maps, blend="over", feather=64, border_value=None, out=None, border_mode=BORDER_CONSTANT, rgb=False, gains=None):
     """remap_stitch of the decoders' NV12 frames, converted on the way: bit for bit
 
         remap_stitch([cvtColor(nv12_k, COLOR_YUV2BGR_NV12) ...], warp_maps, blend, feather, border_value, ...)   (rgb=True: COLOR_YUV2RGB_NV12)
@@ -926,15 +954,18 @@ def remap_stitch_nv12(ys, uvs, warp_maps, blend="over", feather=64, border_value
                One B and one device.
     warp_maps, blend, feather, border_mode, out   as remap_stitch.
     border_value   (BORDER_CONSTANT only) a scalar or 3 values in the RESULT's channel order, not converted; None = 0.
+    gains      as remap_stitch, applied to every CONVERTED tap: channel c is channel c of the result (B, G, R; rgb=True: R, G, B).
     Returns (B, h, w, 3), or (h, w, 3) for single frames, or `out`.  Asynchronous on the current stream."""
     ys, uvs, warp_maps = list(ys), list(uvs), list(warp_maps)
     interp, (dw, dh), border_mode = _stitch_maps_call("remap_stitch_nv12", len(ys), warp_maps, blend, feather, border_mode)
+    gain_flag, words = _stitch_gains("remap_stitch_nv12", gains, len(ys))
     planes, cams, B, device = _nv12_map_cameras("remap_stitch_nv12", ys, uvs, warp_maps)
+    _set_gain_words(cams, words)
     _stitch_maps_dst(out, ys[0].dim() + 1, B, dh, dw, 3)
     d4 = _pixel_dst(out, torch.uint8, device, B, dh, dw, 3, zeroed=border_mode == BORDER_TRANSPARENT)
     bv = _border(border_value, 3) if border_mode == BORDER_CONSTANT else None
     _lib.launch("bevwarp_stitch_maps_nv12", device, ctypes.addressof(cams), len(planes), d4.data_ptr(), B, dh, dw, d4.stride(0), d4.stride(1), interp,
-                _BLENDS[blend], int(feather) if blend == "feather" else 0, 1 if rgb else 0, border_mode, _ptr(bv))
+                _BLENDS[blend] | gain_flag, int(feather) if blend == "feather" else 0, 1 if rgb else 0, border_mode, _ptr(bv))
     return _like_src(d4, ys[0].dim() + 1, out)
 
 
@@ -1343,7 +1374,7 @@ def _stitch_maps_nv12_out_call(who, n_cams, warp_maps, blend, feather):
     return interp, (dw, dh)
 
 
-def remap_stitch_to_nv12(srcs, warp_maps, blend="over", feather=64, border_value=None, out=None, rgb=False):
+def remap_stitch_to_nv12(srcs, warp_maps, blend="over", feather=64, border_value=None, out=None, rgb=False, gains=None):
     """remap_stitch of 8-bit BGR cameras, written as the NV12 frame a video encoder takes: bit for bit
 
         BGR->NV12(remap_stitch(srcs, warp_maps, blend, feather, border_value))               (rgb=True: the frames are R, G, B)
@@ -1354,17 +1385,21 @@ def remap_stitch_to_nv12(srcs, warp_maps, blend="over", feather=64, border_value
     warp_maps, blend, feather   as remap_stitch; the maps' dsize is even.
     border_value   a scalar or 3 values in the SOURCES' channel order: the pixel that no camera covers, converted like any other.
     out        as warp_perspective_to_nv12: a joined buffer or a (y, uv) pair.
+    gains      as remap_stitch: channel c is the frames' channel c.
     Returns `out` if given, otherwise a new joined buffer.  Asynchronous on the current stream."""
     srcs, warp_maps = list(srcs), list(warp_maps)
     interp, (dw, dh) = _stitch_maps_nv12_out_call("remap_stitch_to_nv12", len(srcs), warp_maps, blend, feather)
+    gain_flag, words = _stitch_gains("remap_stitch_to_nv12", gains, len(srcs))
     frames, cams, B, device = _bgr_map_cameras("remap_stitch_to_nv12", srcs, warp_maps)
+    _set_gain_words(cams, words)
     y3, uv4, ret = _nv12_dst("remap_stitch_to_nv12", out, device, B, dh, dw, srcs[0].dim() == 3)
     _lib.launch("bevwarp_stitch_maps_to_nv12", device, ctypes.addressof(cams), len(frames), y3.data_ptr(), uv4.data_ptr(), B, dh, dw, y3.stride(0), y3.stride(1),
-                uv4.stride(0), uv4.stride(1), interp, _BLENDS[blend], int(feather) if blend == "feather" else 0, 1 if rgb else 0, _ptr(_border(border_value, 3)))
+                uv4.stride(0), uv4.stride(1), interp, _BLENDS[blend] | gain_flag, int(feather) if blend == "feather" else 0, 1 if rgb else 0,
+                _ptr(_border(border_value, 3)))
     return ret
 
 
-def remap_stitch_nv12_to_nv12(ys, uvs, warp_maps, blend="over", feather=64, border_value=None, out=None):
+def remap_stitch_nv12_to_nv12(ys, uvs, warp_maps, blend="over", feather=64, border_value=None, out=None, gains=None):
     """remap_stitch_nv12 of the decoders' NV12 frames, written as the NV12 frame a video encoder takes: bit for bit
 
         BGR->NV12(remap_stitch_nv12(ys, uvs, warp_maps, blend, feather, border_value))
@@ -1374,13 +1409,17 @@ def remap_stitch_nv12_to_nv12(ys, uvs, warp_maps, blend="over", feather=64, bord
     ys, uvs, warp_maps, blend, feather   as remap_stitch_nv12; the maps' dsize is even.
     border_value   a scalar or 3 values in B, G, R order: the pixel that no camera covers, converted like any other.
     out        as warp_perspective_to_nv12: a joined buffer or a (y, uv) pair.
+    gains      as remap_stitch, applied to every converted tap: channel c is B, G, R.
     Returns `out` if given, otherwise a new joined buffer.  Asynchronous on the current stream."""
     ys, uvs, warp_maps = list(ys), list(uvs), list(warp_maps)
     interp, (dw, dh) = _stitch_maps_nv12_out_call("remap_stitch_nv12_to_nv12", len(ys), warp_maps, blend, feather)
+    gain_flag, words = _stitch_gains("remap_stitch_nv12_to_nv12", gains, len(ys))
     planes, cams, B, device = _nv12_map_cameras("remap_stitch_nv12_to_nv12", ys, uvs, warp_maps)
+    _set_gain_words(cams, words)
     dy3, duv4, ret = _nv12_dst("remap_stitch_nv12_to_nv12", out, device, B, dh, dw, ys[0].dim() == 2)
     _lib.launch("bevwarp_stitch_maps_nv12_to_nv12", device, ctypes.addressof(cams), len(planes), dy3.data_ptr(), duv4.data_ptr(), B, dh, dw, dy3.stride(0),
-                dy3.stride(1), duv4.stride(0), duv4.stride(1), interp, _BLENDS[blend], int(feather) if blend == "feather" else 0, _ptr(_border(border_value, 3)))
+                dy3.stride(1), duv4.stride(0), duv4.stride(1), interp, _BLENDS[blend] | gain_flag, int(feather) if blend == "feather" else 0,
+                _ptr(_border(border_value, 3)))
     return ret
 
 
@@ -1427,7 +1466,8 @@ def remap_to_planar(src, warp_map, scale=1.0 / 255.0, bias=0.0, border_mode=BORD
     return _like_src(d4, src.dim(), out)
 
 
-def remap_stitch_to_planar(srcs, warp_maps, scale=1.0 / 255.0, bias=0.0, blend="over", feather=64, border_value=None, out=None, out_dtype=torch.float32):
+def remap_stitch_to_planar(srcs, warp_maps, scale=1.0 / 255.0, bias=0.0, blend="over", feather=64, border_value=None, out=None, out_dtype=torch.float32,
+                           gains=None):
     """remap_stitch of 8-bit BGR cameras, written as the normalised channel planes a detector takes: bit for bit
 
         out[b, c] = convert(float32(remap_stitch(srcs, warp_maps, blend, feather, border_value)[b, :, :, c]) * scale[c] + bias[c])
@@ -1439,23 +1479,26 @@ def remap_stitch_to_planar(srcs, warp_maps, scale=1.0 / 255.0, bias=0.0, blend="
     scale, bias, border_value   scalars or 3 values in the frames' channel order; border_value is the 8-bit pixel that no camera covers,
                                 put through the plane stage like any other.  "feather" is the 8-bit integer mean, then the plane stage.
     out_dtype, out   as remap_to_planar.
+    gains      as remap_stitch: channel c is the frames' channel c, plane c.
     Returns (B, 3, h, w), or (3, h, w) for single frames.  Asynchronous on the current stream."""
     srcs, warp_maps = list(srcs), list(warp_maps)
     interp, (dw, dh), _ = _stitch_maps_call("remap_stitch_to_planar", len(srcs), warp_maps, blend, feather, BORDER_CONSTANT)
     _plane_format("remap_stitch_to_planar", interp, out_dtype, out)
+    gain_flag, words = _stitch_gains("remap_stitch_to_planar", gains, len(srcs))
     frames, cams, B, device = _bgr_map_cameras("remap_stitch_to_planar", srcs, warp_maps)
+    _set_gain_words(cams, words)
     _planes_out_fits(out, srcs[0].dim(), dw, dh, "maps'")
     d4 = _plane_dst(out, out_dtype, device, B, 3, dh, dw)
     sc, bi = _per_channel(scale, 3), _per_channel(bias, 3)
     esz = d4.element_size()
     _lib.launch("bevwarp_stitch_maps_planes", device, ctypes.addressof(cams), len(frames), d4.data_ptr(), B, dh, dw, d4.stride(0) * esz, d4.stride(1) * esz,
-                d4.stride(2) * esz, interp, _BLENDS[blend], int(feather) if blend == "feather" else 0, _ptr(_border(border_value, 3)), _ptr(sc), _ptr(bi),
+                d4.stride(2) * esz, interp, _BLENDS[blend] | gain_flag, int(feather) if blend == "feather" else 0, _ptr(_border(border_value, 3)), _ptr(sc), _ptr(bi),
                 _PLANE_DTYPES[out_dtype])
     return _like_src(d4, srcs[0].dim(), out)
 
 
 def remap_stitch_nv12_to_planar(ys, uvs, warp_maps, scale=1.0 / 255.0, bias=0.0, blend="over", feather=64, border_value=None, out=None, rgb=False,
-                                out_dtype=torch.float32):
+                                out_dtype=torch.float32, gains=None):
     """remap_stitch_nv12 of the decoders' NV12 frames, written as the normalised channel planes a detector takes: bit for bit
 
         out[b, c] = convert(float32(remap_stitch_nv12(ys, uvs, warp_maps, blend, feather, border_value, rgb=rgb)[b, :, :, c]) * scale[c] + bias[c])
@@ -1466,17 +1509,20 @@ def remap_stitch_nv12_to_planar(ys, uvs, warp_maps, scale=1.0 / 255.0, bias=0.0,
     scale, bias, border_value   scalars or 3 values in the RESULT's channel order (B, G, R; rgb=True: R, G, B); border_value is the 8-bit
                                 pixel that no camera covers, not converted, put through the plane stage like any other.
     out_dtype, out   as remap_to_planar.
+    gains      as remap_stitch, applied to every converted tap: channel c is plane c (B, G, R; rgb=True: R, G, B).
     Returns (B, 3, h, w), or (3, h, w) for single frames.  Asynchronous on the current stream."""
     ys, uvs, warp_maps = list(ys), list(uvs), list(warp_maps)
     interp, (dw, dh), _ = _stitch_maps_call("remap_stitch_nv12_to_planar", len(ys), warp_maps, blend, feather, BORDER_CONSTANT)
     _plane_format("remap_stitch_nv12_to_planar", interp, out_dtype, out)
+    gain_flag, words = _stitch_gains("remap_stitch_nv12_to_planar", gains, len(ys))
     planes, cams, B, device = _nv12_map_cameras("remap_stitch_nv12_to_planar", ys, uvs, warp_maps)
+    _set_gain_words(cams, words)
     _planes_out_fits(out, ys[0].dim() + 1, dw, dh, "maps'")
     d4 = _plane_dst(out, out_dtype, device, B, 3, dh, dw)
     sc, bi = _per_channel(scale, 3), _per_channel(bias, 3)
     esz = d4.element_size()
     _lib.launch("bevwarp_stitch_maps_nv12_planes", device, ctypes.addressof(cams), len(planes), d4.data_ptr(), B, dh, dw, d4.stride(0) * esz, d4.stride(1) * esz,
-                d4.stride(2) * esz, interp, _BLENDS[blend], int(feather) if blend == "feather" else 0, 1 if rgb else 0, _ptr(_border(border_value, 3)), _ptr(sc),
+                d4.stride(2) * esz, interp, _BLENDS[blend] | gain_flag, int(feather) if blend == "feather" else 0, 1 if rgb else 0, _ptr(_border(border_value, 3)), _ptr(sc),
                 _ptr(bi), _PLANE_DTYPES[out_dtype])
     return _like_src(d4, ys[0].dim() + 1, out)
 

@@ -460,7 +460,7 @@ typedef struct bevwarp_map_camera {      /* HOST; 112 bytes */
     int64_t xy_frame_stride, xy_row_stride, frac_frame_stride, frac_row_stride;
     int src_h, src_w;
     int map_count;                       /* 1 (shared by the batch) or batch */
-    int reserved;                        /* 0 */
+    int reserved;                        /* 0; under BEVWARP_STITCH_GAIN (below) the camera's gain word, otherwise not looked at */
 } bevwarp_map_camera;
 int bevwarp_stitch_maps(const bevwarp_map_camera *cams /*HOST*/, int n_cams, void *dst, int batch, int dst_h, int dst_w, int channels,
                         int64_t dst_frame_stride, int64_t dst_row_stride, int dtype, int interp, int blend, int feather,
@@ -468,6 +468,30 @@ int bevwarp_stitch_maps(const bevwarp_map_camera *cams /*HOST*/, int n_cams, voi
 int bevwarp_stitch_maps_nv12(const bevwarp_map_camera *cams /*HOST*/, int n_cams, void *dst, int batch, int dst_h, int dst_w,
                              int64_t dst_frame_stride, int64_t dst_row_stride, int interp, int blend, int feather, int rgb_order,
                              int border_mode, const double *border_value /*HOST*/, void *stream);
+
+/*
+ * BEVWARP_STITCH_GAIN: per-camera exposure gains in the stitches through maps, selected by ORing the flag into `blend` of
+ * bevwarp_stitch_maps, bevwarp_stitch_maps_nv12, bevwarp_stitch_maps_to_nv12, bevwarp_stitch_maps_nv12_to_nv12, bevwarp_stitch_maps_planes
+ * and bevwarp_stitch_maps_nv12_planes (BEVWARP_LENS_FISHEYE's way: the flag is taken out of the word before any check, and what is left of
+ * the word is judged exactly as without it).  Cameras of one site run their own auto-exposure; the gain is applied to every tap while it
+ * is in registers, instead of one multiply-and-clamp pass over every camera's frames before each stitch.  Defined to the bit.
+ *   the gain word   under the flag `reserved` of camera k is G0 | G1 << 10 | G2 << 20: each Gc in 0..1023 is a Q8 fixed-point gain
+ *                   (256 is 1.0, the largest gain is 1023 / 256); bits 30 and 31 must be 0.  Read during the call only, by value.
+ *   the gain step   every tap p of camera k -- after the NV12 conversion where the frames are NV12, before the interpolation -- is
+ *                   replaced channel by channel by
+ *                       gain(p, Gc) = min(255, (p * Gc + 128) >> 8)
+ *                   where channel c is channel c of the pixel the sampler blends: the frames' own order, or for NV12 frames the order
+ *                   rgb_order names (bevwarp_stitch_maps_nv12_to_nv12: B, G, R).  Gc = 256 is the identity, Gc = 0 gives 0.
+ *   everything else is unchanged: the bilinear fixed-point blend, the cover test (a property of the map entry: it does not see the gain),
+ *                   OVER, FEATHER, the single-cover rule, the border pixel (which is NOT gained), the NV12 and the plane store stages.
+ * Hence the entry under the flag equals, by bits, the same entry without it on frames that were put through `gain` beforehand (NV12
+ * frames: on the converted frames, through bevwarp_stitch_maps and its BGR kin).
+ * Formats under the flag: 8 bits, 3 channels -- bevwarp_stitch_maps with another dtype or channel count is BEVWARP_ERR_UNSUPPORTED, where
+ * the format is judged; both border modes where the entry has them.  bevwarp_warp_stitch does not know the flag (BEVWARP_ERR_UNSUPPORTED).
+ * Status under the flag: the cams / n_cams / feather checks as without it; then BEVWARP_ERR_BAD_ARG for the first camera, in ascending k,
+ * whose gain word has bit 30 or 31 set; then everything else as without it.  Without the flag `reserved` is not looked at.
+ */
+#define BEVWARP_STITCH_GAIN 0x100
 
 /*
  * bevwarp_warp with the per-tile verdicts of an earlier launch (ABI v7).  Which way a tile is processed -- inside the frame, outside,
