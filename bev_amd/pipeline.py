@@ -63,6 +63,13 @@ def _ok(err):
 _H2D, _D2H = 1, 2  # hipMemcpyHostToDevice / hipMemcpyDeviceToHost
 
 
+def _by_value(v, n):
+    """`n` float64 values of a scalar or a sequence (broadcast), in an array of the pipeline's own.  The prepared launches point into it,
+    and the library reads through that pointer at every commit(): np.ascontiguousarray alone would hand back a VIEW of a caller's
+    contiguous float64 array of that length, and what the caller writes into its array afterwards would reach every later frame."""
+    return np.array(np.broadcast_to(np.asarray(v, dtype=np.float64), (n,)), dtype=np.float64, order="C")
+
+
 class FramePipeline:
     def __init__(self, src_hw, channels, M, dsize, flags=_warp.INTER_LINEAR, depth=3, dtype=torch.uint8, planar=False, scale=1.0 / 255.0, bias=0.0,
                  download=True, device="cuda", zero_copy_out=True, plane_dtype=torch.float32, src_format="bgr", dst_format="bgr", warp_map=None):
@@ -85,7 +92,9 @@ class FramePipeline:
         `device`: every slot's prepared launch then samples through it (BORDER_CONSTANT, border 0), `M` may be None and `flags` is not
         looked at (the map carries its interpolation).  The launch follows the slots' formats: bevwarp_remap (bgr in, bgr out),
         bevwarp_remap_nv12 (nv12 in, bgr out), bevwarp_remap_to_nv12 (bgr in, nv12 out) or bevwarp_remap_nv12_to_nv12 (nv12 in and out);
-        NV12 slots keep their rules above.  With planar it raises ValueError.  None (default): every path above, unchanged."""
+        NV12 slots keep their rules above.  With planar it raises ValueError.  None (default): every path above, unchanged.
+        scale, bias (with planar) are taken by value: the pipeline keeps copies of its own, and the caller's arrays are the caller's again
+        once the constructor has returned."""
         if warp_map is not None:
             if not isinstance(warp_map, _warp.WarpMap) or warp_map.n != 1:
                 raise ValueError("warp_map must be a bev_amd.warp.WarpMap of one frame, got %s" % (
@@ -196,8 +205,7 @@ class FramePipeline:
                         d.stride(0), self.minv.data_ptr(), 1, interp, 0, None, self.s_run)
                 self._launch.append((lib.bevwarp_warp_nv12, args))
             elif planar:
-                sc = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, dtype=np.float64), (self.C,)))
-                bi = np.ascontiguousarray(np.broadcast_to(np.asarray(bias, dtype=np.float64), (self.C,)))
+                sc, bi = _by_value(scale, self.C), _by_value(bias, self.C)
                 self._keep = getattr(self, "_keep", []) + [sc, bi]
                 psz = d.element_size()
                 args = (s.data_ptr(), d.data_ptr(), 1, self.H, self.W, self.dh, self.dw, self.C, s.numel() * esz, s.stride(0) * esz, d.numel() * psz,
@@ -340,6 +348,8 @@ class SitePipeline:
                     scale and bias as bev_amd.warp.remap_stitch_to_planar takes them.
         rgb         NV12 frames into "bgr" or "planes": the result is R, G, B; "bgr" frames into "nv12": the frames are R, G, B.
         download=False leaves the results on the device (valid until `depth` further sets have been committed).
+        border_value, scale, bias   taken by value: the pipeline keeps copies of its own, and the caller's arrays are the caller's again
+                    once the constructor has returned.
         gains       None, or per-camera exposure gains as bev_amd.warp.remap_stitch takes them ((n_cams,) or (n_cams, 3) floats in
                     [0, 1023/256]; bev_amd.exposure.estimate_gains): the launches then carry BEVWARP_STITCH_GAIN.  set_gains() changes them.
         The launch follows the formats: bevwarp_stitch_maps, bevwarp_stitch_maps_nv12, bevwarp_stitch_maps_to_nv12,
@@ -377,7 +387,7 @@ class SitePipeline:
         gain_flag, words = _warp._stitch_gains("SitePipeline", gains, len(src_hws))
         host = {}  # border_value, scale and bias as the prepared launches take them: 3 finite doubles each (border_value: or None)
         for name, v in (("border_value", border_value), ("scale", scale), ("bias", bias)):
-            host[name] = None if v is None and name == "border_value" else np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (3,)))
+            host[name] = None if v is None and name == "border_value" else _by_value(v, 3)
             if host[name] is not None and not np.isfinite(host[name]).all():
                 raise ValueError("%s must be finite, got %r" % (name, v))
         self.device = torch.device(device)

@@ -2,14 +2,18 @@
 bevwarp_stitch_maps* entries under BEVWARP_STITCH_GAIN; bev_amd.pipeline.SitePipeline; bev_amd.exposure): every byte or element against
 the numpy definition (tests/stitch_gain_ref.py: the plain definition of frames gained beforehand), and device against device against the
 route the flag replaces -- bev_amd.exposure.apply_gains per camera, then the plain entry.  There is no tolerance anywhere.  Interleaved
-canvases are pre-filled with 77, so a pixel a launch leaves unwritten does not pass as zero.
+canvases are pre-filled with 77, so a pixel a launch leaves unwritten does not pass as zero.  The flag adds no ABI symbol, so the table of
+tests/launch_contexts.py does not ask for the gained kernels: CONTEXT_CASES below puts the six entries under gains on a side stream and
+under graph replay with that module's checks (tests/test_stitch_gain_cpu.py holds the cases' preconditions on the host).
 Run on the GPU box:  python -m pytest tests -m gpu -q"""
 import ctypes
+import functools
 
 import numpy as np
 import pytest
 import torch
 
+from tests import launch_contexts as LC
 from tests import nv12_ref as NR
 from tests import remap_nv12_ref as RN
 from tests import remap_ref as RR
@@ -426,3 +430,96 @@ def test_estimated_gains_close_the_step_between_two_cameras(W):
         assert after.max() < before.min(), (c, after.max(), before.min())
     # ... and the stitched canvas under "over" steps by less at the seam
     np.testing.assert_array_equal(W.remap_stitch(ts, dmaps, gains=gains).cpu().numpy()[both], fixed[1][both])
+
+
+# ---- 7. launch contexts: the six gained entries on a side stream and under graph replay ----
+# The gain words ride behind the plain kernel arguments through launch functions of their own (the three warp_stitch_gain*.hip units): a
+# stream argument dropped there, or gains read from the caller's array at replay, shows here and nowhere else.
+CONTEXT_GAINS = np.array([[1.25, 0.8, 0.6], [0.5, 2.0, 1.5]])  # per camera, per channel, none of them 1
+
+
+def _context_cases():
+    from bev_amd import warp as Wm
+    G = SG.quantize(CONTEXT_GAINS, 2)
+    MAPPED = LC._values(border=LC.BORDER, gains=CONTEXT_GAINS)
+    MAPPED_PLANES = LC._values(border=LC.BORDER, scale=LC.SCALE, bias=LC.BIAS, gains=CONTEXT_GAINS)
+    feather = (SM.FEATHER, LC.FEATHER)
+    kw = lambda h: dict(blend="feather", feather=LC.FEATHER, border_value=h["border"], gains=h["gains"])  # noqa: E731
+    cam_refs = lambda i: [LC.ref_maps(0)[i], LC.ref_maps(1)[i]]  # noqa: E731
+    cam_frames = lambda which, i: [f[i] for f in LC.camera_frames(which)]  # noqa: E731
+    per_frame = lambda one: [one(i) for i in range(LC.BATCH)]  # noqa: E731
+
+    def cam_nv12(which, i):
+        y0, y1, uv0, uv1 = LC.camera_nv12(which)
+        return [y0[i], y1[i]], [uv0[i], uv1[i]]
+
+    cover = functools.lru_cache(maxsize=None)(lambda: np.stack(per_frame(lambda i: SM.stitch(cam_frames("A", i), cam_refs(i), LINEAR)[1])))
+    cases = []
+    for no_out in (False, True):
+        mode = SM.TRANSPARENT if no_out else SM.CONSTANT
+        cases.append(LC.Case(
+            "gains-remap_stitch" + "-no_out" * no_out, "bevwarp_stitch_maps", LC.camera_frames, MAPPED, LC.camera_maps, None if no_out else LC.PX,
+            lambda t, r, h, o: [Wm.remap_stitch(t, r, out=LC._o(o), border_mode=LC._mode(o), **kw(h))],
+            lambda which, hw, mode=mode: LC._stack(per_frame(lambda i: SG.stitch(cam_frames(which, i), G, cam_refs(i), LINEAR, *feather, mode, LC.BORDER)[0])),
+            sliceable=(0, 1), written=(lambda: cover() > 0) if no_out else None, cover=cover))
+    cases.append(LC.Case(
+        "gains-remap_stitch_nv12", "bevwarp_stitch_maps_nv12", LC.camera_nv12, MAPPED, LC.camera_maps, LC.PX,
+        lambda t, r, h, o: [Wm.remap_stitch_nv12(t[:2], t[2:], r, out=o[0], **kw(h))],
+        lambda which, hw: LC._stack(per_frame(lambda i: SG.stitch_nv12(*cam_nv12(which, i), G, cam_refs(i), LINEAR, *feather, SM.CONSTANT, LC.BORDER)[0])), cover=cover))
+    cases.append(LC.Case(
+        "gains-remap_stitch_to_nv12", "bevwarp_stitch_maps_to_nv12", LC.camera_frames, MAPPED, LC.camera_maps, LC.NV12_OUT,
+        lambda t, r, h, o: list(Wm.remap_stitch_to_nv12(t, r, out=tuple(o), **kw(h))),
+        lambda which, hw: LC._stack_pairs(per_frame(lambda i: SG.stitch_to_nv12(cam_frames(which, i), G, cam_refs(i), LINEAR, *feather, LC.BORDER))),
+        sliceable=(0, 1), cover=cover))
+    cases.append(LC.Case(
+        "gains-remap_stitch_nv12_to_nv12", "bevwarp_stitch_maps_nv12_to_nv12", LC.camera_nv12, MAPPED, LC.camera_maps, LC.NV12_OUT,
+        lambda t, r, h, o: list(Wm.remap_stitch_nv12_to_nv12(t[:2], t[2:], r, out=tuple(o), **kw(h))),
+        lambda which, hw: LC._stack_pairs(per_frame(lambda i: SG.stitch_nv12_to_nv12(*cam_nv12(which, i), G, cam_refs(i), LINEAR, *feather, LC.BORDER))), cover=cover))
+    cases.append(LC.Case(
+        "gains-remap_stitch_to_planar", "bevwarp_stitch_maps_planes", LC.camera_frames, MAPPED_PLANES, LC.camera_maps, LC.planes_out(F32),
+        lambda t, r, h, o: [Wm.remap_stitch_to_planar(t, r, scale=h["scale"], bias=h["bias"], out=o[0], **kw(h))],
+        lambda which, hw: LC._stack(per_frame(lambda i: SG.stitch_planes(cam_frames(which, i), G, cam_refs(i), LINEAR, LC.SCALE, LC.BIAS, *feather, LC.BORDER))),
+        LC.same_planes(F32), sliceable=(0, 1), cover=cover))
+    cases.append(LC.Case(
+        "gains-remap_stitch_nv12_to_planar", "bevwarp_stitch_maps_nv12_planes", LC.camera_nv12, MAPPED_PLANES, LC.camera_maps, LC.planes_out(F32),
+        lambda t, r, h, o: [Wm.remap_stitch_nv12_to_planar(t[:2], t[2:], r, scale=h["scale"], bias=h["bias"], out=o[0], **kw(h))],
+        lambda which, hw: LC._stack(per_frame(lambda i: SG.stitch_nv12_planes(*cam_nv12(which, i), G, cam_refs(i), LINEAR, LC.SCALE, LC.BIAS, *feather, LC.BORDER))),
+        LC.same_planes(F32), cover=cover))
+    return cases
+
+
+CONTEXT_CASES = _context_cases()
+# the ungained case of tests/launch_contexts.py each of them stands beside
+UNGAINED = {c.name: c.name[len("gains-"):] for c in CONTEXT_CASES}
+
+
+@pytest.fixture(scope="module")
+def delay():
+    """(cycles, milliseconds) of the delay every side-stream case runs behind."""
+    assert torch.cuda.is_available(), "GPU tests need a HIP device"
+    cycles, ms = LC.sleep_cycles_for(50.0)
+    print("torch.cuda._sleep(%d) takes %.1f ms" % (cycles, ms))
+    assert ms >= 20.0, "the delay came out at %.2f ms: too short to enqueue a call behind" % ms
+    return cycles, ms
+
+
+@pytest.mark.parametrize("case", CONTEXT_CASES, ids=repr)
+def test_side_stream_behind_a_delay(case, delay):
+    cycles, ms = delay
+    case.assert_preconditions()
+    host_s = LC.check_side_stream(case, LC.Gpu("cuda:0", cycles))
+    print("%s: delay %.1f ms, the call took %.3f ms on the host" % (case.name, ms, host_s * 1e3))
+
+
+@pytest.mark.parametrize("case", CONTEXT_CASES, ids=repr)
+def test_capture_and_replay(case):
+    """The gains are one of the host arrays the replay check overwrites with NaNs after the capture."""
+    case.assert_preconditions()
+    assert "gains" in case.host("A")
+    LC.check_replays(case, LC.Gpu("cuda:0"))
+
+
+@pytest.mark.parametrize("case", [c for c in CONTEXT_CASES if c.sliceable], ids=repr)
+def test_capture_and_replay_copied_source(case):
+    case.assert_preconditions()
+    LC.check_replays(case, LC.Gpu("cuda:0"), sliced=True)

@@ -368,3 +368,55 @@ def test_overlap_stats_twin_on_hand_made_maps():
             np.testing.assert_array_equal(exposure.cover_mask(m, (5, 6))[0].numpy(), RR.written(xy, 6, 5, interp))
     g = exposure.solve_gains(N, S)
     assert g.shape == (2, 3) and (g[0] > 1).all() and (g[1] < 1).all()  # the darker camera is raised, the brighter one lowered
+
+
+# ---- the launch-context cases of tests/test_gpu_stitch_gain.py: what they need in order to show anything ----
+
+def _context_cases():
+    from tests import test_gpu_stitch_gain as TG
+    return TG.CONTEXT_CASES
+
+
+def test_the_context_cases_cover_the_six_gained_entries():
+    from tests import launch_contexts as LC
+    from tests import test_gpu_stitch_gain as TG
+    cases = _context_cases()
+    assert sorted({c.symbol for c in cases}) == sorted(s for s in _lib.SYMBOLS if s.startswith("bevwarp_stitch_maps"))
+    assert len({c.symbol for c in cases}) == 6 and len({c.name for c in cases}) == len(cases)
+    assert [c.name for c in cases if c.no_out] == ["gains-remap_stitch-no_out"]
+    assert sorted(c.symbol for c in cases if c.sliceable and not c.no_out) == ["bevwarp_stitch_maps", "bevwarp_stitch_maps_planes", "bevwarp_stitch_maps_to_nv12"]
+    plain = {c.name: c for c in LC.CASES}
+    for c in cases:  # each stands beside the ungained case of the table: the same symbol, inputs and destination
+        other = plain[TG.UNGAINED[c.name]]
+        assert other.symbol == c.symbol and other.inputs is c.inputs and other.out_shapes == c.out_shapes and other.sliceable == c.sliceable
+    G = SG.quantize(TG.CONTEXT_GAINS, 2)
+    assert G.shape == (2, 3) and (G != 256).all() and len({int(g) for g in G.ravel()}) == 6 and G.min() > 0 and G.max() <= 1023
+
+
+@pytest.mark.parametrize("case", _context_cases(), ids=repr)
+def test_the_context_cases_preconditions_hold_on_the_host(case):
+    """The two sets give different results under the gains, and each differs from the ungained expectation of the same set (a launch that
+    dropped the gain words would pass neither); cover counts 0, 1 and 2; the gains travel as a host value the replay check overwrites."""
+    from tests import launch_contexts as LC
+    from tests import test_gpu_stitch_gain as TG
+    case.assert_preconditions()
+    plain = {c.name: c for c in LC.CASES}[TG.UNGAINED[case.name]]
+    exp = {which: case.expected(which, which) for which in LC.SETS}
+    assert LC.differ(exp["A"], exp["B"])
+    for which in LC.SETS:
+        ungained = plain.expected(which, which)
+        assert [e.shape for e in exp[which]] == [e.shape for e in ungained] and LC.differ(exp[which], ungained)
+        for e, u in zip(exp[which], ungained):
+            assert not (e == LC.POISON).all()
+            if case.cover is not None and e.shape[-1] == 3 and e.dtype == np.uint8:  # interleaved: what no camera covers is not gained
+                uncovered = case.cover() == 0
+                np.testing.assert_array_equal(e[uncovered], u[uncovered])
+    host = case.host("A")
+    assert set(host) >= {"gains", "border"} and all(a.dtype == np.float64 and np.isfinite(a).all() for a in host.values())
+    np.testing.assert_array_equal(host["gains"], TG.CONTEXT_GAINS)
+    assert host["gains"] is not case.host("A")["gains"]  # (fresh arrays per call: the check overwrites its own)
+    for count in case.cover():
+        assert set(np.unique(count)) == {0, 1, 2}
+    if case.no_out:
+        for w, e in zip(case.written(), exp["A"][0]):
+            assert w.any() and not w.all() and (e[~w] == 0).all() and (e[w] != 0).any()
