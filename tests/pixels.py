@@ -230,7 +230,8 @@ def assert_canaries_intact(holder, view, what=""):
         off = off[..., None] + np.arange(n, dtype=np.int64) * s
     inside = np.zeros(holder.numel(), bool)
     inside[off.ravel()] = True
-    host = holder.view(-1).cpu().numpy().view(np.uint8)
+    import torch
+    host = holder.view(-1).view(torch.uint8).cpu().numpy()  # (as bytes on the device: numpy has no bfloat16)
     bad = (host != CANARY) & ~np.repeat(inside, esz)
     if bad.any():
         first = int(np.flatnonzero(bad)[0])

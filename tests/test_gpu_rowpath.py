@@ -312,20 +312,7 @@ def test_turned_footprints_through_unaligned_views(W, c, dtype):
         assert (got[:, :3] == 77).all() and (got[:, 3 + dw:] == 77).all()  # nothing written outside the view, in either mode
 
 
-def _random_homography(rng, sw, sh, dw, dh):
-    """src -> dst map of a random similarity-plus-perspective window: rotation, 0.4 .. 3 x scale, mild keystone, a shift that
-    may push part of the window out of the frame."""
-    ang = rng.uniform(-np.pi, np.pi) if rng.random() < 0.7 else rng.choice([0.0, np.pi / 2, np.pi, -np.pi / 2])
-    zoom = float(np.exp(rng.uniform(np.log(0.4), np.log(3.0))))
-    c, s = np.cos(ang) * zoom, np.sin(ang) * zoom
-    A = np.array([[c, -s, 0.0], [s, c, 0.0], [rng.uniform(-2e-4, 2e-4), rng.uniform(-2e-4, 2e-4), 1.0]])
-    T0 = np.array([[1, 0, -(dw - 1) / 2.0], [0, 1, -(dh - 1) / 2.0], [0, 0, 1.0]])
-    T1 = np.array([[1, 0, (sw - 1) / 2.0 + rng.uniform(-0.4, 0.4) * sw], [0, 1, (sh - 1) / 2.0 + rng.uniform(-0.4, 0.4) * sh], [0, 0, 1.0]])
-    if rng.random() < 0.25:  # integer-valued similarity: every coordinate on a tie boundary
-        A = np.array([[1.0, 0, 0], [0, 1.0, 0], [0, 0, 1.0]]) * [[1], [1], [1]]
-        T1 = np.round(T1)
-        T0 = np.round(T0)
-    return np.linalg.inv(T1 @ A @ T0)
+from tests.random_scenes import _random_homography  # noqa: E402,F401  (it lives there now; tools/soak_*.py take it from here)
 
 
 @pytest.mark.parametrize("seed", range(6))
