@@ -389,19 +389,26 @@ int bevwarp_remap(const void* src, void* dst, int batch, int src_h, int src_w, i
                   int64_t src_row_stride, int64_t dst_frame_stride, int64_t dst_row_stride, const void* map_xy, const void* map_frac, int map_count,
                   int64_t xy_frame_stride, int64_t xy_row_stride, int64_t frac_frame_stride, int64_t frac_row_stride, int dtype, int interp, int border_mode,
                   const double* border_value, void* stream) {
+    const bool bicubic = plan::take_map_bicubic_flag(interp);
     const Call c = plan::remap_call({src, src_frame_stride, src_row_stride}, {dst, dst_frame_stride, dst_row_stride}, {map_xy, xy_frame_stride, xy_row_stride},
                                     {map_frac, frac_frame_stride, frac_row_stride}, {batch, src_h, src_w, dst_h, dst_w, 0, nullptr}, map_count, channels, dtype,
-                                    interp, border_mode);
+                                    interp, border_mode, bicubic);
     RemapArgs a;
     int64_t items;
     const int st = remap_grid_args(c, a, 1, interp, border_mode, items);
     if (!items) return st;
+    if (bicubic) {  // the 4 taps of a bicubic window reach one index beyond a saturated one: bevwarp_warp_border's period plan, every mode
+        const plan::BorderPeriod px = cubic::window_period(border_mode, src_w), py = cubic::window_period(border_mode, src_h);
+        a.per_x = px.per, a.off_x = px.off, a.mag_x = px.mag;
+        a.per_y = py.per, a.off_y = py.off, a.mag_y = py.mag;
+    }
     uint8_t bu[4];  // (border_value is read by the constant border only)
     if (border_values(border_mode == BEVWARP_BORDER_CONSTANT ? border_value : nullptr, channels, a.bv_f, bu) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
     a.bv_u8 = packed4(bu);
     fill_source(a, c.reads[0].im);
     a.dst_vec_ok = plan::wide_stores_ok(c.writes[0], plan::store_align(dtype, channels, false));
     a.src_vec_ok = plan::pixel_loads_ok(c.reads[0].im, plan::pixel_load_align(dtype, channels));
+    if (bicubic) return launched(launch_remap_cubic(a, dtype, channels, border_mode, items, (hipStream_t)stream));
     return launched(launch_remap(a, dtype, channels, interp, border_mode, items, (hipStream_t)stream));
 }
 

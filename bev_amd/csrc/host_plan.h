@@ -250,10 +250,19 @@ inline void read_map_planes(Call& c, Frames xy, Frames frac, int interp) {
     c.read_map(xy.image(c.dst_h, (uint64_t)c.dst_w * 4, n), 4);
     if (interp == BEVWARP_LINEAR) c.read_map(frac.image(c.dst_h, (uint64_t)c.dst_w * 2, n), 2);
 }
-// bevwarp_remap: bevwarp_warp's images and formats without bicubic, with all six borders, and the two map planes.
-inline Call remap_call(Frames src, Frames dst, Frames xy, Frames frac, const Sizes& z, int map_count, int channels, int dtype, int interp, int border_mode) {
+// BEVWARP_MAP_BICUBIC in the `interp` word of bevwarp_remap (and of no other entry): taken out of the word, take_fisheye_flag's way.  True:
+// the call samples a bilinear map bicubically, and what is left of the word must be BEVWARP_LINEAR (remap_call's `bicubic`).
+inline bool take_map_bicubic_flag(int& word) {
+    const bool bicubic = (word & BEVWARP_MAP_BICUBIC) != 0;
+    word &= ~BEVWARP_MAP_BICUBIC;
+    return bicubic;
+}
+// bevwarp_remap: bevwarp_warp's images and formats without bicubic, with all six borders, and the two map planes.  interp: without
+// BEVWARP_MAP_BICUBIC (take_map_bicubic_flag), which `bicubic` carries: under it only a bilinear map is a format.
+inline Call remap_call(Frames src, Frames dst, Frames xy, Frames frac, const Sizes& z, int map_count, int channels, int dtype, int interp, int border_mode,
+                       bool bicubic = false) {
     Call c = warp_call(src, dst, map_sizes(z, xy, map_count), channels, dtype, interp, false);
-    c.format_ok = c.format_ok && border_mode >= BEVWARP_BORDER_CONSTANT && border_mode <= BEVWARP_BORDER_TRANSPARENT;
+    c.format_ok = c.format_ok && border_mode >= BEVWARP_BORDER_CONSTANT && border_mode <= BEVWARP_BORDER_TRANSPARENT && (!bicubic || interp == BEVWARP_LINEAR);
     read_map_planes(c, xy, frac, interp);
     return c;
 }

@@ -1,4 +1,4 @@
-// Internal interface of the fixed-camera warp maps (warp_map.hip): bevwarp_build_map writes the coordinate chain's result as OpenCV's
+// Internal interface of the fixed-camera warp maps (warp_map.hip, warp_map_cubic.hip): bevwarp_build_map writes the coordinate chain's result as OpenCV's
 // fixed-point maps (CV_16SC2 + CV_16UC1, include/bevwarp.h), bevwarp_remap samples frames through such maps with no float64 at all.
 // The launch geometry is the border kernel's flat grid; a remap item covers one tile of several consecutive frames.  Not installed.
 #pragma once
@@ -33,11 +33,17 @@ struct RemapArgs : BorderArgs {
     int map_vec_ok;             // both planes admit a lane's 16-byte / 8-byte load
     float bv_f[4];              // the border value per channel, float32 pixels
     uint32_t bv_u8;             // ... and saturate_cast<uchar> of it, packed: byte k = channel k
+    // (the same border value per channel, as cubic_sample.h's sampler takes it: BORDER_CONSTANT's, 0 for every other mode)
+    __device__ __forceinline__ int cv_int(int k) const { return (int)((bv_u8 >> (8 * k)) & 0xffu); }
+    __device__ __forceinline__ float cv_float(int k) const { return bv_f[k]; }
 };
 
 hipError_t launch_build_map(const MapBuildArgs& a, int interp, bool lens, int64_t items, hipStream_t stream);
 // ... under BEVWARP_LENS_FISHEYE (warp_map_fisheye.hip): lens holds fx, fy, cx, cy, k1, k2, k3, k4 and four zeros, r2_max holds theta_max
 hipError_t launch_build_map_fisheye(const MapBuildArgs& a, int interp, int64_t items, hipStream_t stream);
 hipError_t launch_remap(const RemapArgs& a, int dtype, int channels, int interp, int mode, int64_t items, hipStream_t stream);
+// ... under BEVWARP_MAP_BICUBIC (warp_map_cubic.hip): a bilinear map's entries sampled by the bicubic sampler; per_*, off_*, mag_* are
+// cubic::window_period's for every mode (the 4-tap window reaches one index further than a saturated one)
+hipError_t launch_remap_cubic(const RemapArgs& a, int dtype, int channels, int mode, int64_t items, hipStream_t stream);
 
 }  // namespace bevwarp

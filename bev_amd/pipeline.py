@@ -72,7 +72,7 @@ def _by_value(v, n):
 
 class FramePipeline:
     def __init__(self, src_hw, channels, M, dsize, flags=_warp.INTER_LINEAR, depth=3, dtype=torch.uint8, planar=False, scale=1.0 / 255.0, bias=0.0,
-                 download=True, device="cuda", zero_copy_out=True, plane_dtype=torch.float32, src_format="bgr", dst_format="bgr", warp_map=None):
+                 download=True, device="cuda", zero_copy_out=True, plane_dtype=torch.float32, src_format="bgr", dst_format="bgr", warp_map=None, map_interpolation=None):
         """src_hw (H, W) of the decoded frames; M the forward homography (as for warpPerspective); dsize (u_size, v_size).
         download=False leaves the BEV frames on the device (results are device tensors valid until `depth` further frames
         have been submitted).  zero_copy_out (with download): the kernel stores the BEV frame straight into the pinned host
@@ -93,19 +93,27 @@ class FramePipeline:
         looked at (the map carries its interpolation).  The launch follows the slots' formats: bevwarp_remap (bgr in, bgr out),
         bevwarp_remap_nv12 (nv12 in, bgr out), bevwarp_remap_to_nv12 (bgr in, nv12 out) or bevwarp_remap_nv12_to_nv12 (nv12 in and out);
         NV12 slots keep their rules above.  With planar it raises ValueError.  None (default): every path above, unchanged.
+        map_interpolation   (with warp_map) None (default) or the map's own interpolation: the map's.  INTER_CUBIC with a bilinear map and
+        "bgr" slots on both sides: every frame is sampled bicubically through the map (bev_amd.warp.remap(interpolation=INTER_CUBIC)); with
+        an NV12 slot on either side, with a nearest map or without warp_map it raises ValueError.
         scale, bias (with planar) are taken by value: the pipeline keeps copies of its own, and the caller's arrays are the caller's again
         once the constructor has returned."""
         if warp_map is not None:
             if not isinstance(warp_map, _warp.WarpMap) or warp_map.n != 1:
                 raise ValueError("warp_map must be a bev_amd.warp.WarpMap of one frame, got %s" % (
                     "%d frames" % warp_map.n if isinstance(warp_map, _warp.WarpMap) else type(warp_map).__name__,))
+            self._map_interp = _warp._map_interpolation("FramePipeline", warp_map, map_interpolation)
+            if self._map_interp != warp_map.interp and (src_format == "nv12" or dst_format == "nv12"):
+                raise ValueError("map_interpolation=INTER_CUBIC samples interleaved frames into interleaved frames only: the NV12 samplers have no bicubic")
             if planar:
                 raise ValueError("warp_map writes interleaved or NV12 frames only: planar=True is not available with it")
             if warp_map.dsize != (int(dsize[0]), int(dsize[1])):
                 raise ValueError("warp_map was built for dsize %s, the pipeline's is %s" % (warp_map.dsize, (int(dsize[0]), int(dsize[1]))))
             if warp_map.device.type != torch.device(device).type:
                 raise ValueError("warp_map is on %s, the pipeline runs on %s" % (warp_map.device, device))
-        self.warp_map = warp_map
+        elif map_interpolation is not None:
+            raise ValueError("map_interpolation needs a warp_map")
+        self.warp_map, self.map_interpolation = warp_map, map_interpolation
         if src_format not in ("bgr", "nv12"):
             raise ValueError("unsupported src_format %r (\"bgr\", \"nv12\")" % (src_format,))
         self.nv12 = src_format == "nv12"
@@ -186,7 +194,7 @@ class FramePipeline:
                     self._launch.append((lib.bevwarp_remap_nv12 if self.nv12 else lib.bevwarp_remap_to_nv12, args + (0, None, self.s_run)))
             elif warp_map is not None:
                 args = (s.data_ptr(), d.data_ptr(), 1, self.H, self.W, self.dh, self.dw, self.C, s.numel() * esz, s.stride(0) * esz, d.numel() * esz,
-                        d.stride(0) * esz) + warp_map._planes()[:2] + (1,) + warp_map._planes()[2:] + (_warp._DTYPES[s.dtype], warp_map.interp,
+                        d.stride(0) * esz) + warp_map._planes()[:2] + (1,) + warp_map._planes()[2:] + (_warp._DTYPES[s.dtype], self._map_interp,
                                                                                                      _warp.BORDER_CONSTANT, None, self.s_run)
                 self._launch.append((lib.bevwarp_remap, args))
             elif self.nv12_out:  # (one buffer per side: the (U, V) rows follow the Y rows)
@@ -255,8 +263,10 @@ class FramePipeline:
             if self.warp_map is not None and self.nv12:
                 y, uv = _warp.split_nv12(self.d_in[slot])
                 (_warp.remap_nv12_to_nv12 if self.nv12_out else _warp.remap_nv12)(y, uv, self.warp_map, out=self.d_out[slot])
+            elif self.warp_map is not None and self.nv12_out:
+                _warp.remap_to_nv12(self.d_in[slot], self.warp_map, out=self.d_out[slot])
             elif self.warp_map is not None:
-                (_warp.remap_to_nv12 if self.nv12_out else _warp.remap)(self.d_in[slot], self.warp_map, out=self.d_out[slot])
+                _warp.remap(self.d_in[slot], self.warp_map, out=self.d_out[slot], interpolation=self.map_interpolation)
             elif self.nv12_out and self.nv12:
                 y, uv = _warp.split_nv12(self.d_in[slot])
                 _warp.warp_nv12_to_nv12(y, uv, None, (self.dw, self.dh), flags=self.flags, out=self.d_out[slot], M_inv_device=self.minv)

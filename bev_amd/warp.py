@@ -536,7 +536,8 @@ class WarpMap:
 
     xy       (n, dh, dw, 2) torch.int16: (sx, sy) per destination pixel (CV_16SC2).
     frac     (n, dh, dw) torch.int16 holding (fy << 5) | fx (CV_16UC1; the values are below 1024), or None for INTER_NEAREST.
-    interp   INTER_NEAREST or INTER_LINEAR: the interpolation the map was built for (sx differs by it).
+    interp   INTER_NEAREST or INTER_LINEAR: the interpolation the map was built for (sx differs by it).  An INTER_LINEAR map also serves
+             bicubic sampling: remap(..., interpolation=INTER_CUBIC) -- no map is built for INTER_CUBIC.
     dsize    (width, height).
     The planes may be views (padded rows, an offset base): their strides are passed through.  build_warp_map makes one on the device;
     a hand-made pair (cv2.convertMaps's output, say) is wrapped by calling the class."""
@@ -588,7 +589,8 @@ def build_warp_map(M, dsize, flags=INTER_LINEAR, K=None, dist_coeff=None, r2_max
              values; theta_max None: fisheye_valid_theta(dist_coeff)).  The map's format is the same, so remap, the stitches and the
              pipelines serve a fisheye camera as they stand.
     remap(src, build_warp_map(...)) equals warp_perspective(src, ..., border_mode=m) for every border mode, and warp_perspective_lens
-    for BORDER_CONSTANT and BORDER_TRANSPARENT, by bits.  Asynchronous on the current stream."""
+    for BORDER_CONSTANT and BORDER_TRANSPARENT, by bits.  flags=INTER_CUBIC stays a ValueError: bicubic samples the INTER_LINEAR map,
+    remap(src, build_warp_map(..., flags=INTER_LINEAR), interpolation=INTER_CUBIC).  Asynchronous on the current stream."""
     fisheye = _lens_model("build_warp_map", lens_model, r2_max, theta_max)
     interp = _interp("build_warp_map", flags)
     dw, dh = int(dsize[0]), int(dsize[1])
@@ -646,7 +648,24 @@ def _map_fits(warp_map, B, device):
         raise ValueError("the map is on %s, the frames are on %s" % (warp_map.device, device))
 
 
-def remap(src, warp_map, border_mode=BORDER_CONSTANT, border_value=None, out=None):
+def _map_interpolation(who, warp_map, interpolation):
+    """The `interp` word of bevwarp_remap for a map sampled with `interpolation`: None or the map's own interpolation is the map's;
+    INTER_CUBIC samples a bilinear map bicubically (BEVWARP_MAP_BICUBIC); anything else is refused before a tensor is touched."""
+    if interpolation is None:
+        return warp_map.interp
+    if isinstance(interpolation, bool) or not isinstance(interpolation, (int, np.integer)):
+        raise ValueError("%s: interpolation must be None, the map's own interpolation or INTER_CUBIC, got %r" % (who, interpolation))
+    interpolation = int(interpolation)
+    if interpolation == warp_map.interp:
+        return warp_map.interp
+    if interpolation == INTER_CUBIC:
+        if warp_map.interp != INTER_LINEAR:
+            raise ValueError("%s: bicubic samples a bilinear map (build_warp_map(flags=INTER_LINEAR)); this map was built for INTER_NEAREST" % who)
+        return INTER_LINEAR | _lib.MAP_BICUBIC
+    raise ValueError("%s: interpolation must be None, the map's own interpolation (%d) or INTER_CUBIC, got %r" % (who, warp_map.interp, interpolation))
+
+
+def remap(src, warp_map, border_mode=BORDER_CONSTANT, border_value=None, out=None, interpolation=None):
     """cv2.remap on the GPU, batched: frames sampled through a WarpMap (include/bevwarp.h, bevwarp_remap) -- no coordinate is computed,
     no float64 is touched.  The per-frame half of a fixed camera's loop; build_warp_map is the other.
 
@@ -654,8 +673,14 @@ def remap(src, warp_map, border_mode=BORDER_CONSTANT, border_value=None, out=Non
     warp_map a WarpMap on src's device with n == 1 (shared by all frames) or n == B; its interpolation is the call's.
     border_mode   any of the six BORDER_* modes; border_value (BORDER_CONSTANT only) a scalar or C values, None = 0.
     out      as warp_perspective; BORDER_TRANSPARENT without `out` starts from zeros.
+    interpolation   None (default) or the map's own interpolation: the map's.  INTER_CUBIC with an INTER_LINEAR map: the map is sampled
+             bicubically (BEVWARP_MAP_BICUBIC) -- cv2.INTER_CUBIC is defined on the bilinear map, so no map is built for it, and with a lens
+             or fisheye map this is the bicubic resampling of a raw distorted frame in one pass.  With a pinhole map the result equals
+             warp_perspective(flags=INTER_CUBIC, border_mode=m) by bits in all six modes.  INTER_CUBIC with an INTER_NEAREST map, and any
+             other value, is a ValueError.
     Returns a tensor shaped like src with (height, width) replaced by the map's, or `out`.  Asynchronous on the current stream."""
     border_mode = _map_call("remap", warp_map, border_mode)
+    interp = _map_interpolation("remap", warp_map, interpolation)
     if not isinstance(src, torch.Tensor) or src.dtype not in _DTYPES or src.dim() not in (2, 3, 4):
         raise ValueError("remap needs a uint8 or float32 tensor (B, H, W, C), (H, W, C) or (H, W)")
     B = src.shape[0] if src.dim() == 4 else 1
@@ -675,7 +700,7 @@ def remap(src, warp_map, border_mode=BORDER_CONSTANT, border_value=None, out=Non
     bv = _border(border_value, C) if border_mode == BORDER_CONSTANT else None
     xy_p, fr_p, xy_fs, xy_rs, fr_fs, fr_rs = warp_map._planes()
     _lib.launch("bevwarp_remap", s4.device, s4.data_ptr(), d4.data_ptr(), B, H, W, dh, dw, C, s4.stride(0) * esz, s4.stride(1) * esz, d4.stride(0) * esz,
-                d4.stride(1) * esz, xy_p, fr_p, warp_map.n, xy_fs, xy_rs, fr_fs, fr_rs, _DTYPES[s4.dtype], warp_map.interp, border_mode, _ptr(bv))
+                d4.stride(1) * esz, xy_p, fr_p, warp_map.n, xy_fs, xy_rs, fr_fs, fr_rs, _DTYPES[s4.dtype], interp, border_mode, _ptr(bv))
     return _like_src(d4, src.dim(), out)
 
 

@@ -340,7 +340,7 @@ int bevwarp_warp_lens(const void *src, void *dst, int batch, int src_h, int src_
  *   src, dst, batch, sizes, channels, the four strides, dtype, border_value   as bevwarp_warp_border, with the same checks.
  *   map_xy, map_frac   device, READ; map_count == 1 (shared by all frames; frame strides not looked at) or == batch.  dst must not overlap
  *                 either plane (bounding byte ranges).  map_frac NULL under BEVWARP_LINEAR is BEVWARP_ERR_BAD_ARG.
- *   interp        BEVWARP_NEAREST | BEVWARP_LINEAR: the interpolation the map was built for.
+ *   interp        BEVWARP_NEAREST | BEVWARP_LINEAR: the interpolation the map was built for.  (BEVWARP_LINEAR | BEVWARP_MAP_BICUBIC: below.)
  *   border_mode   all six.  From (sx, sy, fx, fy) on the pixel is defined to the bit by the existing entries: BEVWARP_BORDER_CONSTANT is
  *                 bevwarp_warp_lens's sampler -- each tap outside the source is replaced by the border pixel, all four taps outside -> the
  *                 border value itself --, the other five modes are bevwarp_warp_border's.  With a map from bevwarp_build_map the result
@@ -350,7 +350,35 @@ int bevwarp_warp_lens(const void *src, void *dst, int batch, int src_h, int src_
  * BEVWARP_ERR_UNSUPPORTED; BEVWARP_ERR_OVERLAP; BEVWARP_ERR_TOO_LARGE for a destination side > 2^20; BEVWARP_ERR_NOT_FINITE for border_value
  * (BEVWARP_BORDER_CONSTANT only).  batch == 0 is BEVWARP_OK and launches nothing.
  * Restated from memory of OpenCV's remap / convertMaps (imgwarp.cpp); parity with OpenCV is unpinned, like the rest of the warp.
+ *
+ * BEVWARP_MAP_BICUBIC: bicubic sampling (cv2.INTER_CUBIC) through a BILINEAR map, selected by ORing the flag into `interp` of bevwarp_remap --
+ * and of no other entry.  OpenCV's bicubic is defined on the bilinear map (bevwarp_warp_border, interp == BEVWARP_CUBIC, "maps"), so no map
+ * is built for it: a BEVWARP_LINEAR map entry holds everything the bicubic sampler needs, and bevwarp_build_map, the map format and every
+ * existing map stay as they are.  Without the flag every call is what it was, bit for bit and status for status.  With it, the flag is
+ * taken out of the word before any check, and what is left must be BEVWARP_LINEAR: BEVWARP_NEAREST | flag, BEVWARP_CUBIC | flag and any
+ * other remainder are BEVWARP_ERR_UNSUPPORTED, judged where `interp` is judged without the flag.  Every other check is that of a
+ * BEVWARP_LINEAR call, in the same order: a NULL map_frac is BEVWARP_ERR_BAD_ARG, border_value is BEVWARP_ERR_NOT_FINITE under
+ * BEVWARP_BORDER_CONSTANT only, batch == 0 is BEVWARP_OK and launches nothing.
+ * Per destination pixel, with the entry (sx, sy) as stored (int16) and its frac word v:
+ *   fx = v & 31, fy = (v >> 5) & 31; higher bits are ignored.
+ *   The 4 x 4 tap window starts at wx = sx - 1, wy = sy - 1, computed in int32 (-32769 is a window position like any other).  This is the
+ *   sat16(X >> 5) - 1 of bevwarp_warp_border's BEVWARP_CUBIC, because the map stores the saturated value.
+ * From (wx, wy, fy, fx) on the pixel is bevwarp_warp_border's BEVWARP_CUBIC text above, with (wx, wy) for its (sx, sy), unchanged: the weights;
+ * the inlier test; BEVWARP_BORDER_TRANSPARENT's rule (the pixel is written iff it is an inlier or the entry's own (sx, sy) lies in the source);
+ * BEVWARP_BORDER_CONSTANT's shortcut for a window that is wholly outside; the general path tap by tap through borderInterpolate; the two
+ * summation orders; the 8-bit clamp((sum + 16384) >> 15, 0, 255); float32 with every multiply and add rounded, no FMA.  Window indices lie
+ * in [-32769, 32769].
+ *   - With a pinhole map from bevwarp_build_map(..., BEVWARP_LINEAR) the result equals bevwarp_warp_border(..., BEVWARP_CUBIC, border_mode) by
+ *     bits, in all six modes (BEVWARP_BORDER_CONSTANT: bevwarp_warp(..., BEVWARP_CUBIC)).
+ *   - An invalid entry (-32768, -32768), frac 0 has its whole window at negative indices: BEVWARP_BORDER_CONSTANT stores the border value
+ *     itself, BEVWARP_BORDER_TRANSPARENT does not write the pixel.
+ *   - With a rational-lens or fisheye map this is bicubic resampling of a raw distorted frame in one pass; no other entry offers that.
+ *   dtype BEVWARP_U8 | BEVWARP_F32, channels 1..4, all six border modes; shared or per-frame maps (map_count 1 or batch), as without the flag.
+ * No other entry takes the flag: bevwarp_build_map, bevwarp_warp_lens, bevwarp_remap_nv12, bevwarp_remap_nv12_planes, bevwarp_remap_to_nv12,
+ * bevwarp_remap_nv12_to_nv12, bevwarp_remap_planes and every stitch judge the whole word, and BEVWARP_LINEAR | BEVWARP_MAP_BICUBIC is
+ * BEVWARP_ERR_UNSUPPORTED there.
  */
+#define BEVWARP_MAP_BICUBIC 0x200
 int bevwarp_build_map(const double *M, int m_count, const double *lens /*HOST, 12, or NULL*/, double r2_max, int interp,
                       void *map_xy, void *map_frac, int dst_h, int dst_w, int64_t xy_frame_stride, int64_t xy_row_stride,
                       int64_t frac_frame_stride, int64_t frac_row_stride, void *stream);
