@@ -12,6 +12,7 @@
 // pixels, the taps of a pixel and their blend -- is flat_frame.h, shared with the bicubic, NV12 and stitch kernels; the index remap is
 // warp_border.h (the remap kernel takes it too); this unit holds the kernel body.
 #include "warp_border.h"
+#include "launch_pick.h"
 
 namespace bevwarp {
 namespace {
@@ -58,38 +59,18 @@ __global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(kWavesPerSi
     store_lane_pixels<T, C, kTransparent>(a, b, y, xs, px, wr);
 }
 
-template <typename T, int INTERP, int MODE>
-void launch_c(const BorderArgs& a, int channels, dim3 grid, hipStream_t stream) {
-    const dim3 block(kWG);
-    switch (channels) {
-        case 1: hipLaunchKernelGGL((warp_border_kernel<T, 1, INTERP, MODE>), grid, block, 0, stream, a); break;
-        case 2: hipLaunchKernelGGL((warp_border_kernel<T, 2, INTERP, MODE>), grid, block, 0, stream, a); break;
-        case 3: hipLaunchKernelGGL((warp_border_kernel<T, 3, INTERP, MODE>), grid, block, 0, stream, a); break;
-        default: hipLaunchKernelGGL((warp_border_kernel<T, 4, INTERP, MODE>), grid, block, 0, stream, a); break;
-    }
-}
-
-template <typename T, int INTERP>
-void launch_mode(const BorderArgs& a, int channels, int mode, dim3 grid, hipStream_t stream) {
-    switch (mode) {
-        case kBorderReplicate: launch_c<T, INTERP, kBorderReplicate>(a, channels, grid, stream); break;
-        case kBorderReflect: launch_c<T, INTERP, kBorderReflect>(a, channels, grid, stream); break;
-        case kBorderWrap: launch_c<T, INTERP, kBorderWrap>(a, channels, grid, stream); break;
-        case kBorderReflect101: launch_c<T, INTERP, kBorderReflect101>(a, channels, grid, stream); break;
-        default: launch_c<T, INTERP, kBorderTransparent>(a, channels, grid, stream); break;
-    }
-}
-
 }  // namespace
 
 hipError_t launch_warp_border(const BorderArgs& a, int dtype, int channels, int interp, int mode, int64_t items, hipStream_t stream) {
-    (void)hipGetLastError();  // a stale error left by the host framework is not this call's
-    const dim3 grid((unsigned)items);
-    if (dtype == 0)
-        (interp == kNearest ? launch_mode<uint8_t, kNearest> : launch_mode<uint8_t, kLinear>)(a, channels, mode, grid, stream);
-    else
-        (interp == kNearest ? launch_mode<float, kNearest> : launch_mode<float, kLinear>)(a, channels, mode, grid, stream);
-    return hipGetLastError();
+    return launch_items(a, items, kWG, stream, [&](auto launch) {
+        pick::pixel(dtype, [&](auto t) {
+            pick::value<kNearest, kLinear>(interp, [&](auto i) {
+                pick::value<kBorderReplicate, kBorderReflect, kBorderWrap, kBorderReflect101, kBorderTransparent>(mode, [&](auto m) {
+                    pick::channels(channels, [&](auto c) { launch(warp_border_kernel<typename decltype(t)::type, c(), i(), m()>); });
+                });
+            });
+        });
+    });
 }
 
 }  // namespace bevwarp

@@ -8,6 +8,7 @@
 // source) by row windows, every other written pixel tap by tap.  A wave diverges where a row segment crosses the frame's edge.
 #include "cubic_sample.h"
 #include "warp_cubic.h"
+#include "launch_pick.h"
 
 namespace bevwarp {
 namespace {
@@ -50,39 +51,17 @@ __global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(kWavesPerSi
     store_lane_pixels<T, C, true>(a, b, y, xs, px, wr);
 }
 
-template <typename T, int MODE>
-void launch_c(const CubicArgs& a, int channels, dim3 grid, hipStream_t stream) {
-    const dim3 block(kWG);
-    switch (channels) {
-        case 1: hipLaunchKernelGGL((warp_cubic_kernel<T, 1, MODE>), grid, block, 0, stream, a); break;
-        case 2: hipLaunchKernelGGL((warp_cubic_kernel<T, 2, MODE>), grid, block, 0, stream, a); break;
-        case 3: hipLaunchKernelGGL((warp_cubic_kernel<T, 3, MODE>), grid, block, 0, stream, a); break;
-        default: hipLaunchKernelGGL((warp_cubic_kernel<T, 4, MODE>), grid, block, 0, stream, a); break;
-    }
-}
-
-template <typename T>
-void launch_mode(const CubicArgs& a, int channels, int mode, dim3 grid, hipStream_t stream) {
-    switch (mode) {
-        case BEVWARP_BORDER_CONSTANT: launch_c<T, BEVWARP_BORDER_CONSTANT>(a, channels, grid, stream); break;
-        case BEVWARP_BORDER_REPLICATE: launch_c<T, BEVWARP_BORDER_REPLICATE>(a, channels, grid, stream); break;
-        case BEVWARP_BORDER_REFLECT: launch_c<T, BEVWARP_BORDER_REFLECT>(a, channels, grid, stream); break;
-        case BEVWARP_BORDER_WRAP: launch_c<T, BEVWARP_BORDER_WRAP>(a, channels, grid, stream); break;
-        case BEVWARP_BORDER_REFLECT_101: launch_c<T, BEVWARP_BORDER_REFLECT_101>(a, channels, grid, stream); break;
-        default: launch_c<T, BEVWARP_BORDER_TRANSPARENT>(a, channels, grid, stream); break;
-    }
-}
-
 }  // namespace
 
 hipError_t launch_warp_cubic(const CubicArgs& a, int dtype, int channels, int mode, int64_t items, hipStream_t stream) {
-    (void)hipGetLastError();  // a stale error left by the host framework is not this call's
-    const dim3 grid((unsigned)items);
-    if (dtype == 0)
-        launch_mode<uint8_t>(a, channels, mode, grid, stream);
-    else
-        launch_mode<float>(a, channels, mode, grid, stream);
-    return hipGetLastError();
+    return launch_items(a, items, kWG, stream, [&](auto launch) {
+        pick::pixel(dtype, [&](auto t) {
+            pick::value<BEVWARP_BORDER_CONSTANT, BEVWARP_BORDER_REPLICATE, BEVWARP_BORDER_REFLECT, BEVWARP_BORDER_WRAP, BEVWARP_BORDER_REFLECT_101,
+                        BEVWARP_BORDER_TRANSPARENT>(mode, [&](auto m) {
+                pick::channels(channels, [&](auto c) { launch(warp_cubic_kernel<typename decltype(t)::type, c(), m()>); });
+            });
+        });
+    });
 }
 
 }  // namespace bevwarp

@@ -6,9 +6,10 @@
 // store of a lane's 4 pixels -- is flat_frame.h; the lens step (float64, every operation rounded on its own: the definition in
 // include/bevwarp.h, operation for operation) and the blend of four taps are lens_pixel.h, shared with the map builder; the sampler that
 // guards each tap against the frame and a lane's work are lens_sample.h, shared with the fisheye warp (warp_fisheye.hip).  This unit adds
-// the model's step to them, and the launcher.
+// the model's step to them, and names the instance to launch (launch_pick.h).
 // The lens and r2_max are kernel arguments: wave-uniform, they stay in scalar registers and cost no vector register.
 #include "lens_sample.h"
+#include "launch_pick.h"
 
 namespace bevwarp {
 namespace {
@@ -20,35 +21,18 @@ __global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(kWavesPerSi
 #undef BEVWARP_LENS_STEP
 }
 
-template <typename T, int INTERP, bool TRANSPARENT>
-void launch_c(const LensArgs& a, int channels, dim3 grid, hipStream_t stream) {
-    const dim3 block(kWG);
-    switch (channels) {
-        case 1: hipLaunchKernelGGL((warp_lens_kernel<T, 1, INTERP, TRANSPARENT>), grid, block, 0, stream, a); break;
-        case 2: hipLaunchKernelGGL((warp_lens_kernel<T, 2, INTERP, TRANSPARENT>), grid, block, 0, stream, a); break;
-        case 3: hipLaunchKernelGGL((warp_lens_kernel<T, 3, INTERP, TRANSPARENT>), grid, block, 0, stream, a); break;
-        default: hipLaunchKernelGGL((warp_lens_kernel<T, 4, INTERP, TRANSPARENT>), grid, block, 0, stream, a); break;
-    }
-}
-
-template <typename T, int INTERP>
-void launch_mode(const LensArgs& a, int channels, bool transparent, dim3 grid, hipStream_t stream) {
-    if (transparent)
-        launch_c<T, INTERP, true>(a, channels, grid, stream);
-    else
-        launch_c<T, INTERP, false>(a, channels, grid, stream);
-}
-
 }  // namespace
 
 hipError_t launch_warp_lens(const LensArgs& a, int dtype, int channels, int interp, bool transparent, int64_t items, hipStream_t stream) {
-    (void)hipGetLastError();  // a stale error left by the host framework is not this call's
-    const dim3 grid((unsigned)items);
-    if (dtype == 0)
-        (interp == kNearest ? launch_mode<uint8_t, kNearest> : launch_mode<uint8_t, kLinear>)(a, channels, transparent, grid, stream);
-    else
-        (interp == kNearest ? launch_mode<float, kNearest> : launch_mode<float, kLinear>)(a, channels, transparent, grid, stream);
-    return hipGetLastError();
+    return launch_items(a, items, kWG, stream, [&](auto launch) {
+        pick::pixel(dtype, [&](auto t) {
+            pick::value<kNearest, kLinear>(interp, [&](auto i) {
+                pick::flag(transparent, [&](auto tr) {
+                    pick::channels(channels, [&](auto c) { launch(warp_lens_kernel<typename decltype(t)::type, c(), i(), tr()>); });
+                });
+            });
+        });
+    });
 }
 
 }  // namespace bevwarp

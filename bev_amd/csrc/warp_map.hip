@@ -14,6 +14,7 @@
 #include "lens_pixel.h"
 #include "map_entry.h"
 #include "tap_load.h"
+#include "launch_pick.h"
 
 namespace bevwarp {
 namespace {
@@ -159,56 +160,24 @@ __global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(kWavesPerSi
     }
 }
 
-template <typename T, int INTERP, int MODE>
-void launch_c(const RemapArgs& a, int channels, dim3 grid, hipStream_t stream) {
-    const dim3 block(kWG);
-    switch (channels) {
-        case 1: hipLaunchKernelGGL((remap_kernel<T, 1, INTERP, MODE>), grid, block, 0, stream, a); break;
-        case 2: hipLaunchKernelGGL((remap_kernel<T, 2, INTERP, MODE>), grid, block, 0, stream, a); break;
-        case 3: hipLaunchKernelGGL((remap_kernel<T, 3, INTERP, MODE>), grid, block, 0, stream, a); break;
-        default: hipLaunchKernelGGL((remap_kernel<T, 4, INTERP, MODE>), grid, block, 0, stream, a); break;
-    }
-}
-
-template <typename T, int INTERP>
-void launch_mode(const RemapArgs& a, int channels, int mode, dim3 grid, hipStream_t stream) {
-    switch (mode) {
-        case 0: launch_c<T, INTERP, 0>(a, channels, grid, stream); break;
-        case kBorderReplicate: launch_c<T, INTERP, kBorderReplicate>(a, channels, grid, stream); break;
-        case kBorderReflect: launch_c<T, INTERP, kBorderReflect>(a, channels, grid, stream); break;
-        case kBorderWrap: launch_c<T, INTERP, kBorderWrap>(a, channels, grid, stream); break;
-        case kBorderReflect101: launch_c<T, INTERP, kBorderReflect101>(a, channels, grid, stream); break;
-        default: launch_c<T, INTERP, kBorderTransparent>(a, channels, grid, stream); break;
-    }
-}
-
 }  // namespace
 
 hipError_t launch_build_map(const MapBuildArgs& a, int interp, bool lens, int64_t items, hipStream_t stream) {
-    (void)hipGetLastError();  // a stale error left by the host framework is not this call's
-    const dim3 grid((unsigned)items), block(kWG);
-    if (interp == kNearest) {
-        if (lens)
-            hipLaunchKernelGGL((build_map_kernel<kNearest, true>), grid, block, 0, stream, a);
-        else
-            hipLaunchKernelGGL((build_map_kernel<kNearest, false>), grid, block, 0, stream, a);
-    } else {
-        if (lens)
-            hipLaunchKernelGGL((build_map_kernel<kLinear, true>), grid, block, 0, stream, a);
-        else
-            hipLaunchKernelGGL((build_map_kernel<kLinear, false>), grid, block, 0, stream, a);
-    }
-    return hipGetLastError();
+    return launch_items(a, items, kWG, stream, [&](auto launch) {
+        pick::value<kNearest, kLinear>(interp, [&](auto i) { pick::flag(lens, [&](auto l) { launch(build_map_kernel<i(), l()>); }); });
+    });
 }
 
 hipError_t launch_remap(const RemapArgs& a, int dtype, int channels, int interp, int mode, int64_t items, hipStream_t stream) {
-    (void)hipGetLastError();  // a stale error left by the host framework is not this call's
-    const dim3 grid((unsigned)items);
-    if (dtype == 0)
-        (interp == kNearest ? launch_mode<uint8_t, kNearest> : launch_mode<uint8_t, kLinear>)(a, channels, mode, grid, stream);
-    else
-        (interp == kNearest ? launch_mode<float, kNearest> : launch_mode<float, kLinear>)(a, channels, mode, grid, stream);
-    return hipGetLastError();
+    return launch_items(a, items, kWG, stream, [&](auto launch) {
+        pick::pixel(dtype, [&](auto t) {
+            pick::value<kNearest, kLinear>(interp, [&](auto i) {
+                pick::value<0, kBorderReplicate, kBorderReflect, kBorderWrap, kBorderReflect101, kBorderTransparent>(mode, [&](auto m) {
+                    pick::channels(channels, [&](auto c) { launch(remap_kernel<typename decltype(t)::type, c(), i(), m()>); });
+                });
+            });
+        });
+    });
 }
 
 }  // namespace bevwarp

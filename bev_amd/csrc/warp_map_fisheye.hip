@@ -4,6 +4,7 @@
 // a.lens: fx, fy, cx, cy, k1..k4, four zeros; a.r2_max carries theta_max.  Wave-uniform, in scalar registers.
 #include "warp_map.h"
 #include "fisheye_pixel.h"
+#include "launch_pick.h"
 
 namespace bevwarp {
 namespace {
@@ -18,13 +19,9 @@ __global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(kWavesPerSi
 }  // namespace
 
 hipError_t launch_build_map_fisheye(const MapBuildArgs& a, int interp, int64_t items, hipStream_t stream) {
-    (void)hipGetLastError();  // a stale error left by the host framework is not this call's
-    const dim3 grid((unsigned)items), block(kWG);
-    if (interp == kNearest)
-        hipLaunchKernelGGL((build_map_fisheye_kernel<kNearest>), grid, block, 0, stream, a);
-    else
-        hipLaunchKernelGGL((build_map_fisheye_kernel<kLinear>), grid, block, 0, stream, a);
-    return hipGetLastError();
+    return launch_items(a, items, kWG, stream, [&](auto launch) {
+        pick::value<kNearest, kLinear>(interp, [&](auto i) { launch(build_map_fisheye_kernel<i()>); });
+    });
 }
 
 }  // namespace bevwarp

@@ -20,6 +20,7 @@
 #include "map_entry.h"
 #include "remap_sample_nv12.h"
 #include "warp_kernels.h"
+#include "launch_pick.h"
 
 namespace bevwarp {
 namespace {
@@ -81,61 +82,27 @@ __global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(kWavesPerSi
     });
 }
 
-template <int INTERP, int MODE>
-void launch_order(const RemapNv12Args& a, int rgb_order, dim3 grid, hipStream_t stream) {
-    const dim3 block(kWG);
-    if (rgb_order)
-        hipLaunchKernelGGL((remap_nv12_kernel<INTERP, MODE, 1>), grid, block, 0, stream, a);
-    else
-        hipLaunchKernelGGL((remap_nv12_kernel<INTERP, MODE, 0>), grid, block, 0, stream, a);
-}
-
-template <int INTERP>
-void launch_mode(const RemapNv12Args& a, int mode, int rgb_order, dim3 grid, hipStream_t stream) {
-    switch (mode) {
-        case 0: launch_order<INTERP, 0>(a, rgb_order, grid, stream); break;
-        case kBorderReplicate: launch_order<INTERP, kBorderReplicate>(a, rgb_order, grid, stream); break;
-        case kBorderReflect: launch_order<INTERP, kBorderReflect>(a, rgb_order, grid, stream); break;
-        case kBorderWrap: launch_order<INTERP, kBorderWrap>(a, rgb_order, grid, stream); break;
-        case kBorderReflect101: launch_order<INTERP, kBorderReflect101>(a, rgb_order, grid, stream); break;
-        default: launch_order<INTERP, kBorderTransparent>(a, rgb_order, grid, stream); break;
-    }
-}
-
-template <int INTERP, int MODE>
-void launch_format(const RemapNv12PlanesArgs& a, dim3 grid, hipStream_t stream) {
-    const dim3 block(kWG);
-    if (a.plane == kPlaneF32)
-        hipLaunchKernelGGL((remap_nv12_planes_kernel<INTERP, MODE, false>), grid, block, 0, stream, a);
-    else
-        hipLaunchKernelGGL((remap_nv12_planes_kernel<INTERP, MODE, true>), grid, block, 0, stream, a);
-}
-
-template <int INTERP>
-void launch_planes_mode(const RemapNv12PlanesArgs& a, int mode, dim3 grid, hipStream_t stream) {
-    switch (mode) {
-        case 0: launch_format<INTERP, 0>(a, grid, stream); break;
-        case kBorderReplicate: launch_format<INTERP, kBorderReplicate>(a, grid, stream); break;
-        case kBorderReflect: launch_format<INTERP, kBorderReflect>(a, grid, stream); break;
-        case kBorderWrap: launch_format<INTERP, kBorderWrap>(a, grid, stream); break;
-        default: launch_format<INTERP, kBorderReflect101>(a, grid, stream); break;
-    }
-}
-
 }  // namespace
 
 hipError_t launch_remap_nv12(const RemapNv12Args& a, int interp, int mode, int rgb_order, int64_t items, hipStream_t stream) {
-    (void)hipGetLastError();  // a stale error left by the host framework is not this call's
-    const dim3 grid((unsigned)items);
-    (interp == kNearest ? launch_mode<kNearest> : launch_mode<kLinear>)(a, mode, rgb_order, grid, stream);
-    return hipGetLastError();
+    return launch_items(a, items, kWG, stream, [&](auto launch) {
+        pick::value<kNearest, kLinear>(interp, [&](auto i) {
+            pick::value<0, kBorderReplicate, kBorderReflect, kBorderWrap, kBorderReflect101, kBorderTransparent>(mode, [&](auto m) {
+                pick::flag(rgb_order, [&](auto rgb) { launch(remap_nv12_kernel<i(), m(), rgb()>); });
+            });
+        });
+    });
 }
 
+// (the plane stage writes every pixel: no transparent instance)
 hipError_t launch_remap_nv12_planes(const RemapNv12PlanesArgs& a, int interp, int mode, int64_t items, hipStream_t stream) {
-    (void)hipGetLastError();  // a stale error left by the host framework is not this call's
-    const dim3 grid((unsigned)items);
-    (interp == kNearest ? launch_planes_mode<kNearest> : launch_planes_mode<kLinear>)(a, mode, grid, stream);
-    return hipGetLastError();
+    return launch_items(a, items, kWG, stream, [&](auto launch) {
+        pick::value<kNearest, kLinear>(interp, [&](auto i) {
+            pick::value<0, kBorderReplicate, kBorderReflect, kBorderWrap, kBorderReflect101>(mode, [&](auto m) {
+                pick::flag(a.plane != kPlaneF32, [&](auto wide16) { launch(remap_nv12_planes_kernel<i(), m(), wide16()>); });
+            });
+        });
+    });
 }
 
 }  // namespace bevwarp

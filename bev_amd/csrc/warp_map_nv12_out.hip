@@ -14,6 +14,7 @@
 #include "remap_sample_nv12.h"
 #include "remap_sample_u8x3.h"
 #include "warp_kernels.h"
+#include "launch_pick.h"
 
 namespace bevwarp {
 namespace {
@@ -61,37 +62,22 @@ __global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(kWavesPerSi
     }
 }
 
-// source: 0 = B, G, R frames, 1 = R, G, B frames, 2 = NV12 frames
-template <int INTERP, int MODE>
-void launch_source(const RemapNv12OutArgs& a, int source, dim3 grid, hipStream_t stream) {
-    const dim3 block(kWG);
-    if (source == 2)
-        hipLaunchKernelGGL((remap_nv12_to_nv12_kernel<INTERP, MODE>), grid, block, 0, stream, a);
-    else if (source == 1)
-        hipLaunchKernelGGL((remap_to_nv12_kernel<INTERP, MODE, 1>), grid, block, 0, stream, a);
-    else
-        hipLaunchKernelGGL((remap_to_nv12_kernel<INTERP, MODE, 0>), grid, block, 0, stream, a);
-}
-
-template <int INTERP>
-void launch_mode(const RemapNv12OutArgs& a, int mode, int source, dim3 grid, hipStream_t stream) {
-    switch (mode) {
-        case 0: launch_source<INTERP, 0>(a, source, grid, stream); break;
-        case kBorderReplicate: launch_source<INTERP, kBorderReplicate>(a, source, grid, stream); break;
-        case kBorderReflect: launch_source<INTERP, kBorderReflect>(a, source, grid, stream); break;
-        case kBorderWrap: launch_source<INTERP, kBorderWrap>(a, source, grid, stream); break;
-        default: launch_source<INTERP, kBorderReflect101>(a, source, grid, stream); break;
-    }
-}
-
 }  // namespace
 
 hipError_t launch_remap_nv12_out(const RemapNv12OutArgs& a, int nv12_src, int interp, int mode, int rgb_order, int64_t items, hipStream_t stream) {
-    (void)hipGetLastError();  // a stale error left by the host framework is not this call's
-    const dim3 grid((unsigned)items);
-    const int source = nv12_src ? 2 : (rgb_order ? 1 : 0);
-    (interp == kNearest ? launch_mode<kNearest> : launch_mode<kLinear>)(a, mode, source, grid, stream);
-    return hipGetLastError();
+    const int source = nv12_src ? 2 : (rgb_order ? 1 : 0);  // 0 = B, G, R frames, 1 = R, G, B frames, 2 = NV12 frames
+    return launch_items(a, items, kWG, stream, [&](auto launch) {
+        pick::value<kNearest, kLinear>(interp, [&](auto i) {
+            pick::value<0, kBorderReplicate, kBorderReflect, kBorderWrap, kBorderReflect101>(mode, [&](auto m) {
+                pick::value<2, 1, 0>(source, [&](auto s) {
+                    if constexpr (s() == 2)
+                        launch(remap_nv12_to_nv12_kernel<i(), m()>);
+                    else
+                        launch(remap_to_nv12_kernel<i(), m(), s()>);
+                });
+            });
+        });
+    });
 }
 
 }  // namespace bevwarp

@@ -13,6 +13,7 @@
 #include "map_entry.h"
 #include "remap_sample_u8x3.h"
 #include "warp_kernels.h"
+#include "launch_pick.h"
 
 namespace bevwarp {
 namespace {
@@ -33,33 +34,16 @@ __global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(kWavesPerSi
     }
 }
 
-template <int INTERP, int MODE>
-void launch_format(const RemapPlanesArgs& a, dim3 grid, hipStream_t stream) {
-    const dim3 block(kWG);
-    if (a.plane == kPlaneF32)
-        hipLaunchKernelGGL((remap_planes_kernel<INTERP, MODE, false>), grid, block, 0, stream, a);
-    else
-        hipLaunchKernelGGL((remap_planes_kernel<INTERP, MODE, true>), grid, block, 0, stream, a);
-}
-
-template <int INTERP>
-void launch_mode(const RemapPlanesArgs& a, int mode, dim3 grid, hipStream_t stream) {
-    switch (mode) {
-        case 0: launch_format<INTERP, 0>(a, grid, stream); break;
-        case kBorderReplicate: launch_format<INTERP, kBorderReplicate>(a, grid, stream); break;
-        case kBorderReflect: launch_format<INTERP, kBorderReflect>(a, grid, stream); break;
-        case kBorderWrap: launch_format<INTERP, kBorderWrap>(a, grid, stream); break;
-        default: launch_format<INTERP, kBorderReflect101>(a, grid, stream); break;
-    }
-}
-
 }  // namespace
 
 hipError_t launch_remap_planes(const RemapPlanesArgs& a, int interp, int mode, int64_t items, hipStream_t stream) {
-    (void)hipGetLastError();  // a stale error left by the host framework is not this call's
-    const dim3 grid((unsigned)items);
-    (interp == kNearest ? launch_mode<kNearest> : launch_mode<kLinear>)(a, mode, grid, stream);
-    return hipGetLastError();
+    return launch_items(a, items, kWG, stream, [&](auto launch) {
+        pick::value<kNearest, kLinear>(interp, [&](auto i) {
+            pick::value<0, kBorderReplicate, kBorderReflect, kBorderWrap, kBorderReflect101>(mode, [&](auto m) {
+                pick::flag(a.plane != kPlaneF32, [&](auto wide16) { launch(remap_planes_kernel<i(), m(), wide16()>); });
+            });
+        });
+    });
 }
 
 }  // namespace bevwarp

@@ -8,6 +8,7 @@
 // replaced by the border value afterwards (sample_global's rule), so all loads of a pixel issue before the first wait.
 #include "nv12_sample.h"
 #include "warp_nv12.h"
+#include "launch_pick.h"
 
 namespace bevwarp {
 namespace {
@@ -40,22 +41,12 @@ __global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(kWavesPerSi
     store_lane_pixels<uint8_t, 3, false>(a, b, y, xs, px, wr);
 }
 
-template <int INTERP>
-void launch_order(const Nv12Args& a, int rgb_order, dim3 grid, hipStream_t stream) {
-    const dim3 block(kWG);
-    if (rgb_order)
-        hipLaunchKernelGGL((warp_nv12_kernel<INTERP, 1>), grid, block, 0, stream, a);
-    else
-        hipLaunchKernelGGL((warp_nv12_kernel<INTERP, 0>), grid, block, 0, stream, a);
-}
-
 }  // namespace
 
 hipError_t launch_warp_nv12(const Nv12Args& a, int interp, int rgb_order, int64_t items, hipStream_t stream) {
-    (void)hipGetLastError();  // a stale error left by the host framework is not this call's
-    const dim3 grid((unsigned)items);
-    (interp == kNearest ? launch_order<kNearest> : launch_order<kLinear>)(a, rgb_order, grid, stream);
-    return hipGetLastError();
+    return launch_items(a, items, kWG, stream, [&](auto launch) {
+        pick::value<kNearest, kLinear>(interp, [&](auto i) { pick::flag(rgb_order, [&](auto rgb) { launch(warp_nv12_kernel<i(), rgb()>); }); });
+    });
 }
 
 }  // namespace bevwarp

@@ -10,6 +10,7 @@
 #include "nv12_out.h"
 #include "nv12_sample.h"
 #include "warp_nv12_out.h"
+#include "launch_pick.h"
 
 namespace bevwarp {
 namespace {
@@ -65,28 +66,15 @@ __global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(kWavesPerSi
     }
 }
 
-template <int NV12_SRC, int INTERP>
-void launch_order(const Nv12OutArgs& a, int rgb_order, dim3 grid, hipStream_t stream) {
-    const dim3 block(kWG);
-    if constexpr (!NV12_SRC) {
-        if (rgb_order) {
-            hipLaunchKernelGGL((warp_nv12_out_kernel<0, INTERP, 1>), grid, block, 0, stream, a);
-            return;
-        }
-    }
-    hipLaunchKernelGGL((warp_nv12_out_kernel<NV12_SRC, INTERP, 0>), grid, block, 0, stream, a);
-}
-
 }  // namespace
 
 hipError_t launch_warp_nv12_out(const Nv12OutArgs& a, int nv12_src, int interp, int rgb_order, int64_t items, hipStream_t stream) {
-    (void)hipGetLastError();  // a stale error left by the host framework is not this call's
-    const dim3 grid((unsigned)items);
-    if (nv12_src)
-        (interp == kNearest ? launch_order<1, kNearest> : launch_order<1, kLinear>)(a, 0, grid, stream);
-    else
-        (interp == kNearest ? launch_order<0, kNearest> : launch_order<0, kLinear>)(a, rgb_order, grid, stream);
-    return hipGetLastError();
+    const int source = nv12_src ? 2 : (rgb_order ? 1 : 0);  // 0 = B, G, R frames, 1 = R, G, B frames, 2 = NV12 frames (sampled as B, G, R)
+    return launch_items(a, items, kWG, stream, [&](auto launch) {
+        pick::value<kNearest, kLinear>(interp, [&](auto i) {
+            pick::value<2, 1, 0>(source, [&](auto s) { launch(warp_nv12_out_kernel<s() == 2, i(), s() == 1>); });
+        });
+    });
 }
 
 }  // namespace bevwarp

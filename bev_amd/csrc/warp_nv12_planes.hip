@@ -10,6 +10,7 @@
 #include "nv12_sample.h"
 #include "warp_kernels.h"
 #include "warp_nv12.h"
+#include "launch_pick.h"
 
 namespace bevwarp {
 namespace {
@@ -39,22 +40,12 @@ __global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(kWavesPerSi
 #include "plane_store.inc"
 }
 
-template <int INTERP>
-void launch_format(const Nv12PlanesArgs& a, dim3 grid, hipStream_t stream) {
-    const dim3 block(kWG);
-    if (a.plane == kPlaneF32)
-        hipLaunchKernelGGL((nv12_planes_kernel<INTERP, false>), grid, block, 0, stream, a);
-    else
-        hipLaunchKernelGGL((nv12_planes_kernel<INTERP, true>), grid, block, 0, stream, a);
-}
-
 }  // namespace
 
 hipError_t launch_warp_nv12_planes(const Nv12PlanesArgs& a, int interp, int64_t items, hipStream_t stream) {
-    (void)hipGetLastError();  // a stale error left by the host framework is not this call's
-    const dim3 grid((unsigned)items);
-    (interp == kNearest ? launch_format<kNearest> : launch_format<kLinear>)(a, grid, stream);
-    return hipGetLastError();
+    return launch_items(a, items, kWG, stream, [&](auto launch) {
+        pick::value<kNearest, kLinear>(interp, [&](auto i) { pick::flag(a.plane != kPlaneF32, [&](auto wide16) { launch(nv12_planes_kernel<i(), wide16()>); }); });
+    });
 }
 
 }  // namespace bevwarp

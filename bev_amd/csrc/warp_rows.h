@@ -34,6 +34,7 @@
 // coordinate chain + blending) and the texture path's cost per gather instruction.
 #pragma once
 #include "sample.h"
+#include "launch_pick.h"
 
 namespace bevwarp {
 namespace {
@@ -110,23 +111,13 @@ void launch_tci_planes16(const WarpArgs& a, dim3 grid, hipStream_t stream) {
 }
 template <typename T, int INTERP>
 void launch_channels_planes16(const WarpArgs& a, int channels, dim3 grid, hipStream_t stream) {
-    switch (channels) {
-        case 1: launch_tci_planes16<T, 1, INTERP>(a, grid, stream); break;
-        case 2: launch_tci_planes16<T, 2, INTERP>(a, grid, stream); break;
-        case 3: launch_tci_planes16<T, 3, INTERP>(a, grid, stream); break;
-        default: launch_tci_planes16<T, 4, INTERP>(a, grid, stream); break;
-    }
+    pick::channels(channels, [&](auto c) { launch_tci_planes16<T, c(), INTERP>(a, grid, stream); });
 }
 
 // every channel count of one pixel type and interpolation: what one translation unit instantiates (warp_u8_linear.hip, ...)
 template <typename T, int INTERP>
 void launch_channels(const WarpArgs& a, int channels, dim3 grid, hipStream_t stream) {
-    switch (channels) {
-        case 1: launch_tci<T, 1, INTERP>(a, grid, stream); break;
-        case 2: launch_tci<T, 2, INTERP>(a, grid, stream); break;
-        case 3: launch_tci<T, 3, INTERP>(a, grid, stream); break;
-        default: launch_tci<T, 4, INTERP>(a, grid, stream); break;
-    }
+    pick::channels(channels, [&](auto c) { launch_tci<T, c(), INTERP>(a, grid, stream); });
 }
 
 #ifdef BEVWARP_CLOCK

@@ -5,12 +5,13 @@
 // nearest and bilinear.  See DESIGN.md section 4.16.
 //
 // The frame -- item decoding, the row walk of the exact float64 chain, the rounding with the reference's NaN, the taps of a pixel and the
-// store of a lane's 4 pixels -- is flat_frame.h.  This unit adds the camera loop, the two rules and the launcher.  The cameras are kernel
+// store of a lane's 4 pixels -- is flat_frame.h.  This unit adds the camera loop and the two rules; its launch is launch_pick.h's.  The cameras are kernel
 // arguments and the loop's camera number is wave-uniform: a camera's fields and its matrix of the workgroup's frame are scalar loads and
 // cost no vector register.  The lane's 4 pixels are walked inside the loop, so one matrix serves all four.  FEATHER's division of 8-bit
 // sums, div_byte_mean, is stitch_sample.h's, shared with the stitches through warp maps.
 #include "warp_stitch.h"
 #include "stitch_sample.h"
+#include "launch_pick.h"
 
 #include <type_traits>
 
@@ -119,35 +120,18 @@ __global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(kWavesPerSi
     store_lane_pixels<T, C, true>(a, b, y, xs, px, wr);
 }
 
-template <typename T, int INTERP, int BLEND>
-void launch_c(const StitchArgs& a, int channels, dim3 grid, hipStream_t stream) {
-    const dim3 block(kWG);
-    switch (channels) {
-        case 1: hipLaunchKernelGGL((warp_stitch_kernel<T, 1, INTERP, BLEND>), grid, block, 0, stream, a); break;
-        case 2: hipLaunchKernelGGL((warp_stitch_kernel<T, 2, INTERP, BLEND>), grid, block, 0, stream, a); break;
-        case 3: hipLaunchKernelGGL((warp_stitch_kernel<T, 3, INTERP, BLEND>), grid, block, 0, stream, a); break;
-        default: hipLaunchKernelGGL((warp_stitch_kernel<T, 4, INTERP, BLEND>), grid, block, 0, stream, a); break;
-    }
-}
-
-template <typename T, int INTERP>
-void launch_blend(const StitchArgs& a, int channels, int blend, dim3 grid, hipStream_t stream) {
-    if (blend == kStitchFeather)
-        launch_c<T, INTERP, kStitchFeather>(a, channels, grid, stream);
-    else
-        launch_c<T, INTERP, kStitchOver>(a, channels, grid, stream);
-}
-
 }  // namespace
 
 hipError_t launch_warp_stitch(const StitchArgs& a, int dtype, int channels, int interp, int blend, int64_t items, hipStream_t stream) {
-    (void)hipGetLastError();  // a stale error left by the host framework is not this call's
-    const dim3 grid((unsigned)items);
-    if (dtype == 0)
-        (interp == kNearest ? launch_blend<uint8_t, kNearest> : launch_blend<uint8_t, kLinear>)(a, channels, blend, grid, stream);
-    else
-        (interp == kNearest ? launch_blend<float, kNearest> : launch_blend<float, kLinear>)(a, channels, blend, grid, stream);
-    return hipGetLastError();
+    return launch_items(a, items, kWG, stream, [&](auto launch) {
+        pick::pixel(dtype, [&](auto t) {
+            pick::value<kNearest, kLinear>(interp, [&](auto i) {
+                pick::value<kStitchFeather, kStitchOver>(blend, [&](auto bl) {
+                    pick::channels(channels, [&](auto c) { launch(warp_stitch_kernel<typename decltype(t)::type, c(), i(), bl()>); });
+                });
+            });
+        });
+    });
 }
 
 }  // namespace bevwarp

@@ -40,7 +40,7 @@ struct Gained : Args {
 static_assert(sizeof(Gained<StitchMapsArgs>) <= 4096, "eight cameras and their gains fit the kernel-argument block");
 
 // The gained units -- warp_stitch_gain.hip, warp_stitch_gain_nv12_out.hip, warp_stitch_gain_planes.hip -- are the text of the unit each
-// shadows, compiled once more with BEVWARP_STITCH_GAIN_UNIT defined: the same kernel bodies and launch ladders over Gained<> arguments,
+// shadows, compiled once more with BEVWARP_STITCH_GAIN_UNIT defined: the same kernel bodies and launchers over Gained<> arguments,
 // under names of their own.  (8-bit pixels of 3 channels only: warp_stitch_maps.hip leaves its other formats out.)
 #ifdef BEVWARP_STITCH_GAIN_UNIT
 #define BEVWARP_STITCH_UNIT(plain, gained) gained

@@ -15,10 +15,11 @@
 // warp_map_nv12.hip, where an edge lane falls back to loads tap by tap, describe both.  A camera's entries, the inlier samplers and
 // FEATHER's division are stitch_sample.h, shared with warp_stitch_maps_nv12_out.hip and warp_stitch_maps_planes.hip.
 //
-// warp_stitch_gain.hip is this text once more under BEVWARP_STITCH_GAIN_UNIT (warp_stitch_maps.h): the same body and launch ladders over
+// warp_stitch_gain.hip is this text once more under BEVWARP_STITCH_GAIN_UNIT (warp_stitch_maps.h): the same body and launchers over
 // Gained<> arguments, for 8-bit pixels of 3 channels only, every tap put through its camera's gain (stitch_sample.h: TapGain).
 #include "warp_stitch_maps.h"
 #include "stitch_sample.h"
+#include "launch_pick.h"
 
 #include <type_traits>
 
@@ -150,67 +151,32 @@ __global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(kWavesPerSi
     stitch_maps_body<uint8_t, 3, INTERP, BLEND, true, RGB>(a);
 }
 
-template <typename T, int INTERP, int BLEND>
-void launch_c(const Args& a, int channels, dim3 grid, hipStream_t stream) {
-    const dim3 block(kWG);
-#ifdef BEVWARP_STITCH_GAIN_UNIT
-    hipLaunchKernelGGL((UNIT_KERNEL<T, 3, INTERP, BLEND>), grid, block, 0, stream, a);  // (the host checks admit no other channel count)
-#else
-    switch (channels) {
-        case 1: hipLaunchKernelGGL((UNIT_KERNEL<T, 1, INTERP, BLEND>), grid, block, 0, stream, a); break;
-        case 2: hipLaunchKernelGGL((UNIT_KERNEL<T, 2, INTERP, BLEND>), grid, block, 0, stream, a); break;
-        case 3: hipLaunchKernelGGL((UNIT_KERNEL<T, 3, INTERP, BLEND>), grid, block, 0, stream, a); break;
-        default: hipLaunchKernelGGL((UNIT_KERNEL<T, 4, INTERP, BLEND>), grid, block, 0, stream, a); break;
-    }
-#endif
-}
-
-template <typename T, int INTERP>
-void launch_blend(const Args& a, int channels, int blend, dim3 grid, hipStream_t stream) {
-    if (blend == kStitchFeather)
-        launch_c<T, INTERP, kStitchFeather>(a, channels, grid, stream);
-    else
-        launch_c<T, INTERP, kStitchOver>(a, channels, grid, stream);
-}
-
-template <int INTERP, int BLEND>
-void launch_order(const Args& a, int rgb_order, dim3 grid, hipStream_t stream) {
-    const dim3 block(kWG);
-    if (rgb_order)
-        hipLaunchKernelGGL((UNIT_KERNEL_NV12<INTERP, BLEND, 1>), grid, block, 0, stream, a);
-    else
-        hipLaunchKernelGGL((UNIT_KERNEL_NV12<INTERP, BLEND, 0>), grid, block, 0, stream, a);
-}
-
-template <int INTERP>
-void launch_nv12_blend(const Args& a, int blend, int rgb_order, dim3 grid, hipStream_t stream) {
-    if (blend == kStitchFeather)
-        launch_order<INTERP, kStitchFeather>(a, rgb_order, grid, stream);
-    else
-        launch_order<INTERP, kStitchOver>(a, rgb_order, grid, stream);
-}
-
 }  // namespace
 
 hipError_t UNIT_LAUNCH(const UnitArgs<StitchMapsArgs>& a, int dtype, int channels, int interp, int blend, int64_t items, hipStream_t stream) {
-    (void)hipGetLastError();  // a stale error left by the host framework is not this call's
-    const dim3 grid((unsigned)items);
-#ifdef BEVWARP_STITCH_GAIN_UNIT  // (the host checks admit no float32 pixels under the flag)
-    (interp == kNearest ? launch_blend<uint8_t, kNearest> : launch_blend<uint8_t, kLinear>)(a, channels, blend, grid, stream);
+    return launch_items(a, items, kWG, stream, [&](auto launch) {
+        pick::value<kNearest, kLinear>(interp, [&](auto i) {
+            pick::value<kStitchFeather, kStitchOver>(blend, [&](auto bl) {
+#ifdef BEVWARP_STITCH_GAIN_UNIT  // (the host checks admit 8-bit pixels of 3 channels only under the flag)
+                launch(UNIT_KERNEL<uint8_t, 3, i(), bl()>);
 #else
-    if (dtype == 0)
-        (interp == kNearest ? launch_blend<uint8_t, kNearest> : launch_blend<uint8_t, kLinear>)(a, channels, blend, grid, stream);
-    else
-        (interp == kNearest ? launch_blend<float, kNearest> : launch_blend<float, kLinear>)(a, channels, blend, grid, stream);
+                pick::pixel(dtype, [&](auto t) {
+                    pick::channels(channels, [&](auto c) { launch(UNIT_KERNEL<typename decltype(t)::type, c(), i(), bl()>); });
+                });
 #endif
-    return hipGetLastError();
+            });
+        });
+    });
 }
 
 hipError_t UNIT_LAUNCH_NV12(const UnitArgs<StitchMapsArgs>& a, int interp, int blend, int rgb_order, int64_t items, hipStream_t stream) {
-    (void)hipGetLastError();  // a stale error left by the host framework is not this call's
-    const dim3 grid((unsigned)items);
-    (interp == kNearest ? launch_nv12_blend<kNearest> : launch_nv12_blend<kLinear>)(a, blend, rgb_order, grid, stream);
-    return hipGetLastError();
+    return launch_items(a, items, kWG, stream, [&](auto launch) {
+        pick::value<kNearest, kLinear>(interp, [&](auto i) {
+            pick::value<kStitchFeather, kStitchOver>(blend, [&](auto bl) {
+                pick::flag(rgb_order, [&](auto rgb) { launch(UNIT_KERNEL_NV12<i(), bl(), rgb()>); });
+            });
+        });
+    });
 }
 
 }  // namespace bevwarp

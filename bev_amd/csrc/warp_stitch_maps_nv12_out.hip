@@ -8,10 +8,11 @@
 // as warp_stitch_maps.hip describes.  The samplers are stitch_sample.h's, shared with that unit; the camera loop is stitch_maps_u8x3.inc,
 // shared as text with warp_stitch_maps_planes.hip.
 //
-// warp_stitch_gain_nv12_out.hip is this text once more under BEVWARP_STITCH_GAIN_UNIT (warp_stitch_maps.h): the same kernel and launch
-// ladder over Gained<> arguments, with which the camera loop applies the camera's gain to every tap.
+// warp_stitch_gain_nv12_out.hip is this text once more under BEVWARP_STITCH_GAIN_UNIT (warp_stitch_maps.h): the same kernel and
+// launcher over Gained<> arguments, with which the camera loop applies the camera's gain to every tap.
 #include "warp_stitch_maps_nv12_out.h"
 #include "stitch_sample.h"
+#include "launch_pick.h"
 
 #define UNIT_KERNEL BEVWARP_STITCH_UNIT(stitch_maps_nv12_out_kernel, stitch_gain_nv12_out_kernel)
 #define UNIT_LAUNCH BEVWARP_STITCH_UNIT(launch_stitch_maps_nv12_out, launch_stitch_gain_nv12_out)
@@ -34,33 +35,17 @@ __global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(kWavesPerSi
     store_lane_nv12<RGB>(a, a, b, y, xs, px);
 }
 
-template <int INTERP, int BLEND>
-void launch_source(const Args& a, int source, dim3 grid, hipStream_t stream) {
-    const dim3 block(kWG);
-    if (source == 2)
-        hipLaunchKernelGGL((UNIT_KERNEL<INTERP, BLEND, true, 0>), grid, block, 0, stream, a);
-    else if (source == 1)
-        hipLaunchKernelGGL((UNIT_KERNEL<INTERP, BLEND, false, 1>), grid, block, 0, stream, a);
-    else
-        hipLaunchKernelGGL((UNIT_KERNEL<INTERP, BLEND, false, 0>), grid, block, 0, stream, a);
-}
-
-template <int INTERP>
-void launch_blend(const Args& a, int blend, int source, dim3 grid, hipStream_t stream) {
-    if (blend == kStitchFeather)
-        launch_source<INTERP, kStitchFeather>(a, source, grid, stream);
-    else
-        launch_source<INTERP, kStitchOver>(a, source, grid, stream);
-}
-
 }  // namespace
 
 hipError_t UNIT_LAUNCH(const UnitArgs<StitchMapsNv12OutArgs>& a, int nv12_src, int interp, int blend, int rgb_order, int64_t items, hipStream_t stream) {
-    (void)hipGetLastError();  // a stale error left by the host framework is not this call's
-    const dim3 grid((unsigned)items);
     const int source = nv12_src ? 2 : (rgb_order ? 1 : 0);  // 0 = B, G, R frames, 1 = R, G, B frames, 2 = NV12 frames
-    (interp == kNearest ? launch_blend<kNearest> : launch_blend<kLinear>)(a, blend, source, grid, stream);
-    return hipGetLastError();
+    return launch_items(a, items, kWG, stream, [&](auto launch) {
+        pick::value<kNearest, kLinear>(interp, [&](auto i) {
+            pick::value<kStitchFeather, kStitchOver>(blend, [&](auto bl) {
+                pick::value<2, 1, 0>(source, [&](auto s) { launch(UNIT_KERNEL<i(), bl(), s() == 2, s() == 1>); });
+            });
+        });
+    });
 }
 
 }  // namespace bevwarp

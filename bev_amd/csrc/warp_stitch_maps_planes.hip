@@ -9,10 +9,11 @@
 // as warp_stitch_maps.hip describes.  The samplers are stitch_sample.h's, shared with that unit; the camera loop is stitch_maps_u8x3.inc,
 // shared as text with warp_stitch_maps_nv12_out.hip.
 //
-// warp_stitch_gain_planes.hip is this text once more under BEVWARP_STITCH_GAIN_UNIT (warp_stitch_maps.h): the same kernel and launch ladder
+// warp_stitch_gain_planes.hip is this text once more under BEVWARP_STITCH_GAIN_UNIT (warp_stitch_maps.h): the same kernel and launcher
 // over Gained<> arguments, with which the camera loop applies the camera's gain to every tap.
 #include "warp_stitch_maps_planes.h"
 #include "stitch_sample.h"
+#include "launch_pick.h"
 
 #define UNIT_KERNEL BEVWARP_STITCH_UNIT(stitch_maps_planes_kernel, stitch_gain_planes_kernel)
 #define UNIT_LAUNCH BEVWARP_STITCH_UNIT(launch_stitch_maps_planes, launch_stitch_gain_planes)
@@ -36,41 +37,19 @@ __global__ __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(kWavesPerSi
 #include "plane_store.inc"
 }
 
-template <int INTERP, int BLEND, bool NV12, int RGB>
-void launch_format(const Args& a, dim3 grid, hipStream_t stream) {
-    const dim3 block(kWG);
-    if (a.plane == kPlaneF32)
-        hipLaunchKernelGGL((UNIT_KERNEL<INTERP, BLEND, NV12, RGB, false>), grid, block, 0, stream, a);
-    else
-        hipLaunchKernelGGL((UNIT_KERNEL<INTERP, BLEND, NV12, RGB, true>), grid, block, 0, stream, a);
-}
-
-template <int INTERP, int BLEND>
-void launch_source(const Args& a, int source, dim3 grid, hipStream_t stream) {
-    if (source == 2)
-        launch_format<INTERP, BLEND, true, 1>(a, grid, stream);
-    else if (source == 1)
-        launch_format<INTERP, BLEND, true, 0>(a, grid, stream);
-    else
-        launch_format<INTERP, BLEND, false, 0>(a, grid, stream);
-}
-
-template <int INTERP>
-void launch_blend(const Args& a, int blend, int source, dim3 grid, hipStream_t stream) {
-    if (blend == kStitchFeather)
-        launch_source<INTERP, kStitchFeather>(a, source, grid, stream);
-    else
-        launch_source<INTERP, kStitchOver>(a, source, grid, stream);
-}
-
 }  // namespace
 
 hipError_t UNIT_LAUNCH(const UnitArgs<StitchMapsPlanesArgs>& a, int nv12_src, int interp, int blend, int rgb_order, int64_t items, hipStream_t stream) {
-    (void)hipGetLastError();  // a stale error left by the host framework is not this call's
-    const dim3 grid((unsigned)items);
     const int source = nv12_src ? (rgb_order ? 2 : 1) : 0;  // 0 = interleaved frames, 1 = NV12 frames as B, G, R, 2 = NV12 frames as R, G, B
-    (interp == kNearest ? launch_blend<kNearest> : launch_blend<kLinear>)(a, blend, source, grid, stream);
-    return hipGetLastError();
+    return launch_items(a, items, kWG, stream, [&](auto launch) {
+        pick::value<kNearest, kLinear>(interp, [&](auto i) {
+            pick::value<kStitchFeather, kStitchOver>(blend, [&](auto bl) {
+                pick::value<2, 1, 0>(source, [&](auto s) {
+                    pick::flag(a.plane != kPlaneF32, [&](auto wide16) { launch(UNIT_KERNEL<i(), bl(), s() != 0, s() == 2, wide16()>); });
+                });
+            });
+        });
+    });
 }
 
 }  // namespace bevwarp
