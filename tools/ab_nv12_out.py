@@ -16,37 +16,31 @@ depth 3) over 200 frames of 1080p, every source format into BGR and into NV12 sl
 GPU box, each step under a time limit of its own and none tried again when it fails:
     timeout -k 10 400 python tools/ab_nv12_out.py --step kernels --out profiles/nv12_out_timing.txt && \\
     timeout -k 10 300 python tools/ab_nv12_out.py --step pipeline --out profiles/nv12_out_timing.txt --append"""
-import argparse
-import os
-import sys
-
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from bev_amd import warp  # noqa: E402
-from bev_amd.pipeline import FramePipeline  # noqa: E402
-from tests import workloads as wl  # noqa: E402
-from tools.ab_nv12 import pipeline_ms, to_nv12  # noqa: E402
+import arms
+from arms import B, D, SH, SW, pipeline_ms, to_nv12
+from bev_amd import warp
+from bev_amd.pipeline import FramePipeline
+from tests import workloads as wl
 
-B, SH, SW, D = 32, 1080, 1920, 1024
-ARMS = (("warp", "(a) bevwarp_warp BGR, plain launch"), ("transparent", "(b) warp_border TRANSPARENT BGR"), ("nv12", "(c) bevwarp_warp_nv12"),
-        ("to_nv12", "(d) bevwarp_warp_to_nv12"), ("nv12_to_nv12", "(e) bevwarp_warp_nv12_to_nv12"))
+ARMS = {"warp": "(a) bevwarp_warp BGR, plain launch", "transparent": "(b) warp_border TRANSPARENT BGR", "nv12": "(c) bevwarp_warp_nv12",
+        "to_nv12": "(d) bevwarp_warp_to_nv12", "nv12_to_nv12": "(e) bevwarp_warp_nv12_to_nv12"}
 
 
 def kernels(quick, dev):
-    rounds, per_round, warm = (2, 3, 2) if quick else (7, 10, 5)
+    rounds, per_round, warm = arms.counts(quick)
     lines = ["# warps into NV12 vs bevwarp_warp, bevwarp_warp_border (TRANSPARENT) and bevwarp_warp_nv12, %d x %dx%d -> %dx%d, uint8, bilinear, per-frame jitter_H; us per launch"
              % (B, SW, SH, D, D), "# %d rounds x %d launches per arm, arms interleaved; (a) is the plain launch, no verdict tables; %s" % (rounds, per_round, torch.cuda.get_device_name(dev))]
     nset = 3  # (3 x 199 MB of BGR sources, 3 x 100 MB of NV12 -- with the destinations past the 256 MB Infinity Cache)
-    bgr = [torch.from_numpy(np.stack([wl.frame(B * s + i, SH, SW, np.uint8) for i in range(B)])).to(dev) for s in range(nset)]
+    bgr = arms.frame_sets(nset, dev)
     planes = [warp.split_nv12(to_nv12(t)) for t in bgr]
-    outs = [torch.zeros((B, D, D, 3), dtype=torch.uint8, device=dev) for _ in range(nset)]
-    outs_nv12 = [torch.zeros((B, D * 3 // 2, D), dtype=torch.uint8, device=dev) for _ in range(nset)]
+    outs = arms.dest_sets(nset, dev)
+    outs_nv12 = arms.dest_sets(nset, dev, (B, D * 3 // 2, D))
     verdicts = []
-    for hname, hfn in (("keystone", wl.keystone_H), ("brno", wl.synth_brno_H)):
-        H = hfn(SW, SH, D, D)
-        minv = warp.device_inverse(np.stack([wl.jitter_H(H, i) for i in range(B)]), dev).clone()  # (caller-owned: the plain launch)
+    for hname, _, Ms in arms.footprints():
+        minv = warp.device_inverse(Ms, dev).clone()  # (caller-owned: the plain launch)
         k = [0]
 
         def launch(arm):
@@ -62,28 +56,11 @@ def kernels(quick, dev):
                                       border_mode=warp.BORDER_TRANSPARENT if arm == "transparent" else warp.BORDER_CONSTANT)
             k[0] += 1
 
-        names = [a for a, _ in ARMS]
-        for arm in names:
-            for _ in range(warm):
-                launch(arm)
-        torch.cuda.synchronize()
-        t = {arm: [] for arm in names}
-        for _ in range(rounds):
-            for arm in names:
-                ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(per_round)]
-                for e0, e1 in ev:
-                    e0.record()
-                    launch(arm)
-                    e1.record()
-                torch.cuda.synchronize()
-                t[arm] += [e0.elapsed_time(e1) * 1e3 for e0, e1 in ev]
-        base = float(np.median(t["warp"]))
-        for arm, label in ARMS:
-            med = float(np.median(t[arm]))
-            lines.append("%-9s %-36s median %9.1f us  p10 %9.1f  p90 %9.1f  ratio to (a) %5.2f" % (
-                hname, label, med, np.percentile(t[arm], 10), np.percentile(t[arm], 90), med / base))
+        q = arms.p10_50_90(arms.timed(ARMS, launch, rounds, per_round, warm))
+        for arm, label in ARMS.items():
+            lines.append("%-9s %-36s median %9.1f us  p10 %9.1f  p90 %9.1f  ratio to (a) %5.2f" % (hname, label, q[arm][1], q[arm][0], q[arm][2], q[arm][1] / q["warp"][1]))
         for new, old, tag in (("to_nv12", "transparent", "(d) p10 <= (b) p90"), ("nv12_to_nv12", "nv12", "(e) p10 <= (c) p90")):
-            p10, p90 = float(np.percentile(t[new], 10)), float(np.percentile(t[old], 90))
+            p10, p90 = q[new][0], q[old][2]
             verdicts.append("condition %-9s %s: %9.1f <= %9.1f  %s" % (hname, tag, p10, p90, "holds" if p10 <= p90 else "REFUTED"))
     return lines + verdicts
 
@@ -110,24 +87,14 @@ def pipeline(quick):
 
 
 def main():
-    p = argparse.ArgumentParser()
-    p.add_argument("--quick", action="store_true", help="a few launches per arm (for a profiler run)")
-    p.add_argument("--step", choices=("kernels", "pipeline", "all"), default="all")
-    p.add_argument("--out", default=None, help="also write the table to this file")
-    p.add_argument("--append", action="store_true", help="append to --out instead of replacing it")
-    a = p.parse_args()
+    a = arms.parser(__doc__, steps=("kernels", "pipeline", "all"), step="all").parse_args()
     lines = []
     if a.step in ("kernels", "all"):
         lines += kernels(a.quick, torch.device("cuda", 0))
         torch.cuda.empty_cache()
     if a.step in ("pipeline", "all"):
         lines += pipeline(a.quick)
-    text = "\n".join(lines)
-    print(text, flush=True)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "a" if a.append else "w") as f:
-            f.write(text + "\n")
+    arms.finish(lines, a.out, a.append)
 
 
 if __name__ == "__main__":

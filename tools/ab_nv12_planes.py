@@ -11,48 +11,37 @@ All arms run interleaved in one process after a warm-up, three buffer sets rotat
 pair of launches for (c)), 70 per arm; median, p10, p90.  The condition set beforehand: on both footprints the float16 and the bfloat16 arm
 of (b) have a median below the median of the FASTER route of (c) in the same run.  The ratio of (b) to (a) is reported without a pass mark.
 GPU box:  python tools/ab_nv12_planes.py [--quick] [--out FILE]"""
-import argparse
-import os
-import sys
-
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from bev_amd import warp  # noqa: E402
-from tests import workloads as wl  # noqa: E402
-from tools.ab_nv12 import to_nv12  # noqa: E402
+import arms
+from arms import B, D, SH, SW
+from bev_amd import warp
 
 MEAN, STD = np.array([0.485, 0.456, 0.406]), np.array([0.229, 0.224, 0.225])
+ARMS = {"nv12": "(a)  bevwarp_warp_nv12 (8-bit BGR)", torch.float32: "(b)  nv12_planes float32", torch.float16: "(b)  nv12_planes float16",
+        torch.bfloat16: "(b)  nv12_planes bfloat16", "two_kernel": "(c1) nv12 + warp_to_planar identity f16", "two_torch": "(c2) nv12 + torch permute/float/mul/add/half"}
 
 
 def main():
-    p = argparse.ArgumentParser()
-    p.add_argument("--quick", action="store_true", help="a few launches per arm")
-    p.add_argument("--out", default=None, help="also write the table to this file")
-    a = p.parse_args()
-    B, SH, SW, D = 32, 1080, 1920, 1024
-    rounds, per_round, warm = (2, 3, 2) if a.quick else (7, 10, 5)
+    a = arms.parser(__doc__).parse_args()
+    rounds, per_round, warm = arms.counts(a.quick)
     dev = torch.device("cuda", 0)
     scale, bias = 1.0 / (255.0 * STD), -MEAN / STD
     lines = ["# bevwarp_warp_nv12_planes vs bevwarp_warp_nv12 and the two-pass routes, %d x %dx%d NV12 -> %dx%d x 3 planes, bilinear, per-frame jitter_H, ImageNet scale / bias"
              % (B, SW, SH, D, D), "# median us per launch (per pair of launches for (c)); %d rounds x %d launches per arm, arms interleaved, 3 buffer sets rotated; %s"
              % (rounds, per_round, torch.cuda.get_device_name(dev))]
     nset = 3
-    planes = []
-    for s in range(nset):  # (the BGR frames are only the encoder stand-in's input: one set at a time)
-        bgr = torch.from_numpy(np.stack([wl.frame(B * s + i, SH, SW, np.uint8) for i in range(B)])).to(dev)
-        planes.append(warp.split_nv12(to_nv12(bgr)))
-        del bgr
-    bev = [torch.zeros((B, D, D, 3), dtype=torch.uint8, device=dev) for _ in range(nset)]
-    outs = {dt: [torch.zeros((B, 3, D, D), dtype=dt, device=dev) for _ in range(nset)] for dt in (torch.float32, torch.float16, torch.bfloat16)}
+    # (the BGR frames are only the encoder stand-in's input: one set at a time)
+    planes = [warp.split_nv12(arms.to_nv12(arms.frame_set(s, dev))) for s in range(nset)]
+    bev = arms.dest_sets(nset, dev)
+    outs = {dt: arms.dest_sets(nset, dev, (B, 3, D, D), dt) for dt in (torch.float32, torch.float16, torch.bfloat16)}
     eye = torch.eye(3, dtype=torch.float64, device=dev).reshape(1, 3, 3).contiguous()
     sc_t = torch.tensor(scale, dtype=torch.float32, device=dev).reshape(1, 3, 1, 1)
     bi_t = torch.tensor(bias, dtype=torch.float32, device=dev).reshape(1, 3, 1, 1)
     verdicts = []
-    for hname, hfn in (("keystone", wl.keystone_H), ("brno", wl.synth_brno_H)):
-        H = hfn(SW, SH, D, D)
-        minv = warp.device_inverse(np.stack([wl.jitter_H(H, i) for i in range(B)]), dev).clone()  # (caller-owned)
+    for hname, _, Ms in arms.footprints():
+        minv = warp.device_inverse(Ms, dev).clone()  # (caller-owned)
         k = [0]
 
         def nv12(i):
@@ -72,39 +61,17 @@ def main():
                                          M_inv_device=minv, out_dtype=arm)
             k[0] += 1
 
-        arms = ("nv12", torch.float32, torch.float16, torch.bfloat16, "two_kernel", "two_torch")
-        labels = ("(a)  bevwarp_warp_nv12 (8-bit BGR)", "(b)  nv12_planes float32", "(b)  nv12_planes float16", "(b)  nv12_planes bfloat16",
-                  "(c1) nv12 + warp_to_planar identity f16", "(c2) nv12 + torch permute/float/mul/add/half")
-        for arm in arms:
-            for _ in range(warm):
-                launch(arm)
-        torch.cuda.synchronize()
-        t = {arm: [] for arm in arms}
-        for _ in range(rounds):
-            for arm in arms:
-                ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(per_round)]
-                for e0, e1 in ev:
-                    e0.record()
-                    launch(arm)
-                    e1.record()
-                torch.cuda.synchronize()
-                t[arm] += [e0.elapsed_time(e1) * 1e3 for e0, e1 in ev]
-        med = {arm: float(np.median(t[arm])) for arm in arms}
-        for arm, label in zip(arms, labels):
-            lines.append("%-9s %-46s median %9.1f us  p10 %9.1f  p90 %9.1f  ratio to (a) %5.2f" % (
-                hname, label, med[arm], np.percentile(t[arm], 10), np.percentile(t[arm], 90), med[arm] / med["nv12"]))
+        q = arms.p10_50_90(arms.timed(ARMS, launch, rounds, per_round, warm))
+        med = {arm: q[arm][1] for arm in ARMS}
+        for arm, label in ARMS.items():
+            lines.append("%-9s %-46s median %9.1f us  p10 %9.1f  p90 %9.1f  ratio to (a) %5.2f" % (hname, label, med[arm], q[arm][0], q[arm][2], med[arm] / med["nv12"]))
         faster = min(med["two_kernel"], med["two_torch"])
         ok = med[torch.float16] < faster and med[torch.bfloat16] < faster
         verdicts.append(ok)
         lines.append("%-9s condition: float16 %.1f and bfloat16 %.1f below the faster two-pass route %.1f -> %s (one launch / faster route: %.2f, %.2f)" % (
             hname, med[torch.float16], med[torch.bfloat16], faster, "holds" if ok else "DOES NOT HOLD", med[torch.float16] / faster, med[torch.bfloat16] / faster))
     lines.append("# the condition %s on both footprints" % ("holds" if all(verdicts) else "does NOT hold"))
-    text = "\n".join(lines)
-    print(text, flush=True)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    arms.finish(lines, a.out)
 
 
 if __name__ == "__main__":

@@ -11,19 +11,15 @@ The arms call the C ABI with bound arguments, interleaved in one process after a
 alike), buffer sets rotated past the 256 MB Infinity Cache; HIP-event time per launch, p10 / p50 / p90, and fisheye / rational of the p50s.
 The header states the prediction made from the kernels' static instruction counts before the first run.
 GPU box:  python tools/fisheye_timing.py [--quick] [--out FILE]"""
-import argparse
 import ctypes
-import os
-import sys
 
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from bev_amd import _lib, warp  # noqa: E402
-from tests import workloads as wl  # noqa: E402
+import arms
+from arms import B, C, D, LENS_A, SH, SW, ptr
+from bev_amd import _lib, warp
 
-LENS_A = (-0.30, 0.10, 0.001, -0.0005, -0.01)  # the rational lens of tools/time_lens.py
 FISHEYE_K = (-0.02, 0.004, -0.001, 0.0002)
 FISHEYE = warp.LENS_FISHEYE
 PREDICTION = """# prediction (static instruction counts of the gfx950 code objects, all / float64, made before the first run):
@@ -34,67 +30,40 @@ PREDICTION = """# prediction (static instruction counts of the gfx950 code objec
 #   atan_pos (fisheye): 2 - 3 x at equal steps, so 10 fisheye steps cost about what 20 - 30 rational ones do"""
 
 
-def ptr(a):
-    return a.ctypes.data_as(ctypes.c_void_p)
-
-
-def timed(arms, launch, rounds, per_round, warm):
-    """{arm: [us per launch]}: every arm warmed, then `rounds` rounds of `per_round` launches per arm, the order of the arms reversed every
-    other round."""
-    for arm in arms:
-        for _ in range(warm):
-            launch(arm)
-    torch.cuda.synchronize()
-    t = {arm: [] for arm in arms}
-    for r in range(rounds):
-        for arm in (arms if r % 2 == 0 else arms[::-1]):
-            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(per_round)]
-            for e0, e1 in ev:
-                e0.record()
-                launch(arm)
-                e1.record()
-            torch.cuda.synchronize()
-            t[arm] += [e0.elapsed_time(e1) * 1e3 for e0, e1 in ev]
-    return t
-
-
 def report(lines, tag, t, pairs):
+    q = arms.p10_50_90(t)
     for arm in t:
-        lines.append("%-9s %-22s p10 %9.1f  p50 %9.1f  p90 %9.1f us  (%d launches)" % (tag, arm, np.percentile(t[arm], 10), np.median(t[arm]), np.percentile(t[arm], 90),
-                                                                                        len(t[arm])))
+        lines.append("%-9s %-22s p10 %9.1f  p50 %9.1f  p90 %9.1f us  (%d launches)" % (tag, arm, q[arm][0], q[arm][1], q[arm][2], len(t[arm])))
     for num, den in pairs:
-        lines.append("%-9s %s / %s  %.3f" % (tag, num, den, np.median(t[num]) / np.median(t[den])))
+        lines.append("%-9s %s / %s  %.3f" % (tag, num, den, q[num][1] / q[den][1]))
 
 
 def main():
-    p = argparse.ArgumentParser()
-    p.add_argument("--quick", action="store_true", help="a few launches per arm and 1e6 points")
-    p.add_argument("--out", default=None, help="also write the table to this file")
-    a = p.parse_args()
+    a = arms.parser(__doc__).parse_args()
     assert torch.cuda.is_available(), "no HIP device: nothing to time"
-    B, SH, SW, D, C = 32, 1080, 1920, 1024, 3
-    rounds, per_round, warm = (2, 3, 2) if a.quick else (8, 8, 4)
-    N = 1_000_000 if a.quick else 10_000_000
+    rounds, per_round, warm = arms.counts(a.quick, (8, 8, 4))
+    N = 1_000_000 if a.quick else 10_000_000  # (--quick: 1e6 points)
+
+    def timed(names, launch):
+        return arms.timed(names, launch, rounds, per_round, warm, order="alternate")
+
     dev = torch.device("cuda", 0)
     lib = _lib.load()
     stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    K = np.array([[0.8 * SW, 0, (SW - 1) / 2], [0, 0.816 * SW, (SH - 1) / 2 + 3], [0, 0, 1.0]])
-    intr = [K[0, 0], K[1, 1], K[0, 2], K[1, 2]]
-    lens = {"rational": np.ascontiguousarray(np.concatenate([intr, LENS_A, [0.0, 0.0, 0.0]])), "fisheye": np.ascontiguousarray(np.concatenate([intr, FISHEYE_K, np.zeros(4)]))}
+    K = arms.camera_K(SW, SH)
+    lens = {"rational": arms.lens_array(K, LENS_A), "fisheye": arms.lens_array(K, FISHEYE_K)}
     limit = {"rational": warp.lens_valid_r2(LENS_A), "fisheye": warp.fisheye_valid_theta(FISHEYE_K)}
     flag = {"rational": 0, "fisheye": FISHEYE}
     border = np.zeros(C)
     nset = 3  # (3 x 199 MB of sources, 3 x 101 MB of destinations -- past the 256 MB Infinity Cache)
     gen = torch.Generator(device=dev).manual_seed(1)
     srcs = [torch.randint(0, 256, (B, SH, SW, C), dtype=torch.uint8, device=dev, generator=gen) for _ in range(nset)]
-    outs = [torch.zeros((B, D, D, C), dtype=torch.uint8, device=dev) for _ in range(nset)]
+    outs = arms.dest_sets(nset, dev)
     lines = ["# BEVWARP_LENS_FISHEYE against the rational model, %d x %dx%dx%d -> %dx%dx%d, uint8, bilinear, per-frame jitter_H; us per launch" % (B, SW, SH, C, D, D, C),
              "# rational %s, r2_max %.4f; fisheye %s, theta_max %.4f; %d rounds x %d launches per arm, arms interleaved; %s"
              % (LENS_A, limit["rational"], FISHEYE_K, limit["fisheye"], rounds, per_round, torch.cuda.get_device_name(dev)), PREDICTION]
     models = ("rational", "fisheye")
-    for hname, hfn in (("keystone", wl.keystone_H), ("brno", wl.synth_brno_H)):
-        H = hfn(SW, SH, D, D)
-        Ms = np.stack([wl.jitter_H(H, i) for i in range(B)])
+    for hname, _, Ms in arms.footprints():
         mray = {"rational": torch.from_numpy(np.ascontiguousarray(warp.ray_matrix(Ms, K))).to(dev),
                 "fisheye": torch.from_numpy(np.ascontiguousarray(warp.ray_matrix(Ms, K, oriented=True))).to(dev)}
         k = [0]
@@ -105,7 +74,7 @@ def main():
             _lib.check(lib.bevwarp_warp_lens(srcs[i].data_ptr(), outs[i].data_ptr(), B, SH, SW, D, D, C, SH * SW * C, SW * C, D * D * C, D * C, mray[arm].data_ptr(), B,
                                              ptr(lens[arm]), limit[arm], _lib.U8, 1 | flag[arm], warp.BORDER_CONSTANT, ptr(border), stream))
 
-        report(lines, hname, timed(models, launch_warp, rounds, per_round, warm), [("fisheye", "rational")])
+        report(lines, hname, timed(models, launch_warp), [("fisheye", "rational")])
 
         # one map of the first frame's matrix; 64 map sets (6 MB each) rotated past the cache for the builder
         nmap = 64
@@ -118,7 +87,7 @@ def main():
             _lib.check(lib.bevwarp_build_map(mray[arm].data_ptr(), 1, ptr(lens[arm]), limit[arm], 1 | flag[arm], xy[j].data_ptr(), fr[j].data_ptr(), D, D, 0, D * 4, 0, D * 2,
                                              stream))
 
-        report(lines, hname, {"build " + m: v for m, v in timed(models, launch_build, rounds, per_round, warm).items()}, [("build fisheye", "build rational")])
+        report(lines, hname, {"build " + m: v for m, v in timed(models, launch_build).items()}, [("build fisheye", "build rational")])
         slot = {"rational": 0, "fisheye": 1}
         for m in models:
             launch_build(m, slot[m])
@@ -130,7 +99,7 @@ def main():
             _lib.check(lib.bevwarp_remap(srcs[i].data_ptr(), outs[i].data_ptr(), B, SH, SW, D, D, C, SH * SW * C, SW * C, D * D * C, D * C, xy[j].data_ptr(), fr[j].data_ptr(), 1,
                                          0, D * 4, 0, D * 2, _lib.U8, 1, warp.BORDER_CONSTANT, ptr(border), stream))
 
-        report(lines, hname, {"remap " + m: v for m, v in timed(models, launch_remap, rounds, per_round, warm).items()}, [("remap fisheye", "remap rational")])
+        report(lines, hname, {"remap " + m: v for m, v in timed(models, launch_remap).items()}, [("remap fisheye", "remap rational")])
         del xy, fr
     del srcs, outs
     torch.cuda.empty_cache()
@@ -142,8 +111,8 @@ def main():
     pouts = [torch.empty_like(x) for x in ins]
     R = {"rational": np.ascontiguousarray(warp.ray_matrix(np.eye(3), K, inverse_given=True)), "fisheye": np.ascontiguousarray(warp.ray_matrix(np.eye(3), K, inverse_given=True, oriented=True))}
     Kc = np.ascontiguousarray(K)
-    arms = [(m, d, it) for d, it in ((0, 0), (1, 5), (1, 10)) for m in models]
-    names = {arm: "%s %s" % (("distort", "undistort_%d" % arm[2])[arm[1]], arm[0]) for arm in arms}
+    cases = [(m, d, it) for d, it in ((0, 0), (1, 5), (1, 10)) for m in models]
+    names = {arm: "%s %s" % (("distort", "undistort_%d" % arm[2])[arm[1]], arm[0]) for arm in cases}
     k = [0]
 
     def launch_points(arm):
@@ -153,15 +122,10 @@ def main():
         _lib.check(lib.bevwarp_project_points_lens(ins[i].data_ptr(), pouts[i].data_ptr(), None, N, ptr(R[m]) if d == 0 else ptr(Kc), ptr(lens[m]), limit[m], d | flag[m], it, 1e-3,
                                                    _lib.F64, stream))
 
-    t = timed(arms, launch_points, rounds, per_round, warm)
+    t = timed(cases, launch_points)
     report(lines, "points", {names[arm]: v for arm, v in t.items()}, [(names[("fisheye", d, it)], names[("rational", d, it)]) for d, it in ((0, 0), (1, 5), (1, 10))])
     lines.append("# points: %d float64 points per launch" % N)
-    text = "\n".join(lines)
-    print(text, flush=True)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    arms.finish(lines, a.out)
 
 
 if __name__ == "__main__":

@@ -15,24 +15,20 @@ FramePipeline(warp_map=..., src_format="nv12") rings plus resident launches, bot
 GPU box, each step under a time limit of its own and none tried again when it fails:
     timeout -k 10 400 python tools/map_planes_timing.py --step kernels --out profiles/map_planes_timing.txt && \\
     timeout -k 10 300 python tools/map_planes_timing.py --step pipeline --out profiles/map_planes_timing.txt --append"""
-import argparse
 import ctypes
-import os
-import sys
 import time
 
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from bev_amd import _lib, warp  # noqa: E402
-from bev_amd.pipeline import FramePipeline, SitePipeline  # noqa: E402
-from tests import lens_ref  # noqa: E402
-from tests import nv12_ref  # noqa: E402
-from tests import workloads as wl  # noqa: E402
-from tools.stitch_timing import views  # noqa: E402
+import arms
+from arms import B, D, SH, SW, lens_map, views
+from bev_amd import _lib, warp
+from bev_amd.pipeline import FramePipeline, SitePipeline
+from tests import nv12_ref
+from tests import workloads as wl
 
-B, SH, SW, D, K = 32, 1080, 1920, 1024, 3
+K = 3
 NSET = 2  # (2 x 199 MB of BGR frames per camera, 2 x 100 MB of NV12 planes per camera, 2 x 100 MB of BGR BEVs, 2 x 201 / 403 MB of planes: past the 256 MB Infinity Cache)
 SINGLE = (("a_two", "(a) remap + identity warp_planes, f16"), ("a_new", "(a) remap_planes, f16"), ("a_pix", "    remap alone"), ("a_nvp", "    remap_nv12_planes, f16"),
           ("a_two32", "(a) remap + identity warp_planes, f32"), ("a_new32", "(a) remap_planes, f32"))
@@ -49,17 +45,13 @@ EXPECT = ("# expectations, stated before the numbers: (a) p90 of bevwarp_remap_p
 SCALE, BIAS = (1 / 255.0, 1 / 255.0, 1 / 255.0), (-0.4, -0.45, -0.5)
 
 
-def lens_map(M, dev):
-    return warp.build_warp_map(M, (D, D), K=lens_ref.camera_K(SW, SH), dist_coeff=lens_ref.LENS_A, device=dev)
-
-
 def kernels(quick, dev):
-    rounds, per_round, warm = (2, 3, 2) if quick else (6, 10, 4)
+    rounds, per_round, warm = arms.counts(quick, (6, 10, 4))
     lib = _lib.load()
     stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    foot = {"keystone": wl.keystone_H(SW, SH, D, D), "brno": wl.synth_brno_H(SW, SH, D, D)}
+    foot = {name: H for name, H, _ in arms.footprints()}
     maps = {k: lens_map(M, dev) for k, M in foot.items()}
-    cam_maps = [lens_map(M, dev) for M in views(SW, SH, D)]
+    cam_maps = [lens_map(M, dev) for M in views()]
     eye = torch.eye(3, dtype=torch.float64, device=dev)[None].contiguous()
     bgr4 = [wl.frame(97 + i, SH, SW, np.uint8) for i in range(4)]
     nv4 = [nv12_ref.frame("video", 131 + i, SH, SW) for i in range(4)]
@@ -68,11 +60,10 @@ def kernels(quick, dev):
     srcs = [[pick(bgr4, s + k) for k in range(K)] for s in range(NSET)]
     ys = [[pick([f[0] for f in nv4], s + k) for k in range(K)] for s in range(NSET)]
     uvs = [[pick([f[1] for f in nv4], s + k) for k in range(K)] for s in range(NSET)]
-    bev = [torch.zeros((B, D, D, 3), dtype=torch.uint8, device=dev) for _ in range(NSET)]
-    out = {16: [torch.zeros((B, 3, D, D), dtype=torch.float16, device=dev) for _ in range(NSET)],
-           32: [torch.zeros((B, 3, D, D), dtype=torch.float32, device=dev) for _ in range(NSET)]}
+    bev = arms.dest_sets(NSET, dev)
+    out = {16: arms.dest_sets(NSET, dev, (B, 3, D, D), torch.float16), 32: arms.dest_sets(NSET, dev, (B, 3, D, D), torch.float32)}
     sc, bi = np.array(SCALE, np.float64), np.array(BIAS, np.float64)
-    psc, pbi = sc.ctypes.data_as(ctypes.c_void_p), bi.ctypes.data_as(ctypes.c_void_p)
+    psc, pbi = arms.ptr(sc), arms.ptr(bi)
     cams = {"bgr": [], "nv12": []}
     for s in range(NSET):
         for kind in cams:
@@ -122,7 +113,7 @@ def kernels(quick, dev):
             _lib.check(lib.bevwarp_stitch_maps_nv12_planes(ctypes.addressof(cams["nv12"][i]), K, o, B, D, D, *dst, 1, OVER, 64, 0, *planes_tail))
 
     # results must not change: every new arm leaves, bit for bit, the planes of the two-launch route it replaces, at the timed size
-    arms = [(key, label, fp) for fp in foot for key, label in SINGLE] + [(key, label, None) for key, label in STITCH]
+    rows = [(key, label, fp) for fp in foot for key, label in SINGLE] + [(key, label, None) for key, label in STITCH]
     for _, two, new, single in PAIRS:
         for fp in (foot if single else (None,)):
             o = out[32 if two.endswith("32") else 16][0]
@@ -140,22 +131,9 @@ def kernels(quick, dev):
              "# (b), (c): %d cameras, tools/stitch_timing.py's views; %d rounds x %d runs per arm, arms interleaved; %s" % (K, rounds, per_round, torch.cuda.get_device_name(dev)),
              "# checked before timing: each new arm leaves bit for bit the planes of the two-launch route beside it; the baselines are entries this change does not touch"]
     lines += list(EXPECT)
-    for key, _, fp in arms:
-        for _ in range(warm):
-            launch(key, fp)
-    torch.cuda.synchronize()
-    t = {(key, fp): [] for key, _, fp in arms}
-    for _ in range(rounds):
-        for key, _, fp in arms:
-            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(per_round)]
-            for e0, e1 in ev:
-                e0.record()
-                launch(key, fp)
-                e1.record()
-            torch.cuda.synchronize()
-            t[key, fp] += [e0.elapsed_time(e1) * 1e3 for e0, e1 in ev]
-    q = {k: [float(np.percentile(v, x)) for x in (10, 50, 90)] for k, v in t.items()}
-    for key, label, fp in arms:
+    t = arms.timed([(key, fp) for key, _, fp in rows], lambda arm: launch(*arm), rounds, per_round, warm)
+    q = arms.p10_50_90(t)
+    for key, label, fp in rows:
         lines.append("%-9s %-52s p10 %8.1f  p50 %8.1f  p90 %8.1f us  (%d runs)" % ((fp or "3 views", label) + tuple(q[key, fp]) + (len(t[key, fp]),)))
     for name, two, new, single in PAIRS:
         expected = name in ("(a)", "(b)", "(c)")
@@ -239,7 +217,7 @@ def rings_ms(rings, frames, n, dev):
 
 def pipeline(quick, dev):
     n = 40 if quick else 200
-    cam_maps = [lens_map(M, dev) for M in views(SW, SH, D)]
+    cam_maps = [lens_map(M, dev) for M in views()]
     frames = [nv12_ref.join(*nv12_ref.frame("video", 3 + k, SH, SW)) for k in range(K)]
     lines = ["# (d) %d sets of %d x %dx%d NV12 frames -> 3 x %dx%d float16 planes, lens-A maps on tools/stitch_timing.py's views, depth 3: ms per set (host clock around the loop), 3 repeats, arms alternated" % (
         n, K, SW, SH, D, D)]
@@ -263,19 +241,9 @@ def pipeline(quick, dev):
 
 
 def main():
-    p = argparse.ArgumentParser()
-    p.add_argument("--step", choices=("kernels", "pipeline"), required=True)
-    p.add_argument("--quick", action="store_true", help="a few launches per arm (for a profiler run)")
-    p.add_argument("--out", default=None, help="also write the table to this file")
-    p.add_argument("--append", action="store_true", help="append to --out instead of replacing it")
-    a = p.parse_args()
+    a = arms.parser(__doc__, steps=("kernels", "pipeline")).parse_args()
     dev = torch.device("cuda", 0)
-    text = "\n".join((kernels if a.step == "kernels" else pipeline)(a.quick, dev))
-    print(text, flush=True)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "a" if a.append else "w") as f:
-            f.write(text + "\n")
+    arms.finish((kernels if a.step == "kernels" else pipeline)(a.quick, dev), a.out, a.append)
 
 
 if __name__ == "__main__":

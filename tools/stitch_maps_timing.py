@@ -12,38 +12,31 @@ process after a warm-up, buffer sets rotated past the Infinity Cache:
 (a), (b) and (f) are entries this change does not touch: the baseline of the same run.  HIP-event time per arm (the whole of (b) and (f):
 the fill and the three launches), p10 / p50 / p90, and the three expectations, each confirmed or refuted.
 GPU box:  python tools/stitch_maps_timing.py [--quick] [--out FILE]"""
-import argparse
 import ctypes
-import os
-import sys
 
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from bev_amd import _lib, warp  # noqa: E402
-from tests import lens_ref  # noqa: E402
-from tests import nv12_ref  # noqa: E402
-from tests import workloads as wl  # noqa: E402
-from tools.stitch_timing import views  # noqa: E402
+import arms
+from arms import B, C, D, SH, SW
+from bev_amd import _lib, warp
+from tests import nv12_ref
+from tests import workloads as wl
 
 ARMS = ("(a) warp_stitch over", "(b) fill + 3 x remap transparent", "(c) stitch_maps over", "(d) stitch_maps over, lens maps", "(e) stitch_maps feather 64",
         "(f) fill + 3 x remap_nv12 transparent", "(g) stitch_maps_nv12 over")
 
 
 def main():
-    p = argparse.ArgumentParser()
-    p.add_argument("--quick", action="store_true", help="a few launches per arm (for a profiler run)")
-    p.add_argument("--out", default=None, help="also write the table to this file")
-    a = p.parse_args()
-    B, SH, SW, D, C, K = 32, 1080, 1920, 1024, 3, 3
-    rounds, per_round, warm = (2, 3, 2) if a.quick else (7, 10, 5)
+    a = arms.parser(__doc__).parse_args()
+    K = 3
+    rounds, per_round, warm = arms.counts(a.quick)
     dev = torch.device("cuda", 0)
     lib = _lib.load()
-    Ms = views(SW, SH, D)
+    Ms = arms.views()
     minvs = [torch.from_numpy(warp.invert_homography(M)[None]).to(dev) for M in Ms]
     pin = [warp.build_warp_map(M, (D, D), device=dev) for M in Ms]
-    lens = [warp.build_warp_map(M, (D, D), K=lens_ref.camera_K(SW, SH), dist_coeff=lens_ref.LENS_A, device=dev) for M in Ms]
+    lens = [arms.lens_map(M, dev) for M in Ms]
     torch.cuda.synchronize()
     covers = []
     for maps in (pin, lens):
@@ -58,7 +51,7 @@ def main():
         nv = [[nv12_ref.frame("video", 131 * (K * s + k) + i, SH, SW) for i in range(4)] for k in range(K)]
         ys.append([torch.from_numpy(np.stack([nv[k][i % 4][0] for i in range(B)])).to(dev) for k in range(K)])
         uvs.append([torch.from_numpy(np.stack([nv[k][i % 4][1] for i in range(B)])).to(dev) for k in range(K)])
-    outs = [torch.zeros((B, D, D, C), dtype=torch.uint8, device=dev) for _ in range(nset)]
+    outs = arms.dest_sets(nset, dev)
 
     def map_cams(s, maps, nv12):
         arr = (_lib.MapCamera * K)()
@@ -122,21 +115,8 @@ def main():
              "# views: tools/stitch_timing.py's; %d rounds x %d runs per arm, arms interleaved; %s" % (rounds, per_round, torch.cuda.get_device_name(dev)),
              "# canvas pixels covered by 0 / 1 / 2 / 3 cameras: pinhole maps %s %%; lens-A maps %s %%" % tuple(covers),
              "# checked before timing: (c) leaves bit for bit the canvas of (a) and of (b), (g) that of (f); (a), (b) and (f) are entries this change does not touch"]
-    for arm in ARMS:
-        for _ in range(warm):
-            launch(arm)
-    torch.cuda.synchronize()
-    t = {arm: [] for arm in ARMS}
-    for _ in range(rounds):
-        for arm in ARMS:
-            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(per_round)]
-            for e0, e1 in ev:
-                e0.record()
-                launch(arm)
-                e1.record()
-            torch.cuda.synchronize()
-            t[arm] += [e0.elapsed_time(e1) * 1e3 for e0, e1 in ev]
-    q = {arm: [float(np.percentile(t[arm], x)) for x in (10, 50, 90)] for arm in ARMS}
+    t = arms.timed(ARMS, launch, rounds, per_round, warm)
+    q = arms.p10_50_90(t)
     for arm in ARMS:
         lines.append("%-40s p10 %8.1f  p50 %8.1f  p90 %8.1f us  (%d runs)" % ((arm,) + tuple(q[arm]) + (len(t[arm]),)))
     A, Bm, Cm, Dm, E, F, G = (q[arm] for arm in ARMS)
@@ -145,12 +125,7 @@ def main():
               "(c) p50 below (a) p50 (%.1f vs %.1f us): %s   (c) / (a) p50 %.2f" % (Cm[1], A[1], verdict(Cm[1] < A[1]), Cm[1] / A[1]),
               "(g) p90 not above (f) p10 (%.1f vs %.1f us): %s   (g) / (f) p50 %.2f" % (G[2], F[0], verdict(G[2] <= F[0]), G[1] / F[1]),
               "lens maps / pinhole maps (d) / (c) p50 %.2f   feather / over (e) / (c) p50 %.2f   NV12 / frames (g) / (c) p50 %.2f" % (Dm[1] / Cm[1], E[1] / Cm[1], G[1] / Cm[1])]
-    text = "\n".join(lines)
-    print(text, flush=True)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    arms.finish(lines, a.out)
 
 
 if __name__ == "__main__":

@@ -8,45 +8,27 @@ the same buffers after a warm-up, buffer sets rotated past the Infinity Cache:
   (c) bevwarp_warp_stitch, BEVWARP_STITCH_FEATHER with F = 64
 HIP-event time per arm (the whole of (a): the fill and its three launches), p10 / p50 / p90, and the ratios.
 GPU box:  python tools/stitch_timing.py [--quick] [--out FILE]"""
-import argparse
 import ctypes
-import os
-import sys
 
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from bev_amd import _lib, warp  # noqa: E402
-from tests import border_ref  # noqa: E402
-from tests import workloads as wl  # noqa: E402
+import arms
+from arms import B, C, D, SH, SW
+from bev_amd import _lib, warp
+from tests import border_ref
+from tests import workloads as wl
 
 ARMS = ("fill + 3 x border_transparent", "stitch over", "stitch feather 64")
 
 
-def views(sw, sh, d):
-    """Forward matrices of the three cameras: the Brno-like view turned by -12, 0 and +12 degrees about the canvas centre and shifted by
-    -180, 0 and +180 canvas pixels."""
-    H = wl.synth_brno_H(sw, sh, d, d)
-    out = []
-    for deg, dx in ((-12.0, -180.0), (0.0, 0.0), (12.0, 180.0)):
-        t, c = np.deg2rad(deg), (d - 1) / 2.0
-        R = np.array([[np.cos(t), -np.sin(t), 0], [np.sin(t), np.cos(t), 0], [0, 0, 1.0]])
-        T0, T1 = np.array([[1, 0, -c], [0, 1, -c], [0, 0, 1.0]]), np.array([[1, 0, c + dx], [0, 1, c], [0, 0, 1.0]])
-        out.append(T1 @ R @ T0 @ H)
-    return out
-
-
 def main():
-    p = argparse.ArgumentParser()
-    p.add_argument("--quick", action="store_true", help="a few launches per arm (for a profiler run)")
-    p.add_argument("--out", default=None, help="also write the table to this file")
-    a = p.parse_args()
-    B, SH, SW, D, C, K = 32, 1080, 1920, 1024, 3, 3
-    rounds, per_round, warm = (2, 3, 2) if a.quick else (7, 10, 5)
+    a = arms.parser(__doc__).parse_args()
+    K = 3
+    rounds, per_round, warm = arms.counts(a.quick)
     dev = torch.device("cuda", 0)
     lib = _lib.load()
-    Ms = views(SW, SH, D)
+    Ms = arms.views()
     masks = [border_ref.written_mask((SH, SW), M, (D, D), 1) for M in Ms]
     count = sum(m.astype(np.int64) for m in masks)
     pair = [(i, j, float((masks[i] & masks[j]).sum()) / min(masks[i].sum(), masks[j].sum())) for i in range(K) for j in range(i + 1, K)]
@@ -56,7 +38,7 @@ def main():
     for s in range(nset):  # (four distinct frames per camera and set, repeated over the batch)
         four = [[wl.frame(97 * (K * s + k) + i, SH, SW, np.uint8) for i in range(4)] for k in range(K)]
         srcs.append([torch.from_numpy(np.stack([four[k][i % 4] for i in range(B)])).to(dev) for k in range(K)])
-    outs = [torch.zeros((B, D, D, C), dtype=torch.uint8, device=dev) for _ in range(nset)]
+    outs = arms.dest_sets(nset, dev)
     cams = []
     for s in range(nset):
         arr = (_lib.Camera * K)()
@@ -102,32 +84,14 @@ def main():
              % (" / ".join("%.1f" % (100.0 * (count == c).mean()) for c in range(4)), ", ".join("%d-%d %.0f %%" % (i, j, 100 * f) for i, j, f in pair)),
              "# arm (a)'s kernel, warp_border_kernel<uint8, 3, bilinear, TRANSPARENT>, is byte for byte the one of the commit before the stitch warp (profiles/stitch_isa_identity.txt)",
              "# checked before timing: 'stitch over' leaves bit for bit the canvas of arm (a); 'stitch feather 64' differs from it only where two or more cameras cover"]
-    for arm in ARMS:
-        for _ in range(warm):
-            launch(arm)
-    torch.cuda.synchronize()
-    t = {arm: [] for arm in ARMS}
-    for _ in range(rounds):
-        for arm in ARMS:
-            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(per_round)]
-            for e0, e1 in ev:
-                e0.record()
-                launch(arm)
-                e1.record()
-            torch.cuda.synchronize()
-            t[arm] += [e0.elapsed_time(e1) * 1e3 for e0, e1 in ev]
-    q = {arm: [float(np.percentile(t[arm], x)) for x in (10, 50, 90)] for arm in ARMS}
+    t = arms.timed(ARMS, launch, rounds, per_round, warm)
+    q = arms.p10_50_90(t)
     for arm in ARMS:
         lines.append("%-30s p10 %8.1f  p50 %8.1f  p90 %8.1f us  (%d runs)" % ((arm,) + tuple(q[arm]) + (len(t[arm]),)))
     lines.append("over / route (p50) %.2f   feather / over (p50) %.2f   over's p90 %s the route's p10 (%.1f vs %.1f us): the expectation is %s"
                  % (q[ARMS[1]][1] / q[ARMS[0]][1], q[ARMS[2]][1] / q[ARMS[1]][1], "is not above" if q[ARMS[1]][2] <= q[ARMS[0]][0] else "is above",
                     q[ARMS[1]][2], q[ARMS[0]][0], "confirmed" if q[ARMS[1]][2] <= q[ARMS[0]][0] else "refuted"))
-    text = "\n".join(lines)
-    print(text, flush=True)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    arms.finish(lines, a.out)
 
 
 if __name__ == "__main__":

@@ -8,42 +8,32 @@ launch.  Per arm: median, p10, p90, the algorithmic bytes (destination bytes + w
 its read and its write), the TB/s they make, and the ratio to the float32-plane arm -- whose kernel is byte-identical to the parent's
 (profiles/planes16_isa_identity.txt), so it is the baseline.
 GPU box:  python tools/time_planes.py [--quick] [--out FILE]"""
-import argparse
-import os
-import sys
-
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from bev_amd import warp  # noqa: E402
-from tests import workloads as wl  # noqa: E402
+import arms
+from arms import B, C, D, SH, SW
+from bev_amd import warp
 
 ARMS = ["uint8 interleaved", "float32 planes", "float16 planes", "bfloat16 planes", "float32 planes + .half()"]
 
 
 def main():
-    p = argparse.ArgumentParser()
-    p.add_argument("--quick", action="store_true", help="a few launches per arm (for a profiler run)")
-    p.add_argument("--out", default=None, help="also write the table to this file")
-    a = p.parse_args()
-    B, SH, SW, D, C = 32, 1080, 1920, 1024, 3
-    rounds, per_round, warm = (2, 3, 2) if a.quick else (7, 10, 5)
+    a = arms.parser(__doc__).parse_args()
+    rounds, per_round, warm = arms.counts(a.quick)
     nset = 3  # (3 x 199 MB of sources; destinations: 3 x 101 MB interleaved, 3 x 403 MB float32 planes, 3 x 201 MB 16-bit planes)
     dev = torch.device("cuda", 0)
     scale, bias = 1.0 / (255.0 * np.array([0.229, 0.224, 0.225])), -np.array([0.485, 0.456, 0.406]) / np.array([0.229, 0.224, 0.225])
     lines = ["# plane formats of the one-pass warp, %d x %dx%dx3 uint8 -> %dx%d, bilinear, per-frame jitter_H, ImageNet scale and bias; us per launch" % (B, SW, SH, D, D),
              "# %d rounds x %d launches per arm, arms interleaved, %d buffer sets; %s" % (rounds, per_round, nset, torch.cuda.get_device_name(dev)),
              "# bytes: destination + footprint x 3 (the conversion pass: + its 4-byte read and 2-byte write); ratio: median / median of float32 planes"]
-    srcs = [torch.from_numpy(np.stack([wl.frame(B * s + i, SH, SW, np.uint8) for i in range(B)])).to(dev) for s in range(nset)]
-    out_u8 = [torch.zeros((B, D, D, C), dtype=torch.uint8, device=dev) for _ in range(nset)]
-    out_f32 = [torch.zeros((B, C, D, D), dtype=torch.float32, device=dev) for _ in range(nset)]
-    out_16 = [torch.zeros((B, C, D, D), dtype=torch.int16, device=dev) for _ in range(nset)]
+    srcs, out_u8 = arms.frame_sets(nset, dev), arms.dest_sets(nset, dev)
+    out_f32 = arms.dest_sets(nset, dev, (B, C, D, D), torch.float32)
+    out_16 = arms.dest_sets(nset, dev, (B, C, D, D), torch.int16)
     out_f16, out_bf16 = [t.view(torch.float16) for t in out_16], [t.view(torch.bfloat16) for t in out_16]
     planes = B * C * D * D
     verdict = []
-    for hname, hfn in (("keystone", wl.keystone_H), ("brno", wl.synth_brno_H)):
-        Ms = np.stack([wl.jitter_H(hfn(SW, SH, D, D), i) for i in range(B)])
+    for hname, _, Ms in arms.footprints():
         minv = warp.device_inverse(Ms, dev).clone()  # (caller-owned: the plain launch)
         src_bytes = int(warp.footprint((SH, SW), Ms, (D, D), batch=B, device=dev)[0].sum().item()) * C
         nbytes = {ARMS[0]: planes + src_bytes, ARMS[1]: 4 * planes + src_bytes, ARMS[2]: 2 * planes + src_bytes, ARMS[3]: 2 * planes + src_bytes,
@@ -63,36 +53,18 @@ def main():
                 dt, outs = (torch.float16, out_f16) if arm == ARMS[2] else (torch.bfloat16, out_bf16)
                 warp.warp_to_planar(srcs[i], None, (D, D), scale=scale, bias=bias, out=outs[i], M_inv_device=minv, out_dtype=dt)
 
-        for arm in ARMS:
-            for _ in range(warm):
-                launch(arm)
-        torch.cuda.synchronize()
-        t = {arm: [] for arm in ARMS}
-        for _ in range(rounds):
-            for arm in ARMS:
-                ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(per_round)]
-                for e0, e1 in ev:
-                    e0.record()
-                    launch(arm)
-                    e1.record()
-                torch.cuda.synchronize()
-                t[arm] += [e0.elapsed_time(e1) * 1e3 for e0, e1 in ev]
-        med = {arm: float(np.median(t[arm])) for arm in ARMS}
+        q = arms.p10_50_90(arms.timed(ARMS, launch, rounds, per_round, warm))
+        med = {arm: q[arm][1] for arm in ARMS}
         for arm in ARMS:
             lines.append("%-9s %-25s median %7.1f us  p10 %7.1f  p90 %7.1f  bytes %6.1f MB  %5.2f TB/s  ratio to float32 planes %5.2f" % (
-                hname, arm, med[arm], np.percentile(t[arm], 10), np.percentile(t[arm], 90), nbytes[arm] / 1e6, nbytes[arm] / med[arm] / 1e6, med[arm] / med[ARMS[1]]))
+                hname, arm, med[arm], q[arm][0], q[arm][2], nbytes[arm] / 1e6, nbytes[arm] / med[arm] / 1e6, med[arm] / med[ARMS[1]]))
         for arm in ARMS[2:4]:
             if hname == "keystone":
                 verdict.append("# %s, keystone: p90 %.1f us %s p10 of float32 planes %.1f us" % (
-                    arm, np.percentile(t[arm], 90), "<" if np.percentile(t[arm], 90) < np.percentile(t[ARMS[1]], 10) else "NOT BELOW", np.percentile(t[ARMS[1]], 10)))
+                    arm, q[arm][2], "<" if q[arm][2] < q[ARMS[1]][0] else "NOT BELOW", q[ARMS[1]][0]))
             verdict.append("# %s, %s: median %.1f us %s median of float32 planes + .half() %.1f us" % (
                 arm, hname, med[arm], "<" if med[arm] < med[ARMS[4]] else "NOT BELOW", med[ARMS[4]]))
-    text = "\n".join(lines + verdict)
-    print(text, flush=True)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    arms.finish(lines + verdict, a.out)
 
 
 if __name__ == "__main__":

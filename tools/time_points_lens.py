@@ -6,37 +6,29 @@ Arms, per dtype (float32, float64), N = 1e7 points of a 1920 x 1080 frame each: 
 arms alternate round by round (forwards, backwards) so that drift hits them alike.  Prints p10 / p50 / p90 per arm and the p50 ratio
 to project_points (profiles/points_lens_timing.txt)."""
 import ctypes
-import os
 import sys
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from bev_amd import _lib  # noqa: E402
-from bev_amd.warp import lens_valid_r2, ray_matrix  # noqa: E402
+import arms
+from arms import LENS_A as DIST, SH as H, SW as W, ptr
+from bev_amd import _lib
+from bev_amd.warp import lens_valid_r2, ray_matrix
 
 N = int(float(sys.argv[1])) if len(sys.argv) > 1 else 10_000_000
 ROUNDS, DISCARD = 44, 4
-W, H = 1920, 1080
-K = np.array([[0.8 * W, 0, (W - 1) / 2], [0, 0.816 * W, (H - 1) / 2 + 3], [0, 0, 1.0]])
-DIST = (-0.30, 0.10, 0.001, -0.0005, -0.01)  # tests/lens_ref.py's lens A
+K = arms.camera_K(W, H)
 
 assert torch.cuda.is_available(), "no HIP device: nothing to time"
 lib = _lib.load()
 dev = torch.device("cuda", 0)
 stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
-
-def ptr(a):
-    return a.ctypes.data_as(ctypes.c_void_p)
-
-
 H_plain = np.ascontiguousarray(np.array([[0.02, -0.001, -3.0], [0.0004, 0.05, -20.0], [1e-5, 0.0009, 0.4]]))  # tools/ab_points.py's
 R = np.ascontiguousarray(ray_matrix(np.eye(3), K, inverse_given=True))  # undistorted pixels -> normalised plane
 Kc = np.ascontiguousarray(K)                                          # normalised plane -> undistorted pixels
-lens = np.ascontiguousarray(np.concatenate([[K[0, 0], K[1, 1], K[0, 2], K[1, 2]], DIST, [0, 0, 0]]), dtype=np.float64)
+lens = arms.lens_array(K, DIST)
 r2_max = lens_valid_r2(DIST)
 
 print("device: %s, N = %d, %d timed launches per arm" % (torch.cuda.get_device_name(0), N, ROUNDS - DISCARD))

@@ -11,36 +11,22 @@ Before the arms, the box's streaming figure: tools/libstreamprobe.so reading one
 (plain loads, non-temporal stores), in this process on the arms' own buffers.
 Derived: cubic_map_pinhole p90 against cubic_matrix p10 (the expectation DESIGN.md section 4.25 judges) and cubic_map_pinhole / linear_map.
 GPU box:  python tools/time_remap_cubic.py [--quick] [--out FILE]"""
-import argparse
 import ctypes
 import os
-import sys
 
 import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from bev_amd import _lib, warp  # noqa: E402
-from tests import workloads as wl  # noqa: E402
+import arms
+from arms import B, C, D, LENS_A, SH, SW
+from bev_amd import _lib, warp
 
-LENS_A = (-0.30, 0.10, 0.001, -0.0005, -0.01)
 ARMS = ("cubic_map_pinhole", "cubic_map_lens", "cubic_matrix", "linear_map")
-
-
-def event_us(launch, n):
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n)]
-    for e0, e1 in ev:
-        e0.record()
-        launch()
-        e1.record()
-    torch.cuda.synchronize()
-    return [e0.elapsed_time(e1) * 1e3 for e0, e1 in ev]
 
 
 def streaming_probe(srcs, outs, stream):
     """(us, GB/s) of the best of two grids: median over 20 launches each, after 4 unmeasured ones."""
-    lib = ctypes.CDLL(os.path.join(ROOT, "tools", "libstreamprobe.so"))
+    lib = ctypes.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), "libstreamprobe.so"))
     lib.probe_stream.restype = ctypes.c_int
     lib.probe_stream.argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     read_b, write_b = srcs[0].numel() // 16 * 16, outs[0].numel() // 16 * 16
@@ -55,39 +41,31 @@ def streaming_probe(srcs, outs, stream):
             if lib.probe_stream(srcs[i].data_ptr(), read_b, outs[i].data_ptr(), write_b, 0, 1, grid, stream, clk.data_ptr()):
                 raise RuntimeError("probe_stream failed")
 
-        event_us(launch, 4)
-        t = float(np.median(event_us(launch, 20)))
+        arms.event_us(launch, 4)
+        t = float(np.median(arms.event_us(launch, 20)))
         best = t if best is None else min(best, t)
     return best, (read_b + write_b) / best / 1e3, read_b, write_b
 
 
 def main():
-    p = argparse.ArgumentParser()
-    p.add_argument("--quick", action="store_true", help="a few launches per arm")
-    p.add_argument("--out", default=None, help="also write the table to this file")
-    a = p.parse_args()
-    B, SH, SW, D, C = 32, 1080, 1920, 1024, 3
-    rounds, per_round, warm = (2, 3, 2) if a.quick else (7, 10, 5)
+    a = arms.parser(__doc__).parse_args()
+    rounds, per_round, warm = arms.counts(a.quick)
     dev = torch.device("cuda", 0)
     lib = _lib.load()
-    K = np.array([[0.8 * SW, 0, (SW - 1) / 2], [0, 0.816 * SW, (SH - 1) / 2 + 3], [0, 0, 1.0]])
     border = np.zeros(C)
-    bptr = border.ctypes.data_as(ctypes.c_void_p)
+    bptr = arms.ptr(border)
     nset = 3  # (3 x 199 MB of sources, 3 x 101 MB of destinations -- past the 256 MB Infinity Cache)
-    srcs = [torch.from_numpy(np.stack([wl.frame(B * s + i, SH, SW, np.uint8) for i in range(B)])).to(dev) for s in range(nset)]
-    outs = [torch.zeros((B, D, D, C), dtype=torch.uint8, device=dev) for _ in range(nset)]
+    srcs, outs = arms.frame_sets(nset, dev), arms.dest_sets(nset, dev)
     stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     lines = ["# bevwarp_remap | BEVWARP_MAP_BICUBIC vs bevwarp_warp_border(BEVWARP_CUBIC) vs bevwarp_remap (bilinear), %d x %dx%dx%d -> %dx%dx%d, uint8; us per launch"
              % (B, SW, SH, C, D, D, C),
              "# lens A %s; %d rounds x %d launches per arm, arms interleaved; %s" % (LENS_A, rounds, per_round, torch.cuda.get_device_name(dev))]
     us, gbs, rb, wb = streaming_probe(srcs, outs, stream)
     lines.append("# streaming probe (plain loads, nt stores; reads %d B, writes %d B of one launch's buffers): %.1f us, %.0f GB/s" % (rb, wb, us, gbs))
-    for hname, hfn in (("keystone", wl.keystone_H), ("brno", wl.synth_brno_H)):
-        H = hfn(SW, SH, D, D)
-        Ms = np.stack([wl.jitter_H(H, i) for i in range(B)])
+    for hname, _, Ms in arms.footprints():
         minv = torch.from_numpy(warp.invert_homography(Ms)).to(dev)
         pinhole = warp.build_warp_map(Ms[0], (D, D))
-        lens = warp.build_warp_map(Ms[0], (D, D), K=K, dist_coeff=LENS_A)
+        lens = arms.lens_map(Ms[0], dev)
         torch.cuda.synchronize()
         k = [0]
 
@@ -109,15 +87,8 @@ def main():
                 st = remap(pinhole, _lib.INTER_LINEAR, warp.BORDER_REPLICATE, head)
             _lib.check(st)
 
-        for arm in ARMS:
-            for _ in range(warm):
-                launch(arm)
-        torch.cuda.synchronize()
-        t = {arm: [] for arm in ARMS}
-        for _ in range(rounds):
-            for arm in ARMS:
-                t[arm] += event_us(lambda: launch(arm), per_round)
-        q = {arm: [float(np.percentile(t[arm], v)) for v in (10, 50, 90)] for arm in ARMS}
+        t = arms.timed(ARMS, launch, rounds, per_round, warm)
+        q = arms.p10_50_90(t)
         for arm in ARMS:
             lines.append("%-9s %-18s p10 %8.1f  p50 %8.1f  p90 %8.1f us  (%d launches)" % (hname, arm, q[arm][0], q[arm][1], q[arm][2], len(t[arm])))
         p90, p10 = q["cubic_map_pinhole"][2], q["cubic_matrix"][0]
@@ -125,12 +96,7 @@ def main():
                      "(16 taps against 4)   cubic_map_lens / cubic_map_pinhole %5.2f"
                      % (hname, p90, "<=" if p90 <= p10 else ">", p10, "confirmed" if p90 <= p10 else "refuted", q["cubic_map_pinhole"][1] / q["cubic_matrix"][1],
                         q["cubic_map_pinhole"][1] / q["linear_map"][1], q["cubic_map_lens"][1] / q["cubic_map_pinhole"][1]))
-    text = "\n".join(lines)
-    print(text, flush=True)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    arms.finish(lines, a.out)
 
 
 if __name__ == "__main__":

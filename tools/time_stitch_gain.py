@@ -11,42 +11,33 @@ The calls go through bev_amd.warp with out=: the host runs ahead of the device a
 device time.  Derived: gained p90 against route p10 (the expectation DESIGN.md section 4.24 judges) and gained / plain (against the
 instruction-count prediction there).
 GPU box:  python tools/time_stitch_gain.py [--quick] [--out FILE]"""
-import argparse
-import os
-import sys
-
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from bev_amd import exposure, warp  # noqa: E402
-from tests import workloads as wl  # noqa: E402
+import arms
+from arms import B, D, LENS_A, SH, SW
+from bev_amd import exposure, warp
 
-LENS_A = (-0.30, 0.10, 0.001, -0.0005, -0.01)
 GAINS = [[1.25, 0.8, 1.0], [0.5, 2.0, 3.5], [1.7, 1.0, 0.3]]
+ARMS = ("plain", "gained", "route")
 
 
 def main():
-    p = argparse.ArgumentParser()
-    p.add_argument("--quick", action="store_true", help="a few launches per arm")
-    p.add_argument("--out", default=None, help="also write the table to this file")
-    a = p.parse_args()
-    B, SH, SW, D, N = 32, 1080, 1920, 1024, 3
-    rounds, per_round, warm = (2, 3, 2) if a.quick else (7, 10, 3)
+    a = arms.parser(__doc__).parse_args()
+    N = 3
+    rounds, per_round, warm = arms.counts(a.quick, (7, 10, 3))
     dev = torch.device("cuda", 0)
-    K = np.array([[0.8 * SW, 0, (SW - 1) / 2], [0, 0.816 * SW, (SH - 1) / 2 + 3], [0, 0, 1.0]])
-    H = wl.keystone_H(SW, SH, D, D)
+    _, H, _ = next(arms.footprints())  # (the keystone footprint)
     # the cameras look at thirds of the canvas that overlap: the keystone footprint shifted by -D / 3, 0, +D / 3
-    Ms = [np.array([[1.0, 0, (k - 1) * D / 3.0], [0, 1, 0], [0, 0, 1]]) @ H for k in range(N)]
-    maps = [warp.build_warp_map(M, (D, D), K=K, dist_coeff=LENS_A, device=dev) for M in Ms]
+    maps = [arms.lens_map(np.array([[1.0, 0, (k - 1) * D / 3.0], [0, 1, 0], [0, 0, 1]]) @ H, dev) for k in range(N)]
     G = exposure.quantize_gains(GAINS, N)
     nset = 2  # (2 x 3 x 199 MB of sources, 2 x 101 MB of canvases -- past the 256 MB Infinity Cache)
-    base = torch.from_numpy(np.stack([wl.frame(i, SH, SW, np.uint8) for i in range(B)])).to(dev)
+    base = arms.frame_set(0, dev)
     bgr = [[base.roll(shifts=(N * s + k) * 37 + 1, dims=2) for k in range(N)] for s in range(nset)]  # (the workload's frames, shifted per camera and set)
     ys = [[torch.randint(16, 236, (B, SH, SW), dtype=torch.uint8, device=dev) for _ in range(N)] for _ in range(nset)]
     uvs = [[torch.randint(16, 241, (B, SH // 2, SW // 2, 2), dtype=torch.uint8, device=dev) for _ in range(N)] for _ in range(nset)]
-    canvases = [torch.zeros((B, D, D, 3), dtype=torch.uint8, device=dev) for _ in range(nset)]
-    planes = [torch.zeros((B, 3, D, D), dtype=torch.float16, device=dev) for _ in range(nset)]
+    canvases = arms.dest_sets(nset, dev)
+    planes = arms.dest_sets(nset, dev, (B, 3, D, D), torch.float16)
     cover = [float(exposure.cover_mask(m, (SH, SW)).float().mean()) for m in maps]
     lines = ["# remap_stitch* with gains= (BEVWARP_STITCH_GAIN) vs the plain entry vs apply_gains + the plain entry; %d cameras x %d x %dx%d -> %d x %dx%d, bilinear, lens A %s; "
              "us per call" % (N, B, SW, SH, B, D, D, LENS_A),
@@ -67,33 +58,14 @@ def main():
             srcs = [exposure.apply_gains(bgr[i][c], G[c]) for c in range(N)] if arm == "route" else bgr[i]
             warp.remap_stitch(srcs, maps, blend="feather" if case == "bgr_feather64" else "over", feather=64, out=canvases[i], gains=gains)
 
-    arms = ("plain", "gained", "route")
     for case in ("bgr_over", "bgr_feather64", "nv12_planes"):
-        for arm in arms:
-            for _ in range(warm):
-                call(case, arm)
-        torch.cuda.synchronize()
-        t = {arm: [] for arm in arms}
-        for _ in range(rounds):
-            for arm in arms:
-                ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(per_round)]
-                for e0, e1 in ev:
-                    e0.record()
-                    call(case, arm)
-                    e1.record()
-                torch.cuda.synchronize()
-                t[arm] += [e0.elapsed_time(e1) * 1e3 for e0, e1 in ev]
-        q = {arm: [float(np.percentile(t[arm], v)) for v in (10, 50, 90)] for arm in arms}
-        for arm in arms:
+        t = arms.timed(ARMS, lambda arm: call(case, arm), rounds, per_round, warm)
+        q = arms.p10_50_90(t)
+        for arm in ARMS:
             lines.append("%-14s %-7s p10 %9.1f  p50 %9.1f  p90 %9.1f us  (%d calls)" % (case, arm, q[arm][0], q[arm][1], q[arm][2], len(t[arm])))
         lines.append("%-14s gained p90 %.1f %s route p10 %.1f   gained / plain %5.3f (p50)   route / gained %5.2f (p50)"
                      % (case, q["gained"][2], "<=" if q["gained"][2] <= q["route"][0] else ">", q["route"][0], q["gained"][1] / q["plain"][1], q["route"][1] / q["gained"][1]))
-    text = "\n".join(lines)
-    print(text, flush=True)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    arms.finish(lines, a.out)
 
 
 if __name__ == "__main__":
