@@ -70,7 +70,157 @@ def _by_value(v, n):
     return np.array(np.broadcast_to(np.asarray(v, dtype=np.float64), (n,)), dtype=np.float64, order="C")
 
 
-class FramePipeline:
+def _nv12(t, h, w):
+    """An NV12 frame in ONE (h * 3 / 2, w) byte buffer, the rows of (U, V) pairs behind the Y rows, as the C ABI takes it: (the Y plane's
+    address, the UV plane's), (frame and row stride of Y, frame and row stride of UV)."""
+    return (t.data_ptr(), t.data_ptr() + h * w), (0, w, 0, w)
+
+
+def _buffers(slot):
+    """A slot's input buffers (or their byte counts): FramePipeline has one per slot, SitePipeline a list of them (one per camera)."""
+    return slot if isinstance(slot, list) else [slot]
+
+
+class _Ring:
+    """What FramePipeline and SitePipeline both stand on: `depth` slots per stage, three private streams (upload, run, download) chained by
+    three rings of events, and the raw runtime calls of a slot's way through them -- each written once, here.  A class on it brings
+    self.device, depth, download (and zero_copy_out), _launch_py(slot, stream), _prepared(lib) and the nouns of its messages."""
+
+    zero_copy_out = False  # (the kernel stores into the pinned output slot; only FramePipeline has it)
+    _nouns = None  # of the "ring is full" message: the class, what is in flight, what is undelivered
+
+    def _allocate(self, in_shapes, in_dtype, out_shape, out_dtype):
+        """The pinned and the device slots.  in_shapes: one shape (h_in[slot], d_in[slot] are tensors) or a list of them (lists of tensors)."""
+        def inputs(**kw):
+            if isinstance(in_shapes, list):
+                return [torch.empty(shape, dtype=in_dtype, **kw) for shape in in_shapes]
+            return torch.empty(in_shapes, dtype=in_dtype, **kw)
+
+        self.h_in = [inputs(pin_memory=True) for _ in range(self.depth)]
+        self.d_in = [inputs(device=self.device) for _ in range(self.depth)]
+        self.d_out = [torch.empty(out_shape, dtype=out_dtype, device=self.device) for _ in range(self.depth)]
+        self.h_out = [torch.empty(out_shape, dtype=out_dtype, pin_memory=True) for _ in range(self.depth)] if self.download else None
+
+    def _open(self, streams, handles=None):
+        """The ring's own state: the three streams (kept alive, and drained by close(); `handles`: what the runtime calls take for them,
+        by default the torch streams' raw handles), an empty ring, and 3 * depth events."""
+        self._streams = list(streams)
+        self.s_up, self.s_run, self.s_down = handles or [ctypes.c_void_p(st.cuda_stream) for st in self._streams]
+        self.n_in = 0
+        self.pending = collections.deque()  # slots whose results have not been handed out yet
+        self.ev_up, self.ev_run, self.ev_down = [], [], []
+        self._closed = False  # (from here on close() has streams to drain and events to release, also when the rest of the construction raises)
+        hip = _hip_rt()
+        for evs in (self.ev_up, self.ev_run, self.ev_down):
+            for _ in range(self.depth):
+                e = ctypes.c_void_p()
+                _ok(hip.hipEventCreateWithFlags(ctypes.byref(e), 2))  # hipEventDisableTiming
+                evs.append(e)
+
+    def _start(self, *prepared):
+        """The constructors' tail, once the slots are there: the ring, every slot validated once through the Python layer, and one
+        prepared launch per slot -- the C ABI call with its arguments bound (`prepared`: what the class's builder takes besides)."""
+        self._open([torch.cuda.Stream(self.device) for _ in range(3)])
+        for slot in range(self.depth):
+            self._launch_py(slot, torch.cuda.current_stream(self.device))
+        torch.cuda.synchronize(self.device)
+        self._launch = self._prepared(_lib.load(), *prepared)
+        nbytes = [t.numel() * t.element_size() for t in _buffers(self.h_in[0])]
+        self._in_bytes = nbytes if isinstance(self.h_in[0], list) else nbytes[0]
+        self._out_bytes = self.d_out[0].numel() * self.d_out[0].element_size()
+
+    def close(self):
+        """Drain the three private streams, then release the events.  The device / pinned buffers were only ever handed to those
+        streams as raw addresses (torch does not know they are in use there), so they must not be freed before this."""
+        if getattr(self, "_closed", True):
+            return
+        self._closed = True
+        try:
+            for st in self._streams:
+                st.synchronize()
+            hip = _hip_rt()
+            for e in self.ev_up + self.ev_run + self.ev_down:
+                hip.hipEventDestroy(e)
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+    # -- input side
+    def next_inputs(self):
+        """The pinned host buffers (numpy views) the NEXT frame or set of frames should be decoded into, one per input buffer of the slot
+        -- a site: one per camera, (H_k, W_k, 3), or (H_k * 3 / 2, W_k) for NV12; call commit() when they are filled.  Blocks only if that
+        slot's previous occupant has not left the device yet."""
+        slot = self.n_in % self.depth
+        if self.n_in >= self.depth:
+            _ok((_hip or _hip_rt()).hipEventSynchronize((self.ev_down if self.download and not self.zero_copy_out else self.ev_run)[slot]))  # its previous occupant is through
+        bufs = self.h_in[slot]
+        return [t.numpy() for t in bufs] if isinstance(bufs, list) else [bufs.numpy()]
+
+    def commit(self):
+        """Upload, launch and (where there is a copy down) download what the next pinned slot holds.  Safe without a next_input(s)() call
+        before it: a slot is reused only after its result has been taken (the check below), and result() has then waited for the slot's
+        last launch or copy -- the event next_input(s)() waits for as well."""
+        if len(self.pending) >= self.depth:  # the slot about to be reused still holds a result nobody has taken
+            raise RuntimeError("%s: %d %s are in flight and none has been taken with result(); a ring of depth %d holds at most %d undelivered %s" % (
+                self._nouns[0], len(self.pending), self._nouns[1], self.depth, self.depth, self._nouns[2]))
+        hip = _hip or _hip_rt()
+        slot = self.n_in % self.depth
+        self.n_in += 1
+        s_up, s_run, ev_up, ev_run = self.s_up, self.s_run, self.ev_up[slot], self.ev_run[slot]
+        ds, hs, ns = self.d_in[slot], self.h_in[slot], self._in_bytes
+        if isinstance(ns, list):  # (a list of buffers per slot: one upload each)
+            for d, h, n in zip(ds, hs, ns):
+                _ok(hip.hipMemcpyAsync(d.data_ptr(), h.data_ptr(), n, _H2D, s_up))
+        else:
+            _ok(hip.hipMemcpyAsync(ds.data_ptr(), hs.data_ptr(), ns, _H2D, s_up))
+        _ok(hip.hipEventRecord(ev_up, s_up))
+        _ok(hip.hipStreamWaitEvent(s_run, ev_up, 0))
+        fn, args = self._launch[slot]
+        _lib.check(fn(*args))
+        _ok(hip.hipEventRecord(ev_run, s_run))
+        if self.download and not self.zero_copy_out:
+            s_down = self.s_down
+            _ok(hip.hipStreamWaitEvent(s_down, ev_run, 0))
+            _ok(hip.hipMemcpyAsync(self.h_out[slot].data_ptr(), self.d_out[slot].data_ptr(), self._out_bytes, _D2H, s_down))
+            _ok(hip.hipEventRecord(self.ev_down[slot], s_down))
+        self.pending.append(slot)
+
+    # -- output side
+    def ready(self):
+        return len(self.pending)
+
+    def result(self):
+        """The oldest frame's BEV (set's canvas): a numpy view of a pinned slot (download=True; valid until `depth` further ones have been
+        committed; bfloat16 planes: the pinned tensor itself) or the device tensor.  Blocks until it is through."""
+        slot = self.pending.popleft()
+        _ok((_hip or _hip_rt()).hipEventSynchronize((self.ev_down if self.download and not self.zero_copy_out else self.ev_run)[slot]))
+        if not self.download:
+            return self.d_out[slot]
+        h = self.h_out[slot]
+        return h if h.dtype == torch.bfloat16 else h.numpy()  # (numpy has no bfloat16)
+
+    def run(self, frames):
+        """Generator over an iterable of decoded frames (a site: of N-tuples of them): yields their BEV frames (canvases) in order,
+        keeping depth - 1 of them in flight."""
+        for f in frames:
+            if len(self.pending) >= self.depth - 1:
+                yield self.result()
+            self.submit(f)
+        while self.pending:
+            yield self.result()
+
+
+class FramePipeline(_Ring):
+    _nouns = ("FramePipeline", "frames", "frames")
+
     def __init__(self, src_hw, channels, M, dsize, flags=_warp.INTER_LINEAR, depth=3, dtype=torch.uint8, planar=False, scale=1.0 / 255.0, bias=0.0,
                  download=True, device="cuda", zero_copy_out=True, plane_dtype=torch.float32, src_format="bgr", dst_format="bgr", warp_map=None, map_interpolation=None):
         """src_hw (H, W) of the decoded frames; M the forward homography (as for warpPerspective); dsize (u_size, v_size).
@@ -151,111 +301,47 @@ class FramePipeline:
         out_shape = (self.C, self.dh, self.dw) if planar else (self.dh, self.dw, self.C)
         if self.nv12_out:
             out_shape = (self.dh * 3 // 2, self.dw)
-        out_dtype = plane_dtype if planar else dtype
-        in_shape = (self.H * 3 // 2, self.W) if self.nv12 else (self.H, self.W, self.C)
-        self.h_in = [torch.empty(in_shape, dtype=dtype, pin_memory=True) for _ in range(depth)]
-        self.d_in = [torch.empty(in_shape, dtype=dtype, device=self.device) for _ in range(depth)]
-        self.d_out = [torch.empty(out_shape, dtype=out_dtype, device=self.device) for _ in range(depth)]
-        self.h_out = [torch.empty(out_shape, dtype=out_dtype, pin_memory=True) for _ in range(depth)] if download else None
+        self._allocate((self.H * 3 // 2, self.W) if self.nv12 else (self.H, self.W, self.C), dtype, out_shape, plane_dtype if planar else dtype)
         self.minv = None if warp_map is not None else _warp.device_inverse(M, self.device, inverse_given=bool(int(flags) & _warp.WARP_INVERSE_MAP))
-        self._streams = [torch.cuda.Stream(self.device) for _ in range(3)]  # (kept alive: their raw handles are used below)
-        self.s_up, self.s_run, self.s_down = (ctypes.c_void_p(st.cuda_stream) for st in self._streams)
-        hip = _hip_rt()
+        self._start()
 
-        def events():
-            evs = []
-            for _ in range(depth):
-                e = ctypes.c_void_p()
-                _ok(hip.hipEventCreateWithFlags(ctypes.byref(e), 2))  # hipEventDisableTiming
-                evs.append(e)
-            return evs
-
-        self.ev_up, self.ev_run, self.ev_down = events(), events(), events()
-        # one prepared launch per slot: the C ABI call with its arguments bound (validated once, here, through the Python layer)
-        for slot in range(depth):
-            self._launch_py(slot, torch.cuda.current_stream(self.device))
-        torch.cuda.synchronize(self.device)
-        interp = int(flags) & 7
-        esz = self.d_in[0].element_size()
-        lib = _lib.load()
-        self._launch = []
-        for slot in range(depth):
+    def _prepared(self, lib):
+        """[(the C ABI function, its arguments)] per slot.  An NV12 side is one buffer (_nv12); an interleaved side gives its address and
+        its frame and row strides -- in bytes, which for the 8-bit entries are their elements."""
+        H, W, dh, dw, C, m = self.H, self.W, self.dh, self.dw, self.C, self.warp_map
+        interp, nv = int(self.flags) & 7, (self.nv12, self.nv12_out)
+        self._keep = [_by_value(self.scale, C), _by_value(self.bias, C)] if self.planar else []  # (host arrays the prepared launches point into)
+        launches = []
+        for slot in range(self.depth):
             s, d = self.d_in[slot], (self.h_out[slot] if self.zero_copy_out else self.d_out[slot])  # (pinned host memory is device-addressable)
-            if warp_map is not None and (self.nv12 or self.nv12_out):  # (one buffer per NV12 side: the (U, V) rows follow the Y rows)
-                src = (s.data_ptr(), s.data_ptr() + self.H * self.W) if self.nv12 else (s.data_ptr(),)
-                dst = (d.data_ptr(), d.data_ptr() + self.dh * self.dw) if self.nv12_out else (d.data_ptr(),)
-                src_strides = (0, self.W, 0, self.W) if self.nv12 else (s.numel(), s.stride(0))
-                dst_strides = (0, self.dw, 0, self.dw) if self.nv12_out else (d.numel(), d.stride(0))
-                maps = warp_map._planes()[:2] + (1,) + warp_map._planes()[2:] + (warp_map.interp, _warp.BORDER_CONSTANT)
-                args = src + dst + (1, self.H, self.W, self.dh, self.dw) + src_strides + dst_strides + maps
-                if self.nv12 and self.nv12_out:
-                    self._launch.append((lib.bevwarp_remap_nv12_to_nv12, args + (None, self.s_run)))
-                else:  # (rgb_order 0: the frames on the interleaved side are B, G, R)
-                    self._launch.append((lib.bevwarp_remap_nv12 if self.nv12 else lib.bevwarp_remap_to_nv12, args + (0, None, self.s_run)))
-            elif warp_map is not None:
-                args = (s.data_ptr(), d.data_ptr(), 1, self.H, self.W, self.dh, self.dw, self.C, s.numel() * esz, s.stride(0) * esz, d.numel() * esz,
-                        d.stride(0) * esz) + warp_map._planes()[:2] + (1,) + warp_map._planes()[2:] + (_warp._DTYPES[s.dtype], self._map_interp,
-                                                                                                     _warp.BORDER_CONSTANT, None, self.s_run)
-                self._launch.append((lib.bevwarp_remap, args))
-            elif self.nv12_out:  # (one buffer per side: the (U, V) rows follow the Y rows)
-                dst = (d.data_ptr(), d.data_ptr() + self.dh * self.dw)
-                tail = (self.minv.data_ptr(), 1, interp)
-                if self.nv12:
-                    args = (s.data_ptr(), s.data_ptr() + self.H * self.W) + dst + (1, self.H, self.W, self.dh, self.dw, 0, self.W, 0, self.W, 0, self.dw, 0,
-                                                                                 self.dw) + tail + (None, self.s_run)
-                    self._launch.append((lib.bevwarp_warp_nv12_to_nv12, args))
+            esz, dsz = s.element_size(), d.element_size()
+            src, src_strides = _nv12(s, H, W) if self.nv12 else ((s.data_ptr(),), (s.numel() * esz, s.stride(0) * esz))
+            dst, dst_strides = _nv12(d, dh, dw) if self.nv12_out else ((d.data_ptr(),), (d.numel() * dsz, d.stride(0) * dsz))
+            head, strides = src + dst + (1, H, W, dh, dw), src_strides + dst_strides
+            order = () if all(nv) else (0,)  # (rgb_order 0: the frames on the interleaved side are B, G, R)
+            if m is not None:
+                maps = m._planes()[:2] + (1,) + m._planes()[2:]
+                if any(nv):
+                    fn = {(True, True): lib.bevwarp_remap_nv12_to_nv12, (True, False): lib.bevwarp_remap_nv12, (False, True): lib.bevwarp_remap_to_nv12}[nv]
+                    args = head + strides + maps + (m.interp, _warp.BORDER_CONSTANT) + order + (None, self.s_run)
                 else:
-                    args = (s.data_ptr(),) + dst + (1, self.H, self.W, self.dh, self.dw, s.numel() * esz, s.stride(0) * esz, 0, self.dw, 0, self.dw) + tail + (
-                        0, None, self.s_run)
-                    self._launch.append((lib.bevwarp_warp_to_nv12, args))
-            elif self.nv12:  # (one buffer: the (U, V) rows follow the Y rows)
-                args = (s.data_ptr(), s.data_ptr() + self.H * self.W, d.data_ptr(), 1, self.H, self.W, self.dh, self.dw, 0, self.W, 0, self.W, d.numel(),
-                        d.stride(0), self.minv.data_ptr(), 1, interp, 0, None, self.s_run)
-                self._launch.append((lib.bevwarp_warp_nv12, args))
-            elif planar:
-                sc, bi = _by_value(scale, self.C), _by_value(bias, self.C)
-                self._keep = getattr(self, "_keep", []) + [sc, bi]
-                psz = d.element_size()
-                args = (s.data_ptr(), d.data_ptr(), 1, self.H, self.W, self.dh, self.dw, self.C, s.numel() * esz, s.stride(0) * esz, d.numel() * psz,
-                        d.stride(0) * psz, d.stride(1) * psz, self.minv.data_ptr(), 1, _warp._DTYPES[s.dtype], interp, None,
-                        sc.ctypes.data_as(ctypes.c_void_p), bi.ctypes.data_as(ctypes.c_void_p))
-                if plane_dtype == torch.float32:
-                    self._launch.append((lib.bevwarp_warp_planar, args + (self.s_run,)))
+                    fn = lib.bevwarp_remap
+                    args = head + (C,) + strides + maps + (_warp._DTYPES[s.dtype], self._map_interp, _warp.BORDER_CONSTANT, None, self.s_run)
+            elif any(nv):
+                fn = {(True, True): lib.bevwarp_warp_nv12_to_nv12, (True, False): lib.bevwarp_warp_nv12, (False, True): lib.bevwarp_warp_to_nv12}[nv]
+                args = head + strides + (self.minv.data_ptr(), 1, interp) + order + (None, self.s_run)
+            elif self.planar:
+                sc, bi = (a.ctypes.data_as(ctypes.c_void_p) for a in self._keep)
+                args = head + (C,) + strides + (d.stride(1) * dsz, self.minv.data_ptr(), 1, _warp._DTYPES[s.dtype], interp, None, sc, bi)
+                if self.plane_dtype == torch.float32:
+                    fn, args = lib.bevwarp_warp_planar, args + (self.s_run,)
                 else:
-                    self._launch.append((lib.bevwarp_warp_planes, args + (_warp._PLANE_DTYPES[plane_dtype], self.s_run)))
+                    fn, args = lib.bevwarp_warp_planes, args + (_warp._PLANE_DTYPES[self.plane_dtype], self.s_run)
             else:
-                args = (s.data_ptr(), d.data_ptr(), 1, self.H, self.W, self.dh, self.dw, self.C, s.numel() * esz, s.stride(0) * esz, d.numel() * esz,
-                        d.stride(0) * esz, self.minv.data_ptr(), 1, _warp._DTYPES[s.dtype], interp, None, self.s_run)
-                self._launch.append((lib.bevwarp_warp, args))
-        self._in_bytes = self.h_in[0].numel() * esz
-        self._out_bytes = self.d_out[0].numel() * self.d_out[0].element_size()
-        self.n_in = 0
-        self.pending = collections.deque()  # slots whose results have not been handed out yet
-        self._closed = False
-
-    def close(self):
-        """Drain the three private streams, then release the events.  The device / pinned buffers were only ever handed to those
-        streams as raw addresses (torch does not know they are in use there), so they must not be freed before this."""
-        if getattr(self, "_closed", True):
-            return
-        self._closed = True
-        try:
-            for st in self._streams:
-                st.synchronize()
-            hip = _hip_rt()
-            for e in self.ev_up + self.ev_run + self.ev_down:
-                hip.hipEventDestroy(e)
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        self.close()
+                fn = lib.bevwarp_warp
+                args = head + (C,) + strides + (self.minv.data_ptr(), 1, _warp._DTYPES[s.dtype], interp, None, self.s_run)
+            launches.append((fn, args))
+        return launches
 
     def _launch_py(self, slot, stream):
         """The same launch through bev_amd.warp (argument validation; used once per slot at construction)."""
@@ -281,33 +367,10 @@ class FramePipeline:
             else:
                 _warp.warp_perspective(self.d_in[slot], None, (self.dw, self.dh), flags=self.flags, out=self.d_out[slot], M_inv_device=self.minv)
 
-    # -- input side
     def next_input(self):
         """The pinned host buffer (numpy view; HWC, or (H * 3 / 2, W) for NV12) the NEXT frame should be decoded into; call commit() when it is filled.
-        Blocks only if that slot's previous frame has not left the device yet."""
-        slot = self.n_in % self.depth
-        if self.n_in >= self.depth:
-            _ok(_hip_rt().hipEventSynchronize((self.ev_down if self.download and not self.zero_copy_out else self.ev_run)[slot]))  # its previous occupant is through
-        return self.h_in[slot].numpy()
-
-    def commit(self):
-        if len(self.pending) >= self.depth:  # the slot about to be reused still holds a result nobody has taken
-            raise RuntimeError("FramePipeline: %d frames are in flight and none has been taken with result(); a ring of depth %d "
-                               "holds at most %d undelivered frames" % (len(self.pending), self.depth, self.depth))
-        hip = _hip_rt()
-        slot = self.n_in % self.depth
-        self.n_in += 1
-        _ok(hip.hipMemcpyAsync(self.d_in[slot].data_ptr(), self.h_in[slot].data_ptr(), self._in_bytes, _H2D, self.s_up))
-        _ok(hip.hipEventRecord(self.ev_up[slot], self.s_up))
-        _ok(hip.hipStreamWaitEvent(self.s_run, self.ev_up[slot], 0))
-        fn, args = self._launch[slot]
-        _lib.check(fn(*args))
-        _ok(hip.hipEventRecord(self.ev_run[slot], self.s_run))
-        if self.download and not self.zero_copy_out:
-            _ok(hip.hipStreamWaitEvent(self.s_down, self.ev_run[slot], 0))
-            _ok(hip.hipMemcpyAsync(self.h_out[slot].data_ptr(), self.d_out[slot].data_ptr(), self._out_bytes, _D2H, self.s_down))
-            _ok(hip.hipEventRecord(self.ev_down[slot], self.s_down))
-        self.pending.append(slot)
+        Blocks only if that slot's previous frame has not left the device yet.  (next_inputs(): the same buffer, in a list of one.)"""
+        return self.next_inputs()[0]
 
     def submit(self, frame):
         """A decoded frame from pageable memory (numpy HWC): copied into the next pinned slot, then committed."""
@@ -315,35 +378,13 @@ class FramePipeline:
         np.copyto(buf, np.asarray(frame).reshape(buf.shape))
         self.commit()
 
-    # -- output side
-    def ready(self):
-        return len(self.pending)
 
-    def result(self):
-        """The oldest frame's BEV: a numpy view of a pinned slot (download=True; valid until `depth` further frames have been
-        committed; bfloat16 planes: the pinned tensor itself) or the device tensor.  Blocks until that frame is through."""
-        slot = self.pending.popleft()
-        if self.download:
-            _ok(_hip_rt().hipEventSynchronize((self.ev_run if self.zero_copy_out else self.ev_down)[slot]))
-            h = self.h_out[slot]
-            return h if h.dtype == torch.bfloat16 else h.numpy()  # (numpy has no bfloat16)
-        _ok(_hip_rt().hipEventSynchronize(self.ev_run[slot]))
-        return self.d_out[slot]
-
-    def run(self, frames):
-        """Generator over an iterable of decoded frames: yields their BEV frames in order, keeping depth - 1 frames in flight."""
-        for f in frames:
-            if len(self.pending) >= self.depth - 1:
-                yield self.result()
-            self.submit(f)
-        while self.pending:
-            yield self.result()
-
-
-class SitePipeline:
+class SitePipeline(_Ring):
     """FramePipeline's ingest / egress ring for a site of fixed cameras: every committed SET of frames -- one per camera -- is uploaded,
     stitched through the cameras' warp maps into one canvas by ONE launch, and downloaded, on three private streams with `depth` slots
     per stage.  Results are the resident call's (bev_amd.warp.remap_stitch*), bit for bit: the same kernel runs on the same bytes."""
+
+    _nouns = ("SitePipeline", "sets of frames", "results")
 
     def __init__(self, src_hws, warp_maps, dsize, blend="over", feather=64, border_value=None, depth=3, src_format="bgr", dst_format="bgr", scale=1.0 / 255.0,
                  bias=0.0, plane_dtype=torch.float32, rgb=False, download=True, device="cuda", gains=None):
@@ -408,94 +449,53 @@ class SitePipeline:
         in_shapes = [(h * 3 // 2, w) if self.nv12 else (h, w, 3) for h, w in src_hws]
         out_shape = {"bgr": (dh, dw, 3), "nv12": (dh * 3 // 2, dw), "planes": (3, dh, dw)}[dst_format]
         out_dtype = plane_dtype if dst_format == "planes" else torch.uint8
-        self.h_in = [[torch.empty(shape, dtype=torch.uint8, pin_memory=True) for shape in in_shapes] for _ in range(depth)]  # [slot][camera]
-        self.d_in = [[torch.empty(shape, dtype=torch.uint8, device=self.device) for shape in in_shapes] for _ in range(depth)]
-        self.d_out = [torch.empty(out_shape, dtype=out_dtype, device=self.device) for _ in range(depth)]
-        self.h_out = [torch.empty(out_shape, dtype=out_dtype, pin_memory=True) for _ in range(depth)] if download else None
-        self._streams = [torch.cuda.Stream(self.device) for _ in range(3)]  # (kept alive: their raw handles are used below)
-        self.s_up, self.s_run, self.s_down = (ctypes.c_void_p(st.cuda_stream) for st in self._streams)
-        hip = _hip_rt()
-        self.ev_up, self.ev_run, self.ev_down = [], [], []
-        self._closed = False  # (from here on close() has events to release, also when the rest of the construction raises)
-        for evs in (self.ev_up, self.ev_run, self.ev_down):
-            for _ in range(depth):
-                e = ctypes.c_void_p()
-                _ok(hip.hipEventCreateWithFlags(ctypes.byref(e), 2))  # hipEventDisableTiming
-                evs.append(e)
-        # one prepared launch per slot: the C ABI call with its arguments bound (validated once, here, through the Python layer)
-        for slot in range(depth):
-            self._launch_py(slot, torch.cuda.current_stream(self.device))
-        torch.cuda.synchronize(self.device)
-        lib = _lib.load()
-        bv, sc, bi = host["border_value"], host["scale"], host["bias"]
-        self._keep = [bv, sc, bi]  # (host arrays and camera tables the prepared launches point into)
-        ptr = lambda a: None if a is None else a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
-        interp, blend_id, f = warp_maps[0].interp, _warp._BLENDS[blend] | gain_flag, (int(feather) if blend == "feather" else 0)
-        self._launch, self._cams = [], []
-        for slot in range(depth):
+        self._allocate(in_shapes, torch.uint8, out_shape, out_dtype)  # (h_in, d_in: [slot][camera])
+        self._keep = [host["border_value"], host["scale"], host["bias"]]  # (host arrays the prepared launches point into)
+        self._start(gain_flag, words)
+        # (`blend` stands behind the interpolation in all six argument lists: set_gains rewrites it)
+        self._blend_at = {"nv12": 12, "planes": 10}.get(dst_format, 9 if self.nv12 else 11)
+        assert all(args[self._blend_at] == _warp._BLENDS[blend] | gain_flag and args[self._blend_at - 1] == warp_maps[0].interp for _, args in self._launch)
+
+    def _prepared(self, lib, gain_flag, words):
+        """[(the C ABI function, its arguments)] per slot, and in _cams the slot's camera table, which the arguments point into."""
+        dh, dw, rgb = self.dh, self.dw, int(self.rgb)
+        bv, sc, bi = (None if a is None else a.ctypes.data_as(ctypes.c_void_p) for a in self._keep)
+        blend = (self.warp_maps[0].interp, _warp._BLENDS[self.blend] | gain_flag, self.feather if self.blend == "feather" else 0)
+        launches, self._cams = [], []
+        for ins, d in zip(self.d_in, self.d_out):
             cams = (_lib.MapCamera * self.n_cams)()
-            for cam, s, (h, w), m in zip(cams, self.d_in[slot], src_hws, warp_maps):
-                if self.nv12:  # (one buffer: the (U, V) rows follow the Y rows)
-                    cam.src, cam.uv, cam.frame_stride, cam.row_stride, cam.uv_frame_stride, cam.uv_row_stride = s.data_ptr(), s.data_ptr() + h * w, 0, w, 0, w
+            for cam, s, (h, w), m in zip(cams, ins, self.src_hws, self.warp_maps):
+                if self.nv12:
+                    (cam.src, cam.uv), (cam.frame_stride, cam.row_stride, cam.uv_frame_stride, cam.uv_row_stride) = _nv12(s, h, w)
                 else:
                     cam.src, cam.uv, cam.frame_stride, cam.row_stride = s.data_ptr(), None, s.numel(), s.stride(0)
                 cam.src_h, cam.src_w = h, w
                 _warp._fill_map_camera(cam, m)
             _warp._set_gain_words(cams, words)
             self._cams.append(cams)
-            d = self.d_out[slot]
             head = (ctypes.addressof(cams), self.n_cams)
-            if dst_format == "nv12":  # (one buffer: the (U, V) rows follow the Y rows)
-                args = head + (d.data_ptr(), d.data_ptr() + dh * dw, 1, dh, dw, 0, dw, 0, dw, interp, blend_id, f)
+            if self.dst_format == "nv12":
+                dst, strides = _nv12(d, dh, dw)
+                args = head + dst + (1, dh, dw) + strides + blend
                 if self.nv12:
-                    self._launch.append((lib.bevwarp_stitch_maps_nv12_to_nv12, args + (ptr(bv), self.s_run)))
+                    launches.append((lib.bevwarp_stitch_maps_nv12_to_nv12, args + (bv, self.s_run)))
                 else:
-                    self._launch.append((lib.bevwarp_stitch_maps_to_nv12, args + (1 if rgb else 0, ptr(bv), self.s_run)))
-            elif dst_format == "planes":
+                    launches.append((lib.bevwarp_stitch_maps_to_nv12, args + (rgb, bv, self.s_run)))
+            elif self.dst_format == "planes":
                 psz = d.element_size()
-                args = head + (d.data_ptr(), 1, dh, dw, d.numel() * psz, d.stride(0) * psz, d.stride(1) * psz, interp, blend_id, f)
-                tail = (ptr(bv), ptr(sc), ptr(bi), _warp._PLANE_DTYPES[plane_dtype], self.s_run)
+                args = head + (d.data_ptr(), 1, dh, dw, d.numel() * psz, d.stride(0) * psz, d.stride(1) * psz) + blend
+                tail = (bv, sc, bi, _warp._PLANE_DTYPES[self.plane_dtype], self.s_run)
                 if self.nv12:
-                    self._launch.append((lib.bevwarp_stitch_maps_nv12_planes, args + (1 if rgb else 0,) + tail))
+                    launches.append((lib.bevwarp_stitch_maps_nv12_planes, args + (rgb,) + tail))
                 else:
-                    self._launch.append((lib.bevwarp_stitch_maps_planes, args + tail))
+                    launches.append((lib.bevwarp_stitch_maps_planes, args + tail))
             elif self.nv12:
-                args = head + (d.data_ptr(), 1, dh, dw, d.numel(), d.stride(0), interp, blend_id, f, 1 if rgb else 0, _warp.BORDER_CONSTANT, ptr(bv), self.s_run)
-                self._launch.append((lib.bevwarp_stitch_maps_nv12, args))
+                args = head + (d.data_ptr(), 1, dh, dw, d.numel(), d.stride(0)) + blend + (rgb, _warp.BORDER_CONSTANT, bv, self.s_run)
+                launches.append((lib.bevwarp_stitch_maps_nv12, args))
             else:
-                args = head + (d.data_ptr(), 1, dh, dw, 3, d.numel(), d.stride(0), _lib.U8, interp, blend_id, f, _warp.BORDER_CONSTANT, ptr(bv), self.s_run)
-                self._launch.append((lib.bevwarp_stitch_maps, args))
-        # (`blend` stands behind the interpolation in all six argument lists: set_gains rewrites it)
-        self._blend_at = {"nv12": 12, "planes": 10}.get(dst_format, 9 if self.nv12 else 11)
-        assert all(args[self._blend_at] == blend_id and args[self._blend_at - 1] == interp for _, args in self._launch)
-        self._in_bytes = [t.numel() for t in self.h_in[0]]
-        self._out_bytes = self.d_out[0].numel() * self.d_out[0].element_size()
-        self.n_in = 0
-        self.pending = collections.deque()  # slots whose results have not been handed out yet
-
-    def close(self):
-        """Drain the three private streams, then release the events.  The device / pinned buffers were only ever handed to those
-        streams as raw addresses (torch does not know they are in use there), so they must not be freed before this."""
-        if getattr(self, "_closed", True):
-            return
-        self._closed = True
-        try:
-            for st in self._streams:
-                st.synchronize()
-            hip = _hip_rt()
-            for e in self.ev_up + self.ev_run + self.ev_down:
-                hip.hipEventDestroy(e)
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        self.close()
+                args = head + (d.data_ptr(), 1, dh, dw, 3, d.numel(), d.stride(0), _lib.U8) + blend + (_warp.BORDER_CONSTANT, bv, self.s_run)
+                launches.append((lib.bevwarp_stitch_maps, args))
+        return launches
 
     def set_gains(self, gains):
         """New per-camera gains (as the constructor's `gains`; None: none) for every set of frames committed from now on: the gain words
@@ -528,38 +528,6 @@ class SitePipeline:
             else:
                 _warp.remap_stitch(self.d_in[slot], self.warp_maps, **kw)
 
-    # -- input side
-    def next_inputs(self):
-        """The pinned host buffers (numpy views, one per camera: (H_k, W_k, 3), or (H_k * 3 / 2, W_k) for NV12) the NEXT set of frames
-        should be decoded into; call commit() when they are filled.  Blocks only if that slot's previous set has not left the device yet."""
-        slot = self.n_in % self.depth
-        if self.n_in >= self.depth:
-            _ok(_hip_rt().hipEventSynchronize((self.ev_down if self.download else self.ev_run)[slot]))  # its previous occupant is through
-        return [t.numpy() for t in self.h_in[slot]]
-
-    def commit(self):
-        """Upload, stitch and (download=True) download the set in the next pinned slots.  Safe without a next_inputs() call before it: a
-        slot is reused only after its result has been taken (the check below), and result() has then waited for the slot's last launch
-        or copy -- the event next_inputs() waits for as well."""
-        if len(self.pending) >= self.depth:  # the slot about to be reused still holds a result nobody has taken
-            raise RuntimeError("SitePipeline: %d sets of frames are in flight and none has been taken with result(); a ring of depth %d "
-                               "holds at most %d undelivered results" % (len(self.pending), self.depth, self.depth))
-        hip = _hip_rt()
-        slot = self.n_in % self.depth
-        self.n_in += 1
-        for d, h, n in zip(self.d_in[slot], self.h_in[slot], self._in_bytes):
-            _ok(hip.hipMemcpyAsync(d.data_ptr(), h.data_ptr(), n, _H2D, self.s_up))
-        _ok(hip.hipEventRecord(self.ev_up[slot], self.s_up))
-        _ok(hip.hipStreamWaitEvent(self.s_run, self.ev_up[slot], 0))
-        fn, args = self._launch[slot]
-        _lib.check(fn(*args))
-        _ok(hip.hipEventRecord(self.ev_run[slot], self.s_run))
-        if self.download:
-            _ok(hip.hipStreamWaitEvent(self.s_down, self.ev_run[slot], 0))
-            _ok(hip.hipMemcpyAsync(self.h_out[slot].data_ptr(), self.d_out[slot].data_ptr(), self._out_bytes, _D2H, self.s_down))
-            _ok(hip.hipEventRecord(self.ev_down[slot], self.s_down))
-        self.pending.append(slot)
-
     def submit(self, frames):
         """One decoded frame per camera from pageable memory (numpy): copied into the next pinned slots, then committed."""
         bufs = self.next_inputs()
@@ -568,27 +536,3 @@ class SitePipeline:
         for buf, frame in zip(bufs, frames):
             np.copyto(buf, np.asarray(frame).reshape(buf.shape))
         self.commit()
-
-    # -- output side
-    def ready(self):
-        return len(self.pending)
-
-    def result(self):
-        """The oldest set's canvas: a numpy view of a pinned slot (download=True; valid until `depth` further sets have been committed;
-        bfloat16 planes: the pinned tensor itself) or the device tensor.  Blocks until that set is through."""
-        slot = self.pending.popleft()
-        if self.download:
-            _ok(_hip_rt().hipEventSynchronize(self.ev_down[slot]))
-            h = self.h_out[slot]
-            return h if h.dtype == torch.bfloat16 else h.numpy()  # (numpy has no bfloat16)
-        _ok(_hip_rt().hipEventSynchronize(self.ev_run[slot]))
-        return self.d_out[slot]
-
-    def run(self, frame_sets):
-        """Generator over an iterable of N-tuples of decoded frames: yields their canvases in order, keeping depth - 1 sets in flight."""
-        for frames in frame_sets:
-            if len(self.pending) >= self.depth - 1:
-                yield self.result()
-            self.submit(frames)
-        while self.pending:
-            yield self.result()

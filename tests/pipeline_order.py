@@ -1,8 +1,8 @@
 """The order in which FramePipeline's and SitePipeline's work reaches the device, for tests/test_gpu_pipeline_order.py and
 tests/test_pipeline_order_cpu.py -- TEST INFRASTRUCTURE ONLY, a plain module like tests/launch_contexts.py: no fixtures, no conftest.
 
-Both classes build their own stream graph: three private streams (upload, run, download), three rings of events, raw hipMemcpyAsync /
-hipEventRecord / hipStreamWaitEvent / hipEventSynchronize.  Four edges per slot carry the correctness -- the launch waits for the upload,
+Both classes stand on one ring (bev_amd.pipeline._Ring), which builds its own stream graph: three private streams (upload, run,
+download), three rings of events, raw hipMemcpyAsync / hipEventRecord / hipStreamWaitEvent / hipEventSynchronize.  Four edges per slot carry the correctness -- the launch waits for the upload,
 the download waits for the launch, result() waits for the slot's last event, next_input(s)() waits before the host overwrites a pinned slot
 -- and close() has to drain the streams.  On idle streams a frame of a few KB is through before the host issues its next call, so every one
 of those waits could be missing, or name the other slot's event, and a test that pushes frames through idle streams would still pass.

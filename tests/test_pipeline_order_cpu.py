@@ -2,13 +2,15 @@
 tests/test_launch_contexts_cpu.py.  This stands where a GPU mutation run would: nothing on the GPU removes an edge.
 
 The code under test is the PRODUCTION commit(), result(), next_input(s)(), submit(), run(), close() and set_gains() of
-bev_amd.pipeline.FramePipeline and SitePipeline.  The objects are made without their constructors (which need a device) and given CPU
-tensors; bev_amd.pipeline._hip is replaced for the length of a test by a stand-in runtime:
+bev_amd.pipeline.FramePipeline and SitePipeline -- one body each, in the ring both classes stand on.  The objects are made without their
+constructors (which need a device): they are given CPU tensors as slots, and the ring's own opener (_open) makes the rest from queue
+streams; bev_amd.pipeline._hip is replaced for the length of a test by a stand-in runtime:
 
   a stream                is a queue of deferred operations; nothing runs when it is enqueued
   hipMemcpyAsync          a deferred copy of the bytes between the two addresses
   the prepared launch     a deferred byte function of the slot's device inputs (stand_in), of the host values and of the gain words --
                           those two read when the launch is CALLED, as the library reads its host pointers and the camera table
+  hipEventCreateWithFlags the handle the opener made becomes an event that was never recorded
   hipEventRecord          a marker in the stream's queue; a re-recorded event means its latest record, one never recorded is complete
   hipStreamWaitEvent      captures the event's latest record
   hipEventSynchronize     runs the minimal set of queued operations the record depends on: its stream up to the marker, and, for each wait
@@ -20,7 +22,6 @@ tensors; bev_amd.pipeline._hip is replaced for the length of a test by a stand-i
 With the honest runtime every check passes on every configuration.  Then one call at a time is taken out of the runtime -- the wait of
 s_run, the wait of s_down, the synchronise in result(), the synchronise in next_input(s)(), the record of ev_run, the stream synchronise in
 close() -- and the host-value copy is reverted: each must fail its named check with an AssertionError."""
-import collections
 import ctypes
 import sys
 
@@ -51,6 +52,8 @@ class _Wait:
 
 
 class _Event:
+    """An event of the runtime's own tests below.  A pipeline's events are the ctypes handles its opener made, given this class's `latest`
+    by hipEventCreateWithFlags."""
     latest = None  # (never recorded: complete)
 
 
@@ -88,6 +91,11 @@ class Runtime:
         self.removed, self.calls = removed, 0
 
     # -- the calls
+    def hipEventCreateWithFlags(self, ref, flags):
+        self.calls += 1
+        ref._obj.latest = _Event.latest  # (the opener's own handle is the event)
+        return 0
+
     def hipMemcpyAsync(self, dst, src, nbytes, kind, stream):
         self.calls += 1
         stream.queue.append(lambda: ctypes.memmove(dst, src, nbytes))
@@ -228,15 +236,13 @@ class CpuConfig:
         p.d_out = [u8(OUT_SHAPE) for _ in range(DEPTH)]
         p.h_out = [u8(OUT_SHAPE) for _ in range(DEPTH)] if self.download else None
         p._out_bytes = p.d_out[0].numel()
-        p._streams = [_Stream(rt, name) for name in ("s_up", "s_run", "s_down")]
-        p.s_up, p.s_run, p.s_down = p._streams
-        p.ev_up, p.ev_run, p.ev_down = ([_Event() for _ in range(DEPTH)] for _ in range(3))
+        streams = [_Stream(rt, name) for name in ("s_up", "s_run", "s_down")]
+        p._open(streams, streams)  # (the ring as the constructors open it: a queue is its own handle)
         # the host arrays the prepared launches point into, as the constructors make them: through the production helper
         values = dict(self.host_values(), **(host or {})) if self.has_host else {}
         p._keep = [pipeline._by_value(values[name], 3) for name in ("scale", "bias", "border_value") if name in values]
         # one prepared launch per slot: (callable, arguments); a site's arguments hold `blend` at _blend_at, which set_gains rewrites
         p._launch = [(self._launcher(p, slot), (slot, _lib.STITCH_FEATHER)) for slot in range(DEPTH)]
-        p.n_in, p.pending, p._closed = 0, collections.deque(), False
         if self.site:
             p.n_cams, p.blend, p.gains, p._blend_at = N_CAMS, "feather", None, 1
             p._cams = [(_lib.MapCamera * N_CAMS)() for _ in range(DEPTH)]
@@ -394,10 +400,13 @@ def test_a_view_of_the_callers_array_fails_the_host_values(monkeypatch, config):
 
 
 def test_the_constructors_go_through_the_copy():
-    """Both constructors make their host arrays with _by_value and with nothing else (the stand-in objects above are filled the same way)."""
+    """Both constructors make their host arrays with _by_value and with nothing else (the stand-in objects above are filled the same way):
+    SitePipeline in __init__, FramePipeline in the builder of its prepared launches, which __init__ runs once per pipeline -- outside
+    the loop over the slots."""
     import inspect
     for cls, n in ((pipeline.FramePipeline, 2), (pipeline.SitePipeline, 1)):
-        text = inspect.getsource(cls.__init__)
+        text = inspect.getsource(cls.__init__) + inspect.getsource(cls._prepared)
+        assert "_by_value(" not in text[text.index("\n        for ", text.index("def _prepared")):], cls.__name__
         assert text.count("_by_value(") == n and "ascontiguousarray" not in text, cls.__name__
         assert "by value" in cls.__init__.__doc__
 
