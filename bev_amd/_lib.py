@@ -124,6 +124,7 @@ class MapCamera(_c.Structure):
 
 STITCH_OVER, STITCH_FEATHER, STITCH_MAX_CAMERAS = 0, 1, 8
 MAP_BICUBIC = 0x200  # BEVWARP_MAP_BICUBIC, ORed into `interp` of bevwarp_remap alone: a bilinear map sampled bicubically
+SUPERSAMPLE_2, SUPERSAMPLE_4, SUPERSAMPLE_8 = 0x1000, 0x2000, 0x3000  # BEVWARP_SUPERSAMPLE_*, ORed into `interp` of bevwarp_warp_border alone
 STITCH_GAIN = 0x100  # BEVWARP_STITCH_GAIN, ORed into `blend` of the six stitches through maps: MapCamera.reserved is then the gain word
 
 _lib = None

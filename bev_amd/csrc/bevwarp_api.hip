@@ -24,6 +24,7 @@
 #include "warp_stitch_maps.h"
 #include "warp_stitch_maps_nv12_out.h"
 #include "warp_stitch_maps_planes.h"
+#include "warp_supersample.h"
 
 #pragma clang fp contract(off)
 
@@ -61,13 +62,15 @@ void fill_source(Args& a, const Image& s) {
 int plane_kind(int plane_dtype) { return plane_dtype == BEVWARP_F32 ? kPlaneF32 : (plane_dtype == BEVWARP_F16 ? kPlaneF16 : kPlaneBF16); }
 // What the flat-grid entry points (border, bicubic, NV12, NV12 planes, into NV12) share: the checks, plan_border's grid, and in the zeroed
 // arguments the shared frame's part (flat_frame.h) -- the first written image, the matrices, the grid -- and the source's sides.
-// items = 0: nothing to launch, the status is the call's.  (dst_vec_ok follows each entry point's own layout rule.)
+// items = 0: nothing to launch, the status is the call's.  (dst_vec_ok follows each entry point's own layout rule.)  A supersampled call
+// (c.supersample > 1) takes plan_supersample's grid: the same items, the fine grid's evaluation blocks.
 template <class Args>
 int flat_grid_args(const Call& c, Args& a, int64_t& items) {
     items = 0;
     const int st = plan::check_call(c);
     if (st != BEVWARP_OK || c.batch == 0) return st;
-    const TilePlan p = plan::plan_border(c.batch, c.dst_h, c.dst_w, kBorderTileW, kBorderTileH);
+    const TilePlan p = c.supersample > 1 ? plan::plan_supersample(c.batch, c.dst_h, c.dst_w, kBorderTileW, kBorderTileH, c.supersample)
+                                         : plan::plan_border(c.batch, c.dst_h, c.dst_w, kBorderTileW, kBorderTileH);
     if (p.status != BEVWARP_OK) return p.status;
     memset(&a, 0, sizeof(a));
     const Image& d = c.writes[0].im;
@@ -297,6 +300,30 @@ int warp_impl(const Call& c, int channels, int dtype, int interp, const double* 
     }
     return launched(launch_warp(a, dtype, channels, interp, (hipStream_t)stream));
 }
+// bevwarp_warp_border under BEVWARP_SUPERSAMPLE_* (c: plan::supersample_call, k = c.supersample): the border kernel's arguments, the border
+// pixel of the constant border, and the fine matrix's two constants
+int supersample_impl(const Call& c, int channels, int dtype, int interp, int border_mode, const double* border_value, void* stream) {
+    SupersampleArgs a;
+    int64_t items;
+    const int st = flat_grid_args(c, a, items);
+    if (!items) return st;
+    fill_source(a, c.reads[0].im);
+    const bool constant = border_mode == BEVWARP_BORDER_CONSTANT;
+    if (!constant) {
+        const plan::BorderPeriod px = plan::border_period(border_mode, c.src_w), py = plan::border_period(border_mode, c.src_h);
+        a.per_x = px.per, a.off_x = px.off, a.mag_x = px.mag;
+        a.per_y = py.per, a.off_y = py.off, a.mag_y = py.mag;
+    }
+    uint8_t bu[4];  // (border_value is read by the constant border only)
+    if (border_values(constant ? border_value : nullptr, channels, a.bv_f, bu) != BEVWARP_OK) return BEVWARP_ERR_NOT_FINITE;
+    a.bv_u8 = packed4(bu);
+    const int k = c.supersample;
+    a.log2k = k == 2 ? 1 : (k == 4 ? 2 : 3);
+    a.inv_k = 1.0 / k, a.centre = (1.0 - k) / (2.0 * k);
+    a.dst_vec_ok = plan::wide_stores_ok(c.writes[0], plan::store_align(dtype, channels, false));
+    a.src_vec_ok = plan::pixel_loads_ok(c.reads[0].im, plan::pixel_load_align(dtype, channels));
+    return launched(launch_warp_supersample(a, dtype, channels, interp, border_mode, items, (hipStream_t)stream));
+}
 }  // namespace
 
 extern "C" {
@@ -315,11 +342,18 @@ int bevwarp_warp(const void* src, void* dst, int batch, int src_h, int src_w, in
 int bevwarp_warp_border(const void* src, void* dst, int batch, int src_h, int src_w, int dst_h, int dst_w, int channels,
                         int64_t src_frame_stride, int64_t src_row_stride, int64_t dst_frame_stride, int64_t dst_row_stride, const double* M_inv,
                         int m_count, int dtype, int interp, int border_mode, const double* border_value, void* stream) {
+    const int k = plan::take_supersample(interp);
+    if (k > 1) {  // the supersampled warp: a kernel of its own for all five borders it has, the constant one included
+        if (!plan::border_mode_known(border_mode)) return BEVWARP_ERR_UNSUPPORTED;
+        return supersample_impl(plan::supersample_call({src, src_frame_stride, src_row_stride}, {dst, dst_frame_stride, dst_row_stride},
+                                                       {batch, src_h, src_w, dst_h, dst_w, m_count, M_inv}, channels, dtype, interp, border_mode, k),
+                                channels, dtype, interp, border_mode, border_value, stream);
+    }
     const bool cubic = interp == BEVWARP_CUBIC;
     if (border_mode == BEVWARP_BORDER_CONSTANT && !cubic)  // the constant border is bevwarp_warp itself
         return bevwarp_warp(src, dst, batch, src_h, src_w, dst_h, dst_w, channels, src_frame_stride, src_row_stride, dst_frame_stride, dst_row_stride,
                             M_inv, m_count, dtype, interp, border_value, stream);
-    if (border_mode < BEVWARP_BORDER_CONSTANT || border_mode > BEVWARP_BORDER_TRANSPARENT) return BEVWARP_ERR_UNSUPPORTED;  // (BORDER_ISOLATED too)
+    if (!plan::border_mode_known(border_mode)) return BEVWARP_ERR_UNSUPPORTED;  // (BORDER_ISOLATED too)
     // (border_value is read by no mode but the constant one, as in OpenCV)
     const Call c = plan::warp_call({src, src_frame_stride, src_row_stride}, {dst, dst_frame_stride, dst_row_stride}, {batch, src_h, src_w, dst_h, dst_w, m_count, M_inv},
                                    channels, dtype, interp, true);

@@ -124,6 +124,7 @@ struct Call : Sizes {
     int n_reads, n_writes;
     ReadImage reads[4];
     WrittenImage writes[2];
+    int supersample;  // k of a supersampled call (supersample_call), whose fine grid has sides of their own to judge; 0: none
 
     void read(const Image& im, int cols, int elem) { reads[n_reads++] = {im, cols, elem, false}; }
     void read_map(const Image& im, int elem) { reads[n_reads++] = {im, 0, elem, true}; }
@@ -189,6 +190,9 @@ inline int source_sizes_status(const Call& c) {
     int st = BEVWARP_OK;
     for (int i = 0; i < c.n_reads && st == BEVWARP_OK; i++)
         if (!c.reads[i].map) st = source_size_status(c.reads[i].im, c.reads[i].cols);
+    // (a supersampled call: the fine grid's columns and rows are ints of the coordinate walk)
+    if (st == BEVWARP_OK && c.supersample > 1 && ((int64_t)c.supersample * c.dst_w > 0x7fffffffLL || (int64_t)c.supersample * c.dst_h > 0x7fffffffLL))
+        st = BEVWARP_ERR_TOO_LARGE;
     return st;
 }
 // Every written image against every read one, and the written ones against each other; read images may overlap each other.  An image of
@@ -228,6 +232,23 @@ inline Call warp_call(Frames src, Frames dst, const Sizes& z, int channels, int 
         c.write_planes(dst.image(z.dst_h, (uint64_t)z.dst_w * plane_elem, z.batch), plane_elem, channels, dst_ps);
     else
         c.write(dst.image(z.dst_h, (uint64_t)z.dst_w * channels * elem, z.batch), elem);
+    return c;
+}
+// The border modes bevwarp_warp_border knows (OpenCV's BORDER_ISOLATED bit is none of them): asked before every other check of that entry.
+inline bool border_mode_known(int border_mode) { return border_mode >= BEVWARP_BORDER_CONSTANT && border_mode <= BEVWARP_BORDER_TRANSPARENT; }
+// BEVWARP_SUPERSAMPLE_2 / _4 / _8 in the `interp` word of bevwarp_warp_border (and of no other entry): the 2-bit field is taken out of the
+// word, take_fisheye_flag's way, and every check then sees the word as it always did.  Returns k = 1, 2, 4 or 8; 1: the call is today's.
+inline int take_supersample(int& word) {
+    const int k = 1 << (((unsigned)word & (unsigned)BEVWARP_SUPERSAMPLE_MASK) >> 12);
+    word &= ~BEVWARP_SUPERSAMPLE_MASK;
+    return k;
+}
+// bevwarp_warp_border under the field (k > 1, border_mode known): bevwarp_warp's images and formats without bicubic and without the
+// transparent border, and a fine grid of k dst_w x k dst_h pixels, whose sides source_sizes_status judges.  interp: without the field.
+inline Call supersample_call(Frames src, Frames dst, const Sizes& z, int channels, int dtype, int interp, int border_mode, int k) {
+    Call c = warp_call(src, dst, z, channels, dtype, interp, false);
+    c.format_ok = c.format_ok && border_mode != BEVWARP_BORDER_TRANSPARENT;
+    c.supersample = k;
     return c;
 }
 // bevwarp_warp_lens: bevwarp_warp's images and formats without bicubic, with the constant and the transparent border
@@ -486,6 +507,16 @@ inline TilePlan plan_border(int batch, int dst_h, int dst_w, int tw, int th) {
     if (p.total_tiles > 0x7fffffffLL) return p;
     p.tpf_magic = div_magic((uint64_t)p.total_tiles, (uint32_t)p.tiles_per_frame);
     p.status = BEVWARP_OK;
+    return p;
+}
+
+// The supersampled warp (warp_supersample.hip): plan_border's grid over the DESTINATION, while the evaluation blocks -- bw0 and its magic --
+// are those of the k times finer grid the sub-samples are defined on.  A lane walks fine columns below k (dst_w + tw).
+inline TilePlan plan_supersample(int batch, int dst_h, int dst_w, int tw, int th, int k) {
+    TilePlan p = plan_border(batch, dst_h, dst_w, tw, th);
+    if (p.status != BEVWARP_OK) return p;
+    p.bw0 = block_width(k * dst_w, k * dst_h);
+    p.bw0_magic = div_magic((uint64_t)k * ((uint64_t)dst_w + tw), (uint32_t)p.bw0);
     return p;
 }
 

@@ -8,8 +8,9 @@
 namespace bevwarp {
 namespace {
 
-template <typename T, int C>
-__device__ __forceinline__ Pixel<T, C> border_pixel(const LensArgs& a) {
+// (Args: kernel arguments with the source's sides and strides and the border pixel bv_u8 / bv_f -- LensArgs, or the supersampled warp's)
+template <typename T, int C, class Args>
+__device__ __forceinline__ Pixel<T, C> border_pixel(const Args& a) {
     Pixel<T, C> p;
     if constexpr (sizeof(T) == 1) {
         p.packed = a.bv_u8;
@@ -32,8 +33,8 @@ __device__ __forceinline__ Pixel<T, C> sample_inside(const uint8_t* __restrict__
 // The constant border: a tap inside the frame is its pixel, a tap outside -- every tap of an invalid pixel -- the border pixel; a pixel
 // whose four taps are all outside is the border value itself.  Every tap is loaded from the CLAMPED position (always a source pixel, also
 // for the lanes past the row's end) and replaced afterwards, so the loads are unconditional and all issue before the first wait.
-template <typename T, int C, int INTERP>
-__device__ __forceinline__ Pixel<T, C> sample_guarded(const LensArgs& a, const uint8_t* __restrict__ frame, int sx, int sy, int fx, int fy, bool valid, bool vec) {
+template <typename T, int C, int INTERP, class Args>
+__device__ __forceinline__ Pixel<T, C> sample_guarded(const Args& a, const uint8_t* __restrict__ frame, int sx, int sy, int fx, int fy, bool valid, bool vec) {
     const Pixel<T, C> b = border_pixel<T, C>(a);
     const int w = a.src_w, h = a.src_h;
     const bool xin0 = (unsigned)sx < (unsigned)w, yin0 = (unsigned)sy < (unsigned)h;

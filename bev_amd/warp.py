@@ -353,6 +353,49 @@ def warp_perspective(src, M, dsize, flags=INTER_LINEAR, border_value=None, out=N
     return _like_src(d4, src.dim(), out)
 
 
+_SUPERSAMPLE = {2: _lib.SUPERSAMPLE_2, 4: _lib.SUPERSAMPLE_4, 8: _lib.SUPERSAMPLE_8}  # factor -> the field of the ABI's interp word
+_SUPERSAMPLE_BORDERS = (BORDER_CONSTANT, BORDER_REPLICATE, BORDER_REFLECT, BORDER_WRAP, BORDER_REFLECT_101)
+
+
+def warp_perspective_supersampled(src, M, dsize, supersample=2, flags=INTER_LINEAR, border_value=None, out=None, M_inv_device=None,
+                                  border_mode=BORDER_CONSTANT):
+    """warp_perspective with `supersample`^2 samples per destination pixel, in one pass: what warping into a BEV `supersample` times as
+    large on each side and box-filtering it down is for, where the far half of the view is minified several times over and one sample per
+    pixel aliases -- without the large frames in memory (include/bevwarp.h, BEVWARP_SUPERSAMPLE_*).  Each pixel is the average of the
+    k x k pixels warp_perspective itself would write at the centres of the k x k fine pixels it covers: 8-bit (sum + k^2 / 2) >> 2 log2 k,
+    float32 summed in float32 rows outermost and multiplied by 1 / k^2.  Bit-equal to that two-pass route.
+
+    src, M, dsize, border_value, out, M_inv_device   as warp_perspective.
+    supersample   1, 2, 4 or 8; 1 IS warp_perspective(src, M, dsize, ...).  Anything else: ValueError.
+    flags    INTER_LINEAR (default) or INTER_NEAREST, optionally | WARP_INVERSE_MAP; INTER_CUBIC: ValueError.
+    border_mode   BORDER_CONSTANT (default), BORDER_REPLICATE, BORDER_REFLECT, BORDER_WRAP or BORDER_REFLECT_101; BORDER_TRANSPARENT:
+             ValueError (a pixel that is partly written has no average).
+    For supersample > 1 an identity M does not return src: every pixel is a small box filter of its neighbourhood (the sub-samples sit
+    off the pixel's centre).  The cost is about supersample^2 times warp_perspective's with a source-reading border.  No verdict tables, no
+    plan cache.  Asynchronous on the current stream."""
+    if isinstance(supersample, bool) or supersample not in (1, 2, 4, 8):
+        raise ValueError("warp_perspective_supersampled: supersample must be 1, 2, 4 or 8, got %r" % (supersample,))
+    k = int(supersample)
+    if k == 1:
+        return warp_perspective(src, M, dsize, flags=flags, border_value=border_value, out=out, M_inv_device=M_inv_device, border_mode=border_mode)
+    if border_mode not in _SUPERSAMPLE_BORDERS:
+        raise ValueError("unsupported border mode %r (warp_perspective_supersampled: BORDER_CONSTANT, _REPLICATE, _REFLECT, _WRAP, _REFLECT_101)" % (border_mode,))
+    border_mode = int(border_mode)
+    interp = _interp("warp_perspective_supersampled", flags)
+    dw, dh = int(dsize[0]), int(dsize[1])
+    if k * dw > 0x7fffffff or k * dh > 0x7fffffff:
+        raise ValueError("warp_perspective_supersampled: the fine grid %d x %d has a side beyond 2^31 - 1" % (k * dw, k * dh))
+    s4, _ = _frames("warp_perspective_supersampled", src, _DTYPES)
+    B, H, W, C = s4.shape
+    esz = s4.element_size()
+    M_inv_device, n_m = _matrices(M, flags, M_inv_device, s4.device, B)
+    d4 = _pixel_dst(out, s4.dtype, s4.device, B, dh, dw, C)
+    bv = _border(border_value, C) if border_mode == BORDER_CONSTANT else None
+    _lib.launch("bevwarp_warp_border", s4.device, s4.data_ptr(), d4.data_ptr(), B, H, W, dh, dw, C, s4.stride(0) * esz, s4.stride(1) * esz, d4.stride(0) * esz,
+                d4.stride(1) * esz, M_inv_device.data_ptr(), n_m, _DTYPES[s4.dtype], interp | _SUPERSAMPLE[k], border_mode, _ptr(bv))
+    return _like_src(d4, src.dim(), out)
+
+
 def _intrinsics(K):
     """(fx, fy, cx, cy) of a 3x3 or 3x4 camera matrix without skew."""
     K = np.asarray(K, dtype=np.float64)

@@ -213,6 +213,44 @@ int bevwarp_warp_border(const void *src, void *dst, int batch, int src_h, int sr
                         const double *border_value /*HOST*/, void *stream);
 
 /*
+ * BEVWARP_SUPERSAMPLE_2 / _4 / _8: the supersampled warp, a 2-bit field ORed into `interp` of bevwarp_warp_border -- and of no other
+ * entry: every other entry judges the whole word and refuses one that carries these bits.  The field is taken out of the word before any
+ * check; with the field 0 the call is the one described above, bit for bit and status for status.  With k = 1 << ((interp >> 12) & 3)
+ * in {2, 4, 8}, every destination pixel is the average of the k x k pixels that bevwarp_warp_border ITSELF writes on a k times finer
+ * grid: a BEV whose far half is minified several times over is sampled k^2 times per pixel instead of once, in one pass, with no fine
+ * frame in memory.  M_inv is the same device matrix as ever (destination pixel -> source pixel), m_count 1 or batch.  Every line below
+ * is one correctly rounded float64 operation, no FMA:
+ *   fine matrix   c = (1 - k) / (2 k), exact (-0.25, -0.375, -0.4375); for each row r of M_inv
+ *                     F[r][0] = M[r][0] / k,   F[r][1] = M[r][1] / k,   F[r][2] = (M[r][0] c + M[r][1] c) + M[r][2]:
+ *                 the centre of fine pixel (x', y') is the destination coordinate ((x' + 0.5) / k - 0.5, (y' + 0.5) / k - 0.5).
+ *   fine sample   s(x', y') = the pixel bevwarp_warp_border writes at (x', y') of a (k dst_w) x (k dst_h) destination with inverse matrix
+ *                 F and the call's interp, border_mode and border_value: the evaluation blocks of THAT grid (width
+ *                 min(1024 / min(16, k dst_h), k dst_w) -- no multiple of k in general, a pixel's sub-columns may lie in two blocks),
+ *                 32 / W, half-to-even rounding, NaN -> INT_MAX, int16 saturation, the 8-bit 15-bit blend and the float32 blend, and
+ *                 BEVWARP_BORDER_CONSTANT's "all four taps outside -> the border value itself".
+ *   reduce        8-bit, per channel: (sum of the k^2 sub-samples + k^2 / 2) >> (2 log2 k).
+ *                 float32: acc = s(k x, k y); then, rows outermost (j = 0..k-1, i = 0..k-1, the first skipped),
+ *                 acc = acc + s(k x + i, k y + j), each addition rounded to float32; the pixel is acc * (1 / k^2), one float32 multiply.
+ *                 NaN and +-inf propagate as IEEE says; denormals are not flushed.
+ *   formats       BEVWARP_U8 | BEVWARP_F32, 1-4 channels, BEVWARP_NEAREST | BEVWARP_LINEAR, and the five borders that write every
+ *                 pixel: CONSTANT (a mode of the supersampled kernel -- the call is NOT delegated to bevwarp_warp), REPLICATE, REFLECT,
+ *                 WRAP, REFLECT_101.  Under the field BEVWARP_CUBIC and BEVWARP_BORDER_TRANSPARENT are BEVWARP_ERR_UNSUPPORTED, judged
+ *                 where the format is judged; k dst_w or k dst_h beyond INT_MAX is BEVWARP_ERR_TOO_LARGE, judged where the source's
+ *                 size is judged.  Every other check and the checks' order are bevwarp_warp_border's: an unknown border_mode first,
+ *                 NULLs, sides, the format, m_count, strides, sizes, overlap, and a non-finite border_value last (CONSTANT only).
+ *                 batch == 0 is BEVWARP_OK and launches nothing.
+ * With k > 1 the identity matrix is NOT the identity image: the sub-samples sit at +-1/(2k), +-3/(2k), ... off the pixel's centre, so
+ * every pixel is a small box filter of its neighbourhood.  The ramp row 0, 32, ..., 224 under k = 2, bilinear, REPLICATE becomes
+ * 4, 32, 64, ..., 192, 220.
+ * Cost: k^2 times the coordinate chains and tap gathers of bevwarp_warp_border, against a fine frame set
+ * written once and read once by the two-pass route.
+ */
+#define BEVWARP_SUPERSAMPLE_2    0x1000
+#define BEVWARP_SUPERSAMPLE_4    0x2000
+#define BEVWARP_SUPERSAMPLE_8    0x3000
+#define BEVWARP_SUPERSAMPLE_MASK 0x3000      /* k = 1 << ((interp >> 12) & 3) */
+
+/*
  * The warp of frames as a distorted camera delivers them: the lens model is a step of the coordinate chain, and the raw frame is sampled
  * once.  Destination pixel -> normalised undistorted camera plane (M_ray) -> distorted image point (OpenCV's rational model: k1..k6, p1,
  * p2; no thin-prism or tilt terms; the fisheye model is BEVWARP_LENS_FISHEYE below) -> the taps and the blend of bevwarp_warp_border.  This is OUR chain, the natural extension
