@@ -60,18 +60,15 @@ void fill_source(Args& a, const Image& s) {
 }
 // the kernels' plane format of a plane type that the checks have let through
 int plane_kind(int plane_dtype) { return plane_dtype == BEVWARP_F32 ? kPlaneF32 : (plane_dtype == BEVWARP_F16 ? kPlaneF16 : kPlaneBF16); }
-// What the flat-grid entry points (border, bicubic, NV12, NV12 planes, into NV12) share: the checks, plan_border's grid, and in the zeroed
-// arguments the shared frame's part (flat_frame.h) -- the first written image, the matrices, the grid -- and the source's sides.
-// items = 0: nothing to launch, the status is the call's.  (dst_vec_ok follows each entry point's own layout rule.)  A supersampled call
-// (c.supersample > 1) takes plan_supersample's grid: the same items, the fine grid's evaluation blocks.
+// What the flat-grid entry points (border, bicubic, NV12, NV12 planes, into NV12) share: the checks and the grid (plan::flat_grid: st, p),
+// and in the zeroed arguments the shared frame's part (flat_frame.h) -- the first written image, the matrices, the grid -- and the source's
+// sides.  items = 0: nothing to launch, the status is the call's (c is not looked at where st is not BEVWARP_OK).  (dst_vec_ok follows each
+// entry point's own layout rule.)
 template <class Args>
-int flat_grid_args(const Call& c, Args& a, int64_t& items) {
+int flat_grid_args(const Call& c, int st, const TilePlan& p, Args& a, int64_t& items) {
     items = 0;
-    const int st = plan::check_call(c);
-    if (st != BEVWARP_OK || c.batch == 0) return st;
-    const TilePlan p = c.supersample > 1 ? plan::plan_supersample(c.batch, c.dst_h, c.dst_w, kBorderTileW, kBorderTileH, c.supersample)
-                                         : plan::plan_border(c.batch, c.dst_h, c.dst_w, kBorderTileW, kBorderTileH);
-    if (p.status != BEVWARP_OK) return p.status;
+    if (st != BEVWARP_OK) return st;
+    if (c.batch == 0 || p.status != BEVWARP_OK) return p.status;  // (an empty batch: p is zeros)
     memset(&a, 0, sizeof(a));
     const Image& d = c.writes[0].im;
     a.dst = (uint8_t*)d.base, a.minv = c.minv;
@@ -81,6 +78,12 @@ int flat_grid_args(const Call& c, Args& a, int64_t& items) {
     a.src_h = c.src_h, a.src_w = c.src_w;
     items = p.total_tiles;
     return BEVWARP_OK;
+}
+template <class Args>
+int flat_grid_args(const Call& c, Args& a, int64_t& items) {
+    TilePlan p;
+    const int st = plan::flat_grid(c, kBorderTileW, kBorderTileH, p);
+    return flat_grid_args(c, st, p, a, items);
 }
 // ... and the NV12 kernels' source: the two planes the call reads
 template <class Args>
@@ -123,16 +126,17 @@ int sampled_channel_table(Args& a, int rgb_order, int64_t dst_plane_stride, cons
     }
     return BEVWARP_OK;
 }
-// What the map samplers (bevwarp_remap and its NV12 kin) share: the checks, plan_remap's grid of items of frames_per_item frames, and in
-// the zeroed arguments the destination, the grid, the source's sides with the index remap of the border mode, and the map planes --
+// What the map samplers (bevwarp_remap and its NV12 kin) share: the checks and plan_remap's grid of items of frames_per_item frames
+// (plan::remap_grid), and in the zeroed arguments the destination, the grid, the source's sides with the index remap of the border mode,
+// and the map planes --
 // reads[first_map] and, bilinear, reads[first_map + 1].  items = 0: nothing to launch, the status is the call's.
 template <class Args>
 int remap_grid_args(const Call& c, Args& a, int first_map, int interp, int border_mode, int64_t& items) {
     items = 0;
-    const int st = plan::check_call(c);
-    if (st != BEVWARP_OK || c.batch == 0) return st;
-    const RemapPlan p = plan::plan_remap(c.batch, c.m_count, c.dst_h, c.dst_w, kBorderTileW, kBorderTileH, kRemapMaxFramesPerItem, plan::kRemapFillItems);
-    if (p.status != BEVWARP_OK) return p.status;
+    RemapPlan p;
+    const int st = plan::remap_grid(c, kBorderTileW, kBorderTileH, kRemapMaxFramesPerItem, plan::kRemapFillItems, p);
+    if (st != BEVWARP_OK) return st;
+    if (c.batch == 0 || p.status != BEVWARP_OK) return p.status;  // (an empty batch: p is zeros)
     memset(&a, 0, sizeof(a));
     const Image& d = c.writes[0].im;
     a.dst = (uint8_t*)d.base, a.dst_fs = d.fs, a.dst_rs = d.rs, a.dst_h = c.dst_h, a.dst_w = c.dst_w;
@@ -300,12 +304,12 @@ int warp_impl(const Call& c, int channels, int dtype, int interp, const double* 
     }
     return launched(launch_warp(a, dtype, channels, interp, (hipStream_t)stream));
 }
-// bevwarp_warp_border under BEVWARP_SUPERSAMPLE_* (c: plan::supersample_call, k = c.supersample): the border kernel's arguments, the border
-// pixel of the constant border, and the fine matrix's two constants
-int supersample_impl(const Call& c, int channels, int dtype, int interp, int border_mode, const double* border_value, void* stream) {
+// bevwarp_warp_border under BEVWARP_SUPERSAMPLE_* (c, st, p: plan::supersample_grid's; k = c.supersample): the border kernel's arguments,
+// the border pixel of the constant border, and the fine matrix's two constants
+int supersample_impl(const Call& c, int checked, const TilePlan& p, int channels, int dtype, int interp, int border_mode, const double* border_value, void* stream) {
     SupersampleArgs a;
     int64_t items;
-    const int st = flat_grid_args(c, a, items);
+    const int st = flat_grid_args(c, checked, p, a, items);
     if (!items) return st;
     fill_source(a, c.reads[0].im);
     const bool constant = border_mode == BEVWARP_BORDER_CONSTANT;
@@ -344,10 +348,11 @@ int bevwarp_warp_border(const void* src, void* dst, int batch, int src_h, int sr
                         int m_count, int dtype, int interp, int border_mode, const double* border_value, void* stream) {
     const int k = plan::take_supersample(interp);
     if (k > 1) {  // the supersampled warp: a kernel of its own for all five borders it has, the constant one included
-        if (!plan::border_mode_known(border_mode)) return BEVWARP_ERR_UNSUPPORTED;
-        return supersample_impl(plan::supersample_call({src, src_frame_stride, src_row_stride}, {dst, dst_frame_stride, dst_row_stride},
-                                                       {batch, src_h, src_w, dst_h, dst_w, m_count, M_inv}, channels, dtype, interp, border_mode, k),
-                                channels, dtype, interp, border_mode, border_value, stream);
+        Call c;
+        TilePlan p;
+        const int st = plan::supersample_grid({src, src_frame_stride, src_row_stride}, {dst, dst_frame_stride, dst_row_stride},
+                                              {batch, src_h, src_w, dst_h, dst_w, m_count, M_inv}, channels, dtype, interp, border_mode, k, kBorderTileW, kBorderTileH, c, p);
+        return supersample_impl(c, st, p, channels, dtype, interp, border_mode, border_value, stream);
     }
     const bool cubic = interp == BEVWARP_CUBIC;
     if (border_mode == BEVWARP_BORDER_CONSTANT && !cubic)  // the constant border is bevwarp_warp itself

@@ -1,7 +1,7 @@
 // host_plan.h -- what the C ABI decides before a launch, as plain C++17 (no HIP): the argument checks and the launch geometry.
-// bevwarp_api.hip is its only user in the library; the drivers of tests/ (every *_plan_driver.cpp, the three map-stitch ones through
-// plan_driver_io.h) compile it with g++ under the address and undefined-behaviour sanitizers, and tests/golden/launch_plans.json pins
-// every field of the plans.  Not installed.
+// bevwarp_api.hip is its only user in the library; tests/host_plan_driver.cpp (one program, a family of case lines per entry-point group,
+// with tests/plan_driver_io.h) compiles it with g++ under the address and undefined-behaviour sanitizers, and
+// tests/golden/launch_plans.json pins every field of the plans.  Not installed.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -112,7 +112,7 @@ struct Nv12Images {
 inline Nv12Images nv12_images(Frames y, Frames uv, int h, int w, int batch) { return {y.image(h, (uint64_t)w, batch), uv.image(h / 2, (uint64_t)w, batch)}; }
 
 // What the checks need of one entry point's arguments.  The functions of the last part of this section describe the entry points in
-// these terms; bevwarp_api.hip and the tests' drivers (tests/*_plan_driver.cpp) build their calls with them.
+// these terms; bevwarp_api.hip and the tests' driver (tests/host_plan_driver.cpp) build their calls with them.
 struct Sizes {  // (what every entry point passes besides its images and its format)
     int batch, src_h, src_w, dst_h, dst_w, m_count;
     const double* minv;
@@ -546,6 +546,31 @@ inline RemapPlan plan_remap(int batch, int map_count, int dst_h, int dst_w, int 
     return p;
 }
 constexpr int64_t kRemapFillItems = 4096;  // (four rounds of 1024 resident 4-wave workgroups)
+
+// ---- an entry point's steps up to its grid: bevwarp_api.hip and the tests' driver both call these -----------------------------------------
+// The flat-grid entries (border, bicubic, lens, NV12, NV12 planes, into NV12): check_call's status, and in `p` the grid of tw x th tiles of a
+// call that goes on to a launch (BEVWARP_OK and batch > 0) -- plan_supersample's of a supersampled call, else plan_border's --, zeros of any
+// other.  The entry returns the status where it is not BEVWARP_OK, then p.status likewise.
+inline int flat_grid(const Call& c, int tw, int th, TilePlan& p) {
+    p = {};
+    const int st = check_call(c);
+    if (st == BEVWARP_OK && c.batch > 0) p = c.supersample > 1 ? plan_supersample(c.batch, c.dst_h, c.dst_w, tw, th, c.supersample) : plan_border(c.batch, c.dst_h, c.dst_w, tw, th);
+    return st;
+}
+// The map samplers (bevwarp_remap and its kin; c.m_count is the map count): the same with plan_remap's grid.
+inline int remap_grid(const Call& c, int tw, int th, int max_fpi, int64_t fill, RemapPlan& p) {
+    p = {};
+    const int st = check_call(c);
+    if (st == BEVWARP_OK && c.batch > 0) p = plan_remap(c.batch, c.m_count, c.dst_h, c.dst_w, tw, th, max_fpi, fill);
+    return st;
+}
+// bevwarp_warp_border under BEVWARP_SUPERSAMPLE_* (k > 1; interp: without the field): an unknown border mode is refused before every other
+// check, then flat_grid of supersample_call, which is left in `c`.
+inline int supersample_grid(Frames src, Frames dst, const Sizes& z, int channels, int dtype, int interp, int border_mode, int k, int tw, int th, Call& c, TilePlan& p) {
+    p = {};
+    if (!border_mode_known(border_mode)) return BEVWARP_ERR_UNSUPPORTED;
+    return flat_grid(c = supersample_call(src, dst, z, channels, dtype, interp, border_mode, k), tw, th, p);
+}
 
 // bevwarp_build_map: every check of the call, in the order include/bevwarp.h documents, and in `p` plan_border's grid over the m_count maps.
 // M, xy, frac are device pointers (never dereferenced), lens HOST or NULL.  interp: without BEVWARP_LENS_FISHEYE (take_fisheye_flag), which

@@ -25,6 +25,19 @@ def declared_symbols():
     return sorted(set(re.findall(r"\b(bevwarp_[a-z_0-9]+)\s*\(", text)))
 
 
+def checked_declaration(name, nargs, n64):
+    """An entry point is in the header, in _lib.SYMBOLS and exported by the built library, with `nargs` arguments, `n64` of them int64_t,
+    in the header and in the ctypes table alike.  Returns its declaration in include/bevwarp.h without the comments."""
+    assert name in declared_symbols() and name in _lib.SYMBOLS and getattr(ctypes.CDLL(_lib.LIB_PATH), name) is not None
+    assert len(_lib.SYMBOLS[name][1]) == nargs
+    with open(os.path.join(ROOT, "include", "bevwarp.h")) as f:
+        header = f.read()
+    decl = header[header.index("int %s(" % name):]
+    decl = re.sub(r"/\*.*?\*/", "", decl[:decl.index(";")])
+    assert decl.count(",") + 1 == nargs and decl.count("int64_t") == n64 == _lib.SYMBOLS[name][1].count(ctypes.c_int64), decl
+    return decl
+
+
 def test_every_declared_symbol_is_exported_and_bound(lib):
     names = declared_symbols()
     assert len(names) >= 8 and "bevwarp_warp" in names

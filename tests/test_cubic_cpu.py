@@ -2,7 +2,6 @@
 (tests/cubic_tab_driver.cpp, g++) against the reference bit for bit, the reference on images with known results, the C ABI's argument
 checks, the cv2-compatible constant, and the kernels' code object.  OpenCV's remapBicubic restated from memory: parity unpinned."""
 import ctypes
-import os
 import subprocess
 
 import numpy as np
@@ -13,8 +12,6 @@ from tests import border_ref as BR
 from tests import codeobj
 from tests import cubic_ref as CR
 from tests import hostplan
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 # ---- the tables of the reference ----
@@ -45,12 +42,10 @@ REACH = 32769
 @pytest.fixture(scope="module")
 def driver_output(tmp_path_factory):
     """(float entries, fixed entries, remapped indices [mode][n][p]) as cubic_tab.h computes them.
-    (-static-libasan: see tests/test_host_plan.py; -ffp-contract=off: the definition rounds after every multiply and add.)"""
+    (-ffp-contract=off: the definition rounds after every multiply and add.)"""
     tmp = tmp_path_factory.mktemp("cubic_tab")
-    exe, tables, remap = (str(tmp / n) for n in ("cubic_tab_driver", "tables.bin", "remap.bin"))
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-ffp-contract=off",
-                           "-Wall", "-Werror", "-I", os.path.join(ROOT, "bev_amd", "csrc"), "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cubic_tab_driver.cpp"), "-o", exe])
+    tables, remap = (str(tmp / n) for n in ("tables.bin", "remap.bin"))
+    exe = hostplan.build_driver(source="cubic_tab_driver.cpp", extra_flags=("-ffp-contract=off",))
     r = subprocess.run([exe, tables, remap], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and not r.stderr, (r.returncode, r.stderr[-3000:])
     raw = open(tables, "rb").read()

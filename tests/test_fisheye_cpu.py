@@ -1,6 +1,6 @@
 """The equidistant (fisheye) lens model (include/bevwarp.h, BEVWARP_LENS_FISHEYE) without a device: the definition's arctangent and the
 numpy reference (tests/fisheye_ref.py) against 40-digit arithmetic, the convergence of the inverse, the host helpers, the C ABI's host
-checks under the sanitizers (tests/fisheye_plan_driver.cpp) and through the built library, the Python entries' refusals, and the code
+checks under the sanitizers (tests/host_plan_driver.cpp, family `fisheye`) and through the built library, the Python entries' refusals, and the code
 objects of the three new kernel units."""
 import ctypes
 import os
@@ -184,7 +184,7 @@ def test_fisheye_valid_theta():
 
 @pytest.fixture(scope="module")
 def driver():
-    return hostplan.build_driver(source="fisheye_plan_driver.cpp")
+    return hostplan.build_driver()
 
 
 def _lens_line(lens=GOOD, theta_max=1.5):
@@ -203,7 +203,7 @@ def test_lens_status_under_sanitizers(driver):
     cases += [(_lens_line(theta_max=NAN), BAD_ARG), (_lens_line(theta_max=-1e-300), BAD_ARG), (_lens_line(theta_max=-INF), BAD_ARG)]
     # the order: NOT_FINITE before the BAD_ARGs of the values
     cases += [(_lens_line(_with(0, 0.0)[:5] + [NAN] + GOOD[6:]), NOT_FINITE), (_lens_line(_with(8, NAN), theta_max=-1.0), NOT_FINITE)]
-    got = hostplan.run_driver(driver, [c for c, _ in cases])
+    got = hostplan.run_driver(driver, [c for c, _ in cases], "fisheye")
     for (c, want), g in zip(cases, got):
         assert g == [want], (c, g, want)
 
@@ -249,9 +249,7 @@ def test_flag_and_calls_under_sanitizers(driver):
               (build(lens=0), [BAD_ARG, 0]), (build(lens=2, th="-1"), [NOT_FINITE, 0]), (build(lens=3), [BAD_ARG, 0]), (build(lens=4), [BAD_ARG, 0]),
               (build(th="nan"), [BAD_ARG, 0]), (build(th="-1"), [BAD_ARG, 0]), (build(th="inf"), [OK, 2]), (build(interp=1, lens=4), [OK, 2])]
     cases = flags + warps + pts + builds
-    got = hostplan.run_driver(driver, [c for c, _ in cases])
-    for (c, want), g in zip(cases, got):
-        assert g == want, (c, g, want)
+    hostplan.check_cases(driver, cases, "fisheye")
 
 
 # ---- the same statuses through the built library (fake pointers, never dereferenced: every call ends before a launch) ----

@@ -14,8 +14,6 @@ cases, `compare`, and the preconditions that keep a case from passing vacuously)
 
 Destinations are pre-filled with a signalling NaN (float_domain.CANVAS_BITS), so a pixel a launch must not write is known by its bits.
 Run on the GPU box:  python -m pytest tests -m gpu -q"""
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -29,7 +27,6 @@ from tests import remap_ref as RR
 
 pytestmark = [pytest.mark.gpu, pytest.mark.filterwarnings("ignore::RuntimeWarning")]  # (numpy's: the references compute 0 * Inf on purpose)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEAREST, LINEAR, INVERSE = FD.NEAREST, FD.LINEAR, 16
 BY_KIND = [(kind, interp) for interp in (NEAREST, LINEAR) for kind in FD.kinds(interp)]
 KIND_IDS = ["%s-%s" % (kind, ("nearest", "linear")[interp]) for kind, interp in BY_KIND]
@@ -106,12 +103,9 @@ def test_lens_border_value_with_a_nan_is_refused_and_nothing_is_written(W, inter
 # ---- 2. the map sampler ----
 
 @pytest.fixture(scope="module")
-def plan_driver(tmp_path_factory):
-    """tests/remap_plan_driver.cpp, built plainly (tests/test_remap_cpu.py runs it under the sanitizers)."""
-    exe = str(tmp_path_factory.mktemp("remap_plan_driver") / "remap_plan_driver")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "bev_amd", "csrc"), "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "remap_plan_driver.cpp"), "-o", exe])
-    return exe
+def plan_driver():
+    """tests/host_plan_driver.cpp, family `remap`, built plainly (tests/test_remap_cpu.py runs it under the sanitizers)."""
+    return hostplan.build_driver(sanitize=False)
 
 
 def _frames_per_item(plan_driver, B, sh, sw, dh, dw, c, interp, mode):
@@ -119,7 +113,7 @@ def _frames_per_item(plan_driver, B, sh, sw, dh, dw, c, interp, mode):
     frames per item, the library with fewer: both keep more than one under the same condition, the plan's first doubling."""
     line = "call 4096 %d %d %d %d %d %d %d %d %d %d %d %d %d 1 %d %d %d %d 1 %d %d" % (
         1 << 40, 1 << 44, 1 << 48, B, sh, sw, dh, dw, c, sh * sw * c * 4, sw * c * 4, dh * dw * c * 4, dw * c * 4, dh * dw * 4, dw * 4, dh * dw * 2, dw * 2, interp, mode)
-    status, plan_status, fpi, _ = hostplan.run_driver(plan_driver, [line])[0]
+    status, plan_status, fpi, _ = hostplan.run_driver(plan_driver, [line], "remap")[0]
     assert status == 0 and plan_status == 0, (line, status, plan_status)
     return fpi
 

@@ -286,7 +286,7 @@ def plan_driver():
     exe = hostplan.build_driver(sanitize=False)
 
     def plan(line):
-        r = subprocess.run([exe], input=line + "\n", capture_output=True, text=True, timeout=60, check=True)
+        r = subprocess.run([exe, "plan"], input=line + "\n", capture_output=True, text=True, timeout=60, check=True)
         v = [int(x) for x in r.stdout.split()]
         return dict(status=v[0], tile_h=v[1], tiles_x=v[2], tiles_per_frame=v[3], total_tiles=v[4], chunk=v[5], tpf_magic=v[9])
     return plan

@@ -877,7 +877,7 @@ def flat_plan():
     exe = hostplan.build_driver(sanitize=False)
 
     def plan(batch, dw):
-        r = subprocess.run([exe], input="border %d %d %d 256 4 %d %d %d\n" % (batch, DECODE_DH, dw, br.REPLICATE, lc.DECODE_SRC_HW[0], lc.DECODE_SRC_HW[1]),
+        r = subprocess.run([exe, "plan"], input="border %d %d %d 256 4 %d %d %d\n" % (batch, DECODE_DH, dw, br.REPLICATE, lc.DECODE_SRC_HW[0], lc.DECODE_SRC_HW[1]),
                            capture_output=True, text=True, timeout=60, check=True)
         v = [int(x) for x in r.stdout.split()]
         return dict(status=v[0], tile_h=v[1], tiles_per_frame=v[3], total_tiles=v[4], tpf_magic=v[9])
@@ -886,12 +886,12 @@ def flat_plan():
 
 @pytest.fixture(scope="module")
 def remap_plan():
-    """plan_remap (tests/remap_plan_driver.cpp, built plainly) with the library's bounds: at most BEVWARP_REMAP_MAX_FPI frames per item,
-    4096 items to fill."""
-    exe = hostplan.build_driver(sanitize=False, source="remap_plan_driver.cpp")
+    """plan_remap (tests/host_plan_driver.cpp's `remap` family, built plainly) with the library's bounds: at most BEVWARP_REMAP_MAX_FPI
+    frames per item, 4096 items to fill."""
+    exe = hostplan.build_driver(sanitize=False)
 
     def plan(batch, map_count, dw):
-        r = subprocess.run([exe], input="plan %d %d %d %d 2 4096\n" % (batch, map_count, DECODE_DH, dw), capture_output=True, text=True, timeout=60, check=True)
+        r = subprocess.run([exe, "remap"], input="plan %d %d %d %d 2 4096\n" % (batch, map_count, DECODE_DH, dw), capture_output=True, text=True, timeout=60, check=True)
         v = [int(x) for x in r.stdout.split()]
         return dict(status=v[0], frames_per_item=v[1], groups=v[2], total_tiles=v[3], covered=v[4])
     return plan

@@ -49,7 +49,7 @@ def plans_from_driver(exe, cases):
     kernels' constants are carried over from the fixture."""
     consts = launch_constants(load_fixture())
     out = []
-    for case, nums in zip(cases, run_driver(exe, [driver_line(c, consts) for c in cases])):
+    for case, nums in zip(cases, run_driver(exe, [driver_line(c, consts) for c in cases], "plan")):
         plan = None
         if nums[0] == 0 and case["kind"] == "border":
             plan = dict(zip(PLAN_FIELDS + PERIOD_FIELDS, nums[1:]), tw=256)
@@ -110,7 +110,7 @@ def test_plans_equal_the_recorded_ones(driver, lib):
     bevwarp_tile_classes_bytes of the built library is 12 bytes per tile of the same plan (or its status)."""
     fixture = load_fixture()
     consts = launch_constants(fixture)
-    got = run_driver(driver, [driver_line(c, consts) for c in fixture])
+    got = run_driver(driver, [driver_line(c, consts) for c in fixture], "plan")
     for case, nums in zip(fixture, got):
         assert nums[0] == case["status"], (case, nums)
         if case["plan"]:
@@ -152,15 +152,15 @@ def test_overlap_guard_under_the_sanitizer(driver):
         dbytes = {d0 + f * dfs + r * drs + c for f in range(batch) for r in range(dh) for c in range(dw)}
         lines.append("overlap %d %d %d %d %d %d %d %d %d %d %d" % (s0, sh, sw, srs, sfs, d0, dh, dw, drs, dfs, batch))
         truth.append(bool(sbytes & dbytes))
-    got = [bool(v[0]) for v in run_driver(driver, lines)]
+    got = [bool(v[0]) for v in run_driver(driver, lines, "plan")]
     assert all(g for g, t in zip(got, truth) if t)                 # no false negative
     assert sum(not g for g in got) > 300                           # and not simply refusing everything
-    assert run_driver(driver, ["overlap 4096 4 6 16 64 4102 4 6 16 64 2"]) == [[0]]  # side by side, interleaved bounding ranges
+    assert run_driver(driver, ["overlap 4096 4 6 16 64 4102 4 6 16 64 2"], "plan") == [[0]]  # side by side, interleaved bounding ranges
     top, imax = (1 << 64) - 1, (1 << 63) - 1
     edge = ["overlap %d 8 24 24 192 %d 8 24 24 192 4" % (top - 4096, top - 2048), "overlap %d 8 24 24 192 16 8 24 24 192 1" % (top - 100),
             "overlap 4096 32767 16 %d %d 8192 32767 16 %d %d 65535" % (imax, imax, imax, imax), "overlap 16 1 1 1 0 16 1 1 1 0 1",
             "overlap 4096 8 8 %d 0 4100 8 8 %d 0 1" % (1 << 62, 1 << 62), "overlap 0 1 1 1 1 %d 1 1 1 1 2147483647" % top]
-    assert len(run_driver(driver, edge)) == len(edge)
+    assert len(run_driver(driver, edge, "plan")) == len(edge)
 
 
 def test_layout_and_size_checks_at_their_limits(driver):
@@ -173,18 +173,18 @@ def test_layout_and_size_checks_at_their_limits(driver):
              ("size 32767 32767 %d 32767 32767 1" % ((1 << 24) - 1), -3), ("size 32767 32767 65539 32767 32767 1", -3), ("size 32767 32767 65538 32767 32767 1", 0),
              ("size 32768 8 8 32767 32767 1", -3), ("size 8 32768 8 32767 32767 1", -3), ("size 8 8 %d 32767 32767 1" % (1 << 24), -3),
              ("size 32767 8 %d 32767 32767 1" % imax, -3), ("size 2147483647 8 %d 2147483647 8 0" % imax, 0), ("size 65536 8 8 65535 16777216 0", -3)]
-    assert [v[0] for v in run_driver(driver, [c for c, _ in cases])] == [st for _, st in cases]
+    assert [v[0] for v in run_driver(driver, [c for c, _ in cases], "plan")] == [st for _, st in cases]
     # destination sides beyond the limit are refused before any arithmetic on them
     big = ["rows 1 8 2147483647 0 256 4 1024", "rows 2147483647 2147483647 2147483647 1 128 4 1024", "border 2147483647 2147483647 2147483647 256 4 2 1 32767",
            "rows 2147483647 1048576 1048576 1 128 4 1024", "border 2147483647 1048576 1048576 256 4 4 32767 32767"]
-    assert [v[0] for v in run_driver(driver, big)] == [TOO_LARGE] * len(big)
+    assert [v[0] for v in run_driver(driver, big, "plan")] == [TOO_LARGE] * len(big)
 
 
 def test_div_magic_divides_exactly(driver):
     """The multiply-high of coords.h's fast_div with div_magic's constant against plain division: every n <= n_max for small divisors,
     and the last n_max that still gets a magic (n_max * d < 2^32) for large ones; beyond it the magic is 0 and the kernel divides."""
     lines = ["magic %d %d" % (n_max, d) for d in range(1, 70) for n_max in (1, 69, 70001)] + ["magic %d %d" % (((1 << 32) - 1) // d, d) for d in (255, 256, 641, 4099, 65537)]
-    for (m, wrong), ln in zip(run_driver(driver, lines), lines):
+    for (m, wrong), ln in zip(run_driver(driver, lines, "plan"), lines):
         d = int(ln.split()[2])
         assert (m, wrong) == ((0, -1) if d == 1 else ((1 << 32) // d + 1, 0)), ln
     edge = []
@@ -192,6 +192,6 @@ def test_div_magic_divides_exactly(driver):
         last = ((1 << 32) - 1) // d
         edge += [(last, d), (last + 1, d), (last - 1, d)]
     wrap = [((1 << 64) - 1, 3), (1 << 63, 2), (1 << 32, (1 << 32) - 1)]  # (a product beyond 64 bits wraps, unsigned: only the sanitizer's silence is asserted)
-    got = run_driver(driver, ["magic_at %d %d" % (n, d) for n, d in edge + wrap])
+    got = run_driver(driver, ["magic_at %d %d" % (n, d) for n, d in edge + wrap], "plan")
     for (n, d), (m, q, exact) in zip(edge, got):
         assert (m != 0) == (n * d < 1 << 32 and d > 1) and q == exact == n // d, (n, d, m, q, exact)

@@ -1,10 +1,9 @@
 """The lens warp (bevwarp_warp_lens, warp_perspective_lens) without a device: the numpy reference (tests/lens_ref.py) against an
 independent 50-digit evaluation and against the trusted pinhole oracle, the host helpers, the C ABI's host checks under the
-sanitizers (tests/lens_plan_driver.cpp), the kernels' code object and the ABI surface."""
+sanitizers (tests/host_plan_driver.cpp, family `lens`), the kernels' code object and the ABI surface."""
 import ctypes
 import decimal
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -177,11 +176,8 @@ def _call(**kw):
 
 
 @pytest.fixture(scope="module")
-def driver(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("lens_plan_driver") / "lens_plan_driver")
-    subprocess.check_call(["g++", "-std=c++17", "-O1"] + hostplan.SANITIZE + ["-I", os.path.join(ROOT, "bev_amd", "csrc"), "-I", os.path.join(ROOT, "include"),
-                                                                            os.path.join(ROOT, "tests", "lens_plan_driver.cpp"), "-o", exe])
-    return exe
+def driver():
+    return hostplan.build_driver()
 
 
 def test_call_checks_under_sanitizers(driver):
@@ -207,9 +203,7 @@ def test_call_checks_under_sanitizers(driver):
               (_call(dst_w=(1 << 20) + 1, dst_h=1, dst_rs=1 << 21, dst_fs=1 << 21, **one), [OK, TOO_LARGE, 0]),
               (_call(dst_w=8, dst_h=(1 << 20) + 1, dst_rs=8, dst_fs=1 << 24, **one), [OK, TOO_LARGE, 0]),
               (_call(batch=big, dst=1 << 40, dst_rs=8, dst_fs=64, **one), [OK, TOO_LARGE, 0])]  # (2 tiles per frame: the grid passes 2^31 - 1 items)
-    got = hostplan.run_driver(driver, [c for c, _ in cases])
-    for (c, want), g in zip(cases, got):
-        assert g == want, (c, g, want)
+    hostplan.check_cases(driver, cases, "lens")
 
 
 def test_lens_status_under_sanitizers(driver):
@@ -225,7 +219,7 @@ def test_lens_status_under_sanitizers(driver):
         for bad in (float("nan"), INF, -INF):
             cases.append((line(good[:i] + [bad] + good[i + 1:], 1.0), NOT_FINITE))
     cases.append((line([0.0, float("nan")] + good[2:], -1.0), NOT_FINITE))  # (a non-finite entry is reported before a zero focal length)
-    got = hostplan.run_driver(driver, [c for c, _ in cases])
+    got = hostplan.run_driver(driver, [c for c, _ in cases], "lens")
     for (c, want), g in zip(cases, got):
         assert g == [want], (c, g, want)
 

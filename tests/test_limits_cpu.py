@@ -273,7 +273,7 @@ def test_nv12_layouts_lie_inside_their_holder_and_the_abi_admits_them():
     def status(lay, batch, rows, fs, rs, uv_off=None):
         uv = lay["uv"][2] if uv_off is None else uv_off
         line = "to_nv12 %d %d %d %d 96 700 %d %d %d %d %d %d %d %d %d 1 0" % (src, base, base + uv, batch, rows, dw, 96 * 2100, 2100, fs, rs, fs, rs, 1)
-        return hostplan.run_driver(hostplan.build_driver(), [line])[0][0]
+        return hostplan.run_driver(hostplan.build_driver(), [line], "plan")[0][0]
     assert status(joined, lc.BIG_BATCH, dh, lc.BEYOND_4G, dw) == 0
     assert status(beside, 1, lc.ROWS_PAST_4G5, 0, lc.ROW_64M) == 0
     overlap = -6  # BEVWARP_ERR_OVERLAP

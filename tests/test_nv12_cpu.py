@@ -209,7 +209,7 @@ def driver():
 
 
 def run_driver(exe, cases):
-    return hostplan.run_driver(exe, ["nv12 " + " ".join(str(int(v)) for v in c) for c in cases])
+    return hostplan.run_driver(exe, ["nv12 " + " ".join(str(int(v)) for v in c) for c in cases], "plan")
 
 
 def model(y, uv, dst, batch, sh, sw, dh, dw, yfs, yrs, uvfs, uvrs, dfs, drs, mc, interp, rgb):

@@ -266,7 +266,7 @@ def driver():
 
 
 def run_driver(exe, cases):
-    return hostplan.run_driver(exe, [c[0] + " " + " ".join(str(int(v)) for v in c[1:]) for c in cases])
+    return hostplan.run_driver(exe, [c[0] + " " + " ".join(str(int(v)) for v in c[1:]) for c in cases], "plan")
 
 
 def model(sources, dsts, batch, sh, sw, dh, dw, mc, interp, rgb, nv12):

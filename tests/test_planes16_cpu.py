@@ -145,7 +145,7 @@ def driver():
 
 
 def run_driver(exe, cases):
-    return hostplan.run_driver(exe, ["planes %d %d %d %d %d %d %d %d %d %d" % c for c in cases])
+    return hostplan.run_driver(exe, ["planes %d %d %d %d %d %d %d %d %d %d" % c for c in cases], "plan")
 
 
 def model(src, dst, batch, c, dh, dw, fs, ps, rs, elem):

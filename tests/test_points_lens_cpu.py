@@ -1,10 +1,9 @@
 """The lens point projection (bevwarp_project_points_lens, bev_amd.points.distort_points / undistort_points) without a device: the
 numpy reference (tests/points_lens_ref.py) against a 50-digit evaluation, against the plain homography and against the lens warp's
-chain, the convergence of the inverse, the C ABI's host checks under the sanitizers (tests/points_lens_driver.cpp), the ABI
+chain, the convergence of the inverse, the C ABI's host checks under the sanitizers (tests/host_plan_driver.cpp, family `points_lens`), the ABI
 surface, the kernels' code object and the Python entries' argument errors."""
 import ctypes
 import os
-import subprocess
 
 import mpmath
 import numpy as np
@@ -195,11 +194,8 @@ def _status(lens=GOOD, **kw):
 
 
 @pytest.fixture(scope="module")
-def driver(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("points_lens_driver") / "points_lens_driver")
-    subprocess.check_call(["g++", "-std=c++17", "-O1"] + hostplan.SANITIZE + ["-I", os.path.join(ROOT, "bev_amd", "csrc"), "-I", os.path.join(ROOT, "include"),
-                                                                            os.path.join(ROOT, "tests", "points_lens_driver.cpp"), "-o", exe])
-    return exe
+def driver():
+    return hostplan.build_driver()
 
 
 def test_status_under_sanitizers(driver):
@@ -235,7 +231,7 @@ def test_status_under_sanitizers(driver):
     # last: alignment (a point moves as one unit)
     cases += [(_status(src=src + 8), BAD_ARG), (_status(dst=dst + 8), BAD_ARG), (_status(dtype=1, src=src + 8), OK), (_status(dtype=1, src=src + 4), BAD_ARG),
               (_status(res=(1 << 22) + 4), BAD_ARG), (_status(dtype=1, res=(1 << 22) + 4), OK), (_status(dtype=1, res=(1 << 22) + 2), BAD_ARG)]
-    got = hostplan.run_driver(driver, [c for c, _ in cases])
+    got = hostplan.run_driver(driver, [c for c, _ in cases], "points_lens")
     for (c, want), g in zip(cases, got):
         assert g == [want], (c, g, want)
 

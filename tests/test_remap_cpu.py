@@ -1,10 +1,9 @@
 """The fixed-camera warp maps (bevwarp_build_map, bevwarp_remap; build_warp_map, remap, convert_maps) without a device: the numpy
 definition (tests/remap_ref.py) tied to the trusted references by bits, convertMaps' known answers, the C ABI's host checks and the
-frames-per-item plan under the sanitizers (tests/remap_plan_driver.cpp), the kernels' code object, the ABI surface and the Python
+frames-per-item plan under the sanitizers (tests/host_plan_driver.cpp, family `remap`), the kernels' code object, the ABI surface and the Python
 entries' own refusals."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -165,11 +164,8 @@ def _call(**kw):
 
 
 @pytest.fixture(scope="module")
-def driver(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("remap_plan_driver") / "remap_plan_driver")
-    subprocess.check_call(["g++", "-std=c++17", "-O1"] + hostplan.SANITIZE + ["-I", os.path.join(ROOT, "bev_amd", "csrc"), "-I", os.path.join(ROOT, "include"),
-                                                                            os.path.join(ROOT, "tests", "remap_plan_driver.cpp"), "-o", exe])
-    return exe
+def driver():
+    return hostplan.build_driver()
 
 
 def test_call_checks_under_sanitizers(driver):
@@ -224,9 +220,7 @@ def test_call_checks_under_sanitizers(driver):
               (_call(batch=2, map_count=2, dst_h=1, xy_fs=huge - 3, frac_fs=huge - 1), [OK, OK, 1, 2]),
               (_call(batch=2, map_count=2, xy_rs=huge - 3, xy_fs=huge - 3), [BAD_ARG, 0, 0, 0]), (_call(batch=2, map_count=2, frac_rs=huge - 1, frac_fs=huge - 1), [BAD_ARG, 0, 0, 0]),
               (_call(batch=3, dst_rs=huge, dst_fs=huge), [BAD_ARG, 0, 0, 0]), (_call(src_rs=huge), [TOO_LARGE, 0, 0, 0])]
-    got = hostplan.run_driver(driver, [c for c, _ in cases])
-    for (c, want), g in zip(cases, got):
-        assert g == want, (c, g, want)
+    hostplan.check_cases(driver, cases, "remap")
 
 
 def test_frames_per_item_plan_under_sanitizers(driver):
@@ -251,7 +245,7 @@ def test_frames_per_item_plan_under_sanitizers(driver):
               "plan 2147483647 2147483647 8 8 8 4096", "plan 2147483647 1 8 8 8 4096", "plan 2 1 1048577 8 8 1"]
     want += [[OK, 8, 4, 4096, 1], [OK, 1, 32, 32768, 1], [OK, 1, 32, 32768, 1], [OK, 1, 1, 1024, 1], [TOO_LARGE, 0, 0, 0, 0], [OK, 8, 268435456, 536870912, 0],
              [TOO_LARGE, 0, 0, 0, 0]]
-    got = hostplan.run_driver(driver, lines)
+    got = hostplan.run_driver(driver, lines, "remap")
     for ln, w, g in zip(lines, want, got):
         assert g == w, (ln, g, w)
         assert g[3] <= 2147483647
@@ -278,9 +272,7 @@ def test_build_map_status_under_sanitizers(driver):
              (line(frac=(1 << 24) + 128), [OVERLAP, 0]), (line(frac=(1 << 24) + 256), [OK, 2]), (line(frac=(1 << 24) - 126), [OVERLAP, 0]), (line(frac=(1 << 24) - 128), [OK, 2]),
              (line(frac=(1 << 24) + 128, interp=0), [OK, 2]),
              (line(lens=2), [NOT_FINITE, 0]), (line(lens=1, r2_max="-1"), [BAD_ARG, 0]), (line(lens=1, r2_max="nan"), [BAD_ARG, 0]), (line(lens=0, r2_max="nan"), [OK, 2])]
-    got = hostplan.run_driver(driver, [c for c, _ in cases])
-    for (c, want), g in zip(cases, got):
-        assert g == want, (c, g, want)
+    hostplan.check_cases(driver, cases, "remap")
 
 
 # ---- the code object: no scratch, no LDS, at most 128 VGPRs ----

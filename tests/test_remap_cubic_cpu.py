@@ -136,18 +136,18 @@ def _status_cases():
 
 @pytest.fixture(scope="module")
 def driver():
-    return hostplan.build_driver(source="remap_cubic_plan_driver.cpp")
+    return hostplan.build_driver()
 
 
 def test_host_checks_under_sanitizers(driver):
     flags = [("flag %d" % w, [f, left]) for w, f, left in ((0, 0, 0), (1, 0, 1), (FLAG, 1, 0), (FLAG | 1, 1, 1), (FLAG | 2, 1, 2), (0x100, 0, 0x100), (0x301, 1, 0x101),
                                                          (-1, 1, -1 & ~FLAG))]
-    got = hostplan.run_driver(driver, [ln for ln, _ in flags])
+    got = hostplan.run_driver(driver, [ln for ln, _ in flags], "remap_cubic")
     for (ln, want), g in zip(flags, got):
         assert g == want, (ln, g, want)
     cases = _status_cases()
     lines = [_call(**kw) for kw, _ in cases]
-    got = hostplan.run_driver(driver, lines)
+    got = hostplan.run_driver(driver, lines, "remap_cubic")
     for (kw, want), ln, g in zip(cases, lines, got):
         a = dict(CALL, **kw)
         flagged = int(bool(a["interp"] & FLAG))
@@ -162,12 +162,12 @@ def test_host_checks_under_sanitizers(driver):
     more = [(_call(batch=0), [1, OK, 0, 0, 0]),
             (_call(dst_w=w20, dst_h=1, dst_rs=w20, dst_fs=w20, xy_rs=4 * w20, frac_rs=2 * w20, **one), [1, OK, OK, 1, 4096]),
             (_call(dst_w=w20 + 1, dst_h=1, dst_rs=2 * w20, dst_fs=2 * w20, xy_rs=8 * w20, frac_rs=4 * w20, **one), [1, OK, TOO_LARGE, 0, 0])]
-    got = hostplan.run_driver(driver, [ln for ln, _ in more])
+    got = hostplan.run_driver(driver, [ln for ln, _ in more], "remap_cubic")
     for (ln, want), g in zip(more, got):
         assert g == want, (ln, g, want)
     # no other entry takes the flag out of its word
     others = [("other %s %d" % (e, w), [want]) for e in OTHERS for w, want in ((1, OK), (0, OK), (FLAG | 1, UNSUPPORTED), (FLAG, UNSUPPORTED), (2, UNSUPPORTED))]
-    got = hostplan.run_driver(driver, [ln for ln, _ in others])
+    got = hostplan.run_driver(driver, [ln for ln, _ in others], "remap_cubic")
     for (ln, want), g in zip(others, got):
         assert g == want, (ln, g, want)
 

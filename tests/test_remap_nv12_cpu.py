@@ -1,11 +1,9 @@
 """NV12 frames through a fixed camera's warp map (bevwarp_remap_nv12, bevwarp_remap_nv12_planes; remap_nv12, remap_nv12_to_planar) without
 a device: the numpy definition (tests/remap_nv12_ref.py) tied to the oracle by bits, the C ABI's host checks under the sanitizers
-(tests/remap_nv12_plan_driver.cpp), the same statuses through the built library, the ABI surface, the Python entries' own refusals and
+(tests/host_plan_driver.cpp, family `remap_nv12`), the same statuses through the built library, the ABI surface, the Python entries' own refusals and
 the kernels' code object."""
 import ctypes
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -18,7 +16,7 @@ from tests import hostplan
 from tests import nv12_ref as NR
 from tests import remap_nv12_ref as RN
 from tests import remap_ref as RR
-from tests.test_abi import declared_symbols
+from tests.test_abi import checked_declaration
 from tests.test_lens_cpu import GEOMS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -77,11 +75,8 @@ def _planes(**kw):
 
 
 @pytest.fixture(scope="module")
-def driver(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("remap_nv12_plan_driver") / "remap_nv12_plan_driver")
-    subprocess.check_call(["g++", "-std=c++17", "-O1"] + hostplan.SANITIZE + ["-I", os.path.join(ROOT, "bev_amd", "csrc"), "-I", os.path.join(ROOT, "include"),
-                                                                            os.path.join(ROOT, "tests", "remap_nv12_plan_driver.cpp"), "-o", exe])
-    return exe
+def driver():
+    return hostplan.build_driver()
 
 
 def _common_cases(call, dst_bytes, wide):
@@ -149,9 +144,7 @@ def test_remap_nv12_call_under_sanitizers(driver):
               (_pix(batch=2, map_count=2, xy_rs=huge - 3, xy_fs=huge - 3), [BAD_ARG] + NONE), (_pix(batch=2, map_count=2, frac_rs=huge - 1, frac_fs=huge - 1), [BAD_ARG] + NONE),
               (_pix(batch=3, dst_rs=huge, dst_fs=huge), [BAD_ARG] + NONE), (_pix(y_rs=huge), [TOO_LARGE] + NONE), (_pix(uv_rs=huge - 1), [TOO_LARGE] + NONE),
               (_pix(uv_rs=huge), [BAD_ARG] + NONE), (_pix(batch=2, y_rs=huge, y_fs=huge), [BAD_ARG] + NONE), (_pix(batch=2, uv_fs=huge - 1, y_fs=huge, dst=16), [OK, OK, 1, 4])]
-    got = hostplan.run_driver(driver, [c for c, _ in cases])
-    for (c, want), g in zip(cases, got):
-        assert g == want, (c, g, want)
+    hostplan.check_cases(driver, cases, "remap_nv12")
 
 
 def test_remap_nv12_planes_call_under_sanitizers(driver):
@@ -173,9 +166,7 @@ def test_remap_nv12_planes_call_under_sanitizers(driver):
               (_planes(dst_rs=14, plane_dtype=7), [UNSUPPORTED] + NONE), (_planes(dst_rs=7, plane_dtype=7), [BAD_ARG] + NONE)]   # (an unknown plane type: 1-byte elements)
     cases += [(_planes(dst_h=1, xy_rs=huge - 3, frac_rs=huge - 1, dst_rs=1 << 62, dst_ps=1 << 62, xy=256, frac=512), [OK, OK, 1, 1]), (_planes(dst_ps=huge - 1, dst_fs=huge - 1, batch=2), [BAD_ARG] + NONE),
               (_planes(y_rs=huge), [TOO_LARGE] + NONE), (_planes(batch=2, map_count=2, xy_rs=huge - 3, xy_fs=huge - 3), [BAD_ARG] + NONE)]
-    got = hostplan.run_driver(driver, [c for c, _ in cases])
-    for (c, want), g in zip(cases, got):
-        assert g == want, (c, g, want)
+    hostplan.check_cases(driver, cases, "remap_nv12")
 
 
 # ---- the same statuses through the built library (fake pointers, never dereferenced: every call below fails validation or launches nothing) ----
@@ -187,11 +178,7 @@ def test_abi_surface_and_statuses_through_the_library():
         header = f.read()
     assert "#define BEVWARP_ABI_VERSION 7" in header
     for name, nargs, n64 in zip(NAMES, (26, 30), (10, 11)):
-        assert name in declared_symbols() and name in _lib.SYMBOLS and getattr(ctypes.CDLL(_lib.LIB_PATH), name) is not None
-        assert len(_lib.SYMBOLS[name][1]) == nargs
-        decl = header[header.index("int %s(" % name):]
-        decl = re.sub(r"/\*.*?\*/", "", decl[:decl.index(";")])
-        assert decl.count(",") + 1 == nargs and decl.count("int64_t") == n64 == _lib.SYMBOLS[name][1].count(ctypes.c_int64), decl
+        decl = checked_declaration(name, nargs, n64)
         for arg in ("map_xy", "map_frac", "map_count", "border_mode", "rgb_order", "uv_row_stride"):
             assert arg in decl, (name, arg)
     assert "bevwarp_remap_nv12, bevwarp_remap_nv12_planes" in header.split("Conventions")[0]

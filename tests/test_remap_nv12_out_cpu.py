@@ -1,13 +1,11 @@
 """The map samplers that write NV12 (bevwarp_remap_to_nv12, bevwarp_remap_nv12_to_nv12, bevwarp_stitch_maps_to_nv12,
 bevwarp_stitch_maps_nv12_to_nv12; remap_to_nv12, remap_nv12_to_nv12, remap_stitch_to_nv12, remap_stitch_nv12_to_nv12) without a device:
 the numpy definition (tests/remap_nv12_out_ref.py) tied to the definitions of the matrix warps into NV12 by bits, what an invalid map
-entry gives, the C ABI's host checks under the sanitizers (tests/remap_nv12_out_plan_driver.cpp) and the same statuses, in their
+entry gives, the C ABI's host checks under the sanitizers (tests/host_plan_driver.cpp, family `remap_nv12_out`) and the same statuses, in their
 documented order, through the built library, the ABI surface, the refusals of the Python entries and of FramePipeline, and the code
 objects of the two kernel units."""
 import ctypes
 import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -22,7 +20,7 @@ from tests import nv12_ref as NR
 from tests import remap_nv12_out_ref as RO
 from tests import remap_ref as RR
 from tests import stitch_maps_ref as SM
-from tests.test_abi import declared_symbols
+from tests.test_abi import checked_declaration
 from tests.test_lens_cpu import GEOMS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -263,16 +261,13 @@ def _stitch_line(kind, cams, a):
 
 
 @pytest.fixture(scope="module")
-def driver(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("remap_nv12_out_plan_driver") / "remap_nv12_out_plan_driver")
-    subprocess.check_call(["g++", "-std=c++17", "-O1"] + hostplan.SANITIZE + ["-I", os.path.join(ROOT, "bev_amd", "csrc"), "-I", os.path.join(ROOT, "include"),
-                                                                            os.path.join(ROOT, "tests", "remap_nv12_out_plan_driver.cpp"), "-o", exe])
-    return exe
+def driver():
+    return hostplan.build_driver()
 
 
 def test_call_descriptions_under_sanitizers(driver):
     single, stitch = _single_cases(), _stitch_cases()
-    got = hostplan.run_driver(driver, [_single_line(kind, a) for kind, a, _ in single] + [_stitch_line(kind, cams, a) for kind, cams, a, _ in stitch])
+    got = hostplan.run_driver(driver, [_single_line(kind, a) for kind, a, _ in single] + [_stitch_line(kind, cams, a) for kind, cams, a, _ in stitch], "remap_nv12_out")
     for (kind, a, want), g in zip(single, got):
         assert g == want, (_single_line(kind, a), g, want)
     for (kind, cams, a, want), g in zip(stitch, got[len(single):]):
@@ -280,7 +275,7 @@ def test_call_descriptions_under_sanitizers(driver):
     # the grid of a stitch that goes on to a launch: 256 x 4 tiles over the canvas, one frame per item whatever the map count
     for kind, k in (("sbgr", CAM), ("snv12", NVCAM)):
         lines = [_stitch_line(kind, [k] * n_, dict(CALL, border=1, **kw)) for n_, kw in ((1, {}), (8, {}), (3, dict(batch=5)), (1, dict(batch=0)))]
-        assert hostplan.run_driver(driver, lines) == [[OK, OK, 2], [OK, OK, 2], [OK, OK, 10], [OK, OK, 0]]
+        assert hostplan.run_driver(driver, lines, "remap_nv12_out") == [[OK, OK, 2], [OK, OK, 2], [OK, OK, 10], [OK, OK, 0]]
 
 
 def _through_the_library(lib, kind, a, border):
@@ -332,11 +327,7 @@ def test_abi_surface():
         header = f.read()
     assert "#define BEVWARP_ABI_VERSION 7" in header
     for name, nargs, n64 in zip(NAMES, (26, 28, 17, 16), (10, 12, 4, 4)):
-        assert name in declared_symbols() and name in _lib.SYMBOLS and getattr(ctypes.CDLL(_lib.LIB_PATH), name) is not None
-        assert len(_lib.SYMBOLS[name][1]) == nargs
-        decl = header[header.index("int %s(" % name):]
-        decl = re.sub(r"/\*.*?\*/", "", decl[:decl.index(";")])
-        assert decl.count(",") + 1 == nargs and decl.count("int64_t") == n64 == _lib.SYMBOLS[name][1].count(ctypes.c_int64), decl
+        decl = checked_declaration(name, nargs, n64)
         for arg in ("dst_y", "dst_uv", "uv_row_stride", "interp", "border_value"):
             assert arg in decl, (name, arg)
     assert ", ".join(NAMES) in header.split("Conventions")[0]

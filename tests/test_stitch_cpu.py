@@ -1,9 +1,8 @@
 """The multi-camera warp (bevwarp_warp_stitch, warp_stitch) without a device: the numpy reference (tests/stitch_ref.py) against the
 one-call-per-camera route of tests/border_ref.py and against hand-computed weights, the C ABI's host checks through the loaded library
-and under the sanitizers (tests/stitch_plan_driver.cpp), the kernels' code object, the ABI surface and the Python entry's own checks."""
+and under the sanitizers (tests/host_plan_driver.cpp, the `stitch` family), the kernels' code object, the ABI surface and the Python entry's own checks."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -209,11 +208,8 @@ def test_status_order_through_the_library():
 # ---- the host checks under the sanitizers ----
 
 @pytest.fixture(scope="module")
-def driver(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("stitch_plan_driver") / "stitch_plan_driver")
-    subprocess.check_call(["g++", "-std=c++17", "-O1"] + hostplan.SANITIZE + ["-I", os.path.join(ROOT, "bev_amd", "csrc"), "-I", os.path.join(ROOT, "include"),
-                                                                            os.path.join(ROOT, "tests", "stitch_plan_driver.cpp"), "-o", exe])
-    return exe
+def driver():
+    return hostplan.build_driver()
 
 
 CAM = dict(src=16, h=8, w=8, fs=192, rs=24, m_count=1, m_null=0)
@@ -277,9 +273,7 @@ def test_stitch_status_under_sanitizers(driver):
               (_line([c1], dw=(1 << 20) + 1, dh=1, drs=1 << 21, dfs=1 << 21, border=2, **one), large),
               (_line([g], batch=0), [OK, OK, 0]), (_line([g], batch=0, border=2), nonfinite), (_line([g, _c(src=1 << 30)], batch=0), [OK, OK, 0]),
               (_line([c1], batch=0, dh=(1 << 20) + 1, drs=8, dfs=1 << 24, **one), large), (_line([g], batch=-1), bad)]
-    got = hostplan.run_driver(driver, [c for c, _ in cases])
-    for (c, want), out in zip(cases, got):
-        assert out == want, (c, out, want)
+    hostplan.check_cases(driver, cases, "stitch")
 
 
 # ---- the code object: no scratch, no LDS, at most 128 VGPRs ----

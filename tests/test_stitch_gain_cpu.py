@@ -1,6 +1,6 @@
 """Per-camera exposure gains in the stitches through warp maps (BEVWARP_STITCH_GAIN, bev_amd.warp.remap_stitch*(..., gains=),
 bev_amd.exposure) without a device: the gain step over its whole domain, the six entries' host checks under the flag -- through
-tests/stitch_gain_plan_driver.cpp under the sanitizers and through the loaded library -- the header, the gained units' code objects, the
+tests/host_plan_driver.cpp, family `stitch_gain` under the sanitizers and through the loaded library -- the header, the gained units' code objects, the
 Python entries' and SitePipeline's refusals, and the gain solver."""
 import ctypes
 import os
@@ -182,9 +182,9 @@ def test_status_through_the_library():
 
 
 def test_status_under_sanitizers():
-    driver = hostplan.build_driver(source="stitch_gain_plan_driver.cpp")
+    driver = hostplan.build_driver()
     cases = _cases()
-    got = hostplan.run_driver(driver, [_line(kind, cams, a) for kind, cams, a, _ in cases])
+    got = hostplan.run_driver(driver, [_line(kind, cams, a) for kind, cams, a, _ in cases], "stitch_gain")
     for (kind, cams, a, want), out in zip(cases, got):
         flagged = int(a["blend"] & GAIN != 0)
         assert out[0] == want and out[3] == flagged and (want == OK or out[1:3] == [0, 0]), (_line(kind, cams, a), out, want)
@@ -193,12 +193,12 @@ def test_status_under_sanitizers():
     for kind in KINDS:
         cams = [_cam(kind, reserved=w) for w in words]
         lines = [_line(kind, cams[:n], dict(dict(CALL, border=1, **DEST.get(kind, {})), **kw)) for n, kw in ((1, {}), (8, {}), (3, dict(batch=0)), (2, dict(blend=GAIN | 1)))]
-        assert hostplan.run_driver(driver, lines) == [[OK, OK, 2, 1] + words[:1], [OK, OK, 2, 1] + words, [OK, OK, 0, 1] + words[:3], [OK, OK, 2, 1] + words[:2]], kind
+        assert hostplan.run_driver(driver, lines, "stitch_gain") == [[OK, OK, 2, 1] + words[:1], [OK, OK, 2, 1] + words, [OK, OK, 0, 1] + words[:3], [OK, OK, 2, 1] + words[:2]], kind
         plain = _line(kind, cams[:2], dict(dict(CALL, border=1, blend=1, **DEST.get(kind, {}))))
-        assert hostplan.run_driver(driver, [plain]) == [[OK, OK, 2, 0]]
+        assert hostplan.run_driver(driver, [plain], "stitch_gain") == [[OK, OK, 2, 0]]
     wide = dict(dw=260, dh=22, drs=780, dfs=780 * 22, dst=1 << 40, batch=3, border=1)
     cam = _cam("maps", xy=1 << 44, frac=1 << 48, xy_rs=1040, fr_rs=520, xy_fs=1040 * 22, fr_fs=520 * 22, map_count=3)
-    assert hostplan.run_driver(driver, [_line("maps", [cam], dict(CALL, **wide))]) == [[OK, OK, 2 * 6 * 3, 1, WORD]]
+    assert hostplan.run_driver(driver, [_line("maps", [cam], dict(CALL, **wide))], "stitch_gain") == [[OK, OK, 2 * 6 * 3, 1, WORD]]
 
 
 # ---- the code objects of the gained units ----

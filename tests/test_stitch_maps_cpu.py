@@ -1,10 +1,9 @@
 """The multi-camera stitch through warp maps (bevwarp_stitch_maps / bevwarp_stitch_maps_nv12, remap_stitch / remap_stitch_nv12) without a
 device: the numpy definition (tests/stitch_maps_ref.py) against the routes that exist -- tests/stitch_ref.py's stitch for pinhole maps,
 chained tests/remap_ref.py remaps for OVER -- and against hand-computed weights; the C ABI's host checks through the loaded library and
-under the sanitizers (tests/stitch_maps_plan_driver.cpp); the kernels' code object, the ABI surface and the Python entries' own checks."""
+under the sanitizers (tests/host_plan_driver.cpp, family `stitch_maps`); the kernels' code object, the ABI surface and the Python entries' own checks."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -302,25 +301,22 @@ def test_status_order_through_the_library():
 # ---- the host checks under the sanitizers ----
 
 @pytest.fixture(scope="module")
-def driver(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("stitch_maps_plan_driver") / "stitch_maps_plan_driver")
-    subprocess.check_call(["g++", "-std=c++17", "-O1"] + hostplan.SANITIZE + ["-I", os.path.join(ROOT, "bev_amd", "csrc"), "-I", os.path.join(ROOT, "include"),
-                                                                            os.path.join(ROOT, "tests", "stitch_maps_plan_driver.cpp"), "-o", exe])
-    return exe
+def driver():
+    return hostplan.build_driver()
 
 
 def test_status_under_sanitizers(driver):
     cases = _cases()
-    got = hostplan.run_driver(driver, [_line(kind, cams, a) for kind, cams, a, _ in cases])
+    got = hostplan.run_driver(driver, [_line(kind, cams, a) for kind, cams, a, _ in cases], "stitch_maps")
     for (kind, cams, a, want), out in zip(cases, got):
         assert out[0] == want and (want == OK or out[1:] == [0, 0]), (_line(kind, cams, a), out, want)
     # the grid of a call that goes on to a launch: kBorderTileW x kBorderTileH tiles over the canvas, one frame per item whatever the map count
     for kind, k in (("maps", _c()), ("nv12", _n())):
         lines = [_line(kind, [k] * n, dict(dict(CALL, border=1), **kw)) for n, kw in ((1, {}), (8, {}), (3, dict(batch=5, dfs=192)), (1, dict(batch=0)), (1, dict(mode=5, border=2)))]
-        assert hostplan.run_driver(driver, lines) == [[OK, OK, 2], [OK, OK, 2], [OK, OK, 10], [OK, OK, 0], [OK, OK, 2]]
+        assert hostplan.run_driver(driver, lines, "stitch_maps") == [[OK, OK, 2], [OK, OK, 2], [OK, OK, 10], [OK, OK, 0], [OK, OK, 2]]
         wide = dict(dw=260, dh=22, drs=780, dfs=780 * 22, dst=1 << 40)
         lines = [_line(kind, [dict(k, xy=1 << 44, frac=1 << 48, xy_rs=1040, fr_rs=520, xy_fs=1040 * 22, fr_fs=520 * 22, map_count=m)], dict(CALL, border=0, batch=3, **wide)) for m in (1, 3)]
-        assert hostplan.run_driver(driver, lines) == [[OK, OK, 2 * 6 * 3]] * 2
+        assert hostplan.run_driver(driver, lines, "stitch_maps") == [[OK, OK, 2 * 6 * 3]] * 2
 
 
 # ---- the code object: no scratch, no LDS, at most 128 VGPRs ----

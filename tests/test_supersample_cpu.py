@@ -1,5 +1,5 @@
 """The supersampled warp without a device: the numpy reference (tests/supersample_ref.py) against hand answers, the host checks of
-BEVWARP_SUPERSAMPLE_* through tests/supersample_plan_driver.cpp (under the sanitizers) and through the built library with pointers that
+BEVWARP_SUPERSAMPLE_* through tests/host_plan_driver.cpp, family `supersample` (under the sanitizers) and through the built library with pointers that
 are never dereferenced, the header's text, the Python entry's refusals, and the new kernels' code object."""
 import ctypes
 import os
@@ -102,13 +102,13 @@ def test_straddling_shapes_straddle():
 
 @pytest.fixture(scope="module")
 def driver():
-    return hostplan.build_driver(source="supersample_plan_driver.cpp")
+    return hostplan.build_driver()
 
 
 def test_take_supersample(driver):
     words = [0, 1, 2, 0x100, 0x200, S2 | 1, S8 | 0, S4 | 2, -1]
     want = [[1, 0], [1, 1], [1, 2], [1, 0x100], [1, 0x200], [2, 1], [8, 0], [4, 2], [8, -1 & ~0x3000]]
-    assert hostplan.run_driver(driver, ["field %d" % w for w in words]) == want
+    assert hostplan.run_driver(driver, ["field %d" % w for w in words], "supersample") == want
     assert want[-1][1] == -12289
 
 
@@ -171,7 +171,7 @@ def test_call_statuses_in_their_documented_order(driver):
     add([2, OK, OK, 73, 4], interp=1 | S2, batch=2, dst_w=50, dst_h=7, dst_rs=150, dst_fs=1050)
     add([4, OK, OK, 85, 1], interp=1 | S4, dst_w=30, dst_h=3, dst_rs=90, dst_fs=270)
     add([8, OK, OK, 64, 2 * 3], interp=1 | S8, dst_w=257, dst_h=9, dst_rs=771, dst_fs=6939)
-    got = hostplan.run_driver(driver, cases)
+    got = hostplan.run_driver(driver, cases, "supersample")
     for line, g, w in zip(cases, got, want):
         assert g == w, (line, g, w)
 
@@ -188,7 +188,7 @@ def test_other_entries_judge_the_whole_word(driver):
     for field in (S2, S4, S8):
         lines += ["other lens %d" % (1 | 0x100 | field), "other build %d" % (1 | 0x100 | field), "other remap %d" % (1 | 0x200 | field)]
         want += [[UNSUPPORTED]] * 3
-    assert hostplan.run_driver(driver, lines) == want
+    assert hostplan.run_driver(driver, lines, "supersample") == want
 
 
 # ---- the same statuses through the built library (fake pointers, never dereferenced: every call ends before a launch) ---------------------
